@@ -6,9 +6,12 @@ README F0Model 600->512->128->32->1 on synthetic 256 x 1000-frame utterance batc
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.  Inputs are resident in HBM before the timed region.  `roofline` is measured live with
-HIP events on the kernel's own stream for the dominant kernel; `cpu_baseline` times the oracle's torch-CPU restatement
-of the reference step on a bounded sample on the host cores (rank 0, N=1 only).
+Prints ONE JSON line on rank 0.  Inputs are resident in HBM before the timed region.  A plain run sets up, warms up, times
+--steps steps and prints the headline line.  --full adds the legs that take runs of their own: `roofline` is measured live
+with HIP events on the kernel's own stream for the dominant kernel; `cpu_baseline` times the oracle's torch-CPU restatement
+of the reference step on a bounded sample on the host cores (rank 0, N=1 only); C2 adds the frame-rate order, the other
+configs, bf16x3, train_epoch and the loss-curve deviation.  --dump-outputs DIR writes what the last timed step computed
+(loss, output features, updated parameters) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -53,17 +56,27 @@ def parse_args():
                     help='C2: training steps captured into one HIP graph (0 = the largest divisor of --steps up to 25)')
     ap.add_argument('--no-graph', action='store_true',
                     help='c2: launch every kernel of the step from Python instead of replaying the captured HIP graph')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: roofline, CPU baseline, exposed exchange time and (c2) the frame-rate order, the other '
+                         'configs, bf16x3, train_epoch and the loss-curve deviation; --no-compare / --no-cpu-baseline / --no-roofline '
+                         'leave parts out again')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps: the loss, output features and updated parameters of the last step as DIR/<name>.npy '
+                         '(float32; at most 64 MB in all, larger arrays as a fixed seeded sample of their elements)')
     ap.add_argument('--no-compare', action='store_true',
-                    help='c2: skip the extra leg that times the frame-rate order of operations (frame_rate_order in the JSON line)')
+                    help='with --full, c2: skip the extra legs (frame_rate_order, c4, other_workloads, bf16x3, train_epoch, '
+                         'loss_curve_deviation; exposed_us of the exchange)')
     ap.add_argument('--rehearse-exchange', action='store_true',
                     help='one rank only: run the MULTI-rank code path (gradient buckets, all-reduce through a world-size-1 RCCL group, '
                          'no deferred slabs) - what a rank of an N-GPU job executes per step, without the peers')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip cpu_baseline')
     ap.add_argument('--dry-run-ranks', action='store_true',
                     help='rendezvous only: every rank joins the process group, one all-reduce counts them, rank 0 prints '
                          '{"n_gpus": N, "dry_run": true} - checks the launcher path without touching a GPU')
-    ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip roofline')
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.steps is None:
         args.steps = 200 if args.config == 'c2' else 30
     if args.warmup is None:
@@ -946,14 +959,15 @@ def other_workloads(dev, precision):
     return out
 
 
-def exchange_record(optimizer, step, world, rehearse, device, calls=20):
+def exchange_record(optimizer, step, world, rehearse, device, calls=20, measure=True):
     """First-contact diagnostics of the gradient exchange, carried by EVERY bench line:
     how many ranks a real all-reduce counted, how the exchange ran (mode), what one exchange of the model's flat gradient costs on
     its own (`us`: device events around `calls` back-to-back all-reduces of a buffer of that size, per-call mean, MAX over ranks;
     host clock when the group's tensors live on the CPU), and what the capture probe found (`capture_probe`: its verdict, whether the
     captured graph held a collective at all, whether the replayed sums equalled the world size).  `exposed_us` - the step with the
     exchange minus the step without it - is filled in by the caller (it needs a second timed loop).  Works on any process group:
-    the CPU / gloo test drives it without a GPU."""
+    the CPU / gloo test drives it without a GPU.  ``measure`` False (a run without --full): the ranks are counted, `us` and
+    `capture_probe` stay None."""
     dist = torch.distributed
     live = dist.is_available() and dist.is_initialized()
     rec = {'world_size': dist.get_world_size() if live else 1, 'backend': dist.get_backend() if live else None,
@@ -966,6 +980,8 @@ def exchange_record(optimizer, step, world, rehearse, device, calls=20):
     count = torch.ones(1, dtype=torch.float32, device=where)
     dist.all_reduce(count)                                             # a real collective: every rank that is really there adds 1
     rec['ranks_counted'] = int(round(float(count.item())))
+    if not measure:
+        return rec
     flat = optimizer.flat_buffers() if optimizer is not None else None
     if flat is not None and optimizer.exchanging():
         scratch = torch.zeros(flat['grad'].numel(), dtype=torch.float32, device=flat['grad'].device)
@@ -999,6 +1015,40 @@ def exchange_record(optimizer, step, world, rehearse, device, calls=20):
         rec['capture_probe'] = {'verdict': False, 'world': rec['world_size'], 'backend': rec['backend'],
                                 'error': 'not an RCCL group: nothing to capture'}
     return rec
+
+
+DUMP_BUDGET_BYTES = 60 << 20      # --dump-outputs: data of all arrays together (64 MB with room for the .npy headers)
+
+
+def dump_outputs(out_dir, loss, outputs, model):
+    """--dump-outputs: what the caller of the timed step holds after its last step - the loss, the output features and the
+    parameters after the update - as ``out_dir/<name>.npy`` (``loss``, ``output.<key>``, ``param.<name>``), float32 (float64 stays
+    float64).  At most DUMP_BUDGET_BYTES in all: the smallest arrays are written whole first, and an array larger than its share of
+    what is left becomes a fixed sample of its flattened elements (indices drawn without replacement by a generator seeded with
+    the array's name, ascending), so two builds run with the same arguments write the same elements.  Returns the bytes written."""
+    import zlib
+    named = [('loss', loss)]
+    named += [('output.' + key, value) for key, value in sorted(outputs.items()) if torch.is_tensor(value)]
+    named += [('param.' + key, prm) for key, prm in model.named_parameters()]
+    arrays = []
+    for name, tensor in named:
+        tensor = tensor.detach()
+        arrays.append((name, tensor.to(torch.float64 if tensor.dtype == torch.float64 else torch.float32)))
+    os.makedirs(out_dir, exist_ok=True)
+    left, written = DUMP_BUDGET_BYTES, 0
+    by_size = sorted(arrays, key=lambda item: (item[1].numel() * item[1].element_size(), item[0]))
+    for i, (name, tensor) in enumerate(by_size):
+        share = left // (len(by_size) - i) // tensor.element_size()
+        if tensor.numel() > share:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.sort(rng.choice(tensor.numel(), size=share, replace=False))
+            values = tensor.reshape(-1)[torch.from_numpy(idx).to(tensor.device)].cpu().numpy()
+        else:
+            values = tensor.cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), values)
+        left -= values.nbytes
+        written += values.nbytes
+    return written
 
 
 def spawn_ranks(n):
@@ -1097,12 +1147,15 @@ def main():
         torch.distributed.init_process_group(backend='nccl', rank=0, world_size=1)
     # the loop below is the reference's loop body
     optimizer = optim.Adam(model.parameters(), lr=0.01, fused_loop=True, exchange_always=rehearse)
+    last_outputs = {} if args.dump_outputs else None     # --dump-outputs: the output features of the latest eager step
 
     def step():
         optimizer.zero_grad()
-        loss, _ = model(features)
+        loss, outputs = model(features)
         F_hip.backward(loss)             # what ExperimentBuilder.train_epoch calls: loss.backward() with a cached unit gradient
         optimizer.step()
+        if last_outputs is not None:
+            last_outputs['features'] = outputs
         return loss
 
     # The F0Model step's kernels sum to ~0.3 ms, less than the Python / autograd / launch path around them: replay the step as a
@@ -1160,11 +1213,15 @@ def main():
         elapsed = float(tmax.item())
     ops.check_persistent_status()        # raises if a persistent recurrent kernel timed out (results would be invalid)
     final_loss = float(distributed.mean_scalar(loss.detach()).item())
+    if args.dump_outputs and rank == 0:
+        # the graph replay's output features are its captured buffers, which the last replay wrote
+        dumped = dump_outputs(args.dump_outputs, loss, last_outputs['features'] if last_outputs else step.output, model)
+        sys.stderr.write('bench: %.1f MB of outputs of the last timed step in %s\n' % (dumped / 1e6, args.dump_outputs))
 
-    # the exchange's own record (every rank takes part in its collectives), and - where the step has an exchange - the same step
-    # timed WITHOUT it right after: exposed_us = what the data-parallel form costs a step beyond the one-rank step
-    exchange = exchange_record(optimizer, step, world, rehearse, dev)
-    if optimizer.exchanging() and args.config == 'c2' and not args.no_compare:
+    # the exchange's own record (every rank takes part in its collectives), and - with --full, where the step has an exchange - the
+    # same step timed WITHOUT it right after: exposed_us = what the data-parallel form costs a step beyond the one-rank step
+    exchange = exchange_record(optimizer, step, world, rehearse, dev, measure=args.full)
+    if args.full and optimizer.exchanging() and args.config == 'c2' and not args.no_compare:
         try:
             from morgana_amd import graphs
             alone_model = models.F0Model(precision=args.precision).to(dev)
@@ -1207,7 +1264,7 @@ def main():
     # C2, one rank: the same model and batch with every product at frame rate (the reference's order of operations,
     # MORGANA_PHONE_RATE=0), timed the same way right after - reported next to the headline value, never as it
     frame_rate = None
-    if (args.config == 'c2' and world == 1 and args.precision == 'bf16' and ops.PHONE_RATE and not args.no_graph
+    if (args.full and args.config == 'c2' and world == 1 and args.precision == 'bf16' and ops.PHONE_RATE and not args.no_graph
             and not args.no_compare):
         try:
             from morgana_amd import graphs
@@ -1347,15 +1404,16 @@ def main():
                                                   'what': 'FLOPs of the reference\'s order of operations (SURVEY.md section 8d) divided by the '
                                                           'phone-rate step time: an equivalence figure, not an achieved rate and not a '
                                                           'fraction of any roof - the achieved frame-rate figure is frame_rate_order'}
-    if rank == 0 and args.config == 'c2' and not args.no_roofline:
+    # everything below measures beyond the headline figure: --full only
+    if rank == 0 and args.full and args.config == 'c2' and not args.no_roofline:
         result['roofline'] = roofline_f0(features, model, args.precision)
-    if rank == 0 and args.config in ('c4', 'c5') and not args.no_roofline:
+    if rank == 0 and args.full and args.config in ('c4', 'c5') and not args.no_roofline:
         result['roofline'] = roofline_gru(features, model, args.precision, target)
-    if rank == 0 and args.config == 'lstm' and not args.no_roofline:
+    if rank == 0 and args.full and args.config == 'lstm' and not args.no_roofline:
         roof = roofline_lstm(features, model, args.precision)
         if roof is not None:
             result['roofline'] = roof
-    if rank == 0 and n_gpus == 1 and args.config == 'c2' and args.precision == 'bf16' and not args.no_compare:
+    if rank == 0 and args.full and n_gpus == 1 and args.config == 'c2' and args.precision == 'bf16' and not args.no_compare:
         try:
             result['c4'] = c4_leg(dev, args.precision)
         except Exception as exc:
@@ -1367,7 +1425,7 @@ def main():
             result['loss_curve_deviation'] = loss_curve_deviation(dev)
         except Exception as exc:
             result['loss_curve_deviation'] = {'error': str(exc).splitlines()[0][:200]}
-    if rank == 0 and n_gpus == 1 and args.config == 'c2' and not args.no_cpu_baseline:
+    if rank == 0 and args.full and n_gpus == 1 and args.config == 'c2' and not args.no_cpu_baseline:
         result['cpu_baseline'] = cpu_baseline_f0(per_gpu, args.frames)
     distributed.barrier()
     if rank == 0:

@@ -9,7 +9,7 @@ if [ -n "$K" ]; then
   [ $rc -ne 0 ] && exit $rc
 fi
 EXTRA=${MG_BENCH_EXTRA:-}
-NOCMP=--no-compare; [ -n "$MG_BENCH_COMPARE" ] && NOCMP=   # MG_BENCH_COMPARE=1: time the frame-rate order as well
+NOCMP=--no-compare; [ -n "$MG_BENCH_COMPARE" ] && NOCMP=--full   # MG_BENCH_COMPARE=1: time the frame-rate order as well
 for i in 1 2 3; do
   for leg in "$@"; do
     tag=$(echo "$leg" | tr ':,' '__')

@@ -3,7 +3,10 @@
  * workspace planning, error formatting, launch set-up) is instrumented; device code is not.  No GPU is needed: calls are made
  * with arguments that validation must reject (MG_EINVAL) or - with plausible shapes and fake, never dereferenced device
  * pointers - run up to the launch, which fails with MG_ELAUNCH on a box without a device.  The pass is "no ASan report and
- * every return code is one the header documents". */
+ * every return code is one the header documents".  The launches must fail: with a GPU visible the program refuses to run
+ * (make asan-check hides every device from it). */
+#define _GNU_SOURCE
+#include <dlfcn.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -28,7 +31,23 @@ static void expect_code(const char* what, int rc) {
     }
 }
 
+/* Devices the HIP runtime (loaded with libmorgana_hip) reports; 0 when it reports an error, e.g. that there is none. */
+static int visible_devices(void) {
+    int (*get_count)(int*) = (int (*)(int*))dlsym(RTLD_DEFAULT, "hipGetDeviceCount");
+    int n = 0;
+    if (!get_count) {
+        fprintf(stderr, "hipGetDeviceCount not found\n");
+        return -1;
+    }
+    return get_count(&n) == 0 ? n : 0;
+}
+
 int main(void) {
+    const int n_dev = visible_devices();
+    if (n_dev != 0) {
+        fprintf(stderr, "refusing to run: %d GPU(s) visible, and the calls below launch on fake device addresses\n", n_dev);
+        return 2;
+    }
     /* fake device addresses: 16-byte aligned, never dereferenced on the host */
     void* d = (void*)(uintptr_t)0x7f0000001000ull;
     float* df = (float*)d;
