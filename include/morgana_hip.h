@@ -557,6 +557,41 @@ int mg_dropout(const void* x, void* y, int64_t n, int bf16, float p, uint64_t se
 int mg_dropout_advance(uint64_t* state, uint64_t* used, void* stream);
 /* Host-only: one Philox4x32-10 block (the generator mg_dropout draws from), for known-answer tests. */
 void mg_philox4x32_10(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
+/* Latent-conditioned models (BaseVAE, reference base_models.py:288-381; csrc/vae.hip).  Leading dims are flattened to `rows`; mean and
+ * logvar are [rows, Z] with row strides ldm / ldv (column views of one [rows, 2Z] encoder output are fine); z, eps, dz, dmean, dlogvar
+ * are contiguous [rows, Z] f32.
+ * mg_vae_sample_f32: z = mean + exp(0.5 logvar) * eps and eps written out, eps ~ N(0, 1).  Noise mapping (restatable on the host with
+ *   mg_philox4x32_10): flat element i = r * Z + c belongs to Philox block q = i / 4, counter words (q low, q high, ctr low,
+ *   site ^ ctr high), key (seed low, seed high), ctr = *counter (DEVICE uint64, NULL = 0; the dropout step counter: mg_dropout_advance).
+ *   A word w becomes u(w) = ((w >> 8) | 1) * 2^-24, exact in fp32 and inside (0, 1) (no log(0)).  The block's words (x, y, z, w) give
+ *   elements 4q..4q+3 = Box-Muller pairs  R(x) cos(2 pi u(y)), R(x) sin(2 pi u(y)), R(z) cos(2 pi u(w)), R(z) sin(2 pi u(w)),
+ *   R(a) = sqrt(-2 ln u(a)).
+ * mg_vae_sample_bwd_f32: dmean = dz (dmean may be NULL), dlogvar = 0.5 dz eps exp(0.5 logvar).
+ * mg_kld_standard_normal_f32: out[0] (DEVICE f32) = mean over rows of -0.5 sum_z (1 + lv - m^2 - exp(lv)) (reference losses.py:64-67); one
+ *   workgroup, fixed summation order (fp64 partials): the same bits on every call.
+ * mg_kld_standard_normal_bwd_f32: with g = grad[0] (DEVICE f32, the upstream gradient; no host read): dmean = g m / rows,
+ *   dlogvar = g 0.5 (exp(lv) - 1) / rows.
+ * mg_gather_concat_latent_*: mg_gather_concat_* with the latent behind the frame features:
+ *   out[m] = [src[rows[m]] (0 for rows[m] < 0; rows NULL = src row m) | extra[m, 0:C] | z[m / rows_per_item, 0:Z] | 0 up to ldo].
+ *   C may be 0 (extra NULL).  The bf16 form needs ldo % 8 == 0 and 16-byte aligned src / out.
+ * mg_rows_add_per_item_f32: P[r, 0:N] += U[r / rows_per_item, 0:N] for r < rows (the rows behind, e.g. a table's extra rows, untouched).
+ * mg_rows_sum_per_item: s[b, 0:N] = sum_{r = b rows_per_item}^{(b + 1) rows_per_item - 1} G[r, 0:N] (times H (1 - H) elementwise when H
+ *   [rows, ldh] f32 is given: a sigmoid's gradient factor) for b < B <= 65535; G f32 (bf16 = 0) or bf16 (bf16 = 1) with row stride ldg;
+ *   s f32 with row stride lds.  Fixed summation order. */
+int mg_vae_sample_f32(const float* mean, int ldm, const float* logvar, int ldv, int64_t rows, int Z, uint64_t seed, uint32_t site,
+                      const uint64_t* counter, float* z, float* eps, void* stream);
+int mg_vae_sample_bwd_f32(const float* dz, const float* eps, const float* logvar, int ldv, int64_t rows, int Z, float* dmean, float* dlogvar,
+                          void* stream);
+int mg_kld_standard_normal_f32(const float* mean, int ldm, const float* logvar, int ldv, int64_t rows, int Z, float* out, void* stream);
+int mg_kld_standard_normal_bwd_f32(const float* grad, const float* mean, int ldm, const float* logvar, int ldv, int64_t rows, int Z,
+                                   float* dmean, float* dlogvar, void* stream);
+int mg_gather_concat_latent_f32(const float* src, const int32_t* rows, const float* extra, const float* z, float* out, int64_t M, int F, int C,
+                                int Z, int64_t rows_per_item, int ldo, void* stream);
+int mg_gather_concat_latent_bf16(const float* src, const int32_t* rows, const float* extra, const float* z, uint16_t* out, int64_t M, int F,
+                                 int C, int Z, int64_t rows_per_item, int ldo, void* stream);
+int mg_rows_add_per_item_f32(float* P, int ldp, int64_t rows, int N, const float* U, int ldu, int64_t rows_per_item, void* stream);
+int mg_rows_sum_per_item(const void* G, int ldg, int bf16, const float* H, int ldh, int64_t B, int64_t rows_per_item, int N, float* s, int lds,
+                         void* stream);
 /* CALIBRATION (a measurement entry; no training step calls it): one launch of a register-operand bf16 MFMA loop - n_workgroups x 512
  * threads (two waves per SIMD), every wave issues 16 x trips v_mfma_f32_16x16x32_bf16 on operands read once from `operands`
  * (bf16, at least 4096 x 64 values: the caller chooses the data, e.g. random) and writes one float per thread to `sink`

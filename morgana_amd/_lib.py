@@ -98,6 +98,17 @@ SIGNATURES = {
     'mg_dropout': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p]),
     'mg_dropout_advance': (c_int, [c_void_p, c_void_p, c_void_p]),
     'mg_philox4x32_10': (None, [c_void_p, c_void_p, c_void_p]),
+    'mg_vae_sample_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
+    'mg_vae_sample_bwd_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    'mg_kld_standard_normal_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p]),
+    'mg_kld_standard_normal_bwd_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    'mg_gather_concat_latent_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int64, c_int,
+                                            c_void_p]),
+    'mg_gather_concat_latent_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int64, c_int,
+                                             c_void_p]),
+    'mg_rows_add_per_item_f32': (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int64, c_void_p]),
+    'mg_rows_sum_per_item': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p]),
     'mg_calib_mfma_bf16': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'mg_sigmoid_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     'mg_sigmoid_grad_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

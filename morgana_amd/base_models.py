@@ -1,4 +1,4 @@
-"""Mirror of the model contract in ``morgana.base_models``: ``BaseModel`` :9-253 and ``BaseSPSS`` :256-285.
+"""Mirror of the model contract in ``morgana.base_models``: ``BaseModel`` :9-253, ``BaseSPSS`` :256-285 and ``BaseVAE`` :288-381.
 
 A model written against the reference (subclass ``BaseSPSS``; implement ``normaliser_sources`` /
 ``train_data_sources`` / ``predict`` / ``loss``) runs unchanged on top of this class, with ``morgana_amd.utils`` /
@@ -9,7 +9,9 @@ import os
 import torch
 import torch.nn as nn
 
+from . import functional as F_hip
 from . import metrics
+from . import ops
 
 
 class BaseModel(nn.Module):
@@ -108,3 +110,64 @@ class BaseSPSS(BaseModel):
         output_features = self.predict(features)
         loss = self.loss(features, output_features)
         return loss, output_features
+
+
+class BaseVAE(BaseSPSS):
+    r"""Abstract VAE model whose decoder is an SPSS model (base_models.py:288-381).
+
+    Parameters
+    ----------
+    z_dim : int
+        Dimensionality of the latent space.
+    kld_weight : float
+        Weight of the Kullback-Leibler divergence cost (mitigates posterior collapse).
+
+    Subclasses implement ``encode`` (features -> mean, log_variance, each (batch_size, z_dim)) and ``decode`` (latent, features ->
+    output features), and ``loss`` as any ``BaseSPSS``.  ``sample`` runs on the HIP path (csrc/vae.hip): the noise is drawn from the
+    device's step counter, so a captured training step draws new noise on every replay.
+    """
+
+    def __init__(self, z_dim=16, kld_weight=1.):
+        super(BaseVAE, self).__init__()
+        self.z_dim = z_dim
+        self.kld_weight = kld_weight
+
+        self.metrics.add_metrics(
+            'all',
+            kld=metrics.Mean())
+
+    def encode(self, features):
+        raise NotImplementedError("Encoder must be implemented in a subclass.")
+
+    def sample(self, mean, log_variance):
+        r"""One reparameterised sample of the approximate posterior N(mean, exp(log_variance)): mean + exp(0.5 log_variance) eps."""
+        ops._require(mean[..., :0], torch.float32, 'mean')
+        return F_hip.SampleFn.apply(mean, log_variance)
+
+    def decode(self, latent, features):
+        raise NotImplementedError("Decoder must be implemented in a subclass.")
+
+    def forward(self, features):
+        r"""Encodes the input features, samples from the encoding, reconstructs the input, and calculates the loss."""
+        mean, log_variance = self.encode(features)
+        latent_sample = self.sample(mean, log_variance)
+        output_features = self.decode(latent_sample, features)
+
+        output_features['latent'] = latent_sample
+        output_features['mean'] = mean
+        output_features['log_variance'] = log_variance
+
+        loss = self.loss(features, output_features)
+
+        return loss, output_features
+
+    def predict(self, features):
+        r"""Runs the decoder alone: on ``features['latent']`` when given, else on the zero vector (batch_size, z_dim)."""
+        if 'latent' in features:
+            latent = features['latent']
+        else:
+            # batch size and device from the first tensor (the loader's dict also carries the utterance names, a list)
+            feature = next(v for v in features.values() if torch.is_tensor(v))
+            latent = torch.zeros((feature.shape[0], self.z_dim), device=feature.device)
+
+        return self.decode(latent, features)

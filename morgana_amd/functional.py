@@ -228,6 +228,60 @@ class DropoutFn(torch.autograd.Function):
         return ops.dropout(grad.contiguous(), p, seed, site, used), None, None
 
 
+class SampleFn(torch.autograd.Function):
+    """The reparameterised sample of ``BaseVAE.sample`` (reference base_models.py:330-345): z = mean + exp(0.5 log_variance) eps,
+    eps ~ N(0, 1) from Philox words of (torch's seed, ops.SAMPLE_SITE, one draw of the device's step counter, element) - csrc/vae.hip.
+    The counter is the dropout one (ops.dropout_draw): a replayed graph draws new noise.  ``ctx.eps`` is the noise of the call."""
+
+    @staticmethod
+    def forward(ctx, mean, log_variance):
+        seed, used = ops.dropout_seed(), ops.dropout_draw(mean.device)
+        z, eps = ops.vae_sample(mean, log_variance, seed, ops.SAMPLE_SITE, used)
+        ctx.save_for_backward(eps, log_variance)
+        return z
+
+    @staticmethod
+    def backward(ctx, grad):
+        eps, log_variance = ctx.saved_tensors
+        dmean, dlogvar = ops.vae_sample_backward(grad.contiguous(), eps, log_variance)
+        return dmean, dlogvar
+
+
+class KLDFn(torch.autograd.Function):
+    """``losses.KLD_standard_normal`` (reference losses.py:64-67): one deterministic reduction forward, and a backward that reads the
+    upstream gradient on the device (no host read)."""
+
+    @staticmethod
+    def forward(ctx, mean, log_variance):
+        ctx.save_for_backward(mean, log_variance)
+        return ops.kld_standard_normal(mean, log_variance)
+
+    @staticmethod
+    def backward(ctx, grad):
+        mean, log_variance = ctx.saved_tensors
+        return ops.kld_standard_normal_backward(grad, mean, log_variance)
+
+
+class LatentConcatFn(torch.autograd.Function):
+    """Dense fp32 ``cat(x, frame features, z broadcast over the rows of its item)``: the materialised form of a latent-conditioned
+    ``utils.UpsampledConcat`` (one mg_gather_concat_latent_f32 pass).  Only z is differentiable; its gradient is the per-item sum of
+    the latent columns' gradient.  forward(ctx, z, src2d, rows, extra2d, rows_per_item)."""
+
+    @staticmethod
+    def forward(ctx, z, src2d, rows, extra2d, rows_per_item):
+        ctx.col0, ctx.rows_per_item = src2d.shape[1] + (extra2d.shape[1] if extra2d is not None else 0), int(rows_per_item)
+        return ops.gather_concat_latent(src2d, rows, extra2d, z, rows_per_item)
+
+    @staticmethod
+    def backward(ctx, grad):
+        g = grad.contiguous()
+        dz = None
+        if ctx.needs_input_grad[0]:
+            b = g.shape[0] // ctx.rows_per_item
+            dz = ops.rows_sum_per_item(g[:, ctx.col0:], b, ctx.rows_per_item, n=g.shape[1] - ctx.col0)
+        return dz, None, None, None, None
+
+
 class _RunDropout(object):
     """The dropout masks of one LinearStackFn node: ``drops[i]`` = probability behind layer i (0 = none), one draw of the device's
     step counter for the node, site = site0 + i.  ``apply`` is forward and backward alike (the mask multiplies either)."""
@@ -253,6 +307,9 @@ class LinearStackFn(torch.autograd.Function):
     With ``rows`` the input row m is ``x2d[rows[m]]`` (zero row for -1): the frame-rate tensor is never materialised.
     When such a gathered input needs a gradient (packed frames, ``utils.FrameLayout``: the rows are distinct) the input gradient is
     scattered back to the rows of ``x2d``; rows no index points at get zeros.
+    Latent entry (spec[7] = (col0, rows_per_item)): the input's columns col0 : col0 + Z hold the latent z (B, Z) of row m's item
+    m / rows_per_item (ops.gather_concat_latent made the operand), and z follows the parameters as one more differentiable input:
+    its gradient is the per-item row sum of the first layer's pre-activation gradient times W[:, col0 : col0 + Z].
     """
 
     @staticmethod
@@ -273,6 +330,18 @@ class LinearStackFn(torch.autograd.Function):
         n_layers = len(acts)
         weights = [params[2 * i] for i in range(n_layers)]
         biases = [params[2 * i + 1] for i in range(n_layers)]
+        latent = spec[7] if len(spec) > 7 else None
+        if latent is not None:
+            z = params[2 * n_layers]
+            if front is not None or ctx.needs_input_grad[1]:
+                raise ValueError('LinearStackFn: a latent entry goes with a generic layer-1 operand that needs no gradient')
+            if z.dim() != 2 or latent[0] + z.shape[1] > weights[0].shape[1] or z.shape[0] * latent[1] != (rows.numel() if rows is not None
+                                                                                                           else x2d.shape[0]):
+                raise ValueError('LinearStackFn: latent %s does not fit the first layer %s at column %d with %d rows per item'
+                                 % (tuple(z.shape), tuple(weights[0].shape), latent[0], latent[1]))
+            ctx.latent = (latent[0], latent[1], z.shape[0], z.shape[1])
+        else:
+            ctx.latent = None
         # a bf16 input is an already padded layer-1 operand (ops.gather_concat); anything else must be fp32
         pre_cast = precision == 'bf16' and x2d.dtype == torch.bfloat16
         x2d = ops._require(x2d, torch.bfloat16 if pre_cast else torch.float32, 'input')
@@ -393,6 +462,15 @@ class LinearStackFn(torch.autograd.Function):
             # sigmoid gradient the dgrad kernels fuse, which reads the unmasked activation)
             return g_ if drop is None else drop.apply(g_, i, inplace=True)
 
+        latent = ctx.latent
+        dz = None
+
+        def latent_grad(g0, bf16_cols=None, h=None):
+            # dz = (per-item row sums of the first layer's pre-activation gradient) . W_z
+            col0, per_item, n_items, zdim = latent
+            sums = ops.rows_sum_per_item(g0, n_items, per_item, n=ctx.dims[0][0], h=h)
+            return ops.linear_dgrad_f32(sums, weights[0][:, col0:col0 + zdim].contiguous(), None)
+
         g = grad_out.contiguous()
         if drop is not None and drop.active(n_layers - 1):
             g = drop.apply(g, n_layers - 1)
@@ -403,6 +481,8 @@ class LinearStackFn(torch.autograd.Function):
             for i in range(n_layers - 1, -1, -1):
                 n, k = ctx.dims[i]
                 a_in, r = (x_in, rows) if i == 0 else (masked_input(i), None)
+                if i == 0 and latent is not None:
+                    dz = latent_grad(g)
                 dw, db = ops.linear_wgrad_f32(g, a_in, r, n, k, want_bias=ctx.has_bias[i])
                 grads[2 * i], grads[2 * i + 1] = dw, db
                 if i > 0:
@@ -421,6 +501,8 @@ class LinearStackFn(torch.autograd.Function):
             for i in range(n_layers - 1, -1, -1):
                 n, k = ctx.dims[i]
                 a_in, r = (x_in, rows) if i == 0 else (masked_input(i), None)
+                if i == 0 and latent is not None:
+                    dz = latent_grad(g, h=sig)         # a sigmoid factor still owed to g rides in the row sums
                 if not split[i]:                       # a narrow layer: exact fp32 products (see _x3_layer)
                     grads[2 * i], grads[2 * i + 1] = ops.linear_wgrad_f32(g, a_in, r, n, k, want_bias=ctx.has_bias[i])
                     if i > 0:
@@ -487,6 +569,8 @@ class LinearStackFn(torch.autograd.Function):
                         ops.feat_wgrad_reduce(slabs, feat.shape[1], sums.shape[1], n, dw, k_lab)
                         grads[0], grads[1] = dw, db
                     continue
+                if i == 0 and latent is not None:
+                    dz = latent_grad(g)                # g: the padded bf16 gradient, its sigmoid factor applied by the dgrad before
                 if beside and (i > 0 or need_x):
                     # the weight gradient feeds only the update: beside the dgrad chain (the last layer of the pass has no chain left
                     # on this node, its weight gradient stays in line)
@@ -509,7 +593,7 @@ class LinearStackFn(torch.autograd.Function):
         if need_x and scatter_to is not None:
             # the input rows were gathered (distinct rows): their gradients go back where they came from, all other rows get zeros
             grad_x = ops.scatter_rows(grad_x, scatter_to, ctx.n_src)
-        return (None, grad_x, None) + tuple(grads)
+        return (None, grad_x, None) + tuple(grads) + ((dz,) if latent is not None else ())
 
 
 class RepeatTableRowsFn(torch.autograd.Function):

@@ -1,4 +1,5 @@
-"""Mirror of ``morgana.losses`` for the hot path.  Reference: morgana/losses.py:9-51 (``sequence_loss`` / ``mse``)."""
+"""Mirror of ``morgana.losses`` for the hot path.  Reference: morgana/losses.py:9-51 (``sequence_loss`` / ``mse``) and :64-67
+(``KLD_standard_normal``)."""
 import torch
 
 from . import functional as F_hip
@@ -41,3 +42,10 @@ def multi_stream(predictions, targets, kinds, seq_len=None, want_prob=False):
         seq_len = seq_len.long()
     targets = [y if y.dtype == torch.float32 else y.float() for y in targets]
     return F_hip.StreamLossFn.apply(predictions, seq_len, tuple(kinds), want_prob, *targets)
+
+
+def KLD_standard_normal(mean, log_variance):
+    r"""KL divergence of N(``mean``, exp(``log_variance``)) from N(0, I): ``-0.5 sum_z (1 + log_variance - mean^2 - exp(log_variance))``
+    averaged over the leading dims (reference losses.py:64-67).  One HIP reduction with a fixed order and its backward
+    (csrc/vae.hip); column views of one encoder output are read in place."""
+    return F_hip.KLDFn.apply(mean, log_variance)

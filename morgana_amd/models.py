@@ -7,6 +7,8 @@
                  GRU-64 x 3 / Linear-64 / sigmoid / Linear-3 (lf0 + deltas).
 * ``LSTMAcousticModel`` - the reference's shipped acoustic model, models/RNN_SPSS.py:20-139: 609-dim input (labels +
                  counters), Linear-512 / sigmoid / 8 x LSTM-512 / Linear-256 / sigmoid / Linear-199, four output streams.
+* ``VAEF0Model`` - a ``BaseVAE`` (base_models.py:288-381) built from ``GRUF0Model``: a GRU-64 encoder over the lf0 deltas gives an
+                 utterance-level latent that is appended to every frame of the decoder's input.
 ``SequentialWithRecurrent`` returns ``(output, hiddens)`` (utils.py:418), so all of them unpack it.
 """
 import os
@@ -19,7 +21,8 @@ from . import losses
 from . import metrics
 from . import utils
 from . import viz
-from .base_models import BaseSPSS
+from . import functional as F_hip
+from .base_models import BaseSPSS, BaseVAE
 
 
 def _has_delta_params(normalisers, name):
@@ -377,3 +380,52 @@ class GRUF0Model(StreamModel):
         layers = _gru_f0_stack(input_dim, output_dim, dropout_prob, precision)
         streams = [Stream('lf0', output_dim, 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'))]
         super(GRUF0Model, self).__init__(layers, streams, fused_upsample=fused_upsample, fused_loss=False, generate=generate)
+
+
+class VAEF0Model(StreamModel, BaseVAE):
+    """``GRUF0Model`` as the decoder of a VAE (``BaseVAE``): the encoder, a GRU over ``normalised_lf0_deltas`` (valid frames only), gives
+    mean | log_variance of an utterance-level latent through one Linear on its last state; the latent is sampled on the HIP path and
+    appended to every frame of the decoder's input (``utils.concat_frame_features(..., latent)``: one gather pass, its gradient summed
+    per utterance by the first layer's run).  Loss = the lf0 stream's masked MSE + ``kld_weight`` * KLD; ``kld`` is a metric of every
+    collection.  State_dict keys: the decoder's ``layers.*`` as ``GRUF0Model`` (input ``input_dim + z_dim`` wide),
+    ``encoder.0.layer.*`` and ``encoder_projection.0.*``."""
+
+    def __init__(self, z_dim=16, kld_weight=1., encoder_hidden=64, dropout_prob=0., input_dim=600 + 9, output_dim=1 * 3, precision=None,
+                 fused_upsample=True, generate=True):
+        self.input_dim, self.output_dim = input_dim, output_dim
+        layers = _gru_f0_stack(input_dim + z_dim, output_dim, dropout_prob, precision)
+        streams = [Stream('lf0', output_dim, 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'))]
+        super(VAEF0Model, self).__init__(layers, streams, fused_upsample=fused_upsample, fused_loss=False, generate=generate)
+        self.z_dim, self.kld_weight = z_dim, kld_weight
+        # the encoder's parameters go first in parameters() (and so in the optimiser's flat buffer): behind the decoder's 3-wide output
+        # bias they would sit at offsets that are not 16-byte aligned, and the one-launch GRU-64 forward needs an aligned w_hh (with a
+        # misaligned one the recurrence falls back to a launch per frame: 5.6 ms of a 64 x 1000 step instead of 0.8)
+        layers = self._modules.pop('layers')
+        self.encoder = utils.SequentialWithRecurrent(
+            utils.RecurrentCuDNNWrapper(nn.GRU(output_dim, encoder_hidden, batch_first=True), precision=precision), precision=precision)
+        self.encoder_projection = utils.SequentialWithRecurrent(nn.Linear(encoder_hidden, 2 * z_dim), precision=precision)
+        self.layers = layers
+
+    def encode(self, features):
+        deltas = features['normalised_lf0_deltas']
+        _, hiddens = self.encoder(deltas, seq_len=features['n_frames'], max_len=deltas.shape[1])
+        statistics, _ = self.encoder_projection(hiddens[0][0])
+        return statistics[:, :self.z_dim], statistics[:, self.z_dim:]
+
+    def decode(self, latent, features):
+        norm_counters = features['normalised_counters']
+        norm_lab_at_frame_rate = utils.upsample_to_repetitions(features['normalised_lab'], features['dur'],
+                                                               max_len=norm_counters.shape[1], fused=self.fused_upsample,
+                                                               phone_rate=self.phone_rate)
+        model_inputs = utils.concat_frame_features(norm_lab_at_frame_rate, norm_counters, latent)
+        prediction, _ = self.layers(model_inputs, seq_len=features['n_frames'], max_len=norm_counters.shape[1])
+        return self._with_trajectories(self._split(prediction), features['n_frames'])
+
+    forward = BaseVAE.forward
+    predict = BaseVAE.predict
+
+    def loss(self, features, output_features):
+        kld = losses.KLD_standard_normal(output_features['mean'], output_features['log_variance'])
+        if self.mode in self.metrics.collections:
+            self.metrics.accumulate(self.mode, kld=kld)
+        return StreamModel.loss(self, features, output_features) + self.kld_weight * kld

@@ -752,6 +752,118 @@ def dropout(x, p, seed, site, used, out=None):
     return y
 
 
+# ------------------------------------------------------------------------------------------------ latent-conditioned models (VAE)
+SAMPLE_SITE = 0x56414500     # the Philox site of the VAE sampler's noise (dropout masks use the module index of their layer)
+
+
+def _latent_rows(t, name):
+    """(rows, Z) f32 view of ``t`` with unit column stride (a column view of a wider row stays a view) and its row stride."""
+    _require(t[..., :0], torch.float32, name)                  # type and device only: the view itself may be strided
+    t2 = t.reshape(-1, t.shape[-1]) if t.dim() != 2 else t
+    if t2.stride(-1) != 1 or (t2.shape[0] > 1 and t2.stride(0) < t2.shape[1]):
+        t2 = t2.contiguous()
+    return t2, (t2.stride(0) if t2.shape[0] > 1 else t2.shape[1])
+
+
+def vae_sample(mean, logvar, seed, site, used):
+    """z = mean + exp(0.5 logvar) eps with eps ~ N(0, 1) drawn from (seed, site, used[0], element) - mg_vae_sample_f32.  mean, logvar:
+    (..., Z) f32, column views allowed.  Returns (z, eps), both contiguous with mean's shape."""
+    if tuple(mean.shape) != tuple(logvar.shape):
+        raise ValueError('vae_sample: mean %s and log_variance %s differ in shape' % (tuple(mean.shape), tuple(logvar.shape)))
+    m2, ldm = _latent_rows(mean, 'mean')
+    v2, ldv = _latent_rows(logvar, 'log_variance')
+    z = torch.empty(tuple(mean.shape), dtype=torch.float32, device=mean.device)
+    eps = torch.empty_like(z)
+    _lib.check(_lib.load().mg_vae_sample_f32(_p(m2), ldm, _p(v2), ldv, m2.shape[0], m2.shape[1], int(seed), int(site) & 0xFFFFFFFF, _p(used),
+                                             _p(z), _p(eps), _stream()), 'mg_vae_sample_f32')
+    return z, eps
+
+
+def vae_sample_backward(dz, eps, logvar):
+    """(dmean, dlogvar) of vae_sample: dz and 0.5 dz eps exp(0.5 logvar) - mg_vae_sample_bwd_f32."""
+    dz = _require(dz, torch.float32, 'gradient')
+    v2, ldv = _latent_rows(logvar, 'log_variance')
+    dmean = torch.empty_like(eps)
+    dlogvar = torch.empty_like(eps)
+    _lib.check(_lib.load().mg_vae_sample_bwd_f32(_p(dz), _p(eps), _p(v2), ldv, v2.shape[0], v2.shape[1], _p(dmean), _p(dlogvar), _stream()),
+               'mg_vae_sample_bwd_f32')
+    return dmean, dlogvar
+
+
+def kld_standard_normal(mean, logvar):
+    """mean over the leading dims of -0.5 sum_z (1 + logvar - mean^2 - exp(logvar)): a 0-dim f32 device tensor (mg_kld_standard_normal_f32)."""
+    if tuple(mean.shape) != tuple(logvar.shape):
+        raise ValueError('KLD_standard_normal: mean %s and log_variance %s differ in shape' % (tuple(mean.shape), tuple(logvar.shape)))
+    m2, ldm = _latent_rows(mean, 'mean')
+    v2, ldv = _latent_rows(logvar, 'log_variance')
+    out = torch.empty((), dtype=torch.float32, device=mean.device)
+    _lib.check(_lib.load().mg_kld_standard_normal_f32(_p(m2), ldm, _p(v2), ldv, m2.shape[0], m2.shape[1], _p(out), _stream()),
+               'mg_kld_standard_normal_f32')
+    return out
+
+
+def kld_standard_normal_backward(grad, mean, logvar):
+    """(dmean, dlogvar) = (g mean / rows, g 0.5 (exp(logvar) - 1) / rows) with g = grad (a 1-element device tensor, read on the device)."""
+    grad = _require(grad.reshape(1), torch.float32, 'gradient')
+    m2, ldm = _latent_rows(mean, 'mean')
+    v2, ldv = _latent_rows(logvar, 'log_variance')
+    dmean = torch.empty(tuple(mean.shape), dtype=torch.float32, device=mean.device)
+    dlogvar = torch.empty_like(dmean)
+    _lib.check(_lib.load().mg_kld_standard_normal_bwd_f32(_p(grad), _p(m2), ldm, _p(v2), ldv, m2.shape[0], m2.shape[1], _p(dmean), _p(dlogvar),
+                                                          _stream()), 'mg_kld_standard_normal_bwd_f32')
+    return dmean, dlogvar
+
+
+def gather_concat_latent(src2d, rows, extra2d, z2d, rows_per_item, out_bf16=False):
+    """[src2d[rows] | extra2d | z2d[m / rows_per_item]] per row (mg_gather_concat_latent_*): f32 (M, F+C+Z), or bf16 (M, pad_ld(F+C+Z))
+    zero padded.  rows None: src2d is already one row per output row; extra2d None: no frame features (C = 0)."""
+    lib = _lib.load()
+    src2d = _require(src2d, torch.float32, 'src')
+    z2d = _require(z2d, torch.float32, 'latent')
+    rows = _require(rows, torch.int32, 'rows') if rows is not None else None
+    extra2d = _require(extra2d, torch.float32, 'extra') if extra2d is not None else None
+    m = rows.numel() if rows is not None else src2d.shape[0]
+    f, c, zd = src2d.shape[1], (extra2d.shape[1] if extra2d is not None else 0), z2d.shape[1]
+    if extra2d is not None and extra2d.shape[0] != m:
+        raise ValueError('gather_concat_latent: %d rows but %d rows of frame-level features' % (m, extra2d.shape[0]))
+    if z2d.shape[0] * int(rows_per_item) != m:
+        raise ValueError('gather_concat_latent: %d latent rows x %d rows per item != %d rows' % (z2d.shape[0], int(rows_per_item), m))
+    if out_bf16:
+        ldo = pad_ld(f + c + zd)
+        out = torch.empty((m, ldo), dtype=torch.bfloat16, device=src2d.device)
+        _lib.check(lib.mg_gather_concat_latent_bf16(_p(src2d), _p(rows), _p(extra2d), _p(z2d), _p(out), m, f, c, zd, int(rows_per_item), ldo,
+                                                    _stream()), 'mg_gather_concat_latent_bf16')
+    else:
+        out = torch.empty((m, f + c + zd), dtype=torch.float32, device=src2d.device)
+        _lib.check(lib.mg_gather_concat_latent_f32(_p(src2d), _p(rows), _p(extra2d), _p(z2d), _p(out), m, f, c, zd, int(rows_per_item), f + c + zd,
+                                                   _stream()), 'mg_gather_concat_latent_f32')
+    return out
+
+
+def rows_add_per_item(p, u, rows, rows_per_item):
+    """In place: p[r, :N] += u[r / rows_per_item, :N] for r < rows (mg_rows_add_per_item_f32); p, u f32 with unit column stride."""
+    if p.dtype != torch.float32 or u.dtype != torch.float32 or p.stride(-1) != 1 or u.stride(-1) != 1 or not p.is_cuda or not u.is_cuda:
+        raise TypeError('rows_add_per_item: f32 device tensors with unit column stride are required')
+    n = u.shape[1]
+    _lib.check(_lib.load().mg_rows_add_per_item_f32(_p(p), p.stride(0), int(rows), n, _p(u), u.stride(0), int(rows_per_item), _stream()),
+               'mg_rows_add_per_item_f32')
+    return p
+
+
+def rows_sum_per_item(g, n_items, rows_per_item, n=None, h=None):
+    """(n_items, n) f32: the sum of g's rows of every item (item b owns rows b rows_per_item ...), times h (1 - h) when h is given
+    (mg_rows_sum_per_item).  g: f32 or bf16 (padded columns past n are not read), unit column stride; h: f32 like g."""
+    if g.dtype not in (torch.float32, torch.bfloat16) or g.stride(-1) != 1 or not g.is_cuda:
+        raise TypeError('rows_sum_per_item: an f32 or bf16 device tensor with unit column stride is required')
+    n = g.shape[1] if n is None else int(n)
+    if h is not None:
+        h = _require(h, torch.float32, 'sigmoid output')
+    s = torch.empty((int(n_items), n), dtype=torch.float32, device=g.device)
+    _lib.check(_lib.load().mg_rows_sum_per_item(_p(g), g.stride(0), int(g.dtype == torch.bfloat16), _p(h), h.stride(0) if h is not None else 0,
+                                                int(n_items), int(rows_per_item), n, _p(s), n, _stream()), 'mg_rows_sum_per_item')
+    return s
+
+
 # ----------------------------------------------------------------------------------------- precision 'bf16x3' (split-bf16 operands)
 CAPTURE_EPOCH = [0]      # bumped by graphs.GraphedTrainStep at the start of every capture (see x3_weight_operands)
 

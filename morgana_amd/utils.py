@@ -218,31 +218,54 @@ class FrameLayout(object):
 class UpsampledConcat(object):
     """Lazy ``torch.cat((upsample_to_repetitions(sequence_feature, repeats), frame_feature), dim=-1)`` - the model input of
     models/RNN_SPSS.py:76-81 and models/f0_test_model.py:78-79.  ``SequentialWithRecurrent`` turns it into the first Linear's
-    operand with one gather+concat pass (bf16 and padded in bf16 mode); ``materialise()`` gives the dense fp32 tensor."""
+    operand with one gather+concat pass (bf16 and padded in bf16 mode); ``materialise()`` gives the dense fp32 tensor.
+    ``latent`` (B, Z) (a VAE's sample, ``base_models.BaseVAE``): its row b is appended to every frame of item b, behind the frame
+    features - the only part of the input that may need a gradient (``functional.LinearStackFn``'s latent entry)."""
 
-    def __init__(self, upsampled, frame_feature):
+    def __init__(self, upsampled, frame_feature, latent=None):
         if frame_feature.shape[:2] != tuple(upsampled.shape[:2]):
             raise RuntimeError('Sizes of tensors must match except in dimension 2. Expected %s but got %s'
                                % (tuple(upsampled.shape[:2]), tuple(frame_feature.shape[:2])))
+        if latent is not None and (latent.dim() != 2 or latent.shape[0] != upsampled.shape[0]):
+            raise RuntimeError('latent must be (batch_size, z_dim) = (%d, .), got %s' % (upsampled.shape[0], tuple(latent.shape)))
         self.upsampled = upsampled
         self.frame_feature = frame_feature
-        self.shape = tuple(upsampled.shape[:2]) + (upsampled.shape[2] + frame_feature.shape[2],)
+        self.latent = latent
+        z_dim = latent.shape[1] if latent is not None else 0
+        self.shape = tuple(upsampled.shape[:2]) + (upsampled.shape[2] + frame_feature.shape[2] + z_dim,)
+
+    def latent_entry(self):
+        """(first latent column, rows per item) of the operand: LinearStackFn's latent entry."""
+        return (self.upsampled.shape[2] + self.frame_feature.shape[2], self.shape[1])
 
     def operand(self, out_bf16):
         up = self.upsampled
-        return ops.gather_concat(up.source.reshape(-1, up.source.shape[-1]), up.rows.reshape(-1),
-                                 self.frame_feature.reshape(-1, self.frame_feature.shape[-1]), out_bf16=out_bf16)
+        src, rows, extra = up.source.reshape(-1, up.source.shape[-1]), up.rows.reshape(-1), self.frame_feature.reshape(-1, self.frame_feature.shape[-1])
+        if self.latent is not None:
+            return ops.gather_concat_latent(src, rows, extra, self.latent.detach(), self.shape[1], out_bf16=out_bf16)
+        return ops.gather_concat(src, rows, extra, out_bf16=out_bf16)
 
     def materialise(self):
+        if self.latent is not None:
+            up = self.upsampled
+            return F_hip.LatentConcatFn.apply(self.latent, up.source.reshape(-1, up.source.shape[-1]), up.rows.reshape(-1),
+                                              self.frame_feature.reshape(-1, self.frame_feature.shape[-1]), self.shape[1]).view(self.shape)
         return self.operand(False).view(self.shape)
 
 
-def concat_frame_features(upsampled, frame_feature):
-    """``torch.cat((upsampled, frame_feature), dim=-1)`` that keeps a fused upsample lazy (see ``UpsampledConcat``)."""
+def concat_frame_features(upsampled, frame_feature, latent=None):
+    """``torch.cat((upsampled, frame_feature), dim=-1)`` that keeps a fused upsample lazy (see ``UpsampledConcat``).  ``latent`` (not in
+    the reference; optional): a (B, Z) latent appended to every frame of its item - the decoder input of a ``BaseVAE``."""
     if isinstance(upsampled, UpsampledSequence) and not frame_feature.requires_grad:
-        return UpsampledConcat(upsampled, frame_feature)
+        return UpsampledConcat(upsampled, frame_feature, latent)
     if isinstance(upsampled, UpsampledSequence):
         upsampled = upsampled.materialise()
+    if latent is not None:
+        b, t = upsampled.shape[0], upsampled.shape[1]
+        if frame_feature.requires_grad or upsampled.requires_grad:
+            raise RuntimeError('concat_frame_features: a latent goes with inputs that need no gradient')
+        src, extra = upsampled.reshape(b * t, -1).contiguous(), frame_feature.reshape(b * t, -1).contiguous()
+        return F_hip.LatentConcatFn.apply(latent, src, None, extra, t).view(b, t, -1)
     return torch.cat((upsampled, frame_feature), dim=-1)
 
 
@@ -838,7 +861,7 @@ class SequentialWithRecurrent(nn.Sequential):
                 if isinstance(input, UpsampledSequence):
                     lead, x2d, rows = input.shape[:2], input.source.reshape(-1, input.source.shape[-1]), \
                         input.rows.reshape(-1)
-                elif (isinstance(input, UpsampledConcat) and precision == 'bf16' and CONCAT_PHONE_RATE
+                elif (isinstance(input, UpsampledConcat) and precision == 'bf16' and CONCAT_PHONE_RATE and input.latent is None
                       and input.frame_feature.shape[-1] <= 16
                       and ops.phone_rate_gru_ok(input.upsampled.source.shape[0] * input.upsampled.source.shape[1],
                                                 input.upsampled.rows.numel(), 8, input.upsampled.phone_rate)):
@@ -853,6 +876,16 @@ class SequentialWithRecurrent(nn.Sequential):
                     spec = (tuple(act for _, act in run), precision, ops.PHONE_RATE_EXTRA, False, run.drop_spec(), None,
                             (rows_mapped.reshape(-1), seg, feat.contiguous()))
                     out = F_hip.LinearStackFn.apply(spec, up.source.reshape(-1, up.source.shape[-1]), None, *params)
+                    input = out.view(*input.shape[:2], out.shape[-1])
+                    i = end
+                    continue
+                elif isinstance(input, UpsampledConcat) and input.latent is not None:
+                    # [labels | counters | z of the item] in one gather pass; z's gradient comes from the run's latent entry
+                    params = []
+                    for lin, _ in run:
+                        params += [lin.weight, lin.bias]
+                    spec = (tuple(act for _, act in run), precision, 0, False, run.drop_spec(), None, None, input.latent_entry())
+                    out = F_hip.LinearStackFn.apply(spec, input.operand(precision == 'bf16'), None, *params, input.latent)
                     input = out.view(*input.shape[:2], out.shape[-1])
                     i = end
                     continue
