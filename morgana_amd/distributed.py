@@ -16,8 +16,9 @@ def env_world():
     return int(os.environ.get('RANK', 0)), int(os.environ.get('LOCAL_RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
 
 
-def init(backend=None):
-    """Initialise the default process group from torchrun's environment; returns (rank, local_rank, world)."""
+def init(backend=None, init_method=None):
+    """Initialise the default process group from torchrun's environment; returns (rank, local_rank, world).  ``init_method``: where
+    the ranks meet (torch.distributed's URL, e.g. a ``file://`` path every rank sees); None = MASTER_ADDR / MASTER_PORT."""
     rank, local_rank, world = env_world()
     if world > 1 and not dist.is_initialized():
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
@@ -27,7 +28,7 @@ def init(backend=None):
             backend = os.environ.get('MG_DIST_BACKEND') or ('nccl' if torch.cuda.is_available() else 'gloo')
         if backend == 'nccl':
             torch.cuda.set_device(local_rank)
-        dist.init_process_group(backend=backend, rank=rank, world_size=world)
+        dist.init_process_group(backend=backend, rank=rank, world_size=world, init_method=init_method)
     return rank, local_rank, world
 
 

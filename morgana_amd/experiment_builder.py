@@ -126,7 +126,7 @@ class ExperimentBuilder(object):
                     loss_log = torch.zeros(max(n_batches, 1), dtype=torch.float32, device=self.device)
                 slot = loss_log[i] if i < loss_log.numel() else None
                 batch_loss, output_features = self._graph_cache.step(features, clone_loss=False, loss_slot=slot)
-                filed = slot is not None and self._graph_cache._pending_loss is not None      # rides in the next batch's load launch
+                filed = slot is not None          # step files it: a replayed step's in the next batch's load launch, an eager one at once
                 self._graph_cache.prefetch(ahead)                                # (MORGANA_GRAPH_PREFETCH: measured, off)
             else:
                 optimizer.zero_grad()                                            # :468

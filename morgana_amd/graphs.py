@@ -23,7 +23,7 @@ import warnings
 
 import torch
 
-from . import functional
+from . import _lib, functional
 
 
 _CAPTURE_VERDICT = {}
@@ -176,6 +176,7 @@ class GraphedTrainStep(object):
             self._capture(mode)
         except Exception:
             _leave_failed_capture(entry_stream)        # so that the caller's eager fallback finds a usable stream
+            _forget_failed_capture(model, optimizer)
             raise
         # the bf16 operand copies the captured update keeps current: what a replay re-stamps (optim.Adam.note_replayed)
         self._refreshed = self.optimizer.refreshed_shadows() if hasattr(self.optimizer, 'refreshed_shadows') else []
@@ -274,6 +275,18 @@ class GraphedTrainStep(object):
         return self.loss
 
 
+def _forget_failed_capture(model, optimizer):
+    """A capture that failed has RECORDED launches that never ran, and the host bookkeeping of everything it recorded says they did:
+    a bf16 operand copy whose re-cast was recorded (ops.param_shadows / pair_shadows, or the captured update's re-casts) is stamped
+    current while it still holds the old weight, and the optimiser holds slabs and a deferred tail nobody computed.  Every operand copy
+    of the model is marked stale (its next reader casts it again: one batched launch, on a path that is taken once per signature) rather
+    than restored from a snapshot - a snapshot would have to cover every stamp any layer may set, this covers them by construction."""
+    from . import ops
+    ops.invalidate_operand_copies(model.parameters())
+    if hasattr(optimizer, 'forget_capture'):
+        optimizer.forget_capture()
+
+
 def early_exchange_is_safe(optimizer, stack_params, group=0):
     """May the step all-reduce ``flat['grad'][bucket_split:]`` the moment a stack reports that everything but its first layer's
     gradient is final?  Only when the stack's parameter list is exactly the optimiser's flat parameter list (same objects, same
@@ -283,6 +296,18 @@ def early_exchange_is_safe(optimizer, stack_params, group=0):
         return False
     own = flat['params']
     return len(stack_params) == len(own) and all(a is b for a, b in zip(stack_params, own))
+
+
+def _capture_refusal(exc):
+    """Did a capture fail because the step cannot be captured (a host read of a device value, a stream-capture status from HIP) -
+    rather than because something in it is wrong?  A bad kernel argument (ValueError: the library's MG_EINVAL), a launch error of a
+    kernel that is not a capture status (MorganaHipError) and a failed allocation are faults of the step: raised, not turned into
+    ordinary launches.  (Every HIP stream-capture status, hipErrorStreamCapture* and hipErrorCapturedEvent, says "captur" in its text.)"""
+    if isinstance(exc, (ValueError, torch.cuda.OutOfMemoryError)):
+        return False
+    if isinstance(exc, _lib.MorganaHipError):
+        return 'captur' in str(exc)
+    return True
 
 
 # Load the next batch into a second captured step's buffers on a side stream while the current step runs (GraphedStepCache.prefetch).
@@ -440,10 +465,18 @@ class GraphedStepCache(object):
         try:
             return GraphedTrainStep(self.model, self.optimizer, features, warmup=0, steps_per_replay=k)
         except Exception as exc:                          # noqa: BLE001 - whatever the capture tripped over, the eager loop does not
+            if not _capture_refusal(exc):
+                raise                                     # a fault of the step itself: the eager loop would trip over it too
             self._no_capture.add(key)
             warnings.warn('GraphedStepCache: this step cannot be captured into a HIP graph (%s) - batches of this shape run as ordinary '
                           'launches' % (str(exc).splitlines()[0][:160] if str(exc) else type(exc).__name__))
             return None
+
+    def _eager_filed(self, features, key, loss_slot):
+        loss, output = self._eager(features, key)         # (files a pending loss first: the slots are written in step order)
+        if loss_slot is not None:
+            loss_slot.copy_(loss.detach().reshape(loss_slot.shape))
+        return loss, output
 
     def _eager(self, features, key):
         self._before_replay = None                        # an eager step: a batch loaded ahead waits for all of it
@@ -474,7 +507,8 @@ class GraphedStepCache(object):
         """zero_grad, forward, backward, optimizer step on ``features``; returns (loss, output_features).  ``clone_loss`` False: the
         replayed graph's own loss tensor is handed out - valid until the next replay of that graph (a caller that files it away at once).
         ``loss_slot``: a 0-d device tensor that receives the step's loss - for a replayed step LATER, in the launch that loads the next
-        batch (or in ``flush``): a small copy of its own costs a launch and its gap, 14 us of a 0.1 ms step."""
+        batch (or in ``flush``): a small copy of its own costs a launch and its gap, 14 us of a 0.1 ms step; for a step run as ordinary
+        launches (first sight, a capture that failed, no graph left in the budget) at once."""
         key = self.signature(features)
         pair = self._steps.get(key)
         graphed = None
@@ -491,7 +525,7 @@ class GraphedStepCache(object):
             static = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in features.items()}
             graphed = self._try_capture(key, static, 1)
             if graphed is None:
-                return self._eager(features, key)         # (capture runs nothing: the step has not been taken yet)
+                return self._eager_filed(features, key, loss_slot)        # (capture runs nothing: the step has not been taken yet)
             self._steps.setdefault(key, []).append(graphed)
             self._turn[key] = 0 if len(self._steps[key]) < 2 else 1
         elif graphed is None and pair:
@@ -516,4 +550,4 @@ class GraphedStepCache(object):
             if loss_slot is not None:
                 self._pending_loss = (loss_slot, loss.detach().reshape(loss_slot.shape))
             return (loss.clone() if clone_loss else loss), graphed.output      # the loss buffer is rewritten by that graph's next replay
-        return self._eager(features, key)
+        return self._eager_filed(features, key, loss_slot)

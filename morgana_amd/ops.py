@@ -690,6 +690,17 @@ def param_shadows(weights, want_t=()):
     return [w._mg_shadow['plain'] for w in weights], [w._mg_shadow['t'] if i in want_t else None for i, w in enumerate(weights)]
 
 
+def invalidate_operand_copies(params):
+    """Mark every operand copy of ``params`` stale - bf16 copies (param_shadows), pair planes (pair_shadows), 'bf16x3' splits
+    (x3_weight_operands): the next reader casts or splits it again.  For a HIP-graph capture that failed
+    (graphs.GraphedTrainStep): the casts it recorded never ran, the stamps it set say they did."""
+    for p in params:
+        for attr in ('_mg_shadow', '_mg_pair', '_mg_x3'):
+            sh = getattr(p, attr, None)
+            if sh is not None:
+                sh['version'] = None
+
+
 def refresh_shadows(params):
     """Re-cast the EXISTING bf16 operand copies of ``params`` (plain, and transposed where one is allocated) from their fp32 weights:
     one batched launch per MG_CAST_MAX parameters on the current stream, no allocation, no stamp (the caller stamps).  Used by

@@ -240,6 +240,17 @@ class Adam(torch.optim.Optimizer):
         # what this update refreshed, by identity of the copies: a graph that captured it re-stamps exactly these after a replay
         flat['refreshed'] = [(sh[5], sh[3], sh[4]) for sh in every if sh not in stale_pairs]
 
+    def forget_capture(self):
+        """A capture of the step failed (graphs.GraphedTrainStep): what it registered here was recorded, never run - slabs and a
+        deferred tail nobody computed, an update that "zeroed" the gradient and "refreshed" operand copies.  Drop them; the next
+        ``zero_grad`` clears the gradient itself.  (The copies' stamps are the caller's: ops.invalidate_operand_copies.)"""
+        for flat in self._flat:
+            if flat is not None:
+                flat['pending'] = []
+                flat['tail'] = None
+                flat['clean'] = False
+                flat['refreshed'] = []
+
     def refreshed_shadows(self):
         """[(parameter, plain copy, transposed copy or None)] the last update kernel launch (or its capture) kept current."""
         out = []

@@ -12,7 +12,7 @@ import torch.distributed as dist
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-from morgana_amd import data, distributed, graphs, models, optim, synthetic  # noqa: E402
+from morgana_amd import data, distributed, graphs, models, ops, optim, synthetic  # noqa: E402
 from morgana_amd import functional as F_hip  # noqa: E402
 
 
@@ -43,23 +43,34 @@ def run_steps(feats_np, n_steps, precision, form, dev, which='f0'):
     feats = data.to_device(feats_np, dev, bf16_tables=model.bf16_table_features())
     opt = optim.Adam(model.parameters(), lr=0.01, fused_loop=True)
 
+    # The recurrent models' persistent recurrences need every workgroup of their launch resident at once; two ranks on ONE GPU that
+    # launch theirs together can each hold part of the device and time out waiting for the rest (mg_gru_persist_status 8: results
+    # invalid).  Their ranks take turns with forward and backward; the exchange and the update stay as the product runs them.
+    turns = which != 'f0' and dist.is_initialized() and dist.get_world_size() > 1
+
     def eager_step():
         opt.zero_grad()
-        loss, _ = model(feats)
-        F_hip.backward(loss)
+        for turn in range(dist.get_world_size() if turns else 1):
+            if not turns or turn == dist.get_rank():
+                loss, _ = model(feats)
+                F_hip.backward(loss)
+            if turns:
+                torch.cuda.synchronize()
+                dist.barrier()
         opt.step()
         return loss
 
     step = graphs.GraphedTrainStep(model, opt, feats, warmup=1) if form == 'graph' else eager_step
     losses = [float(distributed.mean_scalar(step().detach().clone()).item()) for _ in range(n_steps)]
     torch.cuda.synchronize()
+    ops.check_persistent_status()                  # a persistent recurrence that gave up waiting left invalid results: say so here
     return opt.flat_buffers()['param'].clone(), losses, getattr(step, 'exchange_mode', 'eager loop')
 
 
 def main():
     out_path, n_steps, precision, form, ragged = sys.argv[1], int(sys.argv[2]), sys.argv[3], sys.argv[4], sys.argv[5] == '1'
     which = sys.argv[6] if len(sys.argv) > 6 else 'f0'
-    rank, _, world = distributed.init(backend='gloo')
+    rank, _, world = distributed.init(backend='gloo', init_method=os.environ.get('MG_TEST_RENDEZVOUS'))
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(dev)
     shard = synthetic.shard_batch(global_batch(which, ragged), rank, world)

@@ -17,7 +17,7 @@ import helpers  # noqa: E402
 
 def main():
     out_path, n_steps, ragged = sys.argv[1], int(sys.argv[2]), sys.argv[3] == 'ragged'
-    rank, _, world = distributed.init(backend='gloo')
+    rank, _, world = distributed.init(backend='gloo', init_method=os.environ.get('MG_TEST_RENDEZVOUS'))
     torch.set_num_threads(1)
     model = helpers.init_small(helpers.CpuF0Model(dims=(24, 16, 8, 1)), seed=1)
     distributed.broadcast_parameters(model)

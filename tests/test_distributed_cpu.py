@@ -1,7 +1,6 @@
 """world_size-2 gloo tests on CPU of the data-parallel path: contiguous utterance shards + ONE flat all-reduce per step
 must reproduce the single-process run on the global batch."""
 import os
-import socket
 import subprocess
 import sys
 
@@ -17,12 +16,10 @@ import helpers
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
+def _rendezvous(tmp_path):
+    """A file the ranks meet at (torch.distributed ``file://``): nothing another process can take between choosing it and the ranks'
+    start, as it can a TCP port found free and released again."""
+    return 'file://' + str(tmp_path / 'rendezvous')
 
 
 def _single_process(n_steps, ragged):
@@ -45,11 +42,11 @@ def _single_process(n_steps, ragged):
 @pytest.mark.parametrize('mode', ['fixed', 'ragged'])
 def test_data_parallel_equals_global_batch(tmp_path, world, mode):
     out = str(tmp_path / 'dp.npz')
-    port = _free_port()
+    rendezvous = _rendezvous(tmp_path)
     procs = []
     for rank in range(world):
-        env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR='127.0.0.1',
-                   MASTER_PORT=str(port), OMP_NUM_THREADS='1')
+        env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MG_TEST_RENDEZVOUS=rendezvous,
+                   OMP_NUM_THREADS='1')
         procs.append(subprocess.Popen([sys.executable, os.path.join(REPO, 'tests', '_dist_worker.py'), out, '4', mode],
                                       env=env, cwd=REPO))
     for p in procs:
@@ -79,7 +76,7 @@ def test_shard_slices_and_cropping():
         distributed.shard_slice(10, 0, 4)
 
 
-def _bucket_worker(rank, world, port, out_dir):
+def _bucket_worker(rank, world, rendezvous, out_dir):
     """Two-bucket gradient exchange (optim.Adam.exchange_gradients('early' / 'late'), graphs.GraphedTrainStep's multi-rank path) against
     the single whole-buffer all-reduce: every element reduced exactly once, bit-identical sums."""
     import os
@@ -88,8 +85,7 @@ def _bucket_worker(rank, world, port, out_dir):
     import torch.distributed as dist
     from morgana_amd import optim
     import helpers
-    os.environ['MASTER_ADDR'], os.environ['MASTER_PORT'] = '127.0.0.1', str(port)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
+    dist.init_process_group('gloo', init_method=rendezvous, rank=rank, world_size=world)
     try:
         results = {}
         for mode in ('whole', 'buckets'):
@@ -115,15 +111,14 @@ def _bucket_worker(rank, world, port, out_dir):
 def test_two_bucket_exchange_equals_single_all_reduce(tmp_path):
     import numpy as np
     import torch.multiprocessing as mp
-    port = 29641
-    mp.spawn(_bucket_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_bucket_worker, args=(2, _rendezvous(tmp_path), str(tmp_path)), nprocs=2, join=True)
     a, b = np.load(tmp_path / 'bucket_rank0.npy'), np.load(tmp_path / 'bucket_rank1.npy')
     assert np.array_equal(a, b)                           # replicas hold identical reduced gradients
     want = np.random.RandomState(100).standard_normal(a.size).astype(np.float32) + np.random.RandomState(101).standard_normal(a.size).astype(np.float32)
     np.testing.assert_array_equal(a, want)
 
 
-def _exchange_record_worker(rank, world, port, out_dir):
+def _exchange_record_worker(rank, world, rendezvous, out_dir):
     import json
     import os
     import sys
@@ -133,8 +128,7 @@ def _exchange_record_worker(rank, world, port, out_dir):
     import helpers
     sys.path.insert(0, REPO)
     import bench
-    os.environ['MASTER_ADDR'], os.environ['MASTER_PORT'] = '127.0.0.1', str(port)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
+    dist.init_process_group('gloo', init_method=rendezvous, rank=rank, world_size=world)
     try:
         model = helpers.init_small(helpers.CpuF0Model(dims=(24, 16, 8, 1)), seed=3)
         opt = optim.Adam(model.parameters(), lr=0.01, kernel=helpers.cpu_adam_kernel)
@@ -155,7 +149,7 @@ def test_exchange_record_fields_over_gloo(tmp_path):
     measurement switch `exchange_never` gives an optimiser that does not exchange (the `exposed_us` leg's step)."""
     import json
     import torch.multiprocessing as mp
-    mp.spawn(_exchange_record_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_exchange_record_worker, args=(2, _rendezvous(tmp_path), str(tmp_path)), nprocs=2, join=True)
     recs = [json.load(open(tmp_path / ('exchange_rank%d.json' % r))) for r in range(2)]
     for rec in recs:
         assert rec['world_size'] == 2 and rec['ranks_counted'] == 2 and rec['backend'] == 'gloo'

@@ -344,19 +344,16 @@ def test_two_ranks_on_one_gpu_equal_the_global_batch(tmp_path, precision, form, 
     ``which``: the README F0Model; 'rnn187' = BASELINE config C5's model (RNN_SPSS GRU-512, 187 outputs, ragged shards) and 'lstm' = the
     shipped LSTM acoustic model - the recurrent layers' DIRECT gradients (GRUFn / LSTMStackPersistFn add into the flat bucket inside
     functional.backward) meet the exchange here (/root/reference/morgana/losses.py:37-42)."""
-    import socket
     import subprocess
     import sys
     import _dist_gpu_worker as worker
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with socket.socket() as sock:
-        sock.bind(('127.0.0.1', 0))
-        port = sock.getsockname()[1]
+    rendezvous = 'file://' + str(tmp_path / 'rendezvous')   # a file the ranks meet at: no port to lose to another process before they start
     out = str(tmp_path / 'dp_gpu.npz')
     n_steps = 4
     procs = []
     for rank in range(2):
-        env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE='2', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port),
+        env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE='2', MG_TEST_RENDEZVOUS=rendezvous,
                    OMP_NUM_THREADS='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
         log = open(str(tmp_path / ('rank%d.log' % rank)), 'w')
         procs.append((subprocess.Popen([sys.executable, os.path.join(repo, 'tests', '_dist_gpu_worker.py'), out, str(n_steps), precision, form,

@@ -240,3 +240,40 @@ def test_dropout_with_p_one_equals_torch_also_for_non_finite_activations():
     y[..., 0].sum().backward()
     want[..., 0].sum().backward()
     assert torch.equal(x.grad, want_in.grad)
+
+
+def test_a_failed_capture_is_told_from_a_faulty_step():
+    """graphs._capture_refusal: a step that cannot be captured (a host read of a device value; a launch that meets one of HIP's
+    stream-capture statuses - their texts below) falls back to ordinary launches; a bad kernel argument, any other launch error and a
+    failed allocation are faults of the step and are raised."""
+    from morgana_amd import _lib, graphs
+    capture_statuses = ['operation not permitted when stream is capturing', 'operation failed due to a previous error during capture',
+                        'operation would result in a merge of separate capture sequences',
+                        'capture was not ended in the same stream as it began', 'capturing stream has unjoined work',
+                        'dependency created on uncaptured work in another stream',
+                        'operation would make the legacy stream depend on a capturing blocking stream',
+                        'operation not permitted on an event last recorded in a capturing stream',
+                        'attempt to terminate a thread-local capture sequence from another thread']
+    assert graphs._capture_refusal(RuntimeError('CUDA error: operation not permitted when stream is capturing'))
+    for status in capture_statuses:
+        assert graphs._capture_refusal(_lib.MorganaHipError('mg_cast_params_bf16 failed (code -2): launch failed: %s' % status)), status
+    assert not graphs._capture_refusal(_lib.MorganaHipError('mg_cast_params_bf16 failed (code -2): launch failed: invalid argument'))
+    assert not graphs._capture_refusal(ValueError('mg_linear_fwd_bf16: K must be a multiple of 8'))
+    assert not graphs._capture_refusal(torch.cuda.OutOfMemoryError('out of memory'))
+
+
+def test_a_failed_capture_leaves_no_copy_stamped_current():
+    """graphs._forget_failed_capture: every operand copy of the model (bf16, pair planes, 'bf16x3' splits) loses its stamp, and the
+    optimiser drops what the capture registered (slabs, a deferred tail, the "gradient already zeroed" mark, the refreshed copies)."""
+    from morgana_amd import graphs
+    model = helpers.init_small(helpers.CpuF0Model(dims=(24, 16, 8, 1)), seed=1)
+    opt = optim.Adam(model.parameters(), lr=0.01, kernel=helpers.cpu_adam_kernel, fused_loop=True)
+    for p in model.parameters():
+        for attr in ('_mg_shadow', '_mg_pair', '_mg_x3'):
+            setattr(p, attr, {'plain': None, 't': None, 'version': (p._version, 1)})
+    flat = opt.flat_buffers()
+    flat.update(pending=[(0, 4, None, 1, 4)], tail={'rows': None}, clean=True, refreshed=[(flat['params'][0], None, None)])
+    graphs._forget_failed_capture(model, opt)
+    for p in model.parameters():
+        assert p._mg_shadow['version'] is None and p._mg_pair['version'] is None and p._mg_x3['version'] is None
+    assert flat['pending'] == [] and flat['tail'] is None and flat['clean'] is False and opt.refreshed_shadows() == []
