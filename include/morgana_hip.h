@@ -217,6 +217,9 @@ int mg_metric_accumulate_f32(int kind, const float* target, const float* pred, c
  * cut to its length and its first / last frame repeated `padding` times (:113-120, :156-157).  Per (b, d) the banded SPD system
  * sum_w W_w^T diag(1/var_w) W_w x = sum_w W_w^T (mean_w/var_w) is solved in float64 (LDL^T on the band); out [B,T,D] (f32, or
  * f64 if out_f64) holds the trajectory, zero past seq_len.  workspace: mg_mlpg_workspace_bytes(...) bytes. */
+/* var_per_frame selects the layout of `variances`: 0 = global [W*D], MG_MLPG_VAR_ITEM = one row per utterance [B, W*D] (speaker-dependent
+ * variances: the same values as the per-frame form fed that row T times, bit for bit), any other value = per frame [B,T,W*D]. */
+#define MG_MLPG_VAR_ITEM 2
 size_t mg_mlpg_workspace_bytes(int B, int T, int D, int padding, int n_windows, const int* win_l, const int* win_u);
 int mg_mlpg_f32(const float* means, const float* variances, int var_per_frame, const int64_t* seq_len, int B, int T, int D,
                 int n_windows, const int* win_l, const int* win_u, const double* win_coeff, int padding, void* out, int out_f64,
@@ -244,6 +247,20 @@ int mg_pad_normalise_bf16_f32(const float* packed, const int64_t* offsets, int B
                               float* raw_out, float* norm_out, uint16_t* table_bf16, int ldb, int extra_rows, void* stream);
 int mg_normalise_f32(const float* x, float* out, const float* p0, const float* p1, int64_t n_rows, int D, int kind,
                      void* stream);
+/* Per-item (speaker-dependent) normalisers    reference: morgana/data.py:388-530, :567-576, :619-628        csrc/items_norm.hip
+ * p0, p1 are TABLES [S, D] f32 (one row per speaker) and item_row [B] int32 names the row of every batch item; the arithmetic per
+ * element is that of mg_normalise_f32 with that row (bit for bit).  x, out [B, rows_per_item, D] f32, in place allowed; D <= 8192.
+ * grad_mode != 0: x is a gradient and out = x * d out / d x of `kind` (the per-item, per-column scale; the offsets are not applied).
+ * An item_row entry outside [0, S) is never used as an index: that item's output is NaN. */
+int mg_normalise_items_f32(const float* x, float* out, const float* p0, const float* p1, const int32_t* item_row, int B,
+                           int64_t rows_per_item, int D, int S, int kind, int grad_mode, void* stream);
+/* mg_pad_normalise_f32 with tables [S, D] and one row per utterance: packed [sum_b len_b, D] + offsets [B+1] -> raw_out (may be
+ * NULL) and norm_out [B,T,D], zero in the pad frames; kind MG_NORM_MVN or MG_NORM_MINMAX.  Bad item_row entry: NaN in that
+ * utterance's valid frames of norm_out. */
+int mg_pad_normalise_items_f32(const float* packed, const int64_t* offsets, int B, int T, int D, const float* p0, const float* p1,
+                               const int32_t* item_row, int S, int kind, float* raw_out, float* norm_out, void* stream);
+/* out[b, :] = table[item_row[b], :] (table [S, D], out [B, D] f32); NaN where item_row[b] is outside [0, S). */
+int mg_item_rows_f32(const float* table, int S, int D, const int32_t* item_row, int B, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * K2  Linear (+Sigmoid) stack             reference: nn.Linear / nn.Sigmoid in README.rst:65-73 run by

@@ -19,6 +19,8 @@
 //                      frames [padding, N - padding).  The chain is latency bound (one fp64 reciprocal + ~12 FMA per row, 2 N
 //                      steps per system): rows are fetched 8 at a time, a block ahead of the arithmetic, and the reciprocal is
 //                      v_rcp_f64 + two Newton steps instead of the IEEE division sequence.
+// The variances are global (W D,), per frame (B, T, W D) or per item (B, W D) - MG_MLPG_VAR_ITEM: speaker-dependent delta variances,
+// one row per utterance; only the address the band kernel reads them from differs, the systems and the solve are the same.
 // Summation order differs from bandmat's (which adds the windows band by band), so results agree to float64 rounding, not bit
 // for bit: tests hold the float32 trajectories to 1e-6 relative against the float64 CPU restatement.
 #include "common.h"
@@ -57,7 +59,8 @@ __global__ __launch_bounds__(256) void mlpg_band_kernel(const float* __restrict_
             int f = s - padding;
             f = f < 0 ? 0 : (f >= len ? len - 1 : f);
             const size_t at = ((size_t)b * T + f) * width + (size_t)w * D + d;
-            const float var = var_per_frame ? variances[at] : variances[w * D + d];
+            const float var = var_per_frame == MG_MLPG_VAR_ITEM ? variances[(size_t)b * width + w * D + d]
+                              : var_per_frame ? variances[at] : variances[w * D + d];
             const float mu_tau = means[at] / var, tau = 1.0f / var;           // float32, as numpy does on the model's arrays
             const double ck = win.c[w][l + k];
             rhs += ck * (double)mu_tau;

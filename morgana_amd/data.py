@@ -41,6 +41,22 @@ class _NormFn(torch.autograd.Function):
         return grad * scale, None, None, None
 
 
+class _ItemNormFn(torch.autograd.Function):
+    """out = kernel(x; row item_row[b] of the tables p0, p1).  d out / d x is the same per-column scale as ``_NormFn``'s, taken from
+    the item's row: one launch of the per-item kernel in its gradient mode."""
+
+    @staticmethod
+    def forward(ctx, x, p0, p1, item_row, kind):
+        ctx.kind = kind
+        ctx.save_for_backward(p0, p1, item_row)
+        return ops.normalise_items(x, p0, p1, item_row, kind)
+
+    @staticmethod
+    def backward(ctx, grad):
+        p0, p1, item_row = ctx.saved_tensors
+        return ops.normalise_items_backward(grad, p0, p1, item_row, ctx.kind), None, None, None, None
+
+
 def _device_norm(feature, p0, p1, kind):
     if not feature.is_cuda:
         raise RuntimeError('morgana_amd normalisers take NumPy arrays (host, loader side) or device tensors; '
@@ -182,6 +198,173 @@ class MinMaxNormaliser(FeatureNormaliser):
 
 _FeatureNormaliser = FeatureNormaliser      # the reference's name for the base class
 
+SPEAKER_ID_KEY, SPEAKER_INDEX_KEY = 'speaker_id', 'speaker_index'
+
+
+def _read_id_list(path):
+    with open(path, 'r') as f:
+        return [line.strip() for line in f if line.strip()]
+
+
+class _SpeakerDependentNormaliser(FeatureNormaliser):
+    """One parameter group per speaker (data.py:388-530): ``{speaker_id}/{name}_<kind>.json`` for every name of ``speaker_id_list``;
+    ``normalise`` / ``denormalise`` / ``fetch_params`` take the speakers of the batch items (a list of names, or one name), and
+    ``params`` / ``params_torch`` / ``delta_params`` / ``delta_params_torch`` are keyed by speaker.  The arithmetic is the shared
+    classes' (the ``_KINDS`` table); what differs is WHICH parameter row an item gets.
+
+    Host side (NumPy features): the rows are gathered into (B, D) arrays and broadcast, as in the reference.  Device side: the
+    parameters of all speakers live on the device once, stacked as (S, D) tables in ``speaker_ids`` order, and the per-item kernel
+    (``ops.normalise_items``) picks row ``index[b]`` for item b.  ``speaker_ids`` may then also be that index itself - an integer tensor
+    (B,) of rows of ``self.speaker_ids``, what the loaders put into ``features['speaker_index']``.  Names are resolved on the host and
+    uploaded; inside a HIP graph capture that upload would be baked into the graph and go stale with the next batch, so names are
+    refused there (RuntimeError -> ``GraphedStepCache`` runs such a step as ordinary launches): pass the index."""
+
+    def __init__(self, name, speaker_id_list, use_deltas=False):
+        super(_SpeakerDependentNormaliser, self).__init__(name, use_deltas=use_deltas)
+        self.speaker_id_list = speaker_id_list
+        self.speaker_ids = None
+        self._tables = {}                                 # (deltas, device) -> (p0 table, p1 table), each (S, D) float32
+
+    # -- parameters ------------------------------------------------------------------------------------------------------------------
+    def _view(self, deltas, side):
+        groups = self._groups.get(bool(deltas))
+        if groups is None:
+            return None if deltas else {}
+        return {speaker: getattr(group, side) for speaker, group in groups.items()}
+
+    def _install(self, deltas, groups):
+        self._groups[bool(deltas)] = groups
+        self._tables = {key: value for key, value in self._tables.items() if key[0] != bool(deltas)}
+
+    def set_params(self, params, delta_params=None, device='cpu'):
+        """``params`` (and ``delta_params``): {speaker: {parameter name: vector}}.  Sets ``speaker_ids`` to the keys' order unless it
+        is set already."""
+        if self.speaker_ids is None:
+            self.speaker_ids = list(params)
+        self._install(False, {spk: _ParamGroup(self.kind, params[spk], device=device) for spk in self.speaker_ids})
+        if self.use_deltas and delta_params is not None:
+            self._install(True, {spk: _ParamGroup(self.kind, delta_params[spk], device=device) for spk in self.speaker_ids})
+        return self
+
+    def load_params(self, data_dir, data_root='.', device='cpu'):
+        if self.speaker_ids is None:
+            self.speaker_ids = _read_id_list(os.path.join(data_root, self.speaker_id_list))
+        pattern = _KINDS[self.kind]['file']
+        for deltas in ((False, True) if self.use_deltas else (False,)):
+            file_name = pattern.format(name=self.name + ('_deltas' if deltas else ''))
+            self._install(deltas, {spk: _ParamGroup.from_json(self.kind, os.path.join(data_root, data_dir, spk, file_name), device=device)
+                                   for spk in self.speaker_ids})
+
+    def _names(self, speaker_ids):
+        """Speaker names of the batch items from a name, a list of names or an integer index array / tensor (host side)."""
+        if isinstance(speaker_ids, torch.Tensor):
+            speaker_ids = speaker_ids.detach().cpu().numpy()
+        if isinstance(speaker_ids, np.ndarray) and speaker_ids.dtype.kind in 'iu':
+            return [self.speaker_ids[int(i)] for i in speaker_ids.reshape(-1)]
+        if isinstance(speaker_ids, np.ndarray):
+            speaker_ids = speaker_ids.reshape(-1).tolist()
+        return list(speaker_ids) if isinstance(speaker_ids, (list, tuple)) else [speaker_ids]
+
+    def fetch_params(self, speaker_ids, data_type=np.ndarray, deltas=False):
+        """{parameter name: (B, D)} for the speakers of B batch items - (D,) when there is one (data.py:460-501); an unknown speaker is
+        a KeyError."""
+        per_speaker = self._view(deltas, 'torch' if data_type == torch.Tensor else 'host')
+        if per_speaker is None:
+            raise RuntimeError('normaliser %r has no delta parameters: call load_params or set_params first' % self.name)
+        rows = [per_speaker[speaker] for speaker in self._names(speaker_ids)]
+        stack = torch.stack if data_type == torch.Tensor else np.stack
+        return {n: rows[0][n] if len(rows) == 1 else stack([row[n] for row in rows]) for n in rows[0]}
+
+    # -- device side -----------------------------------------------------------------------------------------------------------------
+    def tables(self, device, deltas=False):
+        """The two (S, D) float32 parameter tables on ``device``, rows in ``speaker_ids`` order (built on first use, then kept)."""
+        device = torch.device(device)
+        key = (bool(deltas), str(device))
+        if key not in self._tables:
+            groups = self._groups.get(bool(deltas))
+            if not groups:
+                raise RuntimeError('normaliser %r has no %sparameters: call load_params or set_params first' % (
+                    self.name, 'delta ' if deltas else ''))
+            self._tables[key] = tuple(torch.from_numpy(np.stack([groups[spk].host[n] for spk in self.speaker_ids])).to(device)
+                                      for n in _KINDS[self.kind]['params'])
+        return self._tables[key]
+
+    def speaker_rows(self, speaker_ids):
+        """Rows of ``self.speaker_ids`` for a name or a list of names (host side; KeyError for an unknown speaker)."""
+        lookup = {speaker: row for row, speaker in enumerate(self.speaker_ids or ())}
+        return [lookup[speaker] for speaker in self._names(speaker_ids)]
+
+    def speaker_index(self, speaker_ids, device):
+        """The (B,) int32 row index on ``device`` the per-item kernels take: an integer tensor passes through, names are resolved on
+        the host and uploaded - not while the current stream is being captured into a graph (see the class docstring)."""
+        if isinstance(speaker_ids, torch.Tensor):
+            if speaker_ids.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+                raise TypeError('speaker index must be an integer tensor, got %s' % speaker_ids.dtype)
+            return speaker_ids.reshape(-1).to(device=device, dtype=torch.int32)
+        device = torch.device(device)
+        if device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("normaliser %r: pass features['%s'], not speaker NAMES, while a HIP graph is being captured (an index "
+                               "built from names here would be baked into the graph and go stale with the next batch)"
+                               % (self.name, SPEAKER_INDEX_KEY))
+        return torch.tensor(self.speaker_rows(speaker_ids), dtype=torch.int32).to(device)
+
+    # -- the map ---------------------------------------------------------------------------------------------------------------------
+    def _map(self, feature, speaker_ids, deltas, inverse):
+        if isinstance(feature, np.ndarray):
+            values = self.fetch_params(speaker_ids, np.ndarray, deltas=deltas)
+            p0, p1 = (values[n] for n in _KINDS[self.kind]['params'])
+            return _apply_kind(self.kind, feature, p0, p1, inverse)
+        if not feature.is_cuda:
+            raise RuntimeError('morgana_amd normalisers take NumPy arrays (host, loader side) or device tensors; '
+                               'got a CPU torch tensor (there is no CPU fallback for the device path)')
+        p0, p1 = self.tables(feature.device, deltas=deltas)
+        index = self.speaker_index(speaker_ids, feature.device)
+        single = feature.dim() == 2                       # one (T, D) sequence and one speaker
+        batched = feature[None] if single else feature
+        if index.numel() != batched.shape[0]:
+            raise ValueError('%d speakers for a batch of %d items' % (index.numel(), batched.shape[0]))
+        out = _ItemNormFn.apply(batched, p0, p1, index, _KINDS[self.kind]['inverse' if inverse else 'forward'])
+        return out[0] if single else out
+
+    def normalise(self, feature, speaker_ids, deltas=False):
+        return self._map(feature, speaker_ids, deltas, inverse=False)
+
+    def denormalise(self, feature, speaker_ids, deltas=False):
+        return self._map(feature, speaker_ids, deltas, inverse=True)
+
+
+class SpeakerDependentMeanVarianceNormaliser(_SpeakerDependentNormaliser):
+    """Per-speaker zero mean / unit variance; ``{speaker_id}/{name}_mvn.json`` (data.py:567-576)."""
+    kind = 'mvn'
+
+
+class SpeakerDependentMinMaxNormaliser(_SpeakerDependentNormaliser):
+    """Per-speaker range [0, 1]; ``{speaker_id}/{name}_minmax.json`` (data.py:619-628)."""
+    kind = 'minmax'
+
+
+def _speaker_order(normalisers):
+    """The one ``speaker_ids`` order all speaker-dependent normalisers of ``normalisers`` share (None if there is none): the loaders
+    write ONE ``speaker_index`` per batch, so the (S, D) tables of every normaliser must have their rows in the same order."""
+    order = None
+    for name, normaliser in (normalisers or {}).items():
+        if not isinstance(normaliser, _SpeakerDependentNormaliser):
+            continue
+        if normaliser.speaker_ids is None:
+            raise ValueError('speaker-dependent normaliser %r has no parameters: call load_params or set_params first' % name)
+        if order is None:
+            order = list(normaliser.speaker_ids)
+        elif list(normaliser.speaker_ids) != order:
+            raise ValueError('speaker-dependent normaliser %r lists its speakers in another order than the others of this dict: '
+                             'one speaker_index per batch needs one order' % name)
+    return order
+
+
+def speaker_index_of(speaker_ids, order):
+    """Positions of the names ``speaker_ids`` in ``order`` as an int32 array (KeyError for an unknown speaker)."""
+    lookup = {speaker: row for row, speaker in enumerate(order)}
+    return np.array([lookup[speaker] for speaker in speaker_ids], dtype=np.int32)
+
 
 class Normalisers(dict):
     """name -> normaliser, every member's parameters loaded from ``data_root/normalisation_dir`` on construction (data.py:225-247)."""
@@ -231,8 +414,11 @@ def add_bf16_table(features, key='normalised_lab', extra_rows=None):
     return features
 
 
-def to_device(features, device, bf16_tables=()):
+def to_device(features, device, bf16_tables=(), normalisers=None):
     """``ToDeviceWrapper.to_device`` over a feature dict (data.py:648-663); numpy arrays are uploaded too.
+
+    ``normalisers``: when it holds speaker-dependent normalisers and the batch carries ``speaker_id`` (the list of names), the batch
+    also gets ``speaker_index``: int32 (B,), the names' rows in the normalisers' ``speaker_ids``.
 
     ``bf16_tables``: names of phone-level features whose bf16 operand table the batch should carry (``add_bf16_table``; what a
     bf16-precision model's ``bf16_table_features()`` names) - the loader-side half of bf16 mode.
@@ -252,6 +438,10 @@ def to_device(features, device, bf16_tables=()):
         name, _, kind = key.partition(':')
         if name in out and name + (X3_TABLE_SUFFIX if kind == 'x3' else BF16_TABLE_SUFFIX) not in out:
             add_bf16_table(out, key)
+    order = _speaker_order(normalisers)
+    if order is not None and SPEAKER_ID_KEY in out and SPEAKER_INDEX_KEY not in out:
+        # next to the reference's list of names: their rows in the normalisers' tables, on the device (what a captured step reads)
+        out[SPEAKER_INDEX_KEY] = torch.from_numpy(speaker_index_of(out[SPEAKER_ID_KEY], order)).to(device)
     return out
 
 
@@ -295,7 +485,8 @@ def load_utterance(features, normalisers):
     out = dict(features)
     for name, normaliser in normalisers.items():
         if name in features:
-            out['normalised_' + name] = normaliser.normalise(features[name]).astype(np.float32)
+            who = (features[SPEAKER_ID_KEY],) if isinstance(normaliser, _SpeakerDependentNormaliser) else ()
+            out['normalised_' + name] = normaliser.normalise(features[name], *who).astype(np.float32)
     return out
 
 
@@ -410,6 +601,13 @@ def collate_to_device(batch, normalisers, device, bf16_tables=()):
     device = torch.device(device)
     bf16_tables = tuple(bf16_tables or ())
     out, rest = {}, []
+    order = _speaker_order(normalisers)
+    if order is not None:
+        if SPEAKER_ID_KEY not in batch[0]:
+            raise KeyError("speaker-dependent normalisers need a '%s' entry in every utterance" % SPEAKER_ID_KEY)
+        # uploaded first (pinned staging, asynchronous): the per-item passes below read it
+        speaker_index = torch.from_numpy(speaker_index_of([item[SPEAKER_ID_KEY] for item in batch], order))
+        out[SPEAKER_INDEX_KEY] = _small_to_device({SPEAKER_INDEX_KEY: speaker_index}, device)[SPEAKER_INDEX_KEY]
     for key in batch[0].keys():
         first = batch[0][key]
         if not (isinstance(first, np.ndarray) and first.ndim == 2 and first.dtype == np.float32):
@@ -425,6 +623,13 @@ def collate_to_device(batch, normalisers, device, bf16_tables=()):
             packed = torch.from_numpy(np.ascontiguousarray(np.concatenate(items, axis=0)))
         kind = p0 = p1 = None
         normaliser = normalisers.get(key) if normalisers is not None else None
+        if isinstance(normaliser, _SpeakerDependentNormaliser):
+            # the per-item pass: row speaker_index[b] of the (S, D) tables for utterance b.  (A bf16 table of such a feature is
+            # made by the add_bf16_table pass at the end.)
+            p0, p1 = normaliser.tables(device)
+            out[key], out['normalised_' + key] = ops.pad_normalise_items(packed, offsets, int(lens.max()), p0, p1, out[SPEAKER_INDEX_KEY],
+                                                                         _KINDS[normaliser.kind]['forward'])
+            continue
         if isinstance(normaliser, FeatureNormaliser):
             spec, prm = _KINDS[normaliser.kind], normaliser.fetch_params(torch.Tensor)
             kind, (p0, p1) = spec['forward'], (prm[n].to(device) for n in spec['params'])
@@ -444,7 +649,9 @@ def collate_to_device(batch, normalisers, device, bf16_tables=()):
         for key in rest:                                  # integer sequence features with a normaliser (dur) stay on the host path
             normaliser = normalisers.get(key) if normalisers is not None else None
             if normaliser is not None and isinstance(batch[0][key], np.ndarray):
-                plain['normalised_' + key] = collate_fn([{key: normaliser.normalise(item[key]).astype(np.float32)} for item in batch])[key]
+                sd = isinstance(normaliser, _SpeakerDependentNormaliser)
+                plain['normalised_' + key] = collate_fn([{key: normaliser.normalise(
+                    item[key], *((item[SPEAKER_ID_KEY],) if sd else ())).astype(np.float32)} for item in batch])[key]
         out.update(_small_to_device(plain, device))
     for key in bf16_tables:                               # features that did not take the fused pass (no normaliser, host path; pair planes)
         name, _, kind = key.partition(':')
@@ -493,6 +700,20 @@ class TextSource(object):
             return {self.name: float(text)}
 
 
+class StringSource(object):
+    """``{data_dir}/{name}/{base_name}.txt`` -> ``{name: its text}``: the ``speaker_id`` data source a corpus with speaker-dependent
+    normalisers defines (data.py:85, :134-136)."""
+
+    use_deltas = False
+
+    def __init__(self, name, ext='txt'):
+        self.name, self.ext = name, ext
+
+    def __call__(self, base_name, data_dir):
+        with open(os.path.join(data_dir, self.name, '{}.{}'.format(base_name, self.ext))) as f:
+            return {self.name: f.read().strip()}
+
+
 class FilesDataset(object):
     """File-backed utterances in front of ``DeviceBatches``: the reference's ``FilesDataset`` (data.py:60-157) - same constructor
     arguments, id-list handling (joined to ``data_root``, not to the split directory: data.py:100) and checks (:89-94).
@@ -500,10 +721,13 @@ class FilesDataset(object):
     ``dataset[i]`` is what the reference's ``__getitem__`` returns: the features of every data source plus, for each feature with a
     normaliser, its ``normalised_`` twin computed on the host in NumPy and cast to float32 (:119-127, :144-150).
     ``dataset.raw(i)`` is the same utterance WITHOUT the twins - what ``DeviceBatches`` takes, because ``collate_to_device`` pads
-    and normalises on the device in one pass.  Speaker-dependent normalisers are out of scope."""
+    and normalises on the device in one pass.  With a speaker-dependent normaliser a data source named ``speaker_id`` must exist
+    (:88-91); it is read first and its value handed to those normalisers (:119-136)."""
 
     def __init__(self, data_sources, data_dir, id_list, normalisers, data_root='.'):
         for name, normaliser in normalisers.items():
+            if isinstance(normaliser, _SpeakerDependentNormaliser) and SPEAKER_ID_KEY not in data_sources:
+                raise KeyError(f"{name} is a speaker-dependent normaliser, but no 'speaker_id' data_source was defined")
             if name in data_sources and normaliser.use_deltas and not data_sources[name].use_deltas:
                 raise ValueError(f'To normalise deltas of {name}, set `data_source.use_deltas` to True.')
         self.data_sources = data_sources
@@ -520,20 +744,24 @@ class FilesDataset(object):
     def raw(self, index):
         base_name = self.file_ids[index]
         features = {'name': base_name}
-        for data_source in self.data_sources.values():
-            features.update(data_source(base_name, self.data_dir))
+        if SPEAKER_ID_KEY in self.data_sources:           # first, so that the normalisers of the other features can use it
+            features.update(self.data_sources[SPEAKER_ID_KEY](base_name, self.data_dir))
+        for name, data_source in self.data_sources.items():
+            if name != SPEAKER_ID_KEY:
+                features.update(data_source(base_name, self.data_dir))
         return features
 
     def __getitem__(self, index):
         features = self.raw(index)
         for name in self.data_sources:
             normaliser = self.normalisers.get(name)
-            if normaliser is None:
+            if normaliser is None or name == SPEAKER_ID_KEY:
                 continue
-            features['normalised_' + name] = normaliser.normalise(features[name]).astype(np.float32)
+            who = (features[SPEAKER_ID_KEY],) if isinstance(normaliser, _SpeakerDependentNormaliser) else ()
+            features['normalised_' + name] = normaliser.normalise(features[name], *who).astype(np.float32)
             if normaliser.use_deltas:
                 deltas = name + '_deltas'
-                features['normalised_' + deltas] = normaliser.normalise(features[deltas], deltas=True).astype(np.float32)
+                features['normalised_' + deltas] = normaliser.normalise(features[deltas], *who, deltas=True).astype(np.float32)
         return features
 
     collate_fn = staticmethod(collate_fn)

@@ -19,6 +19,7 @@ import torch.nn as nn
 from . import data
 from . import losses
 from . import metrics
+from . import ops
 from . import utils
 from . import viz
 from . import functional as F_hip
@@ -197,12 +198,16 @@ class StreamModel(BaseSPSS):
     ``predict`` / ``loss`` / ``forward`` as the shipped models define them: input = upsampled labels concatenated with the frame
     counters, per-stream outputs under the reference's keys, loss = mean of the streams' masked losses, trajectories and metrics on
     the device whenever the normalisers carry delta parameters (i.e. under ``ExperimentBuilder``; ``generate=False`` turns both off).
-    ``fused_loss``: the split, the sigmoid and all masked losses as one pass over the prediction (``losses.multi_stream``)."""
+    ``fused_loss``: the split, the sigmoid and all masked losses as one pass over the prediction (``losses.multi_stream``).
+    ``speaker_id_list`` (a file of speaker names): the delta streams are normalised PER SPEAKER
+    (``data.SpeakerDependentMeanVarianceNormaliser``); trajectories are then denormalised with ``features['speaker_index']`` and MLPG
+    runs under each utterance's own delta variances (``ops.mlpg``'s per-item mode).  None changes nothing."""
 
-    def __init__(self, layers, streams, fused_upsample=True, fused_loss=False, generate=True):
+    def __init__(self, layers, streams, fused_upsample=True, fused_loss=False, generate=True, speaker_id_list=None):
         super(StreamModel, self).__init__()
         self.layers = layers
         self.streams = tuple(streams)
+        self.speaker_id_list = speaker_id_list
         self.fused_upsample, self.fused_loss, self.generate = fused_upsample, fused_loss, generate
         registered = {st.metric[0]: st.metric[1]() for st in self.streams if st.metric is not None}
         if registered:
@@ -212,7 +217,9 @@ class StreamModel(BaseSPSS):
         sources = {'dur': data.MeanVarianceNormaliser('dur'), 'lab': data.MinMaxNormaliser('lab'),
                    'counters': data.MinMaxNormaliser('counters')}
         for st in self.streams:
-            if st.is_delta:
+            if st.is_delta and self.speaker_id_list is not None:
+                sources[st.name] = data.SpeakerDependentMeanVarianceNormaliser(st.name, self.speaker_id_list, use_deltas=True)
+            elif st.is_delta:
                 sources[st.name] = data.MeanVarianceNormaliser(st.name, use_deltas=True)
         return sources
 
@@ -241,17 +248,26 @@ class StreamModel(BaseSPSS):
     def _generating(self):
         return self.generate and all(_has_delta_params(self.normalisers, st.name) for st in self.streams if st.is_delta)
 
-    def _trajectory(self, name, pred_norm_deltas, seq_len=None):
+    def _trajectory(self, name, pred_norm_deltas, seq_len=None, speaker_index=None):
         """Denormalised deltas -> most probable static trajectory under the global delta variances, padding 100
-        (models/RNN_SPSS.py:107-118, models/f0_test_model.py:83-89), without leaving the device."""
+        (models/RNN_SPSS.py:107-118, models/f0_test_model.py:83-89), without leaving the device.  With a speaker-dependent
+        normaliser: each utterance under the delta variances of its own speaker (row ``speaker_index[b]`` of the tables)."""
         normaliser = self.normalisers[name]
+        if isinstance(normaliser, data._SpeakerDependentNormaliser):
+            if speaker_index is None:
+                raise KeyError("the normaliser of %r is speaker-dependent: the batch needs features['%s'] (the loaders write it)"
+                               % (name, data.SPEAKER_INDEX_KEY))
+            pred_deltas = normaliser.denormalise(pred_norm_deltas.detach(), speaker_index, deltas=True)
+            index = normaliser.speaker_index(speaker_index, pred_deltas.device)
+            std_dev = ops.item_rows(normaliser.tables(pred_deltas.device, deltas=True)[1], index)
+            return ops.mlpg(pred_deltas, std_dev ** 2, viz.synthesis.DEFAULT_WINDOWS, padding_size=100, seq_len=seq_len)
         pred_deltas = normaliser.denormalise(pred_norm_deltas.detach(), deltas=True)
         return viz.synthesis.MLPG(means=pred_deltas, variances=normaliser.delta_params_torch['std_dev'] ** 2, padding_size=100,
                                   seq_len=seq_len)
 
     _prepare_output = _trajectory      # the reference's name for it
 
-    def _with_trajectories(self, outputs, n_frames):
+    def _with_trajectories(self, outputs, n_frames, speaker_index=None):
         if self._generating():
             delta = [st for st in self.streams if st.is_delta]
             first = outputs[delta[0].output_key] if delta else None
@@ -265,13 +281,13 @@ class StreamModel(BaseSPSS):
                 for st, side in zip(delta, pool):
                     side.wait_stream(main)
                     with torch.cuda.stream(side):
-                        outputs[st.name] = self._trajectory(st.name, outputs[st.output_key], n_frames)
+                        outputs[st.name] = self._trajectory(st.name, outputs[st.output_key], n_frames, speaker_index)
                 for st, side in zip(delta, pool):
                     main.wait_stream(side)
                     outputs[st.name].record_stream(main)
             else:
                 for st in delta:
-                    outputs[st.name] = self._trajectory(st.name, outputs[st.output_key], n_frames)
+                    outputs[st.name] = self._trajectory(st.name, outputs[st.output_key], n_frames, speaker_index)
         return outputs
 
     def _accumulate_metrics(self, features, outputs):
@@ -298,7 +314,8 @@ class StreamModel(BaseSPSS):
 
     # -- the plugin surface ----------------------------------------------------------------------------------------------------------
     def predict(self, features):
-        return self._with_trajectories(self._split(self._run_layers(features)), features['n_frames'])
+        return self._with_trajectories(self._split(self._run_layers(features)), features['n_frames'],
+                                       features.get(data.SPEAKER_INDEX_KEY))
 
     def loss(self, features, output_features):
         n_frames = features['n_frames']
@@ -320,7 +337,8 @@ class StreamModel(BaseSPSS):
         targets = [self._target(features, st) for st in self.streams]
         kinds = [st.loss for st in self.streams]
         loss, probabilities = losses.multi_stream(prediction, targets, kinds, features['n_frames'], want_prob=True)
-        outputs = self._with_trajectories(self._split(prediction.detach(), probabilities), features['n_frames'])
+        outputs = self._with_trajectories(self._split(prediction.detach(), probabilities), features['n_frames'],
+                                          features.get(data.SPEAKER_INDEX_KEY))
         self._accumulate_metrics(features, outputs)
         return loss, outputs
 
@@ -357,7 +375,7 @@ class LSTMAcousticModel(StreamModel):
     STREAMS = ('lf0', 'vuv', 'mcep', 'bap')
 
     def __init__(self, input_dim=600 + 9, output_dims=None, dropout_prob=0., num_layers=8, hidden_dim=512, post_dim=256,
-                 precision=None, fused_upsample=True, fused_loss=True, generate=True):
+                 precision=None, fused_upsample=True, fused_loss=True, generate=True, speaker_id_list=None):
         if output_dims is None:
             output_dims = {'lf0': 1 * 3, 'vuv': 1, 'mcep': 60 * 3, 'bap': 5 * 3}
         self.input_dim, self.output_dims, self.dropout_prob, self.num_layers = input_dim, output_dims, dropout_prob, num_layers
@@ -367,7 +385,7 @@ class LSTMAcousticModel(StreamModel):
                  'bap': Stream('bap', output_dims['bap'], 'mse', ('BAP_distortion', metrics.Distortion, 'trajectory'))}
         layers = _lstm_stack(input_dim, hidden_dim, post_dim, sum(output_dims.values()), num_layers, dropout_prob, precision)
         super(LSTMAcousticModel, self).__init__(layers, [table[name] for name in self.STREAMS], fused_upsample=fused_upsample,
-                                                fused_loss=fused_loss, generate=generate)
+                                                fused_loss=fused_loss, generate=generate, speaker_id_list=speaker_id_list)
 
 
 class GRUF0Model(StreamModel):
@@ -375,11 +393,13 @@ class GRUF0Model(StreamModel):
     MSE and the LF0 RMSE in Hz over the frames the DATA calls voiced (``features['vuv']``, :101-103).  Same constructor arguments and
     state_dict keys (``layers.0.weight``, ``layers.3.layer.weight_ih_l0`` ...)."""
 
-    def __init__(self, dropout_prob=0., input_dim=600 + 9, output_dim=1 * 3, precision=None, fused_upsample=True, generate=True):
+    def __init__(self, dropout_prob=0., input_dim=600 + 9, output_dim=1 * 3, precision=None, fused_upsample=True, generate=True,
+                 speaker_id_list=None):
         self.input_dim, self.output_dim = input_dim, output_dim
         layers = _gru_f0_stack(input_dim, output_dim, dropout_prob, precision)
         streams = [Stream('lf0', output_dim, 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'))]
-        super(GRUF0Model, self).__init__(layers, streams, fused_upsample=fused_upsample, fused_loss=False, generate=generate)
+        super(GRUF0Model, self).__init__(layers, streams, fused_upsample=fused_upsample, fused_loss=False, generate=generate,
+                                         speaker_id_list=speaker_id_list)
 
 
 class VAEF0Model(StreamModel, BaseVAE):
@@ -391,11 +411,12 @@ class VAEF0Model(StreamModel, BaseVAE):
     ``encoder.0.layer.*`` and ``encoder_projection.0.*``."""
 
     def __init__(self, z_dim=16, kld_weight=1., encoder_hidden=64, dropout_prob=0., input_dim=600 + 9, output_dim=1 * 3, precision=None,
-                 fused_upsample=True, generate=True):
+                 fused_upsample=True, generate=True, speaker_id_list=None):
         self.input_dim, self.output_dim = input_dim, output_dim
         layers = _gru_f0_stack(input_dim + z_dim, output_dim, dropout_prob, precision)
         streams = [Stream('lf0', output_dim, 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'))]
-        super(VAEF0Model, self).__init__(layers, streams, fused_upsample=fused_upsample, fused_loss=False, generate=generate)
+        super(VAEF0Model, self).__init__(layers, streams, fused_upsample=fused_upsample, fused_loss=False, generate=generate,
+                                         speaker_id_list=speaker_id_list)
         self.z_dim, self.kld_weight = z_dim, kld_weight
         # the encoder's parameters go first in parameters() (and so in the optimiser's flat buffer): behind the decoder's 3-wide output
         # bias they would sit at offsets that are not 16-byte aligned, and the one-launch GRU-64 forward needs an aligned w_hh (with a
@@ -419,7 +440,7 @@ class VAEF0Model(StreamModel, BaseVAE):
                                                                phone_rate=self.phone_rate)
         model_inputs = utils.concat_frame_features(norm_lab_at_frame_rate, norm_counters, latent)
         prediction, _ = self.layers(model_inputs, seq_len=features['n_frames'], max_len=norm_counters.shape[1])
-        return self._with_trajectories(self._split(prediction), features['n_frames'])
+        return self._with_trajectories(self._split(prediction), features['n_frames'], features.get(data.SPEAKER_INDEX_KEY))
 
     forward = BaseVAE.forward
     predict = BaseVAE.predict

@@ -318,6 +318,71 @@ def pad_normalise(packed, offsets, t, p0=None, p1=None, kind=None, want_raw=True
     return raw, norm
 
 
+def _item_tables(p0, p1, item_row, b, d, what):
+    """The (S, D) parameter tables and the (B,) int32 row index of the per-item kernels, checked against B items of D columns."""
+    p0 = _require(p0, torch.float32, 'param0 table')
+    p1 = _require(p1, torch.float32, 'param1 table')
+    item_row = _require(item_row, torch.int32, 'item_row')
+    if p0.dim() != 2 or p0.shape != p1.shape or p0.shape[1] != d:
+        raise ValueError('%s: parameter tables %s / %s must both be (speakers, %d)' % (what, tuple(p0.shape), tuple(p1.shape), d))
+    if item_row.dim() != 1 or item_row.numel() != b:
+        raise ValueError('%s: item_row %s must hold one row index for each of the %d batch items' % (what, tuple(item_row.shape), b))
+    return p0, p1, item_row
+
+
+def normalise_items(x, p0, p1, item_row, kind, grad=False):
+    """``normalise`` with a parameter row per batch item: x (B, ..., D) f32, tables p0 / p1 (S, D), item_row (B,) int32; item b is mapped
+    with row item_row[b] (NaN for an index outside [0, S)).  ``grad=True``: x is a gradient and the result is x * d out / d x of
+    ``kind`` - the per-item, per-column scale, in the same launch."""
+    lib = _lib.load()
+    x = _require(x, torch.float32, 'feature')
+    if x.dim() < 2:
+        raise ValueError('normalise_items: the feature must be (batch, ..., features), got %s' % (tuple(x.shape),))
+    b, d = x.shape[0], x.shape[-1]
+    p0, p1, item_row = _item_tables(p0, p1, item_row, b, d, 'normalise_items')
+    out = torch.empty_like(x)
+    if x.numel() == 0:
+        return out
+    _lib.check(lib.mg_normalise_items_f32(_p(x), _p(out), _p(p0), _p(p1), _p(item_row), b, x.numel() // (b * d), d, p0.shape[0], kind,
+                                          int(bool(grad)), _stream()), 'mg_normalise_items_f32')
+    return out
+
+
+def normalise_items_backward(grad, p0, p1, item_row, kind):
+    """Gradient of ``normalise_items`` with respect to its feature."""
+    return normalise_items(grad, p0, p1, item_row, kind, grad=True)
+
+
+def pad_normalise_items(packed, offsets, t, p0, p1, item_row, kind, want_raw=True):
+    """``pad_normalise`` with tables (S, D) and one row index per utterance (speaker-dependent normalisers in the device loader):
+    packed (sum len, D) + offsets (B+1) -> (raw (B,t,D) or None, normalised (B,t,D))."""
+    lib = _lib.load()
+    packed = _require(packed, torch.float32, 'packed feature')
+    offsets = _require(offsets, torch.int64, 'offsets')
+    b, d = offsets.numel() - 1, packed.shape[1]
+    p0, p1, item_row = _item_tables(p0, p1, item_row, b, d, 'pad_normalise_items')
+    raw = torch.empty((b, t, d), dtype=torch.float32, device=packed.device) if want_raw else None
+    norm = torch.empty((b, t, d), dtype=torch.float32, device=packed.device)
+    _lib.check(lib.mg_pad_normalise_items_f32(_p(packed), _p(offsets), b, int(t), d, _p(p0), _p(p1), _p(item_row), p0.shape[0], kind,
+                                              _p(raw), _p(norm), _stream()), 'mg_pad_normalise_items_f32')
+    return raw, norm
+
+
+def item_rows(table, item_row):
+    """table (S, D) f32, item_row (B,) int32 -> (B, D): row item_row[b] for every batch item, NaN for an index outside [0, S) (the
+    guarded form of ``table[item_row]``: a bad index must not fault a device that others share)."""
+    lib = _lib.load()
+    table = _require(table, torch.float32, 'table')
+    item_row = _require(item_row, torch.int32, 'item_row')
+    if table.dim() != 2 or item_row.dim() != 1 or item_row.numel() == 0:
+        raise ValueError('item_rows: table %s must be (speakers, features) and item_row %s (batch,)' % (
+            tuple(table.shape), tuple(item_row.shape)))
+    out = torch.empty((item_row.numel(), table.shape[1]), dtype=torch.float32, device=table.device)
+    _lib.check(lib.mg_item_rows_f32(_p(table), table.shape[0], table.shape[1], _p(item_row), item_row.numel(), _p(out), _stream()),
+               'mg_item_rows_f32')
+    return out
+
+
 def normalise(x, p0, p1, kind):
     lib = _lib.load()
     x = _require(x, torch.float32, 'feature')
@@ -2055,11 +2120,13 @@ def metric_accumulate(kind, accum, target, pred=None, voiced=None, seq_len=None,
 
 
 MLPG_MAX_WINDOWS, MLPG_MAX_COEFF = 4, 5
+MLPG_VAR_ITEM = 2           # MG_MLPG_VAR_ITEM: variances (B, W*D), one row per utterance
 
 
 def mlpg(means, variances, windows, padding_size=0, seq_len=None, out_dtype=torch.float32):
     """Most probable trajectories of (B, T, W*D) f32 delta-stream means (csrc/mlpg.hip, morgana/viz/synthesis.py:79-178).
-    variances (W*D,) global or (B, T, W*D) per frame, f32; windows [(l, u, coeffs)]; returns (B, T, D), zero past seq_len."""
+    variances (W*D,) global, (B, T, W*D) per frame or (B, W*D) per item (one row per utterance: speaker-dependent variances, the same
+    result as that row repeated over T), f32; windows [(l, u, coeffs)]; returns (B, T, D), zero past seq_len."""
     lib = _lib.load()
     means = _require(means, torch.float32, 'means')
     variances = _require(variances, torch.float32, 'variances')
@@ -2074,8 +2141,10 @@ def mlpg(means, variances, windows, padding_size=0, seq_len=None, out_dtype=torc
         per_frame = 0
     elif variances.shape == means.shape:
         per_frame = 1
+    elif variances.dim() == 2 and tuple(variances.shape) == (b, width):
+        per_frame = MLPG_VAR_ITEM
     else:
-        raise ValueError('variances %s fit neither (%d,) nor %s' % (tuple(variances.shape), width, tuple(means.shape)))
+        raise ValueError('variances %s fit neither (%d,) nor %s nor (%d, %d)' % (tuple(variances.shape), width, tuple(means.shape), b, width))
     win_l = (ctypes.c_int * n_win)()
     win_u = (ctypes.c_int * n_win)()
     win_c = (ctypes.c_double * (n_win * MLPG_MAX_COEFF))()

@@ -205,6 +205,42 @@ def acoustic_normalisers(model, device='cpu', seed=REFERENCE_SEED):
     return model.normalisers
 
 
+def speaker_names(n_speakers):
+    return ['spk%02d' % i for i in range(n_speakers)]
+
+
+def speaker_acoustic_normalisers(model, n_speakers=8, device='cpu', seed=REFERENCE_SEED):
+    """``acoustic_normalisers`` for a model built with ``speaker_id_list``: synthetic mean-variance parameters (static and delta) PER
+    SPEAKER on its speaker-dependent normalisers, standing in for the ``{speaker_id}/*_mvn.json`` files (morgana/data.py:503-530).
+    The speakers are ``speaker_names(n_speakers)``, in that order, on every normaliser."""
+    rng = np.random.RandomState((seed + 32452843) % (2 ** 32))
+    model.normalisers = model.normaliser_sources()
+    widths = getattr(model, 'output_dims', None) or {'lf0': model.output_dim}
+    names = speaker_names(n_speakers)
+    for name, norm in model.normalisers.items():
+        if not getattr(norm, 'use_deltas', False):
+            continue
+        width = widths[name]
+        params, delta_params = {}, {}
+        for speaker in names:
+            mean = rng.standard_normal(width).astype(np.float32) * 0.1
+            mean[:width // 3] += (5.0 if name == 'lf0' else 0.0) + rng.uniform(-0.3, 0.3)
+            std = rng.uniform(0.2, 0.6, width).astype(np.float32)
+            params[speaker] = {'mean': mean[:width // 3], 'std_dev': std[:width // 3]}
+            delta_params[speaker] = {'mean': mean, 'std_dev': std}
+        norm.speaker_ids = list(names)
+        norm.set_params(params, delta_params, device=device)
+    return model.normalisers
+
+
+def speaker_batch_ids(batch_size, n_speakers=8, seed=REFERENCE_SEED, rank=0):
+    """A speaker name per utterance of a synthetic batch (``features['speaker_id']``) and the names' rows (``'speaker_index'``, int32)."""
+    rng = np.random.RandomState((seed + rank + 49979687) % (2 ** 32))
+    rows = rng.randint(0, n_speakers, size=batch_size).astype(np.int32)
+    names = speaker_names(n_speakers)
+    return [names[r] for r in rows], rows
+
+
 def gru_f0_state(seed=REFERENCE_SEED, input_dim=609, d1=256, hidden=64, post=64, output_dim=3):
     """state_dict (numpy) of the shipped F0 model (models/f0_test_model.py:28-45): Linear(input, d1), Sigmoid, Dropout,
     GRU(d1, hidden), Dropout, GRU(hidden, hidden), Dropout, GRU(hidden, hidden), Dropout, Linear(hidden, post), Sigmoid,
