@@ -33,6 +33,11 @@ extern "C" {
 
 #define MG_ACT_NONE 0
 #define MG_ACT_SIGMOID 1
+/* torch.nn.Tanh / torch.nn.ReLU behind an nn.Linear (reference: the modules SequentialWithRecurrent.forward runs one by one,
+ * morgana/utils.py:401-418).  Accepted by mg_linear_fwd_f32, mg_linear_fwd_bf16, mg_phone_front_linear_fwd_bf16,
+ * mg_phone_concat_layer_bf16, mg_linear_dgrad_act_* and mg_act_*; the shape-specialised fused kernels stay Sigmoid only. */
+#define MG_ACT_TANH 2
+#define MG_ACT_RELU 3
 /* OR-ed into `act` of mg_linear_fwd_bf16: `rows` is made of RUNS of equal consecutive indices (the frame map of
  * upsample_to_repetitions: every phone row repeated `dur` times).  A performance hint only - results do not depend on it: the
  * gathered operand is then staged once per distinct row (csrc/gemm_nt_runs.hip); rows without runs cost up to 4 passes there. */
@@ -274,6 +279,11 @@ int mg_linear_fwd_f32(const float* A, int lda, const int32_t* rows, int64_t M, i
 /* dX = (dY W) [* H (1-H)].  dY [M,N]; W [N,K]; H NULL or [M,K] = the sigmoid OUTPUT feeding this layer; dX [M,K]. */
 int mg_linear_dgrad_f32(const float* dY, int64_t M, int N, const float* W, int K, const float* H, float* dX,
                         void* stream);
+/* dX = (dY W) * f'(H), H [M,K] the OUTPUT of activation `act` feeding this layer: f' = H (1-H) (MG_ACT_SIGMOID), 1 - H^2
+ * (MG_ACT_TANH), H > 0 (MG_ACT_RELU); MG_ACT_NONE (H may be NULL): dX = dY W.  mg_linear_dgrad_f32 is this with MG_ACT_SIGMOID.
+ * What it replaces: autograd's backward of torch.nn.Tanh / ReLU + nn.Linear inside morgana/utils.py:401-418. */
+int mg_linear_dgrad_act_f32(const float* dY, int64_t M, int N, const float* W, int K, const float* H, int act, float* dX,
+                            void* stream);
 /* dW[n,k] (+)= sum_m dY[m,n] A[row(m),k];  db[n] (+)= sum_m dY[m,n].  accumulate != 0 adds into dW/db.
  * workspace: mg_linear_wgrad_workspace_bytes(M,N,K).  Deterministic (split-M slabs + ordered reduce). */
 size_t mg_linear_wgrad_workspace_bytes(int64_t M, int N, int K);
@@ -378,6 +388,9 @@ int mg_linear_fwd_bf16(const uint16_t* A, int lda, const int32_t* rows, int64_t 
 /* WT = W^T as bf16 [K,N] (ldwt). */
 int mg_linear_dgrad_bf16(const uint16_t* dY, int lddy, int64_t M, int N, const uint16_t* WT, int ldwt, int K,
                          const uint16_t* H, int ldh, void* dX, int lddx, int dx_f32, void* stream);
+/* The same for H the output of `act` (see mg_linear_dgrad_act_f32); mg_linear_dgrad_bf16 is this with MG_ACT_SIGMOID. */
+int mg_linear_dgrad_act_bf16(const uint16_t* dY, int lddy, int64_t M, int N, const uint16_t* WT, int ldwt, int K,
+                             const uint16_t* H, int ldh, int act, void* dX, int lddx, int dx_f32, void* stream);
 /* The same with H read from a table: frame m's sigmoid output is H[h_rows[m]] (phone-rate first layer; h_rows >= 0).  Needs the
  * wide-tile shape (M >= 2048, K % 128 == 0, lddy and ldwt multiples of 64); MG_EINVAL otherwise. */
 int mg_linear_dgrad_gathered_bf16(const uint16_t* dY, int lddy, int64_t M, int N, const uint16_t* WT, int ldwt, int K,
@@ -620,6 +633,11 @@ int mg_cast_bf16_f32(const uint16_t* src, int lds, float* dst, int ldd, int64_t 
 /* elementwise sigmoid forward / backward for a stand-alone nn.Sigmoid. */
 int mg_sigmoid_f32(const float* x, float* y, int64_t n, void* stream);
 int mg_sigmoid_grad_f32(const float* dy, const float* y, float* dx, int64_t n, void* stream);
+/* y = act(x) and dx = dy f'(y) for act = MG_ACT_SIGMOID / MG_ACT_TANH / MG_ACT_RELU: a stand-alone torch.nn.Tanh / ReLU / Sigmoid
+ * of the container (morgana/utils.py:401-418, e.g. behind a recurrent wrapper) and the gradient of a Linear run's trailing
+ * activation.  ReLU as torch.relu / threshold_backward: NaN passes through, relu(-0.0) = -0.0, dx = 0 where y <= 0. */
+int mg_act_f32(const float* x, float* y, int64_t n, int act, void* stream);
+int mg_act_grad_f32(const float* dy, const float* y, float* dx, int64_t n, int act, void* stream);
 
 /* Fused tail of a Linear/Sigmoid stack ending in ... -> 128 -> 32 -> 1 under the masked MSE (the README F0Model's layers 3-4,
  * README.rst:65-73, with morgana/losses.py:29-51), bf16 mode: forward of both layers, the loss, and the whole backward

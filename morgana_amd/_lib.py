@@ -53,6 +53,7 @@ SIGNATURES = {
     'mg_linear_fwd_f32': (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                   c_int, c_int, c_void_p]),
     'mg_linear_dgrad_f32': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'mg_linear_dgrad_act_f32': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'mg_linear_wgrad_workspace_bytes': (c_size_t, [c_int64, c_int, c_int]),
     'mg_linear_wgrad_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
                                     c_int, c_void_p, c_size_t, c_void_p]),
@@ -60,6 +61,8 @@ SIGNATURES = {
                                    c_void_p, c_int, c_int, c_int, c_void_p]),
     'mg_linear_dgrad_bf16': (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
                                      c_void_p, c_int, c_int, c_void_p]),
+    'mg_linear_dgrad_act_bf16': (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
+                                         c_void_p, c_int, c_int, c_void_p]),
     'mg_linear_wgrad_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p,
                                      c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'mg_linear_wgrad_rows_bf16': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p,
@@ -117,6 +120,8 @@ SIGNATURES = {
     'mg_calib_mfma_bf16': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'mg_sigmoid_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     'mg_sigmoid_grad_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    'mg_act_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    'mg_act_grad_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     'mg_f0_tail_workspace_bytes': (c_size_t, [c_int64]),
     'mg_f0_tail_bf16': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                 c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,

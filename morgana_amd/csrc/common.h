@@ -58,6 +58,67 @@ __device__ __forceinline__ float mg_sigmoid_fast(float x) {
     return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
 }
 
+// Epilogues of the Linear GEMM kernels (their EPI template parameter): bias (+ activation) forward, or the dgrad form
+// dX = (dY W) * f'(H) with f' written in the activation's OUTPUT H: H (1 - H), 1 - H^2, H > 0.
+#define EPI_BIAS 0
+#define EPI_BIAS_SIGMOID 1
+#define EPI_SIGMOID_GRAD 2
+#define EPI_BIAS_TANH 3
+#define EPI_BIAS_RELU 4
+#define EPI_TANH_GRAD 5
+#define EPI_RELU_GRAD 6
+#define EPI_IS_GRAD(e) ((e) == EPI_SIGMOID_GRAD || (e) == EPI_TANH_GRAD || (e) == EPI_RELU_GRAD)
+
+// One launch statement per forward / dgrad epilogue: CALL is a one-argument macro that launches its EPI instantiation.
+#define MG_SWITCH_FWD_EPI(epi, CALL)                                 \
+    do {                                                             \
+        switch (epi) {                                               \
+            case EPI_BIAS_SIGMOID: CALL(EPI_BIAS_SIGMOID); break;    \
+            case EPI_BIAS_TANH: CALL(EPI_BIAS_TANH); break;          \
+            case EPI_BIAS_RELU: CALL(EPI_BIAS_RELU); break;          \
+            default: CALL(EPI_BIAS); break;                          \
+        }                                                            \
+    } while (0)
+#define MG_SWITCH_GRAD_EPI(epi, CALL)                                \
+    do {                                                             \
+        switch (epi) {                                               \
+            case EPI_TANH_GRAD: CALL(EPI_TANH_GRAD); break;          \
+            case EPI_RELU_GRAD: CALL(EPI_RELU_GRAD); break;          \
+            default: CALL(EPI_SIGMOID_GRAD); break;                  \
+        }                                                            \
+    } while (0)
+
+static inline bool mg_act_known(int act) { return act >= MG_ACT_NONE && act <= MG_ACT_RELU; }
+static inline int mg_epi_fwd(int act) {
+    return act == MG_ACT_SIGMOID ? EPI_BIAS_SIGMOID : act == MG_ACT_TANH ? EPI_BIAS_TANH : act == MG_ACT_RELU ? EPI_BIAS_RELU : EPI_BIAS;
+}
+// the dgrad epilogue for an input that is the OUTPUT of `act` (MG_ACT_NONE: plain dX = dY W, the EPI_BIAS form without a bias)
+static inline int mg_epi_grad(int act) {
+    return act == MG_ACT_SIGMOID ? EPI_SIGMOID_GRAD : act == MG_ACT_TANH ? EPI_TANH_GRAD : act == MG_ACT_RELU ? EPI_RELU_GRAD : EPI_BIAS;
+}
+
+// relu as torch.relu has it (clamp_min(0)): NaN stays NaN and -0.0 stays -0.0
+__device__ __forceinline__ float mg_relu(float x) { return x < 0.f ? 0.f : x; }
+
+// z = the pre-activation (bias added).  FAST selects the hardware-exp sigmoid of the bf16 kernels.  Tanh is tanhf in every mode:
+// the hardware-exp form the GRU candidate gate uses (gru_cell.h: 2 sigmoid_fast(2x) - 1) cancels near 0 - its absolute error stays
+// near 2^-23 while a bf16 output rounds to |x| 2^-9, so it is above the output rounding for every |x| < 2^-14 (flushing them to
+// 0) - and the bf16x3 mode runs these kernels with fp32 outputs held to 1e-4.
+template <int EPI, bool FAST>
+__device__ __forceinline__ float mg_epi_act(float z) {
+    if (EPI == EPI_BIAS_SIGMOID) return FAST ? mg_sigmoid_fast(z) : mg_sigmoid(z);
+    if (EPI == EPI_BIAS_TANH) return tanhf(z);
+    if (EPI == EPI_BIAS_RELU) return mg_relu(z);
+    return z;
+}
+// v f'(h), h the activation's output; ReLU as torch's threshold_backward (h <= 0 ? 0 : v, so a NaN h passes v on)
+template <int EPI>
+__device__ __forceinline__ float mg_epi_dact(float v, float h) {
+    if (EPI == EPI_TANH_GRAD) return v * (1.f - h * h);
+    if (EPI == EPI_RELU_GRAD) return h <= 0.f ? 0.f : v;
+    return v * h * (1.f - h);
+}
+
 // The 32x32x16 bf16 MFMA of the large GEMM kernels behind one name, so that a PROBE build (make probe16 -> libmorgana_hip_probe16.so,
 // -DMG_PROBE16, results garbage, never loaded by the package) can issue two v_mfma_f32_16x16x32_bf16 in its place on the same
 // registers: same matrix cycles, same operand traffic, a different clock under load (MI355X_MICROARCH.md, DVFS give-back item 7).

@@ -24,10 +24,6 @@ typedef __bf16 bfv8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bfv4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-#define EPI_BIAS 0
-#define EPI_BIAS_SIGMOID 1
-#define EPI_SIGMOID_GRAD 2
-
 #define NT_BK 32  // contraction depth per LDS tile (2 MFMA k-steps)
 
 __device__ __forceinline__ u32x4 ldg16(const uint16_t* p) { return *reinterpret_cast<const u32x4*>(p); }
@@ -176,17 +172,14 @@ __global__ __launch_bounds__(256) void gemm_nt_bf16_kernel(const uint16_t* __res
         const f32x4 v1 = *reinterpret_cast<const f32x4*>(&stg[rl * STG_LD + cl + 4]);
         float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
         bfv8 hv;
-        if (EPI == EPI_SIGMOID_GRAD) hv = *reinterpret_cast<const bfv8*>(H + (size_t)row * ldh + col);
+        if (EPI_IS_GRAD(EPI)) hv = *reinterpret_cast<const bfv8*>(H + (size_t)row * ldh + col);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             float x = v[e];
             if (col + e >= N) x = 0.f;
             else if (EPI == EPI_BIAS) x += bias ? bias[col + e] : 0.f;
-            else if (EPI == EPI_BIAS_SIGMOID) x = mg_sigmoid_fast(x + (bias ? bias[col + e] : 0.f));
-            else {
-                const float h = (float)hv[e];
-                x = x * h * (1.f - h);
-            }
+            else if (!EPI_IS_GRAD(EPI)) x = mg_epi_act<EPI, true>(x + (bias ? bias[col + e] : 0.f));
+            else x = mg_epi_dact<EPI>(x, (float)hv[e]);
             v[e] = x;
         }
         if (c_f32) {
@@ -380,7 +373,7 @@ int mg_try_nt_big(const uint16_t* A, int lda, const int32_t* rows, int64_t M, in
                   const float* bias, const uint16_t* H, int ldh, const int32_t* h_rows, void* C, int ldc, int c_f32, int epi,
                   hipStream_t st);
 int mg_try_nt_runs(const uint16_t* A, int lda, const int32_t* rows, int64_t M, int K, const uint16_t* Bm, int ldb, int N,
-                   const float* bias, uint16_t* C, int ldc, int sigmoid, hipStream_t st);       // gemm_nt_runs.hip
+                   const float* bias, uint16_t* C, int ldc, int epi, hipStream_t st);           // gemm_nt_runs.hip
 int mg_wgrad_big_plan(int64_t M, int N, int K, int lda, int lddy, int* S_out, int* m_chunk_out);
 int mg_launch_wgrad_big(const uint16_t* dY, int lddy, const uint16_t* A, int lda, const int32_t* rows, int64_t M, int N, int K,
                         int S, int m_chunk, float* slab, float* bslab, int64_t sstride, hipStream_t st, const int32_t* dy_rows = nullptr, int x3 = 0);
@@ -407,17 +400,17 @@ int mg_linear_fwd_bf16(const uint16_t* A, int lda, const int32_t* rows, int64_t 
     MG_CHECK_ARG(al16(A) && al16(W) && al16(Y), "mg_linear_fwd_bf16: buffers must be 16-byte aligned");
     const int runs_hint = act & MG_ACT_ROWS_RUNS;
     act &= ~MG_ACT_ROWS_RUNS;
-    MG_CHECK_ARG(act == MG_ACT_NONE || act == MG_ACT_SIGMOID, "mg_linear_fwd_bf16: unknown activation %d", act);
+    MG_CHECK_ARG(mg_act_known(act), "mg_linear_fwd_bf16: unknown activation %d", act);
     if (M == 0) return MG_OK;
+    const int epi = mg_epi_fwd(act);
     hipStream_t st = (hipStream_t)stream;
     // rows made of runs (frame map of upsample_to_repetitions): the gathered operand staged once per distinct row, two workgroups per CU
     if (runs_hint && rows && !y_f32 && ldy == N && g_mg_tuning[MG_TUNE_FORM] != 14 &&
-        mg_try_nt_runs(A, lda, rows, M, K, W, ldw, N, bias, (uint16_t*)Y, ldy, act == MG_ACT_SIGMOID, st) > 0) {
+        mg_try_nt_runs(A, lda, rows, M, K, W, ldw, N, bias, (uint16_t*)Y, ldy, epi, st) > 0) {
         MG_CHECK_LAUNCH("mg_linear_fwd_bf16/runs");
         return MG_OK;
     }
-    if (ldy == N && mg_try_nt_big(A, lda, rows, M, K, W, ldw, N, bias, nullptr, 0, nullptr, Y, ldy, y_f32,
-                                  act == MG_ACT_SIGMOID ? EPI_BIAS_SIGMOID : EPI_BIAS, st) > 0) {
+    if (ldy == N && mg_try_nt_big(A, lda, rows, M, K, W, ldw, N, bias, nullptr, 0, nullptr, Y, ldy, y_f32, epi, st) > 0) {
         MG_CHECK_LAUNCH("mg_linear_fwd_bf16/big");
         return MG_OK;
     }
@@ -425,55 +418,70 @@ int mg_linear_fwd_bf16(const uint16_t* A, int lda, const int32_t* rows, int64_t 
         const int tn = (int)mg_ceil_div(ldy, 32);
         const int64_t blocks = mg_ceil_div(M, 128) * tn;
         MG_CHECK_ARG(blocks < 2147483647LL, "mg_linear_fwd_bf16: grid too large");
-        if (act == MG_ACT_SIGMOID)
-            hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 32, 4, 1, EPI_BIAS_SIGMOID>), dim3((unsigned)blocks), dim3(256), 0, st, A, lda, rows, M, W, ldw, N, bias, nullptr, 0, Y, ldy, tn, y_f32);
-        else
-            hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 32, 4, 1, EPI_BIAS>), dim3((unsigned)blocks), dim3(256), 0, st, A, lda, rows, M, W, ldw, N, bias, nullptr, 0, Y, ldy, tn, y_f32);
+#define FWD_NARROW(EPI_) hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 32, 4, 1, EPI_>), dim3((unsigned)blocks), dim3(256), 0, st, A, lda, rows, M, W, ldw, N, bias, nullptr, 0, Y, ldy, tn, y_f32)
+        MG_SWITCH_FWD_EPI(epi, FWD_NARROW);
+#undef FWD_NARROW
     } else {
         const int tn = (int)mg_ceil_div(ldy, 128);
         const int64_t blocks = mg_ceil_div(M, 128) * tn;
         MG_CHECK_ARG(blocks < 2147483647LL, "mg_linear_fwd_bf16: grid too large");
-        if (act == MG_ACT_SIGMOID)
-            hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 128, 2, 2, EPI_BIAS_SIGMOID>), dim3((unsigned)blocks), dim3(256), 0, st, A, lda, rows, M, W, ldw, N, bias, nullptr, 0, Y, ldy, tn, y_f32);
-        else
-            hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 128, 2, 2, EPI_BIAS>), dim3((unsigned)blocks), dim3(256), 0, st, A, lda, rows, M, W, ldw, N, bias, nullptr, 0, Y, ldy, tn, y_f32);
+#define FWD_WIDE(EPI_) hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 128, 2, 2, EPI_>), dim3((unsigned)blocks), dim3(256), 0, st, A, lda, rows, M, W, ldw, N, bias, nullptr, 0, Y, ldy, tn, y_f32)
+        MG_SWITCH_FWD_EPI(epi, FWD_WIDE);
+#undef FWD_WIDE
     }
     MG_CHECK_LAUNCH("mg_linear_fwd_bf16");
     return MG_OK;
 }
 
+// dX = (dY W) * f'(H): H the output of activation `act` that fed this layer (MG_ACT_NONE or H == NULL: dX = dY W)
+int mg_linear_dgrad_act_bf16(const uint16_t* dY, int lddy, int64_t M, int N, const uint16_t* WT, int ldwt, int K,
+                             const uint16_t* H, int ldh, int act, void* dX, int lddx, int dx_f32, void* stream) {
+    MG_CHECK_ARG(dY && WT && dX && M >= 0 && N > 0 && K > 0, "mg_linear_dgrad_act_bf16: bad arguments (M=%lld N=%d K=%d)", (long long)M, N, K);
+    MG_CHECK_ARG(mg_act_known(act), "mg_linear_dgrad_act_bf16: unknown activation %d", act);
+    MG_CHECK_ARG(H || act == MG_ACT_NONE, "mg_linear_dgrad_act_bf16: activation %d needs its output H", act);
+    MG_CHECK_ARG(lddy >= N && ldwt >= N && lddx >= K && lddy % 8 == 0 && ldwt % 8 == 0 && lddx % 8 == 0 && (!H || (ldh >= K && ldh % 8 == 0)),
+                 "mg_linear_dgrad_act_bf16: leading dimensions must be multiples of 8 and cover N=%d / K=%d (lddy=%d ldwt=%d lddx=%d ldh=%d)", N, K, lddy, ldwt, lddx, ldh);
+    MG_CHECK_ARG(al16(dY) && al16(WT) && al16(dX) && (!H || al16(H)), "mg_linear_dgrad_act_bf16: buffers must be 16-byte aligned");
+    if (M == 0) return MG_OK;
+    if (act == MG_ACT_NONE) H = nullptr;
+    const int epi = mg_epi_grad(act);
+    hipStream_t st = (hipStream_t)stream;
+    // C[M,K] = dY[M,N] * WT[K,N]^T : the NT kernel with contraction N, output width K.
+    if (lddx == K && mg_try_nt_big(dY, lddy, nullptr, M, N, WT, ldwt, K, nullptr, H, ldh, nullptr, dX, lddx, dx_f32, epi, st) > 0) {
+        MG_CHECK_LAUNCH("mg_linear_dgrad_act_bf16/big");
+        return MG_OK;
+    }
+    if (K <= 32) {
+        const int tn = (int)mg_ceil_div(lddx, 32);
+        const int64_t blocks = mg_ceil_div(M, 128) * tn;
+        MG_CHECK_ARG(blocks < 2147483647LL, "mg_linear_dgrad_act_bf16: grid too large");
+#define DGRAD_NARROW(EPI_) hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 32, 4, 1, EPI_>), dim3((unsigned)blocks), dim3(256), 0, st, dY, lddy, nullptr, M, WT, ldwt, K, nullptr, H, ldh, dX, lddx, tn, dx_f32)
+        if (H) MG_SWITCH_GRAD_EPI(epi, DGRAD_NARROW);
+        else
+            hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 32, 4, 1, EPI_BIAS>), dim3((unsigned)blocks), dim3(256), 0, st, dY, lddy, nullptr, M, WT, ldwt, K, nullptr, nullptr, 0, dX, lddx, tn, dx_f32);
+#undef DGRAD_NARROW
+    } else {
+        const int tn = (int)mg_ceil_div(lddx, 128);
+        const int64_t blocks = mg_ceil_div(M, 128) * tn;
+        MG_CHECK_ARG(blocks < 2147483647LL, "mg_linear_dgrad_act_bf16: grid too large");
+#define DGRAD_WIDE(EPI_) hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 128, 2, 2, EPI_>), dim3((unsigned)blocks), dim3(256), 0, st, dY, lddy, nullptr, M, WT, ldwt, K, nullptr, H, ldh, dX, lddx, tn, dx_f32)
+        if (H) MG_SWITCH_GRAD_EPI(epi, DGRAD_WIDE);
+        else
+            hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 128, 2, 2, EPI_BIAS>), dim3((unsigned)blocks), dim3(256), 0, st, dY, lddy, nullptr, M, WT, ldwt, K, nullptr, nullptr, 0, dX, lddx, tn, dx_f32);
+#undef DGRAD_WIDE
+    }
+    MG_CHECK_LAUNCH("mg_linear_dgrad_act_bf16");
+    return MG_OK;
+}
+
+// the Sigmoid form of mg_linear_dgrad_act_bf16 (H == NULL: no activation)
 int mg_linear_dgrad_bf16(const uint16_t* dY, int lddy, int64_t M, int N, const uint16_t* WT, int ldwt, int K,
                          const uint16_t* H, int ldh, void* dX, int lddx, int dx_f32, void* stream) {
     MG_CHECK_ARG(dY && WT && dX && M >= 0 && N > 0 && K > 0, "mg_linear_dgrad_bf16: bad arguments (M=%lld N=%d K=%d)", (long long)M, N, K);
     MG_CHECK_ARG(lddy >= N && ldwt >= N && lddx >= K && lddy % 8 == 0 && ldwt % 8 == 0 && lddx % 8 == 0 && (!H || (ldh >= K && ldh % 8 == 0)),
                  "mg_linear_dgrad_bf16: leading dimensions must be multiples of 8 and cover N=%d / K=%d (lddy=%d ldwt=%d lddx=%d ldh=%d)", N, K, lddy, ldwt, lddx, ldh);
     MG_CHECK_ARG(al16(dY) && al16(WT) && al16(dX) && (!H || al16(H)), "mg_linear_dgrad_bf16: buffers must be 16-byte aligned");
-    if (M == 0) return MG_OK;
-    hipStream_t st = (hipStream_t)stream;
-    // C[M,K] = dY[M,N] * WT[K,N]^T : the NT kernel with contraction N, output width K.
-    if (lddx == K && mg_try_nt_big(dY, lddy, nullptr, M, N, WT, ldwt, K, nullptr, H, ldh, nullptr, dX, lddx, dx_f32,
-                                   H ? EPI_SIGMOID_GRAD : EPI_BIAS, st) > 0) {
-        MG_CHECK_LAUNCH("mg_linear_dgrad_bf16/big");
-        return MG_OK;
-    }
-    if (K <= 32) {
-        const int tn = (int)mg_ceil_div(lddx, 32);
-        const int64_t blocks = mg_ceil_div(M, 128) * tn;
-        if (H)
-            hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 32, 4, 1, EPI_SIGMOID_GRAD>), dim3((unsigned)blocks), dim3(256), 0, st, dY, lddy, nullptr, M, WT, ldwt, K, nullptr, H, ldh, dX, lddx, tn, dx_f32);
-        else
-            hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 32, 4, 1, EPI_BIAS>), dim3((unsigned)blocks), dim3(256), 0, st, dY, lddy, nullptr, M, WT, ldwt, K, nullptr, nullptr, 0, dX, lddx, tn, dx_f32);
-    } else {
-        const int tn = (int)mg_ceil_div(lddx, 128);
-        const int64_t blocks = mg_ceil_div(M, 128) * tn;
-        MG_CHECK_ARG(blocks < 2147483647LL, "mg_linear_dgrad_bf16: grid too large");
-        if (H)
-            hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 128, 2, 2, EPI_SIGMOID_GRAD>), dim3((unsigned)blocks), dim3(256), 0, st, dY, lddy, nullptr, M, WT, ldwt, K, nullptr, H, ldh, dX, lddx, tn, dx_f32);
-        else
-            hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 128, 2, 2, EPI_BIAS>), dim3((unsigned)blocks), dim3(256), 0, st, dY, lddy, nullptr, M, WT, ldwt, K, nullptr, nullptr, 0, dX, lddx, tn, dx_f32);
-    }
-    MG_CHECK_LAUNCH("mg_linear_dgrad_bf16");
-    return MG_OK;
+    return mg_linear_dgrad_act_bf16(dY, lddy, M, N, WT, ldwt, K, H, ldh, H ? MG_ACT_SIGMOID : MG_ACT_NONE, dX, lddx, dx_f32, stream);
 }
 
 // dX = (dY W) * H[h_rows] (1 - H[h_rows]): mg_linear_dgrad_bf16 with the sigmoid outputs read from a TABLE (the phone-rate first
@@ -676,12 +684,12 @@ int mg_phone_front_linear_fwd_bf16(const int64_t* dur, int B, int P, int T, cons
     int rc = mg_phone_front_check(dur, B, P, T, target, extra, rows32, rows_mapped, seg_start, seg_end, ybar, weight, workspace, workspace_bytes,
                                   "mg_phone_front_linear_fwd_bf16");
     if (rc != MG_OK) return rc;
-    MG_CHECK_ARG(A && W && Y && M > 0 && N > 0 && K > 0 && (act == MG_ACT_NONE || act == MG_ACT_SIGMOID),
+    MG_CHECK_ARG(A && W && Y && M > 0 && N > 0 && K > 0 && mg_act_known(act),
                  "mg_phone_front_linear_fwd_bf16: bad GEMM arguments (M=%lld N=%d K=%d act=%d)", (long long)M, N, K, act);
     PhoneFrontArgs pf{dur, target, seq_len, B, P, T, extra, rows32, rows_mapped, pad_row, seg_start, seg_end, ybar, weight, (float*)workspace, 0, 0};
+    // (the one-grid form holds the bias / bias + sigmoid epilogues only: Tanh and ReLU layers take the two launches)
     if (bias && lda >= K && ldw >= K && lda % 8 == 0 && ldw % 8 == 0 &&
-        mg_launch_phone_front_gemm(pf, A, lda, M, K, W, ldw, N, bias, Y, ldy, act == MG_ACT_SIGMOID ? EPI_BIAS_SIGMOID : EPI_BIAS,
-                                   (hipStream_t)stream) > 0) {
+        mg_launch_phone_front_gemm(pf, A, lda, M, K, W, ldw, N, bias, Y, ldy, mg_epi_fwd(act), (hipStream_t)stream) > 0) {
         MG_CHECK_LAUNCH("mg_phone_front_linear_fwd_bf16/one grid");
         return MG_OK;
     }

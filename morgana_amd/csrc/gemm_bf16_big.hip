@@ -24,9 +24,6 @@
 typedef __bf16 bfv8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bfv4 __attribute__((ext_vector_type(4)));
 
-#define EPI_BIAS 0
-#define EPI_BIAS_SIGMOID 1
-#define EPI_SIGMOID_GRAD 2
 
 #define MG_ZERO_ELEMS 16384
 __device__ uint16_t g_zero_row[MG_ZERO_ELEMS];   // zero-initialised: source of pad rows / out-of-range rows
@@ -236,7 +233,7 @@ __device__ __forceinline__ void gemm_nt_big_body(unsigned char* __restrict__ sme
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
-                    if (EPI == EPI_SIGMOID_GRAD) acc[i][j] = mg_mfma_32x32x16(a[i], b[j], acc[i][j]);
+                    if (EPI_IS_GRAD(EPI)) acc[i][j] = mg_mfma_32x32x16(a[i], b[j], acc[i][j]);
                     else acc[i][j] = mg_mfma_32x32x16(b[j], a[i], acc[i][j]);
                 }
         }
@@ -246,8 +243,8 @@ __device__ __forceinline__ void gemm_nt_big_body(unsigned char* __restrict__ sme
     MG_STAMP(ts2);
     // the diagnostic build ends with the epilogue's stores drained, so that its stamp covers them
 #endif
-    if (EPI == EPI_SIGMOID_GRAD) {
-        // Memory-bound variant (dX = (dY W) * H (1 - H), K small): plain C layout, fp32 sub-tiles staged through LDS so that
+    if (EPI_IS_GRAD(EPI)) {
+        // Memory-bound variant (dX = (dY W) * f'(H): H (1 - H), 1 - H^2 or H > 0; K small): plain C layout, fp32 sub-tiles staged through LDS so that
         // H is read and dX written as whole 16-byte row pieces (8 lanes per 128-byte row segment).
         constexpr int STG_LD = 68;
         WAIT_LGKM_BARRIER();                                   // all waves are done with the tile stages
@@ -294,10 +291,7 @@ __device__ __forceinline__ void gemm_nt_big_body(unsigned char* __restrict__ sme
                     continue;
                 }
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float h = (float)hv[e];
-                    v[e] = v[e] * h * (1.f - h);
-                }
+                for (int e = 0; e < 8; ++e) v[e] = mg_epi_dact<EPI>(v[e], (float)hv[e]);
                 if (c_f32) {
                     float* crow = reinterpret_cast<float*>(Cv) + (size_t)row * ldc + col;
                     *reinterpret_cast<f32x4*>(crow) = f32x4{v[0], v[1], v[2], v[3]};
@@ -330,7 +324,7 @@ __device__ __forceinline__ void gemm_nt_big_body(unsigned char* __restrict__ sme
     // Accumulator layout of sub-tile (i, j): this lane's frame row m = m0 + wm0 + 32 i + (lane & 31); register 4g + e is
     // column n0 + wn0 + 32 j + 8 g + 4 (lane >> 5) + e.
     float bv[TN][16];
-    if (EPI != EPI_SIGMOID_GRAD) {
+    if (!EPI_IS_GRAD(EPI)) {
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -356,7 +350,7 @@ __device__ __forceinline__ void gemm_nt_big_body(unsigned char* __restrict__ sme
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float x = acc[i][j][4 * g + e] + bv[j][4 * g + e];
-                        if (EPI == EPI_BIAS_SIGMOID) x = mg_sigmoid_fast(x);
+                        x = mg_epi_act<EPI, true>(x);
                         v[e] = x;
                     }
                     typedef __bf16 bfv2 __attribute__((ext_vector_type(2)));
@@ -390,7 +384,7 @@ __device__ __forceinline__ void gemm_nt_big_body(unsigned char* __restrict__ sme
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float x = acc[i][j][4 * g + e] + bv[j][4 * g + e];
-                    if (EPI == EPI_BIAS_SIGMOID) x = mg_sigmoid_fast(x);
+                    x = mg_epi_act<EPI, true>(x);
                     v[e] = x;
                 }
                 *reinterpret_cast<f32x4*>(crow + 8 * g) = f32x4{v[0], v[1], v[2], v[3]};
@@ -923,7 +917,7 @@ __device__ __forceinline__ void gemm_nt_persist_body(unsigned char* __restrict__
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             float x = acc[i][j][4 * q + e] + bq[e];
-                            if (EPI == EPI_BIAS_SIGMOID) x = mg_sigmoid_fast(x);
+                            x = mg_epi_act<EPI, true>(x);
                             v[e] = x;
                         }
                         typedef __bf16 bfv2 __attribute__((ext_vector_type(2)));
@@ -972,7 +966,7 @@ __device__ __forceinline__ void gemm_nt_persist_body(unsigned char* __restrict__
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float x = acc[i][j][4 * q + e] + bv[j][q][e];
-                        if (EPI == EPI_BIAS_SIGMOID) x = mg_sigmoid_fast(x);
+                        x = mg_epi_act<EPI, true>(x);
                         v[e] = x;
                     }
                     const bfv2 h01 = bfv2{(__bf16)v[0], (__bf16)v[1]}, h23 = bfv2{(__bf16)v[2], (__bf16)v[3]};
@@ -1491,7 +1485,7 @@ int mg_try_nt_big(const uint16_t* A, int lda, const int32_t* rows, int64_t M, in
                   hipStream_t st) {
     if (M < 2048 || lda % 64 != 0 || ldb % 64 != 0 || lda > MG_ZERO_ELEMS - 64 || ldb > MG_ZERO_ELEMS - 64) return 0;
     if (N % 128 != 0 || ldc < N || ldc % 8 != 0 || !big16(A) || !big16(Bm) || !big16(C)) return 0;
-    if (epi == EPI_SIGMOID_GRAD && (!H || ldh % 8 != 0 || ldh < N)) return 0;
+    if (EPI_IS_GRAD(epi) && (!H || ldh % 8 != 0 || ldh < N)) return 0;
     if (ldc != N || lda < (K + 63) / 64 * 64 || ldb < (K + 63) / 64 * 64) return 0;
     // Tile width: 256 where N allows it - unless that leaves most of the chip idle.  At the phone-rate row counts of the recurrent
     // models (RNN_SPSS at C4 / C5: 6,144 table rows = 24 M tiles) a 512-wide layer is 48 workgroups of 256 x 256 on 256 CUs, each a
@@ -1510,7 +1504,7 @@ int mg_try_nt_big(const uint16_t* A, int lda, const int32_t* rows, int64_t M, in
     // Persistent form: bias / bias + sigmoid with bf16 output, at least one ring of k-tiles per tile, a stores-per-row pattern
     // that needs every store of a row in range (M is arbitrary: rows past the end are skipped per lane).
     const int n_kt = (K + 31) / 32;
-    if (!c_f32 && epi != EPI_SIGMOID_GRAD && n_kt >= 5 && M < 2147483647LL && 32 % tiles_n == 0 && g_mg_tuning[MG_TUNE_FORM] != 6) {
+    if (!c_f32 && !EPI_IS_GRAD(epi) && n_kt >= 5 && M < 2147483647LL && 32 % tiles_n == 0 && g_mg_tuning[MG_TUNE_FORM] != 6) {
         int64_t g = 256;                                             // one resident workgroup per CU
         while (mg_ceil_div(blocks, g) > NTP_MAX_TILES(bn)) g += 256;    // more tiles than a workgroup parks rows for: more groups
         if (g > blocks) g = mg_ceil_div(blocks, 8 * tiles_n) * 8 * tiles_n;
@@ -1521,7 +1515,7 @@ int mg_try_nt_big(const uint16_t* A, int lda, const int32_t* rows, int64_t M, in
         // Lab builds only (make lab / diag): measured alternatives of the square tile and its timing probes (results garbage for the
         // probes) - MG_TUNE_FORM 4 = wave groups half a k-step apart, 2 = half-step software pipeline, 5 / 11 = DMA pieces spread between
         // the MFMAs, 9 / 10 / 12 / 13 = role-split probes, 32 + mask / 256 + mask = parts of the k-step switched off.
-        const int form = g_mg_tuning[MG_TUNE_FORM];
+        const int form = (epi == EPI_BIAS || epi == EPI_BIAS_SIGMOID) ? g_mg_tuning[MG_TUNE_FORM] : 0;   // the lab forms know these two only
         const int probe = form >= 256 ? form - 256 : form >= 32 ? form - 32 : 0;
         if (wide && (form == 5 || form == 11)) {
             const int pr = form == 11 ? 32 : 0;
@@ -1545,27 +1539,31 @@ int mg_try_nt_big(const uint16_t* A, int lda, const int32_t* rows, int64_t M, in
 #else
         const int probe = 0;
 #endif
-        if (wide) {
-            if (epi == EPI_BIAS) LAUNCH_NTP(256, EPI_BIAS, false, 32); else LAUNCH_NTP(256, EPI_BIAS_SIGMOID, false, 32);
-        } else if (deep) {
-            if (epi == EPI_BIAS) LAUNCH_NTP(128, EPI_BIAS, false, 64); else LAUNCH_NTP(128, EPI_BIAS_SIGMOID, false, 64);
-        } else {
-            if (epi == EPI_BIAS) LAUNCH_NTP(128, EPI_BIAS, false, 32); else LAUNCH_NTP(128, EPI_BIAS_SIGMOID, false, 32);
-        }
+#define NTP_WIDE(EPI_) LAUNCH_NTP(256, EPI_, false, 32)
+#define NTP_DEEP(EPI_) LAUNCH_NTP(128, EPI_, false, 64)
+#define NTP_HALF(EPI_) LAUNCH_NTP(128, EPI_, false, 32)
+        if (wide) MG_SWITCH_FWD_EPI(epi, NTP_WIDE);
+        else if (deep) MG_SWITCH_FWD_EPI(epi, NTP_DEEP);
+        else MG_SWITCH_FWD_EPI(epi, NTP_HALF);
+#undef NTP_WIDE
+#undef NTP_DEEP
+#undef NTP_HALF
 #undef LAUNCH_NTP
         return 1;
     }
     dim3 grid((unsigned)blocks), block(512);
 #define LAUNCH_NT(BN_, EPI_) hipLaunchKernelGGL((gemm_nt_big_kernel<BN_, EPI_>), grid, block, 0, st, A, lda, rows, M, K, Bm, ldb, N, bias, H, ldh, h_rows, C, ldc, (int)tiles_m, tiles_n, c_f32)
+#define NT_WIDE(EPI_) LAUNCH_NT(256, EPI_)
+#define NT_HALF(EPI_) LAUNCH_NT(128, EPI_)
     if (wide) {
-        if (epi == EPI_BIAS) LAUNCH_NT(256, EPI_BIAS);
-        else if (epi == EPI_BIAS_SIGMOID) LAUNCH_NT(256, EPI_BIAS_SIGMOID);
-        else LAUNCH_NT(256, EPI_SIGMOID_GRAD);
+        if (EPI_IS_GRAD(epi)) MG_SWITCH_GRAD_EPI(epi, NT_WIDE);
+        else MG_SWITCH_FWD_EPI(epi, NT_WIDE);
     } else {
-        if (epi == EPI_BIAS) LAUNCH_NT(128, EPI_BIAS);
-        else if (epi == EPI_BIAS_SIGMOID) LAUNCH_NT(128, EPI_BIAS_SIGMOID);
-        else LAUNCH_NT(128, EPI_SIGMOID_GRAD);
+        if (EPI_IS_GRAD(epi)) MG_SWITCH_GRAD_EPI(epi, NT_HALF);
+        else MG_SWITCH_FWD_EPI(epi, NT_HALF);
     }
+#undef NT_WIDE
+#undef NT_HALF
 #undef LAUNCH_NT
     return 1;
 }

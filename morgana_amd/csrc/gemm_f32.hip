@@ -32,10 +32,6 @@ __device__ __forceinline__ f32x4 load4_guard(const float* p, int valid, bool vec
     return v;
 }
 
-#define EPI_BIAS 0
-#define EPI_BIAS_SIGMOID 1
-#define EPI_SIGMOID_GRAD 2
-
 // C[M,N] = epi( A'[M,Kc] * B ), A' = rows ? A[rows[m]] : A[m]
 //   B_KN == false: Bm is [N, Kc] row-major (C = A Bm^T);  B_KN == true: Bm is [Kc, N] row-major (C = A Bm).
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool B_KN, int EPI>
@@ -174,18 +170,15 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
         for (int j = 0; j < TN; ++j) {
             const int col = n0 + wn0 + j * 32 + lr;
             if (col >= N) continue;
-            const float bv = (EPI != EPI_SIGMOID_GRAD && bias) ? bias[col] : 0.f;
+            const float bv = (!EPI_IS_GRAD(EPI) && bias) ? bias[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int64_t row = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 if (row >= M) continue;
                 float v = acc[i][j][r];
                 if (EPI == EPI_BIAS) v += bv;
-                else if (EPI == EPI_BIAS_SIGMOID) v = mg_sigmoid(v + bv);
-                else {
-                    const float h = H[(size_t)row * ldh + col];
-                    v = v * h * (1.f - h);
-                }
+                else if (!EPI_IS_GRAD(EPI)) v = mg_epi_act<EPI, false>(v + bv);
+                else v = mg_epi_dact<EPI>(v, H[(size_t)row * ldh + col]);
                 C[(size_t)row * ldc + col] = v;
             }
         }
@@ -356,8 +349,9 @@ int mg_linear_fwd_f32(const float* A, int lda, const int32_t* rows, int64_t M, i
                       int N, float* Y, int ldy, int act, void* stream) {
     MG_CHECK_ARG(A && W && Y && M >= 0 && K > 0 && N > 0 && lda >= K && ldy >= N, "mg_linear_fwd_f32: bad arguments (M=%lld K=%d N=%d lda=%d ldy=%d)",
                  (long long)M, K, N, lda, ldy);
-    MG_CHECK_ARG(act == MG_ACT_NONE || act == MG_ACT_SIGMOID, "mg_linear_fwd_f32: unknown activation %d", act);
+    MG_CHECK_ARG(mg_act_known(act), "mg_linear_fwd_f32: unknown activation %d", act);
     if (M == 0) return MG_OK;
+    const int epi = mg_epi_fwd(act);
     const int vec_a = (lda % 4 == 0) && aligned16(A);
     const int vec_b = (K % 4 == 0) && aligned16(W);
     hipStream_t st = (hipStream_t)stream;
@@ -365,26 +359,28 @@ int mg_linear_fwd_f32(const float* A, int lda, const int32_t* rows, int64_t M, i
         const int tn = (int)mg_ceil_div(N, 32);
         const int64_t blocks = mg_ceil_div(M, 128) * tn;
         MG_CHECK_ARG(blocks < 2147483647LL, "mg_linear_fwd_f32: grid too large");
-        if (act == MG_ACT_SIGMOID)
-            hipLaunchKernelGGL((gemm_f32_kernel<128, 32, 4, 1, false, EPI_BIAS_SIGMOID>), dim3((unsigned)blocks), dim3(256), 0, st, A, lda, rows, M, K, W, K, N, bias, nullptr, 0, Y, ldy, tn, vec_a, vec_b);
-        else
-            hipLaunchKernelGGL((gemm_f32_kernel<128, 32, 4, 1, false, EPI_BIAS>), dim3((unsigned)blocks), dim3(256), 0, st, A, lda, rows, M, K, W, K, N, bias, nullptr, 0, Y, ldy, tn, vec_a, vec_b);
+#define FWD_NARROW(EPI_) hipLaunchKernelGGL((gemm_f32_kernel<128, 32, 4, 1, false, EPI_>), dim3((unsigned)blocks), dim3(256), 0, st, A, lda, rows, M, K, W, K, N, bias, nullptr, 0, Y, ldy, tn, vec_a, vec_b)
+        MG_SWITCH_FWD_EPI(epi, FWD_NARROW);
+#undef FWD_NARROW
     } else {
         const int tn = (int)mg_ceil_div(N, 128);
         const int64_t blocks = mg_ceil_div(M, 128) * tn;
         MG_CHECK_ARG(blocks < 2147483647LL, "mg_linear_fwd_f32: grid too large");
-        if (act == MG_ACT_SIGMOID)
-            hipLaunchKernelGGL((gemm_f32_kernel<128, 128, 2, 2, false, EPI_BIAS_SIGMOID>), dim3((unsigned)blocks), dim3(256), 0, st, A, lda, rows, M, K, W, K, N, bias, nullptr, 0, Y, ldy, tn, vec_a, vec_b);
-        else
-            hipLaunchKernelGGL((gemm_f32_kernel<128, 128, 2, 2, false, EPI_BIAS>), dim3((unsigned)blocks), dim3(256), 0, st, A, lda, rows, M, K, W, K, N, bias, nullptr, 0, Y, ldy, tn, vec_a, vec_b);
+#define FWD_WIDE(EPI_) hipLaunchKernelGGL((gemm_f32_kernel<128, 128, 2, 2, false, EPI_>), dim3((unsigned)blocks), dim3(256), 0, st, A, lda, rows, M, K, W, K, N, bias, nullptr, 0, Y, ldy, tn, vec_a, vec_b)
+        MG_SWITCH_FWD_EPI(epi, FWD_WIDE);
+#undef FWD_WIDE
     }
     MG_CHECK_LAUNCH("mg_linear_fwd_f32");
     return MG_OK;
 }
 
-int mg_linear_dgrad_f32(const float* dY, int64_t M, int N, const float* W, int K, const float* H, float* dX, void* stream) {
-    MG_CHECK_ARG(dY && W && dX && M >= 0 && N > 0 && K > 0, "mg_linear_dgrad_f32: bad arguments (M=%lld N=%d K=%d)", (long long)M, N, K);
+// dX = (dY W) * f'(H): H the output of activation `act` that fed this layer (MG_ACT_NONE or H == NULL: dX = dY W)
+int mg_linear_dgrad_act_f32(const float* dY, int64_t M, int N, const float* W, int K, const float* H, int act, float* dX, void* stream) {
+    MG_CHECK_ARG(dY && W && dX && M >= 0 && N > 0 && K > 0, "mg_linear_dgrad_act_f32: bad arguments (M=%lld N=%d K=%d)", (long long)M, N, K);
+    MG_CHECK_ARG(mg_act_known(act), "mg_linear_dgrad_act_f32: unknown activation %d", act);
+    MG_CHECK_ARG(H || act == MG_ACT_NONE, "mg_linear_dgrad_act_f32: activation %d needs its output H", act);
     if (M == 0) return MG_OK;
+    const int epi = H ? mg_epi_grad(act) : EPI_BIAS;
     const int vec_a = (N % 4 == 0) && aligned16(dY);
     const int vec_b = (K % 4 == 0) && aligned16(W);
     hipStream_t st = (hipStream_t)stream;
@@ -392,21 +388,30 @@ int mg_linear_dgrad_f32(const float* dY, int64_t M, int N, const float* W, int K
     if (K <= 32) {
         const int tn = (int)mg_ceil_div(K, 32);
         const int64_t blocks = mg_ceil_div(M, 128) * tn;
-        if (H)
-            hipLaunchKernelGGL((gemm_f32_kernel<128, 32, 4, 1, true, EPI_SIGMOID_GRAD>), dim3((unsigned)blocks), dim3(256), 0, st, dY, N, nullptr, M, N, W, K, K, nullptr, H, K, dX, K, tn, vec_a, vec_b);
+        MG_CHECK_ARG(blocks < 2147483647LL, "mg_linear_dgrad_act_f32: grid too large");
+#define DGRAD_NARROW(EPI_) hipLaunchKernelGGL((gemm_f32_kernel<128, 32, 4, 1, true, EPI_>), dim3((unsigned)blocks), dim3(256), 0, st, dY, N, nullptr, M, N, W, K, K, nullptr, H, K, dX, K, tn, vec_a, vec_b)
+        if (epi != EPI_BIAS) MG_SWITCH_GRAD_EPI(epi, DGRAD_NARROW);
         else
             hipLaunchKernelGGL((gemm_f32_kernel<128, 32, 4, 1, true, EPI_BIAS>), dim3((unsigned)blocks), dim3(256), 0, st, dY, N, nullptr, M, N, W, K, K, nullptr, nullptr, 0, dX, K, tn, vec_a, vec_b);
+#undef DGRAD_NARROW
     } else {
         const int tn = (int)mg_ceil_div(K, 128);
         const int64_t blocks = mg_ceil_div(M, 128) * tn;
-        MG_CHECK_ARG(blocks < 2147483647LL, "mg_linear_dgrad_f32: grid too large");
-        if (H)
-            hipLaunchKernelGGL((gemm_f32_kernel<128, 128, 2, 2, true, EPI_SIGMOID_GRAD>), dim3((unsigned)blocks), dim3(256), 0, st, dY, N, nullptr, M, N, W, K, K, nullptr, H, K, dX, K, tn, vec_a, vec_b);
+        MG_CHECK_ARG(blocks < 2147483647LL, "mg_linear_dgrad_act_f32: grid too large");
+#define DGRAD_WIDE(EPI_) hipLaunchKernelGGL((gemm_f32_kernel<128, 128, 2, 2, true, EPI_>), dim3((unsigned)blocks), dim3(256), 0, st, dY, N, nullptr, M, N, W, K, K, nullptr, H, K, dX, K, tn, vec_a, vec_b)
+        if (epi != EPI_BIAS) MG_SWITCH_GRAD_EPI(epi, DGRAD_WIDE);
         else
             hipLaunchKernelGGL((gemm_f32_kernel<128, 128, 2, 2, true, EPI_BIAS>), dim3((unsigned)blocks), dim3(256), 0, st, dY, N, nullptr, M, N, W, K, K, nullptr, nullptr, 0, dX, K, tn, vec_a, vec_b);
+#undef DGRAD_WIDE
     }
-    MG_CHECK_LAUNCH("mg_linear_dgrad_f32");
+    MG_CHECK_LAUNCH("mg_linear_dgrad_act_f32");
     return MG_OK;
+}
+
+// the Sigmoid form of mg_linear_dgrad_act_f32 (H == NULL: no activation)
+int mg_linear_dgrad_f32(const float* dY, int64_t M, int N, const float* W, int K, const float* H, float* dX, void* stream) {
+    MG_CHECK_ARG(dY && W && dX && M >= 0 && N > 0 && K > 0, "mg_linear_dgrad_f32: bad arguments (M=%lld N=%d K=%d)", (long long)M, N, K);
+    return mg_linear_dgrad_act_f32(dY, M, N, W, K, H, H ? MG_ACT_SIGMOID : MG_ACT_NONE, dX, stream);
 }
 
 size_t mg_linear_wgrad_workspace_bytes(int64_t M, int N, int K) {

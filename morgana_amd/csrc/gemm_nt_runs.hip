@@ -25,8 +25,6 @@ typedef __bf16 bfv2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 
-#define NR_EPI_BIAS 0
-#define NR_EPI_BIAS_SIGMOID 1
 #define NR_ZERO_ELEMS 16384
 __device__ uint16_t g_nr_zero_row[NR_ZERO_ELEMS];      // source of pad rows / unused run slots / out-of-range weight rows
 __device__ uint16_t g_nr_sink[64 * 8];                  // where the stores of rows past M go: every wave issues exactly NST stores
@@ -335,7 +333,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_runs_kernel(const uint16_t* __
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float x = acc[2 * p + ii][j][e] + bv[j][e];
-                        if (EPI == NR_EPI_BIAS_SIGMOID) x = mg_sigmoid_fast(x);
+                        x = mg_epi_act<EPI, true>(x);
                         v[e] = x;
                     }
                     const u32x2_t pk = u32x2_t{__builtin_bit_cast(unsigned int, bfv2{(__bf16)v[0], (__bf16)v[1]}),
@@ -361,7 +359,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_runs_kernel(const uint16_t* __
 
 // Launch helper used by mg_try_nt_big (gemm_bf16_big.hip): 1 if it launched, 0 if the shape does not qualify.
 int mg_try_nt_runs(const uint16_t* A, int lda, const int32_t* rows, int64_t M, int K, const uint16_t* Bm, int ldb, int N,
-                   const float* bias, uint16_t* C, int ldc, int sigmoid, hipStream_t st) {
+                   const float* bias, uint16_t* C, int ldc, int epi, hipStream_t st) {
     if (!rows || M < 2048 || M >= 2147483647LL || N % NR_BN != 0 || ldc != N) return 0;
     if (lda % 64 != 0 || ldb % 64 != 0 || lda > NR_ZERO_ELEMS - 64 || ldb > NR_ZERO_ELEMS - 64) return 0;
     if (lda < (K + 63) / 64 * 64 || ldb < (K + 63) / 64 * 64 || (K + 31) / 32 < 5) return 0;
@@ -375,10 +373,10 @@ int mg_try_nt_runs(const uint16_t* A, int lda, const int32_t* rows, int64_t M, i
     if (g >= 2147483647LL) return 0;
     dim3 grid((unsigned)g), block(256);
 #ifdef MG_EXPERIMENTS
-    if (sigmoid && g_mg_tuning[MG_TUNE_FORM] >= 200 && g_mg_tuning[MG_TUNE_FORM] < 456) {      // lab builds: timing probes 200 + mask
+    if (epi == EPI_BIAS_SIGMOID && g_mg_tuning[MG_TUNE_FORM] >= 200 && g_mg_tuning[MG_TUNE_FORM] < 456) {      // lab builds: timing probes 200 + mask
 #define NR_PROBE_CASE(P)                                                                                                                  \
     case 200 + P:                                                                                                                          \
-        hipLaunchKernelGGL((gemm_nt_runs_kernel<NR_EPI_BIAS_SIGMOID, false, P>), grid, block, 0, st, A, lda, rows, M, K, Bm, ldb, N, bias, C, ldc, \
+        hipLaunchKernelGGL((gemm_nt_runs_kernel<EPI_BIAS_SIGMOID, false, P>), grid, block, 0, st, A, lda, rows, M, K, Bm, ldb, N, bias, C, ldc, \
                            (int)tiles_m, tiles_n);                                                                                         \
         return 1;
         switch (g_mg_tuning[MG_TUNE_FORM]) {
@@ -387,17 +385,22 @@ int mg_try_nt_runs(const uint16_t* A, int lda, const int32_t* rows, int64_t M, i
         }
     }
 #endif
-    const bool pf = g_mg_tuning[MG_TUNE_FORM] == 16;   // A/B: fragments read one k-step ahead
-    if (sigmoid && pf)
-        hipLaunchKernelGGL((gemm_nt_runs_kernel<NR_EPI_BIAS_SIGMOID, true>), grid, block, 0, st, A, lda, rows, M, K, Bm, ldb, N, bias, C, ldc,
+    const bool sigmoid = epi == EPI_BIAS_SIGMOID;
+    const bool pf = g_mg_tuning[MG_TUNE_FORM] == 16 && (sigmoid || epi == EPI_BIAS);   // A/B: fragments read one k-step ahead
+    if (epi == EPI_BIAS_TANH)
+        hipLaunchKernelGGL((gemm_nt_runs_kernel<EPI_BIAS_TANH>), grid, block, 0, st, A, lda, rows, M, K, Bm, ldb, N, bias, C, ldc, (int)tiles_m, tiles_n);
+    else if (epi == EPI_BIAS_RELU)
+        hipLaunchKernelGGL((gemm_nt_runs_kernel<EPI_BIAS_RELU>), grid, block, 0, st, A, lda, rows, M, K, Bm, ldb, N, bias, C, ldc, (int)tiles_m, tiles_n);
+    else if (sigmoid && pf)
+        hipLaunchKernelGGL((gemm_nt_runs_kernel<EPI_BIAS_SIGMOID, true>), grid, block, 0, st, A, lda, rows, M, K, Bm, ldb, N, bias, C, ldc,
                            (int)tiles_m, tiles_n);
     else if (sigmoid)
-        hipLaunchKernelGGL((gemm_nt_runs_kernel<NR_EPI_BIAS_SIGMOID>), grid, block, 0, st, A, lda, rows, M, K, Bm, ldb, N, bias, C, ldc, (int)tiles_m,
+        hipLaunchKernelGGL((gemm_nt_runs_kernel<EPI_BIAS_SIGMOID>), grid, block, 0, st, A, lda, rows, M, K, Bm, ldb, N, bias, C, ldc, (int)tiles_m,
                            tiles_n);
     else if (pf)
-        hipLaunchKernelGGL((gemm_nt_runs_kernel<NR_EPI_BIAS, true>), grid, block, 0, st, A, lda, rows, M, K, Bm, ldb, N, bias, C, ldc, (int)tiles_m,
+        hipLaunchKernelGGL((gemm_nt_runs_kernel<EPI_BIAS, true>), grid, block, 0, st, A, lda, rows, M, K, Bm, ldb, N, bias, C, ldc, (int)tiles_m,
                            tiles_n);
     else
-        hipLaunchKernelGGL((gemm_nt_runs_kernel<NR_EPI_BIAS>), grid, block, 0, st, A, lda, rows, M, K, Bm, ldb, N, bias, C, ldc, (int)tiles_m, tiles_n);
+        hipLaunchKernelGGL((gemm_nt_runs_kernel<EPI_BIAS>), grid, block, 0, st, A, lda, rows, M, K, Bm, ldb, N, bias, C, ldc, (int)tiles_m, tiles_n);
     return 1;
 }

@@ -255,6 +255,22 @@ __global__ __launch_bounds__(256) void sigmoid_grad_kernel(const float* __restri
     }
 }
 
+// stand-alone nn.Sigmoid / nn.Tanh / nn.ReLU: the accurate forms (expf / tanhf), as the fp32 GEMM epilogues
+template <int ACT>
+__global__ __launch_bounds__(256) void act_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float v = x[i];
+        y[i] = ACT == MG_ACT_SIGMOID ? mg_sigmoid(v) : ACT == MG_ACT_TANH ? tanhf(v) : mg_relu(v);
+    }
+}
+
+// dx = dy f'(y), f' in the activation's output y (mg_epi_dact: the dgrad epilogues' expressions)
+template <int EPI>
+__global__ __launch_bounds__(256) void act_grad_kernel(const float* __restrict__ dy, const float* __restrict__ y, float* __restrict__ dx,
+                                                       int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) dx[i] = mg_epi_dact<EPI>(dy[i], y[i]);
+}
+
 // All weight matrices of a layer stack in ONE launch: descriptor d gives an fp32 [rows, cols] matrix and asks for its
 // bf16 copy [rows, ldd] (zero padded) and / or its bf16 transpose [cols, ldt] (zero padded).  blockIdx.y = descriptor.
 struct CastBatch {
@@ -512,6 +528,28 @@ int mg_sigmoid_grad_f32(const float* dy, const float* y, float* dx, int64_t n, v
     if (n == 0) return MG_OK;
     hipLaunchKernelGGL(sigmoid_grad_kernel, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, n);
     MG_CHECK_LAUNCH("mg_sigmoid_grad_f32");
+    return MG_OK;
+}
+
+int mg_act_f32(const float* x, float* y, int64_t n, int act, void* stream) {
+    MG_CHECK_ARG(x && y && n >= 0, "mg_act_f32: bad arguments");
+    MG_CHECK_ARG(act == MG_ACT_SIGMOID || act == MG_ACT_TANH || act == MG_ACT_RELU, "mg_act_f32: unknown activation %d", act);
+    if (n == 0) return MG_OK;
+    if (act == MG_ACT_SIGMOID) hipLaunchKernelGGL(act_kernel<MG_ACT_SIGMOID>, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, x, y, n);
+    else if (act == MG_ACT_TANH) hipLaunchKernelGGL(act_kernel<MG_ACT_TANH>, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, x, y, n);
+    else hipLaunchKernelGGL(act_kernel<MG_ACT_RELU>, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, x, y, n);
+    MG_CHECK_LAUNCH("mg_act_f32");
+    return MG_OK;
+}
+
+int mg_act_grad_f32(const float* dy, const float* y, float* dx, int64_t n, int act, void* stream) {
+    MG_CHECK_ARG(dy && y && dx && n >= 0, "mg_act_grad_f32: bad arguments");
+    MG_CHECK_ARG(act == MG_ACT_SIGMOID || act == MG_ACT_TANH || act == MG_ACT_RELU, "mg_act_grad_f32: unknown activation %d", act);
+    if (n == 0) return MG_OK;
+#define ACT_GRAD(EPI_) hipLaunchKernelGGL(act_grad_kernel<EPI_>, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, n)
+    MG_SWITCH_GRAD_EPI(mg_epi_grad(act), ACT_GRAD);
+#undef ACT_GRAD
+    MG_CHECK_LAUNCH("mg_act_grad_f32");
     return MG_OK;
 }
 

@@ -455,6 +455,8 @@ __global__ __launch_bounds__(256) void phone_concat_layer_kernel(const float* __
 #pragma unroll
                         for (int e = 0; e < COLS; ++e) {
                             if (ACT == MG_ACT_SIGMOID) z[e] = mg_sigmoid_fast(z[e]);
+                            else if (ACT == MG_ACT_TANH) z[e] = tanhf(z[e]);       // as the GEMM epilogues (common.h, mg_epi_act)
+                            else if (ACT == MG_ACT_RELU) z[e] = mg_relu(z[e]);
                             if (c0 + e >= N) z[e] = 0.f;
                         }
                         PclStore<COLS, OutT>::put(Y + (size_t)f * ldy + c0, z);
@@ -566,7 +568,7 @@ int mg_phone_concat_layer_bf16(const float* P, int ldp, const int32_t* rows, int
     MG_CHECK_ARG(C >= 1 && C <= 16 && col0 >= 0 && ldw >= col0 + C, "mg_phone_concat_layer_bf16: C=%d (1..16) col0=%d ldw=%d", C, col0, ldw);
     MG_CHECK_ARG(ldp % 8 == 0 && ldp >= ((N + 7) / 8) * 8 && ldy % 8 == 0 && ldy >= N,
                  "mg_phone_concat_layer_bf16: N=%d ldp=%d ldy=%d (multiples of 8, ldp >= N rounded up to 8)", N, ldp, ldy);
-    MG_CHECK_ARG(act == MG_ACT_NONE || act == MG_ACT_SIGMOID, "mg_phone_concat_layer_bf16: act=%d", act);
+    MG_CHECK_ARG(mg_act_known(act), "mg_phone_concat_layer_bf16: act=%d", act);
     MG_CHECK_ARG(((uintptr_t)P % 16) == 0 && ((uintptr_t)Y % 16) == 0, "mg_phone_concat_layer_bf16: buffers must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int cols = ldy <= 256 ? 4 : 8;                                // columns per lane: 64 lanes cover 256 / 512 columns per pass
@@ -576,6 +578,10 @@ int mg_phone_concat_layer_bf16(const float* P, int ldp, const int32_t* rows, int
 #define LAUNCH_PCL_T(ACT_, T_) do { if (cols == 4) LAUNCH_PCL(ACT_, T_, 4); else LAUNCH_PCL(ACT_, T_, 8); } while (0)
     if (act == MG_ACT_SIGMOID) {
         if (y_f32) LAUNCH_PCL_T(MG_ACT_SIGMOID, float); else LAUNCH_PCL_T(MG_ACT_SIGMOID, uint16_t);
+    } else if (act == MG_ACT_TANH) {
+        if (y_f32) LAUNCH_PCL_T(MG_ACT_TANH, float); else LAUNCH_PCL_T(MG_ACT_TANH, uint16_t);
+    } else if (act == MG_ACT_RELU) {
+        if (y_f32) LAUNCH_PCL_T(MG_ACT_RELU, float); else LAUNCH_PCL_T(MG_ACT_RELU, uint16_t);
     } else {
         if (y_f32) LAUNCH_PCL_T(MG_ACT_NONE, float); else LAUNCH_PCL_T(MG_ACT_NONE, uint16_t);
     }

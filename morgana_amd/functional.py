@@ -476,7 +476,14 @@ class LinearStackFn(torch.autograd.Function):
             g = drop.apply(g, n_layers - 1)
         if acts[-1] == ops.ACT_SIGMOID:
             g = ops.sigmoid_grad(g, hidden[-1])
+        elif acts[-1] != ops.ACT_NONE:
+            g = ops.act_grad(g, hidden[-1], acts[-1])
         grad_x = None
+
+        def fed_by(i):
+            # (output, activation) of the layer feeding layer i: what the dgrad epilogue multiplies f' from
+            return (hidden[i - 1], acts[i - 1]) if acts[i - 1] != ops.ACT_NONE else (None, ops.ACT_NONE)
+
         if precision == 'fp32':
             for i in range(n_layers - 1, -1, -1):
                 n, k = ctx.dims[i]
@@ -486,8 +493,8 @@ class LinearStackFn(torch.autograd.Function):
                 dw, db = ops.linear_wgrad_f32(g, a_in, r, n, k, want_bias=ctx.has_bias[i])
                 grads[2 * i], grads[2 * i + 1] = dw, db
                 if i > 0:
-                    h = hidden[i - 1] if acts[i - 1] == ops.ACT_SIGMOID else None
-                    g = unmask(ops.linear_dgrad_f32(g, weights[i], h), i - 1)
+                    h, h_act = fed_by(i)
+                    g = unmask(ops.linear_dgrad_f32(g, weights[i], h, h_act), i - 1)
                 elif need_x:
                     grad_x = ops.linear_dgrad_f32(g, weights[0], None)
         elif precision == 'bf16x3':
@@ -506,7 +513,7 @@ class LinearStackFn(torch.autograd.Function):
                 if not split[i]:                       # a narrow layer: exact fp32 products (see _x3_layer)
                     grads[2 * i], grads[2 * i + 1] = ops.linear_wgrad_f32(g, a_in, r, n, k, want_bias=ctx.has_bias[i])
                     if i > 0:
-                        g = unmask(ops.linear_dgrad_f32(g, weights[i], hidden[i - 1] if acts[i - 1] == ops.ACT_SIGMOID else None), i - 1)
+                        g = unmask(ops.linear_dgrad_f32(g, weights[i], *fed_by(i)), i - 1)
                     elif need_x:
                         grad_x = ops.linear_dgrad_f32(g, weights[0], None)
                     continue
@@ -542,6 +549,8 @@ class LinearStackFn(torch.autograd.Function):
                             sig = hidden[i - 1]             # layer i - 1 splits g next: the sigmoid gradient rides in that pass
                         else:
                             g = ops.sigmoid_grad(g, hidden[i - 1])
+                    elif acts[i - 1] != ops.ACT_NONE:
+                        g = ops.act_grad(g, hidden[i - 1], acts[i - 1])     # Tanh / ReLU: a launch of its own (the split pass knows s (1 - s))
                 elif need_x:
                     grad_x = ops.linear_dgrad_x3(g3, m, wt3s[0], k)
         else:
@@ -583,8 +592,8 @@ class LinearStackFn(torch.autograd.Function):
                     grads[2 * i], grads[2 * i + 1] = dw, db
                 if i > 0:
                     wt = _w_t(w_params[i])
-                    h = hidden[i - 1] if acts[i - 1] == ops.ACT_SIGMOID else None
-                    g = unmask(ops.linear_dgrad_bf16(g, m, n, wt, k, h), i - 1)
+                    h, h_act = fed_by(i)
+                    g = unmask(ops.linear_dgrad_bf16(g, m, n, wt, k, h, act=h_act), i - 1)
                 elif need_x:
                     wt = _w_t(w_params[0])
                     grad_x = ops.linear_dgrad_bf16(g, m, n, wt, k, None, out_f32=True)
@@ -1097,8 +1106,8 @@ class LinearStackMSEFn(torch.autograd.Function):
                 if i == top and g_below is not None:
                     g = g_below
                 else:
-                    h = hidden[i - 1] if ctx.acts[i - 1] == ops.ACT_SIGMOID else None
-                    g = ops.linear_dgrad_bf16(g, m_rows, n, w_t[i], k, h)
+                    h = hidden[i - 1] if ctx.acts[i - 1] != ops.ACT_NONE else None
+                    g = ops.linear_dgrad_bf16(g, m_rows, n, w_t[i], k, h, act=ctx.acts[i - 1])
                 n_, k_ = ctx.dims[i - 1]
                 _wgrad_into(mode, opt, params[2 * (i - 1)], params[2 * (i - 1) + 1], g, hidden[i - 2] if i > 1 else a0,
                             None if i > 1 else r0, m_rows, n_, k_)
@@ -1147,8 +1156,8 @@ class LinearStackMSEFn(torch.autograd.Function):
                                           out_b=flat[ctx.offsets[1]:ctx.offsets[1] + n0_])
                 break
             if i > 0:
-                h = hidden[i - 1] if ctx.acts[i - 1] == ops.ACT_SIGMOID else None
-                g = ops.linear_dgrad_bf16(g, m, n, w_t[i], k, h)
+                h = hidden[i - 1] if ctx.acts[i - 1] != ops.ACT_NONE else None
+                g = ops.linear_dgrad_bf16(g, m, n, w_t[i], k, h, act=ctx.acts[i - 1])
         grads = _deliver_rest(ctx.params, flat[:flat.numel() - 1], ctx.offsets, grad_loss, early)
         return (None, None, None, None, None) + tuple(grads)
 

@@ -9,7 +9,7 @@ import torch
 
 from . import _lib
 
-ACT_NONE, ACT_SIGMOID = 0, 1
+ACT_NONE, ACT_SIGMOID, ACT_TANH, ACT_RELU = 0, 1, 2, 3      # MG_ACT_* of include/morgana_hip.h
 NORM_MVN, DENORM_MVN, NORM_MINMAX, DENORM_MINMAX = 0, 1, 2, 3
 
 _workspaces = {}
@@ -408,12 +408,15 @@ def linear_fwd_f32(a, rows, m, weight, bias, act):
     return y
 
 
-def linear_dgrad_f32(dy, weight, h):
+def linear_dgrad_f32(dy, weight, h, act=ACT_SIGMOID):
+    """dX = (dY W) * f'(h): ``h`` None or the OUTPUT of activation ``act`` (ACT_SIGMOID / ACT_TANH / ACT_RELU) feeding the layer."""
     lib = _lib.load()
     n, k = weight.shape
     m = dy.shape[0]
     dx = torch.empty((m, k), dtype=torch.float32, device=dy.device)
-    _lib.check(lib.mg_linear_dgrad_f32(_p(dy), m, n, _p(weight), k, _p(h), _p(dx), _stream()), 'mg_linear_dgrad_f32')
+    if h is None:
+        act = ACT_NONE
+    _lib.check(lib.mg_linear_dgrad_act_f32(_p(dy), m, n, _p(weight), k, _p(h), act, _p(dx), _stream()), 'mg_linear_dgrad_act_f32')
     return dx
 
 
@@ -477,14 +480,17 @@ def linear_fwd_bf16(a, rows, m, k, w_bf16, bias, n, act, out_f32=False, rows_run
     return y
 
 
-def linear_dgrad_bf16(dy, m, n, wt_bf16, k, h, out_f32=False):
-    """dy (m, lddy) bf16; wt_bf16 = W^T (k, pad8(n)) bf16; h None or (m, ldh) bf16.  Returns (m, pad8(k)) bf16/f32."""
+def linear_dgrad_bf16(dy, m, n, wt_bf16, k, h, out_f32=False, act=ACT_SIGMOID):
+    """dy (m, lddy) bf16; wt_bf16 = W^T (k, pad8(n)) bf16; h None or (m, ldh) bf16, the OUTPUT of activation ``act`` feeding the
+    layer.  Returns (m, pad8(k)) bf16/f32."""
     lib = _lib.load()
     lddx = pad8(k)
     dx = torch.empty((m, lddx), dtype=torch.float32 if out_f32 else torch.bfloat16, device=dy.device)
-    _lib.check(lib.mg_linear_dgrad_bf16(_p(dy), dy.shape[1], m, n, _p(wt_bf16), wt_bf16.shape[1], k, _p(h),
-                                        h.shape[1] if h is not None else 0, _p(dx), lddx, 1 if out_f32 else 0,
-                                        _stream()), 'mg_linear_dgrad_bf16')
+    if h is None:
+        act = ACT_NONE
+    _lib.check(lib.mg_linear_dgrad_act_bf16(_p(dy), dy.shape[1], m, n, _p(wt_bf16), wt_bf16.shape[1], k, _p(h),
+                                            h.shape[1] if h is not None else 0, act, _p(dx), lddx, 1 if out_f32 else 0,
+                                            _stream()), 'mg_linear_dgrad_act_bf16')
     return dx
 
 
@@ -1527,6 +1533,25 @@ def sigmoid_grad(dy, y):
     dy = _require(dy, torch.float32, 'grad')
     dx = torch.empty_like(y)
     _lib.check(lib.mg_sigmoid_grad_f32(_p(dy), _p(y), _p(dx), y.numel(), _stream()), 'mg_sigmoid_grad_f32')
+    return dx
+
+
+def act(x, act):
+    """Elementwise ACT_SIGMOID / ACT_TANH / ACT_RELU of an fp32 tensor (a stand-alone nn.Sigmoid / nn.Tanh / nn.ReLU)."""
+    lib = _lib.load()
+    x = _require(x, torch.float32, 'input')
+    y = torch.empty_like(x)
+    _lib.check(lib.mg_act_f32(_p(x), _p(y), x.numel(), act, _stream()), 'mg_act_f32')
+    return y
+
+
+def act_grad(dy, y, act):
+    """dy * f'(y) with f' in the activation's output ``y``: y (1 - y), 1 - y^2, y > 0."""
+    lib = _lib.load()
+    dy = _require(dy, torch.float32, 'grad')
+    y = _require(y, torch.float32, 'activation')
+    dx = torch.empty_like(y)
+    _lib.check(lib.mg_act_grad_f32(_p(dy), _p(y), _p(dx), y.numel(), act, _stream()), 'mg_act_grad_f32')
     return dx
 
 

@@ -552,9 +552,12 @@ class RecurrentCuDNNWrapper(nn.Module):
 class SequentialWithRecurrent(nn.Sequential):
     """``nn.Sequential`` taking ``hiddens`` / ``seq_len`` for recurrent members; returns ``(output, hiddens)``.
 
-    Reference: morgana/utils.py:396-418.  Runs of ``nn.Linear`` (+ ``nn.Sigmoid``) are executed as one fused HIP node
-    (MFMA GEMM with bias+sigmoid epilogue forward; wgrad and sigmoid-grad-fused dgrad backward).  The modules stay
-    ordinary ``nn.Linear`` objects, so ``state_dict`` keys (``layers.0.weight`` ...) match the reference's checkpoints.
+    Reference: morgana/utils.py:396-418.  Runs of ``nn.Linear`` (+ ``nn.Sigmoid`` / ``nn.Tanh`` / ``nn.ReLU``) are executed as one
+    fused HIP node (MFMA GEMM with bias+activation epilogue forward; wgrad and activation-grad-fused dgrad backward: all three
+    derivatives are functions of the activation's output).  A stand-alone ``nn.Sigmoid`` / ``nn.Tanh`` / ``nn.ReLU`` (behind a
+    recurrent wrapper) runs as an elementwise HIP kernel.  The F0Model-shaped fusions behind ``forward_mse`` know Sigmoid only; a
+    stack with another activation takes the generic node.  The modules stay ordinary ``nn.Linear`` objects, so ``state_dict`` keys
+    (``layers.0.weight`` ...) match the reference's checkpoints.
     """
 
     def __init__(self, *args, precision=None):
@@ -562,7 +565,7 @@ class SequentialWithRecurrent(nn.Sequential):
         self.precision = precision
 
     def _linear_run(self, modules, start):
-        """Collect [Linear, Sigmoid?, Dropout*]+ starting at ``start``; returns (end, run) with run = [(linear, act), ...] and
+        """Collect [Linear, (Sigmoid | Tanh | ReLU)?, Dropout*]+ starting at ``start``; returns (end, run) with run = [(linear, act), ...] and
         ``run.drops`` = the dropout probability behind each layer (0 = none: ``nn.Dropout`` with p == 0 or in eval mode is the
         identity - the reference's models pass dropout_prob=0., models/RNN_SPSS.py:21).  An ACTIVE dropout does not break the run
         either: the run's autograd node draws its mask in a HIP kernel behind the layer and regenerates it in its backward
@@ -571,8 +574,8 @@ class SequentialWithRecurrent(nn.Sequential):
         while i < len(modules) and type(modules[i]) is nn.Linear:
             act = ops.ACT_NONE
             nxt = i + 1
-            if nxt < len(modules) and type(modules[nxt]) is nn.Sigmoid:
-                act, nxt = ops.ACT_SIGMOID, nxt + 1
+            if nxt < len(modules) and type(modules[nxt]) in _ACT_OF:
+                act, nxt = _ACT_OF[type(modules[nxt])], nxt + 1
             keep = 1.0
             while nxt < len(modules) and type(modules[nxt]) is nn.Dropout:
                 if modules[nxt].p != 0 and modules[nxt].training:
@@ -970,9 +973,10 @@ class SequentialWithRecurrent(nn.Sequential):
                 # a bare recurrent layer in the container (utils.py:412-413): every item runs the full padded length
                 input, hiddens[i] = RecurrentCuDNNWrapper(module, precision=rec_precision).run_full_length(input, hiddens[i])
                 zero_padded = False
-            elif type(module) is nn.Sigmoid:
+            elif type(module) in _ACT_OF:
+                # a stand-alone nn.Sigmoid / nn.Tanh / nn.ReLU (e.g. behind a recurrent wrapper): the elementwise HIP kernels
                 shape = input.shape
-                input = _SigmoidFn.apply(input.reshape(-1)).view(shape)
+                input = _ActFn.apply(input.reshape(-1), _ACT_OF[type(module)]).view(shape)
                 zero_padded = False
             elif type(module) is nn.Dropout:
                 identity = module.p == 0 or not module.training
@@ -1005,17 +1009,24 @@ class _Run(list):
         return (self.drops, self.site0) if any(self.drops) else None
 
 
-class _SigmoidFn(torch.autograd.Function):
+# the activation modules a Linear run fuses (``inplace=True`` on nn.ReLU is the same function: the run owns its buffers)
+_ACT_OF = {nn.Sigmoid: ops.ACT_SIGMOID, nn.Tanh: ops.ACT_TANH, nn.ReLU: ops.ACT_RELU}
+
+
+class _ActFn(torch.autograd.Function):
+    """A stand-alone nn.Sigmoid / nn.Tanh / nn.ReLU: ``mg_act_f32`` forward, ``mg_act_grad_f32`` (the derivative in the output) backward."""
+
     @staticmethod
-    def forward(ctx, x):
-        y = ops.sigmoid(x)
+    def forward(ctx, x, act):
+        y = ops.act(x.contiguous(), act)
+        ctx.act = act
         ctx.save_for_backward(y)
         return y
 
     @staticmethod
     def backward(ctx, grad):
         (y,) = ctx.saved_tensors
-        return ops.sigmoid_grad(grad.contiguous(), y)
+        return ops.act_grad(grad.contiguous(), y, ctx.act), None
 
 
 class ExponentialMovingAverage(object):
