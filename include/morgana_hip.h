@@ -195,6 +195,27 @@ int mg_stream_loss_f32(const float* pred, const mg_stream_desc* streams, int n_s
                        int D, float grad_scale, float* loss, float* grad, float* prob, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* seq_len-masked categorical cross entropy, forward + backward (reference: losses.ce, morgana/losses.py:59-61 -
+ * F.cross_entropy(predictions.transpose(1, 2), targets, reduction='none') - under the sequence_loss wrapper of :29-46).
+ *   l[b,t] = logsumexp_c x[b,t,:] - x[b,t,y[b,t]],  L = mean_b( sum_{t < n_b} l[b,t] / n_b ),  n_b = seq_len[b] clamped to [0, T]
+ *   (T when seq_len == NULL; n_b == 0 gives NaN, as the reference's 0 / 0),
+ *   loss[0] = loss_weight * L + loss_keep * loss[0]   (loss_keep == 0: loss[0] is not read; how a multi-stream loss is summed on the
+ *   device), grad[b,t,c] = grad_scale * (softmax(x[b,t,:])[c] - [c == y[b,t]]) / (n_b B) for t < n_b and exactly 0 for pad frames
+ *   (written, not skipped), argmax[b,t] = the lowest index among the largest logits (0 for pad frames).
+ * pred: f32, frame (b,t) at pred + (b T + t) ldp + col0, C classes - a column slice of a wider prediction is read in place;
+ * grad (may be NULL) likewise with ldg / gcol0: only those C columns of each row are written.  target [B,T] int64; seq_len [B] int64
+ * or NULL; argmax [B,T] int64 or NULL.  A target of -100 in a valid frame (F.cross_entropy's default ignore_index): loss and
+ * gradient of that frame are 0, the frame still counts in n_b.  Any other target outside [0, C) in a valid frame: NaN loss, zero
+ * gradient row, nothing is read or written out of bounds (the reference asserts on the device).  Targets of pad frames are never
+ * looked at and their logits are not read.  The maximum is subtracted before expf; a -inf logit of a non-target class is legal
+ * (probability and gradient 0).  1 <= C <= MG_CE_MAX_CLASSES, B <= 65535.  Per-workgroup partials in a fixed layout and a
+ * one-workgroup finishing pass: no atomics, the same bits on every call.  workspace: mg_masked_ce_workspace_bytes(B,T,C) bytes. */
+#define MG_CE_MAX_CLASSES 65536
+size_t mg_masked_ce_workspace_bytes(int B, int T, int C);
+int mg_masked_ce_f32(const float* pred, int ldp, int col0, const int64_t* target, const int64_t* seq_len, int B, int T, int C,
+                     float grad_scale, float loss_weight, float loss_keep, float* loss, float* grad, int ldg, int gcol0,
+                     int64_t* argmax, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Streaming metrics (reference: morgana/metrics.py:359-695; accumulated inside the shipped model's loss() every step,
  * models/RNN_SPSS.py:120-129): accum[0] += sum, accum[1] += count on the device - no host read-back (the reference calls .item()
  * per accumulate).  kind: MG_METRIC_MEAN (target only), _SQDIFF (RMSE / MelCepDistortion), _ABSDIFF (MAE), _ROOT_SQ (Distortion:

@@ -40,6 +40,9 @@ SIGNATURES = {
     'mg_stream_loss_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'mg_stream_loss_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_size_t, c_void_p]),
+    'mg_masked_ce_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'mg_masked_ce_f32': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p,
+                                 c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'mg_pad_normalise_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                      c_void_p]),
     'mg_pad_normalise_bf16_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
@@ -344,6 +347,7 @@ CAST_MAX = 16
 SPLIT3_MAX = 16
 STREAMS_MAX = 8
 LOSS_MSE, LOSS_SIGMOID_BCE = 0, 1
+CE_MAX_CLASSES = 65536       # MG_CE_MAX_CLASSES
 _lib = None
 
 

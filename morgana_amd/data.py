@@ -448,6 +448,7 @@ def to_device(features, device, bf16_tables=(), normalisers=None):
 _TO_TORCH_DTYPE = {np.dtype('float16'): torch.float16, np.dtype('float32'): torch.float32,
                    np.dtype('float64'): torch.float64, np.dtype('int8'): torch.int8, np.dtype('int16'): torch.int16,
                    np.dtype('int32'): torch.int32, np.dtype('int64'): torch.int64, np.dtype('bool'): torch.bool,
+                   np.dtype('uint8'): torch.uint8,
                    int: torch.int64, float: torch.float32, bool: torch.bool}
 
 

@@ -1968,6 +1968,54 @@ class StreamLossFn(torch.autograd.Function):
         return (grad * grad_loss, None, None, None) + (None,) * ctx.n_targets
 
 
+class MaskedCEFn(torch.autograd.Function):
+    """Masked categorical cross entropy (losses.py:59-61 under :29-46) in one pass: returns (loss, argmax or None).  The gradient is
+    computed in the forward and saved; targets and the argmax are not differentiable."""
+
+    @staticmethod
+    def forward(ctx, predictions, targets, seq_len, want_argmax=False):
+        loss, grad, argmax = ops.masked_ce(predictions, targets, seq_len, want_grad=ctx.needs_input_grad[0], want_argmax=want_argmax)
+        ctx.save_for_backward(grad)
+        ctx.set_materialize_grads(False)
+        if argmax is not None:
+            ctx.mark_non_differentiable(argmax)
+        return loss, argmax
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_argmax):
+        (grad,) = ctx.saved_tensors
+        if grad_loss is None:                        # the loss itself was not used: only the argmax was
+            return None, None, None, None
+        if _is_unit_grad(grad_loss):
+            return grad, None, None, None
+        return grad * grad_loss, None, None, None
+
+
+class StreamLossCEFn(torch.autograd.Function):
+    """``StreamLossFn`` for a stream table with categorical streams (ops.stream_loss_ce): returns (loss, sigmoid of the BCE stream or
+    None, the predicted class of every 'ce' stream)."""
+
+    @staticmethod
+    def forward(ctx, predictions, seq_len, kinds, widths, want_prob, want_argmax, *targets):
+        loss, grad, prob, argmaxes = ops.stream_loss_ce(predictions, targets, kinds, widths, seq_len, want_grad=ctx.needs_input_grad[0],
+                                                        want_prob=want_prob, want_argmax=want_argmax)
+        ctx.save_for_backward(grad)
+        ctx.n_targets = len(targets)
+        ctx.set_materialize_grads(False)
+        extra = [prob] + [a for a in argmaxes if a is not None]
+        ctx.mark_non_differentiable(*[e for e in extra if e is not None])
+        return (loss, prob) + tuple(a for a in argmaxes if a is not None)
+
+    @staticmethod
+    def backward(ctx, grad_loss, *_unused):
+        (grad,) = ctx.saved_tensors
+        if grad_loss is None:
+            return (None,) * (6 + ctx.n_targets)
+        if _is_unit_grad(grad_loss):
+            return (grad, None, None, None, None, None) + (None,) * ctx.n_targets
+        return (grad * grad_loss, None, None, None, None, None) + (None,) * ctx.n_targets
+
+
 class GatherRowsFn(torch.autograd.Function):
     """out[m] = x2d[rows[m]] (zero for -1) with distinct non-negative rows: backward is a scatter."""
 

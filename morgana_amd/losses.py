@@ -1,5 +1,5 @@
-"""Mirror of ``morgana.losses`` for the hot path.  Reference: morgana/losses.py:9-51 (``sequence_loss`` / ``mse``) and :64-67
-(``KLD_standard_normal``)."""
+"""Mirror of ``morgana.losses`` for the hot path.  Reference: morgana/losses.py:9-51 (``sequence_loss`` / ``mse``), :54-56 (``bce``),
+:59-61 (``ce``) and :64-67 (``KLD_standard_normal``)."""
 import torch
 
 from . import functional as F_hip
@@ -31,17 +31,71 @@ def bce(predictions, targets, seq_len=None):
     return F_hip.MaskedMSEFn.apply(predictions, targets, seq_len, 'bce')
 
 
-def multi_stream(predictions, targets, kinds, seq_len=None, want_prob=False):
-    """Mean over streams of ``mse`` / ``bce(sigmoid(.))`` on column slices of one prediction tensor - the loss of the
+def _class_targets(predictions, targets):
+    """Class indices as the kernel reads them: (B, T) int64 (``(B, T, 1)`` is squeezed, int32 / int16 / int8 / uint8 are widened)."""
+    if not isinstance(targets, torch.Tensor):
+        raise TypeError('ce: targets must be a torch.Tensor of class indices, got %s' % type(targets))
+    if targets.is_floating_point() or targets.is_complex() or targets.dtype == torch.bool:
+        raise TypeError('ce: targets must hold integer class indices, got %s' % targets.dtype)
+    if targets.dim() == 3 and targets.shape[2] == 1:
+        targets = targets[:, :, 0]
+    if targets.dim() != 2 or targets.shape[0] != predictions.shape[0]:
+        raise ValueError('ce: targets must be (B, T) or (B, T, 1) class indices for predictions %s, got %s'
+                         % (tuple(predictions.shape), tuple(targets.shape)))
+    if targets.shape[1] != predictions.shape[1]:
+        raise RuntimeError('The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton dimension 1'
+                           % (predictions.shape[1], targets.shape[1]))
+    return targets if targets.dtype == torch.int64 else targets.long()
+
+
+def ce(predictions, targets, seq_len=None, want_argmax=False):
+    """Masked categorical cross entropy with the same per-utterance averaging as ``mse`` (reference: losses.py:59-61,
+    ``F.cross_entropy(predictions.transpose(1, 2), targets, reduction='none')`` under the wrapper of :29-46).
+
+    predictions (B, T, C) float32 logits - a column slice of a wider tensor is read in place; targets (B, T) or (B, T, 1) integer
+    class indices.  A target of -100 (``F.cross_entropy``'s ``ignore_index``) scores 0 and still counts as a valid frame; any other
+    target outside [0, C) in a valid frame makes the loss NaN (the reference asserts on the device).  One HIP pass computes the loss
+    and d loss / d predictions (csrc/ce.hip; the reference runs a transpose, log_softmax, nll_loss, a host-built mask, mul, two sums,
+    div and mean, then their autograd mirrors).  ``want_argmax``: returns (loss, predicted class (B, T) int64 from the same pass; 0 in
+    pad frames)."""
+    if seq_len is not None and seq_len.dtype != torch.int64:
+        seq_len = seq_len.long()
+    if not isinstance(predictions, torch.Tensor) or predictions.dim() != 3:
+        raise ValueError('ce: predictions must be a (B, T, C) tensor')
+    loss, argmax = F_hip.MaskedCEFn.apply(predictions, _class_targets(predictions, targets), seq_len, want_argmax)
+    return (loss, argmax) if want_argmax else loss
+
+
+def multi_stream(predictions, targets, kinds, seq_len=None, want_prob=False, widths=None, want_argmax=False):
+    """Mean over streams of ``mse`` / ``bce(sigmoid(.))`` / ``ce`` on column slices of one prediction tensor - the loss of the
     reference's LSTM acoustic model (models/RNN_SPSS.py:120-139: three ``losses.mse`` + one ``losses.bce``, ``/ 4.``) in one
     pass instead of torch.split + four masked losses and their autograd mirrors.
 
-    predictions (B, T, sum of widths); targets[k] (B, T, width_k) in column order; kinds[k] in {'mse', 'sigmoid_bce'}.
-    Returns (loss, sigmoid(predictions) of the BCE stream if ``want_prob`` else None)."""
+    predictions (B, T, sum of widths); targets[k] (B, T, width_k) in column order; kinds[k] in {'mse', 'sigmoid_bce', 'ce'}.
+    Returns (loss, sigmoid(predictions) of the BCE stream if ``want_prob`` else None).
+
+    A 'ce' stream's target holds integer class indices, (B, T) or (B, T, 1), and its width is its number of classes: ``widths[k]``,
+    or what the other streams leave of the prediction when there is one 'ce' stream.  Such a table takes the one-pass launch over
+    its mse / sigmoid_bce streams plus one categorical launch per 'ce' stream, all writing ONE gradient tensor, the losses summed on
+    the device (no host read).  ``want_argmax`` then makes the result (loss, prob, {k: predicted class (B, T) int64 of stream k})."""
     if seq_len is not None and seq_len.dtype != torch.int64:
         seq_len = seq_len.long()
-    targets = [y if y.dtype == torch.float32 else y.float() for y in targets]
-    return F_hip.StreamLossFn.apply(predictions, seq_len, tuple(kinds), want_prob, *targets)
+    if 'ce' not in kinds:
+        targets = [y if y.dtype == torch.float32 else y.float() for y in targets]
+        loss, prob = F_hip.StreamLossFn.apply(predictions, seq_len, tuple(kinds), want_prob, *targets)
+        return (loss, prob, {}) if want_argmax else (loss, prob)
+    kinds = tuple(kinds)
+    if widths is None:
+        if kinds.count('ce') != 1:
+            raise ValueError("multi_stream: more than one 'ce' stream needs widths (the number of classes of each)")
+        rest = sum(int(y.shape[-1]) for y, kind in zip(targets, kinds) if kind != 'ce')
+        widths = [predictions.shape[-1] - rest if kind == 'ce' else int(y.shape[-1]) for y, kind in zip(targets, kinds)]
+    targets = [_class_targets(predictions, y) if kind == 'ce' else (y if y.dtype == torch.float32 else y.float())
+               for y, kind in zip(targets, kinds)]
+    out = F_hip.StreamLossCEFn.apply(predictions, seq_len, kinds, tuple(int(w) for w in widths), want_prob, want_argmax, *targets)
+    if not want_argmax:
+        return out[0], out[1]
+    return out[0], out[1], dict(zip([k for k, kind in enumerate(kinds) if kind == 'ce'], out[2:]))
 
 
 def KLD_standard_normal(mean, log_variance):

@@ -165,9 +165,12 @@ class RNNSPSS(BaseSPSS):
 class Stream(object):
     """One output stream.  ``name``: feature name ('lf0'); ``dim``: columns of the prediction; ``loss``: 'mse' against
     ``normalised_<name>_deltas`` (a delta stream: static + delta + delta-delta, denormalised and turned into a trajectory by MLPG)
-    or 'sigmoid_bce' against ``<name>`` (a probability stream).  ``metric`` = (registered name, factory, kind): kind 'trajectory'
+    or 'sigmoid_bce' against ``<name>`` (a probability stream) or 'ce' against ``<name>`` as integer class indices, (B, T) or
+    (B, T, 1) (a categorical stream of ``dim`` classes, losses.ce: the logits go out as ``<name>_logits``, the predicted class as
+    ``<name>``, (B, T) int64).  ``metric`` = (registered name, factory, kind): kind 'trajectory'
     feeds (target, trajectory, n_frames), 'voiced_trajectory' adds a voicing mask (the predicted probability stream ``voicing`` >
-    0.5, or the feature of that name when the model predicts none), 'accuracy' feeds the hit rate of a probability stream."""
+    0.5, or the feature of that name when the model predicts none), 'accuracy' feeds the hit rate of a probability or categorical
+    stream."""
 
     def __init__(self, name, dim, loss='mse', metric=None, voicing='vuv'):
         self.name, self.dim, self.loss, self.metric, self.voicing = name, dim, loss, metric, voicing
@@ -177,7 +180,13 @@ class Stream(object):
         return self.loss == 'mse'
 
     @property
+    def is_categorical(self):
+        return self.loss == 'ce'
+
+    @property
     def output_key(self):
+        if self.is_categorical:
+            return self.name + '_logits'
         return 'normalised_%s_deltas' % self.name if self.is_delta else self.name
 
 
@@ -233,14 +242,17 @@ class StreamModel(BaseSPSS):
         prediction, _ = self.layers(model_inputs, seq_len=features['n_frames'], max_len=norm_counters.shape[1])
         return prediction
 
-    def _split(self, prediction, probabilities=None):
+    def _split(self, prediction, probabilities=None, classes=None):
         """Per-stream outputs under the reference's keys; ``probabilities``: the sigmoid of the probability streams when a fused
-        loss pass has computed it already."""
+        loss pass has computed it already; ``classes``: {stream name: predicted class} of the categorical streams likewise."""
         parts = torch.split(prediction, [st.dim for st in self.streams], dim=-1) if len(self.streams) > 1 else (prediction,)
         outputs = {}
         for st, part in zip(self.streams, parts):
             if st.is_delta:
                 outputs[st.output_key] = part
+            elif st.is_categorical:
+                outputs[st.output_key] = part
+                outputs[st.name] = torch.argmax(part.detach(), dim=-1) if classes is None else classes[st.name]
             else:
                 outputs[st.output_key] = torch.sigmoid(part) if probabilities is None else probabilities
         return outputs
@@ -294,13 +306,16 @@ class StreamModel(BaseSPSS):
         if not self._generating():
             return
         n_frames = features['n_frames']
-        predicted = {st.name for st in self.streams if not st.is_delta}
+        predicted = {st.name for st in self.streams if not st.is_delta and not st.is_categorical}
         calls = {}
         for st in self.streams:
             if st.metric is None:
                 continue
             metric_name, _, kind = st.metric
-            if kind == 'accuracy':
+            if kind == 'accuracy' and st.is_categorical:
+                hits = features[st.name].reshape(outputs[st.name].shape) == outputs[st.name]
+                calls[metric_name] = (hits.type(torch.float).unsqueeze(-1), n_frames)
+            elif kind == 'accuracy':
                 calls[metric_name] = ((features[st.name] == (outputs[st.name] > 0.5)).type(torch.float), n_frames)
             elif kind == 'voiced_trajectory':
                 voiced = (outputs[st.voicing] > 0.5) if st.voicing in predicted else features[st.voicing]
@@ -310,7 +325,7 @@ class StreamModel(BaseSPSS):
         self.metrics.accumulate(self.mode, **calls)
 
     def _target(self, features, st):
-        return features[st.output_key]
+        return features[st.name] if st.is_categorical else features[st.output_key]
 
     # -- the plugin surface ----------------------------------------------------------------------------------------------------------
     def predict(self, features):
@@ -325,9 +340,12 @@ class StreamModel(BaseSPSS):
             if st.is_delta:
                 total = total + losses.mse(output_features[st.output_key], self._target(features, st), n_frames)
         for st in self.streams:
-            if not st.is_delta:
+            if not st.is_delta and not st.is_categorical:
                 total = total + losses.bce(output_features[st.output_key].type(torch.float), self._target(features, st).type(torch.float),
                                            n_frames)
+        for st in self.streams:                           # then the categorical streams, on their logits
+            if st.is_categorical:
+                total = total + losses.ce(output_features[st.output_key], self._target(features, st), n_frames)
         return total / float(len(self.streams)) if len(self.streams) > 1 else total
 
     def forward(self, features):
@@ -336,8 +354,15 @@ class StreamModel(BaseSPSS):
         prediction = self._run_layers(features)
         targets = [self._target(features, st) for st in self.streams]
         kinds = [st.loss for st in self.streams]
-        loss, probabilities = losses.multi_stream(prediction, targets, kinds, features['n_frames'], want_prob=True)
-        outputs = self._with_trajectories(self._split(prediction.detach(), probabilities), features['n_frames'],
+        classes = None
+        if 'ce' in kinds:
+            loss, probabilities, by_index = losses.multi_stream(prediction, targets, kinds, features['n_frames'],
+                                                                want_prob='sigmoid_bce' in kinds, widths=[st.dim for st in self.streams],
+                                                                want_argmax=True)
+            classes = {self.streams[k].name: argmax for k, argmax in by_index.items()}
+        else:
+            loss, probabilities = losses.multi_stream(prediction, targets, kinds, features['n_frames'], want_prob=True)
+        outputs = self._with_trajectories(self._split(prediction.detach(), probabilities, classes), features['n_frames'],
                                           features.get(data.SPEAKER_INDEX_KEY))
         self._accumulate_metrics(features, outputs)
         return loss, outputs

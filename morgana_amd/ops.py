@@ -289,6 +289,113 @@ def stream_loss(pred, targets, kinds, seq_len, want_grad, want_prob=False, grad_
     return loss, grad, prob
 
 
+def _rows_in_place(x, name):
+    """(B, T, C) f32 device tensor -> (tensor, row stride) such that frame (b, t) starts at data_ptr + (b T + t) * stride floats: the
+    tensor itself when its last dimension is contiguous and its frames are evenly spaced (a column slice of a contiguous (B, T, D)
+    tensor), else a contiguous copy."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError('%s must be a torch.Tensor, got %s' % (name, type(x)))
+    if not x.is_cuda:
+        raise _lib.MorganaHipError('%s is on %s: the morgana_amd ops run only on an MI355X device (no CPU fallback)' % (name, x.device))
+    if x.dtype != torch.float32:
+        raise TypeError('%s must be %s, got %s' % (name, torch.float32, x.dtype))
+    if x.dim() != 3:
+        raise ValueError('%s must be (B, T, C), got %s' % (name, tuple(x.shape)))
+    b, t, c = x.shape
+    ld = x.stride(1)
+    in_place = (x.stride(2) == 1 or c == 1) and ld >= c and (b == 1 or x.stride(0) == t * ld) and ld < 2 ** 31
+    if not in_place:
+        x = x.contiguous()
+        ld = c
+    return x, ld
+
+
+def masked_ce(pred, target, seq_len, want_grad, grad_scale=1.0, want_argmax=False, col0=0, width=None, grad_out=None, loss_out=None,
+              loss_weight=1.0, loss_keep=0.0):
+    """Masked categorical cross entropy (mg_masked_ce_f32) of columns [col0, col0 + width) of ``pred`` (B, T, D) f32 - all of them by
+    default - against ``target`` (B, T) int64 class indices.  Returns (loss 0-d f32, grad or None, argmax (B, T) int64 or None).
+
+    ``pred`` is read in place when its last dimension is contiguous (a column slice of a wider prediction).  ``grad_out``: a
+    (B, T, D) f32 buffer whose columns [col0, col0 + width) receive the gradient (the other columns are not touched) instead of a
+    new (B, T, width) tensor.  ``loss_out`` / ``loss_weight`` / ``loss_keep``: loss_out = loss_weight * loss + loss_keep * loss_out
+    on the device (``loss_keep == 0``: loss_out is only written)."""
+    lib = _lib.load()
+    pred, ldp = _rows_in_place(pred, 'predictions')
+    b, t, d = pred.shape
+    c = d - col0 if width is None else int(width)
+    if col0 < 0 or c < 1 or col0 + c > d:
+        raise ValueError('ce: columns [%d, %d) do not fit predictions %s' % (col0, col0 + c, tuple(pred.shape)))
+    target = _require(target, torch.int64, 'targets')
+    if tuple(target.shape) != (b, t):
+        raise ValueError('ce: targets %s do not match predictions %s: (B, T) class indices wanted' % (tuple(target.shape), tuple(pred.shape)))
+    if seq_len is not None:
+        seq_len = _require(seq_len, torch.int64, 'seq_len')
+    loss = torch.empty((), dtype=torch.float32, device=pred.device) if loss_out is None else loss_out
+    grad, g, ldg, gcol0 = None, None, 0, 0
+    if want_grad and grad_out is not None:
+        g, ldg = _rows_in_place(grad_out, 'grad_out')
+        if g is not grad_out or tuple(g.shape) != (b, t, d):
+            raise ValueError('ce: grad_out must be a (B, T, D) tensor with evenly spaced rows, shaped like predictions')
+        grad, gcol0 = grad_out, col0
+    elif want_grad:
+        grad = g = torch.empty((b, t, c), dtype=torch.float32, device=pred.device)
+        ldg = c
+    argmax = torch.empty((b, t), dtype=torch.int64, device=pred.device) if want_argmax else None
+    ws = workspace(lib.mg_masked_ce_workspace_bytes(b, t, c), pred.device)
+    _lib.check(lib.mg_masked_ce_f32(_p(pred), ldp, col0, _p(target), _p(seq_len), b, t, c, float(grad_scale), float(loss_weight),
+                                    float(loss_keep), _p(loss), _p(g), ldg, gcol0, _p(argmax), _p(ws), ws.numel(), _stream()),
+               'mg_masked_ce_f32')
+    return loss, grad, argmax
+
+
+def stream_loss_ce(pred, targets, kinds, widths, seq_len, want_grad, want_prob=False, want_argmax=False):
+    """``stream_loss`` for a stream table that holds 'ce' streams: the mse / sigmoid_bce streams take ONE mg_stream_loss_f32 launch
+    over a descriptor table of their own (gradient weight n_rest / n through ``grad_scale``), every 'ce' stream (``targets[k]`` (B, T) int64, ``widths[k]`` classes) one mg_masked_ce_f32
+    launch that writes its column slice of the same gradient tensor with weight 1 / n and adds its loss on the device
+    (loss = loss_rest * n_rest / n + sum_k ce_k / n: the reference-style mean over all n streams).  No host read.  Returns
+    (loss 0-d, grad or None, prob or None, [argmax per stream or None])."""
+    lib = _lib.load()
+    pred = _require(pred, torch.float32, 'predictions')
+    if pred.dim() != 3 or len(targets) != len(kinds) or not 1 <= len(targets) <= _lib.STREAMS_MAX:
+        raise ValueError('stream_loss: predictions must be (B, T, D) with 1..%d streams' % _lib.STREAMS_MAX)
+    b, t, d = pred.shape
+    if seq_len is not None:
+        seq_len = _require(seq_len, torch.int64, 'seq_len')
+    n = len(kinds)
+    widths = [int(w) for w in widths]
+    if len(widths) != n or min(widths) < 1 or sum(widths) != d:
+        raise ValueError('stream_loss: stream widths %s do not add up to D=%d' % (widths, d))
+    rest = [k for k in range(n) if kinds[k] != 'ce']
+    descs = (_lib.StreamDesc * max(len(rest), 1))()
+    keep, prob, col0s = [], None, [sum(widths[:k]) for k in range(n)]
+    for j, k in enumerate(rest):
+        y = _require(targets[k], torch.float32, 'targets[%d]' % k)
+        if y.dim() != 3 or y.shape[0] != b or y.shape[1] != t or y.shape[2] != widths[k]:
+            raise ValueError('stream_loss: targets[%d] %s does not match predictions (%d, %d, *)' % (k, tuple(y.shape), b, t))
+        keep.append(y)
+        descs[j].target, descs[j].ldt, descs[j].col0, descs[j].width = y.data_ptr(), widths[k], col0s[k], widths[k]
+        descs[j].kind = {'mse': _lib.LOSS_MSE, 'sigmoid_bce': _lib.LOSS_SIGMOID_BCE}[kinds[k]]
+        if kinds[k] == 'sigmoid_bce' and want_prob:
+            prob = torch.empty((b, t, widths[k]), dtype=torch.float32, device=pred.device)
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    grad = torch.empty_like(pred) if want_grad else None
+    if rest:
+        # zero in the columns no descriptor covers (the 'ce' streams' columns: overwritten below)
+        ws = workspace(lib.mg_stream_loss_workspace_bytes(b, t, d), pred.device)
+        _lib.check(lib.mg_stream_loss_f32(_p(pred), ctypes.cast(descs, ctypes.c_void_p), len(rest), _p(seq_len), b, t, d,
+                                          float(len(rest)) / n, _p(loss), _p(grad), _p(prob), _p(ws), ws.numel(), _stream()),
+                   'mg_stream_loss_f32')
+    argmaxes, first = [None] * n, True
+    for k in range(n):
+        if kinds[k] != 'ce':
+            continue
+        keep_w = (float(len(rest)) / n if rest else 0.0) if first else 1.0
+        _, _, argmaxes[k] = masked_ce(pred, targets[k], seq_len, want_grad, grad_scale=1.0 / n, want_argmax=want_argmax,
+                                      col0=col0s[k], width=widths[k], grad_out=grad, loss_out=loss, loss_weight=1.0 / n, loss_keep=keep_w)
+        first = False
+    return loss, grad, prob, argmaxes
+
+
 def pad_normalise(packed, offsets, t, p0=None, p1=None, kind=None, want_raw=True, bf16_extra_rows=None):
     """Packed utterances (sum len, D) + offsets (B+1) -> (raw (B,t,D) or None, normalised (B,t,D) or None).
     ``bf16_extra_rows`` (an int, needs ``kind``): the same pass also writes the normalised feature's bf16 operand table
