@@ -643,6 +643,31 @@ int mg_gather_concat_latent_bf16(const float* src, const int32_t* rows, const fl
 int mg_rows_add_per_item_f32(float* P, int ldp, int64_t rows, int N, const float* U, int ldu, int64_t rows_per_item, void* stream);
 int mg_rows_sum_per_item(const void* G, int ldg, int bf16, const float* H, int ldh, int64_t B, int64_t rows_per_item, int N, float* s, int lds,
                          void* stream);
+/* Latent surface samplers (morgana.sampling, reference sampling.py; csrc/sampling.hip): points at a fixed distance from the prior's
+ * centre, fed to a latent-conditioned model's predict().  out, unit, factor, dout are contiguous [rows, D] f32; rows >= 0 (0: nothing
+ * is drawn); seed, site and counter as mg_vae_sample_f32 (counter: DEVICE uint64, NULL = 0; the dropout step counter).  One wave per
+ * row; every reduction and the scan have one fixed order and use no atomics: the same bits on every call.
+ * mg_sphere_sample_f32 (D >= 1): out = centre + radius g / |g|_2 and unit = g / |g|_2 written out; centre [D], radius a DEVICE f32
+ *   scalar.  g ~ N(0, 1) by the noise mapping of mg_vae_sample_f32, word for word: flat element i = r * D + c belongs to Philox block
+ *   q = i / 4 (blocks straddle rows when D % 4 != 0), counter words (q low, q high, ctr low, site ^ ctr high), key (seed low,
+ *   seed high), ctr = *counter; u(w) = ((w >> 8) | 1) * 2^-24; the block's words (x, y, z, w) give elements 4q..4q+3 =
+ *   R(x) cos(2 pi u(y)), R(x) sin(2 pi u(y)), R(z) cos(2 pi u(w)), R(z) sin(2 pi u(w)), R(a) = sqrt(-2 ln u(a)).  Rows of up to 256
+ *   values stay in registers; longer rows loop over chunks of 64 with a carried partial sum.  D = 1 gives exactly centre +- radius.
+ * mg_sphere_sample_bwd_f32: dcentre[c] = sum_r dout[r, c], dradius[0] = sum_{r, c} dout[r, c] unit[r, c]; fp64 partials.
+ * mg_ellipsoid_sample_f32 (D >= 2; the reference's output is ill-formed below): D - 1 uniform angles per row.  Angle element
+ *   i = r * (D - 1) + c draws u = u(word i % 4 of Philox block i / 4), same counter and key words as above; column 0 is
+ *   phi = 2 pi u, columns 1..D-2 are theta = pi u.  factor[r, n] = (prod_{j < n} sin(angle_j)) * cos(angle_n) with an empty product
+ *   = 1 and cos(angle_{D-1}) := 1; out = radii * factor, radii [D].  The reference's `centre` only fixes D and is NOT added
+ *   (sampling.py:113); neither is it here.  The product is a wave scan with a carried prefix between chunks of 64 columns.
+ * mg_ellipsoid_angles_f32: angles [rows, D - 1] of that mapping alone (the reference's sample_angles), as fp32 multiples of pi.
+ * mg_ellipsoid_sample_bwd_f32: dradii[n] = sum_r dout[r, n] factor[r, n]; fp64 partials. */
+int mg_sphere_sample_f32(const float* centre, const float* radius, int64_t rows, int D, uint64_t seed, uint32_t site, const uint64_t* counter,
+                         float* out, float* unit, void* stream);
+int mg_sphere_sample_bwd_f32(const float* dout, const float* unit, int64_t rows, int D, float* dcentre, float* dradius, void* stream);
+int mg_ellipsoid_sample_f32(const float* radii, int64_t rows, int D, uint64_t seed, uint32_t site, const uint64_t* counter, float* out,
+                            float* factor, void* stream);
+int mg_ellipsoid_angles_f32(int64_t rows, int D, uint64_t seed, uint32_t site, const uint64_t* counter, float* angles, void* stream);
+int mg_ellipsoid_sample_bwd_f32(const float* dout, const float* factor, int64_t rows, int D, float* dradii, void* stream);
 /* CALIBRATION (a measurement entry; no training step calls it): one launch of a register-operand bf16 MFMA loop - n_workgroups x 512
  * threads (two waves per SIMD), every wave issues 16 x trips v_mfma_f32_16x16x32_bf16 on operands read once from `operands`
  * (bf16, at least 4096 x 64 values: the caller chooses the data, e.g. random) and writes one float per thread to `sink`

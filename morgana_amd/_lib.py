@@ -120,6 +120,12 @@ SIGNATURES = {
                                              c_void_p]),
     'mg_rows_add_per_item_f32': (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int64, c_void_p]),
     'mg_rows_sum_per_item': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p]),
+    'mg_sphere_sample_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
+    'mg_sphere_sample_bwd_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    'mg_ellipsoid_sample_f32': (c_int, [c_void_p, c_int64, c_int, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mg_ellipsoid_angles_f32': (c_int, [c_int64, c_int, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p]),
+    'mg_ellipsoid_sample_bwd_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     'mg_calib_mfma_bf16': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'mg_sigmoid_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     'mg_sigmoid_grad_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -247,6 +247,47 @@ class SampleFn(torch.autograd.Function):
         return dmean, dlogvar
 
 
+class SphereSampleFn(torch.autograd.Function):
+    """``sampling.UniformSphereSurfaceSampler.rsample`` (reference sampling.py:25-29): ``rows`` points centre + radius g / |g|, g ~ N(0, 1)
+    from Philox words of (torch's seed, ops.SPHERE_SITE, one draw of the device's step counter, element) - csrc/sampling.hip.  The
+    counter is the dropout one (ops.dropout_draw): an eager call and a graph replay each draw new noise.  forward(ctx, centre, radius,
+    rows): centre (D,), radius a 1-element device tensor; the result is (rows, D).  Gradients: sum_r grad for centre, sum grad * g / |g|
+    for radius."""
+
+    @staticmethod
+    def forward(ctx, centre, radius, rows):
+        seed, used = ops.dropout_seed(), ops.dropout_draw(centre.device)
+        out, unit = ops.sphere_sample(centre, radius, rows, seed, ops.SPHERE_SITE, used)
+        ctx.save_for_backward(unit)
+        ctx.radius_shape = tuple(radius.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        (unit,) = ctx.saved_tensors
+        dcentre, dradius = ops.sphere_sample_backward(grad.contiguous(), unit)
+        return (dcentre if ctx.needs_input_grad[0] else None, dradius.view(ctx.radius_shape) if ctx.needs_input_grad[1] else None, None)
+
+
+class EllipsoidSampleFn(torch.autograd.Function):
+    """``sampling.UniformEllipsoidSurfaceApproximateSampler.rsample`` (reference sampling.py:61-113): ``rows`` points radii * factor,
+    factor[n] = prod_{j < n} sin(angle_j) * cos(angle_n) from D - 1 uniform angles per row, drawn from (torch's seed,
+    ops.ELLIPSOID_SITE, one draw of the device's step counter, element).  forward(ctx, radii, rows): radii (D,); the result is (rows, D).
+    The gradient of radii is sum_r grad * factor."""
+
+    @staticmethod
+    def forward(ctx, radii, rows):
+        seed, used = ops.dropout_seed(), ops.dropout_draw(radii.device)
+        out, factor = ops.ellipsoid_sample(radii, rows, seed, ops.ELLIPSOID_SITE, used)
+        ctx.save_for_backward(factor)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        (factor,) = ctx.saved_tensors
+        return ops.ellipsoid_sample_backward(grad.contiguous(), factor), None
+
+
 class KLDFn(torch.autograd.Function):
     """``losses.KLD_standard_normal`` (reference losses.py:64-67): one deterministic reduction forward, and a backward that reads the
     upstream gradient on the device (no host read)."""

@@ -943,6 +943,8 @@ def dropout(x, p, seed, site, used, out=None):
 
 # ------------------------------------------------------------------------------------------------ latent-conditioned models (VAE)
 SAMPLE_SITE = 0x56414500     # the Philox site of the VAE sampler's noise (dropout masks use the module index of their layer)
+SPHERE_SITE = 0x53504800     # the Philox sites of sampling.UniformSphereSurfaceSampler's noise ...
+ELLIPSOID_SITE = 0x454C4C00  # ... and of sampling.UniformEllipsoidSurfaceApproximateSampler's angles: three streams, never one
 
 
 def _latent_rows(t, name):
@@ -1001,6 +1003,76 @@ def kld_standard_normal_backward(grad, mean, logvar):
     _lib.check(_lib.load().mg_kld_standard_normal_bwd_f32(_p(grad), _p(m2), ldm, _p(v2), ldv, m2.shape[0], m2.shape[1], _p(dmean), _p(dlogvar),
                                                           _stream()), 'mg_kld_standard_normal_bwd_f32')
     return dmean, dlogvar
+
+
+# ------------------------------------------------------------------------------------------- latent surface samplers (sampling)
+def _site_args(seed, site, used):
+    return int(seed), int(site) & 0xFFFFFFFF, _p(used)
+
+
+def sphere_sample(centre, radius, rows, seed, site, used):
+    """``rows`` points on the sphere's surface: out = centre + radius g / |g|, g ~ N(0, 1) drawn from (seed, site, used[0], element) -
+    mg_sphere_sample_f32.  centre: (D,) f32; radius: a 1-element f32 DEVICE tensor.  Returns (out, unit), both (rows, D); unit = g / |g|
+    is what the backward needs."""
+    centre = _require(centre, torch.float32, 'centre')
+    radius = _require(radius, torch.float32, 'radius')
+    if centre.dim() != 1 or radius.numel() != 1:
+        raise ValueError('sphere_sample: centre must be (D,) and radius one element, got %s and %s' % (tuple(centre.shape), tuple(radius.shape)))
+    out = torch.empty((int(rows), centre.shape[0]), dtype=torch.float32, device=centre.device)
+    unit = torch.empty_like(out)
+    _lib.check(_lib.load().mg_sphere_sample_f32(_p(centre), _p(radius), int(rows), centre.shape[0], *_site_args(seed, site, used), _p(out),
+                                                _p(unit), _stream()), 'mg_sphere_sample_f32')
+    return out, unit
+
+
+def sphere_sample_backward(dout, unit):
+    """(dcentre (D,), dradius (1,)) of sphere_sample: the column sums of dout and sum(dout * unit) - mg_sphere_sample_bwd_f32."""
+    dout = _require(dout, torch.float32, 'gradient')
+    unit = _require(unit, torch.float32, 'unit')
+    if dout.dim() != 2 or tuple(dout.shape) != tuple(unit.shape):
+        raise ValueError('sphere_sample_backward: gradient %s and unit %s must be one (rows, D) shape' % (tuple(dout.shape), tuple(unit.shape)))
+    dcentre = torch.empty(dout.shape[1], dtype=torch.float32, device=dout.device)
+    dradius = torch.empty(1, dtype=torch.float32, device=dout.device)
+    _lib.check(_lib.load().mg_sphere_sample_bwd_f32(_p(dout), _p(unit), dout.shape[0], dout.shape[1], _p(dcentre), _p(dradius), _stream()),
+               'mg_sphere_sample_bwd_f32')
+    return dcentre, dradius
+
+
+def ellipsoid_sample(radii, rows, seed, site, used):
+    """``rows`` points on the ellipsoid's surface from D - 1 uniform angles each: out = radii * factor, factor[n] = prod_{j < n}
+    sin(angle_j) * cos(angle_n) - mg_ellipsoid_sample_f32.  radii: (D,) f32, D >= 2.  Returns (out, factor), both (rows, D)."""
+    radii = _require(radii, torch.float32, 'radii')
+    if radii.dim() != 1:
+        raise ValueError('ellipsoid_sample: radii must be (D,), got %s' % (tuple(radii.shape),))
+    out = torch.empty((int(rows), radii.shape[0]), dtype=torch.float32, device=radii.device)
+    factor = torch.empty_like(out)
+    _lib.check(_lib.load().mg_ellipsoid_sample_f32(_p(radii), int(rows), radii.shape[0], *_site_args(seed, site, used), _p(out), _p(factor),
+                                                   _stream()), 'mg_ellipsoid_sample_f32')
+    return out, factor
+
+
+def ellipsoid_angles(rows, ndims, device, seed, site, used):
+    """The (rows, ndims - 1) angles ellipsoid_sample draws from the same (seed, site, used[0]) - mg_ellipsoid_angles_f32."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise _lib.MorganaHipError('angles on %s: the morgana_amd ops run only on an MI355X device (no CPU fallback)' % device)
+    angles = torch.empty((int(rows), max(int(ndims) - 1, 0)), dtype=torch.float32, device=device)
+    _lib.check(_lib.load().mg_ellipsoid_angles_f32(int(rows), int(ndims), *_site_args(seed, site, used), _p(angles), _stream()),
+               'mg_ellipsoid_angles_f32')
+    return angles
+
+
+def ellipsoid_sample_backward(dout, factor):
+    """dradii (D,) of ellipsoid_sample: the column sums of dout * factor - mg_ellipsoid_sample_bwd_f32."""
+    dout = _require(dout, torch.float32, 'gradient')
+    factor = _require(factor, torch.float32, 'factor')
+    if dout.dim() != 2 or tuple(dout.shape) != tuple(factor.shape):
+        raise ValueError('ellipsoid_sample_backward: gradient %s and factor %s must be one (rows, D) shape'
+                         % (tuple(dout.shape), tuple(factor.shape)))
+    dradii = torch.empty(dout.shape[1], dtype=torch.float32, device=dout.device)
+    _lib.check(_lib.load().mg_ellipsoid_sample_bwd_f32(_p(dout), _p(factor), dout.shape[0], dout.shape[1], _p(dradii), _stream()),
+               'mg_ellipsoid_sample_bwd_f32')
+    return dradii
 
 
 def gather_concat_latent(src2d, rows, extra2d, z2d, rows_per_item, out_bf16=False):
