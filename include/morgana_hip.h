@@ -134,6 +134,32 @@ size_t mg_pad_rows_colsum_workspace_bytes(int B, int T, int D);
 int mg_pad_rows_colsum_f32(const float* g, const int64_t* seq_len, int B, int T, int D, float* out, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* Ragged pack of padded sequence features (reference: utils.detach_batched_seqs / batched_masked_select, morgana/utils.py:66-102,
+ * :147-166; csrc/unpad.hip).  ONE launch compacts up to MG_UNPAD_MAX features of any element type into one byte buffer: item b of
+ * feature f contributes len = min(max(seq_len[b], 0), T_f) frames, whose bytes land at
+ *   dst + dst_offset_f + row_bytes_f * sum_{b' < b} len_b'      and come from      src_f + b * T_f * row_bytes_f.
+ * The launch moves bytes (bit-identical for every dtype).  seq_len int64 [B] is read ON THE DEVICE and scanned there; `descs` is a
+ * HOST array.  Nothing is written outside [dst_offset_f, dst_offset_f + block_bytes_f), whatever seq_len holds: rows that do not
+ * fit the block are dropped.  Refused (MG_EINVAL): count outside 1..MG_UNPAD_MAX, B outside 0..MG_UNPAD_MAX_ITEMS, row_bytes <= 0,
+ * T < 0, dst_offset not a non-negative multiple of 16, a block outside [0, dst_bytes) or overlapping another, NULL pointers where
+ * bytes would move.  B == 0 or no block that holds a row: MG_OK without a launch. */
+#define MG_UNPAD_MAX 16
+#define MG_UNPAD_MAX_ITEMS 4096
+typedef struct {
+    const void* src;        /* [B, T, row_bytes] contiguous                           */
+    int64_t T;              /* padded axis of THIS feature (features may differ)      */
+    int64_t row_bytes;      /* bytes of one frame: trailing elements x element size   */
+    int64_t dst_offset;     /* start of this feature's block in dst, multiple of 16   */
+    int64_t block_bytes;    /* capacity of the block; nothing is written beyond it    */
+} mg_unpad_desc;
+int mg_unpad_rows(const mg_unpad_desc* descs, int count, const int64_t* seq_len, int B, void* dst, int64_t dst_bytes, void* stream);
+
+/* out[i] = all_k (xs[k][i] != 0) for 1..MG_ALL_NONZERO_MAX float32 inputs of n elements each (reference: utils.both_voiced_mask,
+ * morgana/utils.py:169-172 = prod_k ~torch.eq(x_k, 0.): NaN counts as non-zero, -0.0 as zero).  `xs` is a HOST array of device
+ * pointers; the output element is encoded as in mg_sequence_mask (elem_size 1 / 4 / 8 bytes, as_float). */
+#define MG_ALL_NONZERO_MAX 8
+int mg_all_nonzero_f32(const float* const* xs, int count, int64_t n, void* out, int elem_size, int as_float, void* stream);
+
 /* Gather fused with the frame-level concat the shipped models do right after it (models/RNN_SPSS.py:76-81,
  * models/f0_test_model.py:78-79: upsample_to_repetitions, then torch.cat with `normalised_counters`):
  *   out[m, 0:F] = src[rows[m], :] (0 where rows[m] < 0), out[m, F:F+C] = extra[m, 0:C], out[m, F+C:ldo] = 0.

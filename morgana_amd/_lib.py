@@ -26,6 +26,8 @@ SIGNATURES = {
     'mg_segment_index': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'mg_scatter_rows_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     'mg_frame_layout': (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mg_unpad_rows': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    'mg_all_nonzero_f32': (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_void_p]),
     'mg_pad_rows_colsum_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'mg_pad_rows_colsum_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'mg_gather_concat_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
@@ -274,6 +276,16 @@ class CopyDesc(ctypes.Structure):
 
 
 COPY_MAX = 16
+
+
+class UnpadDesc(ctypes.Structure):
+    """mg_unpad_desc of include/morgana_hip.h."""
+    _fields_ = [('src', c_void_p), ('T', c_int64), ('row_bytes', c_int64), ('dst_offset', c_int64), ('block_bytes', c_int64)]
+
+
+UNPAD_MAX = 16                # MG_UNPAD_MAX
+UNPAD_MAX_ITEMS = 4096        # MG_UNPAD_MAX_ITEMS
+ALL_NONZERO_MAX = 8           # MG_ALL_NONZERO_MAX
 
 
 class Split3Desc(ctypes.Structure):

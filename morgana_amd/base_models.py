@@ -80,7 +80,7 @@ class BaseModel(nn.Module):
         loader then carries ``name + '__bf16_table'`` next to the feature: ``data.DeviceBatches.use_bf16_tables``); () otherwise."""
         return ()
 
-    # analysis hooks (no-ops here; base_models.py:177-253)
+    # analysis hooks (base_models.py:177-271): the train hooks are no-ops, valid chains to train and test to valid, as in the reference
     def analysis_for_train_batch(self, features, output_features, out_dir, **kwargs):
         pass
 
@@ -88,10 +88,10 @@ class BaseModel(nn.Module):
         pass
 
     def analysis_for_valid_batch(self, features, output_features, out_dir, **kwargs):
-        pass
+        self.analysis_for_train_batch(features, output_features, out_dir, **kwargs)
 
     def analysis_for_valid_epoch(self, out_dir, **kwargs):
-        pass
+        self.analysis_for_train_epoch(out_dir, **kwargs)
 
     def analysis_for_test_batch(self, features, output_features, out_dir, **kwargs):
         self.analysis_for_valid_batch(features, output_features, out_dir, **kwargs)

@@ -13,6 +13,7 @@ matrix rate; row-wise Linear / Sigmoid layers only, recurrent cells run their ex
 """
 import os
 
+import numpy as np
 import torch
 
 from . import ops
@@ -2055,6 +2056,39 @@ class StreamLossCEFn(torch.autograd.Function):
         if _is_unit_grad(grad_loss):
             return (grad, None, None, None, None, None) + (None,) * ctx.n_targets
         return (grad * grad_loss, None, None, None, None, None) + (None,) * ctx.n_targets
+
+
+def masked_select_rows(x, seq_len, lens):
+    """(sum_b min(max(lens[b], 0), T), ...) valid frames of a padded device tensor (B, T, ...) of any dtype (ops.unpad_rows); ``lens`` =
+    ``seq_len`` on the host."""
+    buf, ((_, rows),) = ops.unpad_rows([x], seq_len, lens)
+    n_bytes = rows * ops.row_bytes(x)
+    return buf[:n_bytes].view(x.dtype).view((rows,) + tuple(x.shape[2:]))
+
+
+class MaskedSelectFn(torch.autograd.Function):
+    """utils.batched_masked_select for float32: forward the ragged pack, backward its adjoint - the packed gradient scattered into a
+    zero-padded (B, T, ...) tensor (mg_pad_normalise_f32 without a normaliser)."""
+
+    @staticmethod
+    def forward(ctx, x, seq_len, lens):
+        x = ops._require(x, torch.float32, 'sequence_feature')
+        ctx.shape = tuple(x.shape)
+        ends = np.cumsum(np.clip(np.asarray(lens, dtype=np.int64), 0, x.shape[1]))
+        ctx.total = int(ends[-1]) if len(ends) else 0
+        # first packed row of every item (B + 1): what the backward's scatter reads, uploaded once here
+        ctx.save_for_backward(torch.from_numpy(np.concatenate((np.zeros(1, np.int64), ends))).to(x.device))
+        return masked_select_rows(x, seq_len, lens)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (offsets,) = ctx.saved_tensors
+        t = ctx.shape[1]
+        with torch.cuda.device(grad_out.device):
+            if ctx.total == 0 or t == 0:
+                return torch.zeros(ctx.shape, dtype=torch.float32, device=grad_out.device), None, None
+            raw, _ = ops.pad_normalise(grad_out.contiguous().view(ctx.total, -1), offsets, t)
+        return raw.view(ctx.shape), None, None
 
 
 class GatherRowsFn(torch.autograd.Function):

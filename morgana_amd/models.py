@@ -348,6 +348,20 @@ class StreamModel(BaseSPSS):
                 total = total + losses.ce(output_features[st.output_key], self._target(features, st), n_frames)
         return total / float(len(self.streams)) if len(self.streams) > 1 else total
 
+    def analysis_for_valid_batch(self, features, output_features, out_dir, **kwargs):
+        """Saves every stream's generated output per utterance under ``{out_dir}/feats/{stream}/{name}.npy``
+        (``viz.io.save_batched_seqs``): the MLPG trajectory of a delta stream (present when the normalisers carry delta
+        parameters, i.e. under ``ExperimentBuilder``), the probabilities of a 'sigmoid_bce' stream, the predicted classes of a 'ce'
+        stream.  models/RNN_SPSS.py:145-161 - without its WORLD waveform synthesis, which needs ``pyworld`` (not a dependency of
+        this package).  Nothing is written without an ``out_dir`` or without utterance names in ``features['name']``."""
+        super(StreamModel, self).analysis_for_valid_batch(features, output_features, out_dir, **kwargs)
+        names = [st.name for st in self.streams if st.name in output_features]
+        if out_dir is None or not names or features.get('name') is None:
+            return
+        # the classes of a categorical stream are (B, T): a trailing axis makes them a sequence feature that is cropped like the others
+        outputs = [output_features[n].unsqueeze(-1) if output_features[n].ndim == 2 else output_features[n] for n in names]
+        viz.io.save_batched_seqs(outputs, names=features['name'], out_dir=out_dir, seq_len=features['n_frames'], feat_names=names)
+
     def forward(self, features):
         if not self.fused_loss:
             return super(StreamModel, self).forward(features)

@@ -234,6 +234,104 @@ def sequence_mask(seq_len, max_len, dtype):
     return mask
 
 
+def all_nonzero(tensors, dtype):
+    """out = all_k (tensors[k] != 0) in ``dtype`` for up to ``_lib.ALL_NONZERO_MAX`` float32 device tensors of one shape
+    (mg_all_nonzero_f32): NaN counts as non-zero, -0.0 as zero."""
+    lib = _lib.load()
+    if not 1 <= len(tensors) <= _lib.ALL_NONZERO_MAX:
+        raise ValueError('all_nonzero: %d inputs, the kernel takes 1..%d' % (len(tensors), _lib.ALL_NONZERO_MAX))
+    if dtype not in _MASK_TYPES:
+        raise TypeError('all_nonzero: unsupported mask dtype %s' % dtype)
+    tensors = [_require(t, torch.float32, 'sequence_feature') for t in tensors]
+    for t in tensors[1:]:
+        if t.shape != tensors[0].shape:
+            raise ValueError('all_nonzero: shapes %s and %s differ' % (tuple(tensors[0].shape), tuple(t.shape)))
+    elem, as_float = _MASK_TYPES[dtype]
+    out = torch.empty(tensors[0].shape, dtype=dtype, device=tensors[0].device)
+    ptrs = (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+    _lib.check(lib.mg_all_nonzero_f32(ctypes.cast(ptrs, ctypes.c_void_p), len(tensors), tensors[0].numel(), _p(out), elem, as_float,
+                                      _stream()), 'mg_all_nonzero_f32')
+    return out
+
+
+UNPAD_ALIGN = 64      # every feature's block of the packed buffer starts on a multiple of this many bytes
+
+
+def row_bytes(t):
+    """Bytes of one frame of a (B, T, ...) tensor: trailing elements x element size."""
+    n = t.element_size()
+    for k in t.shape[2:]:
+        n *= int(k)
+    return n
+
+
+def unpad_layout(shapes_and_sizes, lens_host):
+    """Blocks of the packed buffer of ``unpad_rows``: for every (T, row_bytes) the (offset, rows) of its block - rows =
+    sum_b min(max(lens_host[b], 0), T), blocks exactly as large as their rows, starts on multiples of ``UNPAD_ALIGN`` - and the
+    buffer's size.  Host arithmetic only."""
+    blocks, size = [], 0
+    for t, rb in shapes_and_sizes:
+        rows = sum(min(max(int(n), 0), int(t)) for n in lens_host)
+        size = (size + UNPAD_ALIGN - 1) // UNPAD_ALIGN * UNPAD_ALIGN
+        blocks.append((size, rows))
+        size += rows * int(rb)
+    return blocks, size
+
+
+def unpad_rows(tensors, seq_len, lens_host):
+    """The valid frames of padded device features, utterance after utterance, as ONE byte buffer (mg_unpad_rows: one launch per
+    ``_lib.UNPAD_MAX`` features; beyond ``_lib.UNPAD_MAX_ITEMS`` items one launch per feature and group of that many items).  tensors: contiguous device tensors (B, T_f, ...) of any dtype; seq_len: int64 (B,) on the same device
+    - the kernel reads the lengths there; lens_host: the same lengths on the host, which size the blocks (a frame beyond a block is
+    dropped, never written).  Returns (uint8 device buffer, [(byte offset, rows)] per feature)."""
+    lib = _lib.load()
+    seq_len = _require(seq_len, torch.int64, 'seq_len')
+    b = seq_len.numel()
+    if len(lens_host) != b:
+        raise ValueError('unpad_rows: %d host lengths for %d items' % (len(lens_host), b))
+    feats = []
+    for k, t in enumerate(tensors):
+        t = _require(t, getattr(t, 'dtype', None), 'sequence_feature %d' % k)      # any dtype: a device tensor, made contiguous
+        if t.dim() < 2 or t.shape[0] != b or t.device != seq_len.device:
+            raise ValueError('unpad_rows: feature %d is %s on %s, expected (%d, T, ...) on %s' % (k, tuple(t.shape), t.device, b, seq_len.device))
+        if row_bytes(t) <= 0:
+            raise ValueError('unpad_rows: feature %d of shape %s has empty frames' % (k, tuple(t.shape)))
+        feats.append((t, int(t.shape[1]), row_bytes(t)))
+    blocks, size = unpad_layout([(t_len, rb) for _, t_len, rb in feats], lens_host)
+    buf = torch.empty(max(size, 1), dtype=torch.uint8, device=seq_len.device)
+    if b > _lib.UNPAD_MAX_ITEMS:
+        _unpad_rows_in_item_groups(lib, feats, blocks, seq_len, lens_host, buf)
+        return buf, blocks
+    for first in range(0, len(feats), _lib.UNPAD_MAX):
+        chunk = feats[first:first + _lib.UNPAD_MAX]
+        descs = (_lib.UnpadDesc * len(chunk))()
+        for i, (t, t_len, rb) in enumerate(chunk):
+            offset, rows = blocks[first + i]
+            descs[i].src, descs[i].T, descs[i].row_bytes = t.data_ptr(), t_len, rb
+            descs[i].dst_offset, descs[i].block_bytes = offset, rows * rb
+        _lib.check(lib.mg_unpad_rows(ctypes.cast(descs, ctypes.c_void_p), len(chunk), _p(seq_len), b, _p(buf), size, _stream()),
+                   'mg_unpad_rows')
+    return buf, blocks
+
+
+def _unpad_rows_in_item_groups(lib, feats, blocks, seq_len, lens_host, buf):
+    """``unpad_rows`` for more items than one launch scans (``_lib.UNPAD_MAX_ITEMS``): per feature, one launch per group of that many
+    items, each writing behind the rows of the groups before it.  A group's first byte is wherever those rows end, so the launch gets
+    the destination pointer moved there and a block at offset 0 (the kernel aligns by address, only ``dst_offset`` must be a
+    multiple of 16)."""
+    b = seq_len.numel()
+    desc = (_lib.UnpadDesc * 1)()
+    for (t, t_len, rb), (offset, _) in zip(feats, blocks):
+        done = 0                                                           # rows of the groups already packed
+        for b0 in range(0, b, _lib.UNPAD_MAX_ITEMS):
+            b1 = min(b0 + _lib.UNPAD_MAX_ITEMS, b)
+            rows = sum(min(max(int(n), 0), t_len) for n in lens_host[b0:b1])
+            desc[0].src, desc[0].T, desc[0].row_bytes = t.data_ptr() + b0 * t_len * rb, t_len, rb
+            desc[0].dst_offset, desc[0].block_bytes = 0, rows * rb
+            _lib.check(lib.mg_unpad_rows(ctypes.cast(desc, ctypes.c_void_p), 1, ctypes.c_void_p(seq_len.data_ptr() + 8 * b0), b1 - b0,
+                                         ctypes.c_void_p(buf.data_ptr() + offset + done * rb), rows * rb, _stream()), 'mg_unpad_rows')
+            done += rows
+
+
 def masked_mse(pred, target, seq_len, want_grad, grad_scale=1.0, kind='mse'):
     """Returns (loss 0-d f32 tensor, grad or None).  kind: 'mse' or 'bce'."""
     lib = _lib.load()

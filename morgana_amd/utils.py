@@ -1,11 +1,15 @@
 """Host-side mirror of ``morgana.utils`` for the training hot path: same names, arguments and error behaviour, with the
 per-frame compute done by the HIP kernels of libmorgana_hip.so (no torch-op or CPU fallback for the in-scope ops).
 
-Reference: morgana/utils.py - ``sequence_mask`` :115-144, ``upsample_to_repetitions`` :175-228,
+Reference: morgana/utils.py - ``listify`` :10-14, ``map_nested`` :37-53, ``detach_batched_seqs`` :66-102,
+``get_epoch_from_checkpoint_path`` :105-112, ``sequence_mask`` :115-144, ``batched_masked_select`` :147-166, ``both_voiced_mask`` :169-172, ``upsample_to_repetitions`` :175-228,
 ``split_to_segments`` :231-285, ``get_segment_ends`` :288-330, ``RecurrentCuDNNWrapper`` :333-393, ``SequentialWithRecurrent`` :396-418, ``ExponentialMovingAverage`` :421-456.
 """
 import os
+import re
+from collections.abc import Iterable, Mapping
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -42,6 +46,146 @@ def sequence_mask(seq_len, max_len=None, dtype=torch.ByteTensor, device=None):
         max_len = torch.max(seq_len).item()
     seq_len = seq_len if seq_len.dtype == torch.int64 else seq_len.long()
     return ops.sequence_mask(seq_len, int(max_len), _as_dtype(dtype))
+
+
+def listify(object_or_list):
+    """Converts input to an iterable if it is not already one.  morgana/utils.py:10-14."""
+    if not isinstance(object_or_list, (list, tuple)):
+        object_or_list = [object_or_list]
+    return object_or_list
+
+
+def map_nested(func, data):
+    """Recursively applies a function on a nested data structure; base cases ``np.ndarray`` and ``torch.Tensor``.  morgana/utils.py:37-53."""
+    if isinstance(data, (np.ndarray, torch.Tensor)):
+        return func(data)
+    if isinstance(data, Mapping):
+        return {k: map_nested(func, v) for k, v in data.items()}
+    if isinstance(data, Iterable) and not isinstance(data, str):
+        return [map_nested(func, v) for v in data]
+    return func(data)
+
+
+def get_epoch_from_checkpoint_path(checkpoint_path):
+    """Epoch number of a path of the form ``.*checkpoints/epoch_(NUM)_.*.pt``, 0 when it does not match.  morgana/utils.py:105-112."""
+    match = re.match(r'.*checkpoints/epoch_(?P<epoch>\d+)(_\w+)?\.\w+', checkpoint_path)
+    return 0 if match is None else int(match['epoch'])
+
+
+_detach_staging = None
+
+
+def _numpy_dtype(dtype):
+    """The NumPy dtype of a torch dtype; TypeError for one NumPy cannot hold (bfloat16), as ``Tensor.numpy()`` raises it."""
+    return torch.empty(0, dtype=dtype).numpy().dtype
+
+
+def _seq_len_on(seq_len_tensor, lens, device):
+    """int64 (B,) lengths on ``device``: the caller's own tensor when it already lives there, else an upload of the host lengths."""
+    if seq_len_tensor is not None and seq_len_tensor.device == device and seq_len_tensor.dim() == 1:
+        return seq_len_tensor.detach() if seq_len_tensor.dtype == torch.int64 else seq_len_tensor.detach().long()
+    return torch.from_numpy(np.ascontiguousarray(lens)).to(device)
+
+
+def _detach_on_device(features, lens, seq_len_tensor, squeeze):
+    """Per feature the list of per-item arrays (len_b, ...) of padded DEVICE features (B, T, ...): one ragged-pack launch per 16
+    features (ops.unpad_rows), one asynchronous device -> host copy of exactly the packed bytes into pinned staging, one wait on an
+    event of the current stream.  The arrays are slices of one host copy per feature, taken out of the reused staging buffer."""
+    global _detach_staging
+    from . import data
+    np_dtypes = [_numpy_dtype(f.dtype) for f in features]          # before any launch: bfloat16 raises here
+    device = features[0].device
+    with torch.cuda.device(device):
+        seq_dev = _seq_len_on(seq_len_tensor, lens, device)
+        buf, blocks = ops.unpad_rows([f.detach() for f in features], seq_dev, lens)
+        n_bytes = max((off + rows * ops.row_bytes(f) for f, (off, rows) in zip(features, blocks)), default=0)
+        stage = None
+        if n_bytes > 0:
+            if _detach_staging is None:
+                _detach_staging = data._Staging()
+            slot = _detach_staging.take(str(device), 'detach', n_bytes)
+            slot[0][:n_bytes].copy_(buf[:n_bytes], non_blocking=True)
+            slot[1] = torch.cuda.Event()
+            slot[1].record(torch.cuda.current_stream(device))
+            slot[1].synchronize()
+            stage = slot[0].numpy()
+    out = []
+    for f, np_dtype, (off, rows) in zip(features, np_dtypes, blocks):
+        trail = tuple(f.shape[2:])
+        row_bytes = ops.row_bytes(f)
+        if rows > 0:
+            whole = stage[off:off + rows * row_bytes].view(np_dtype).reshape((rows,) + trail).copy()
+        else:
+            whole = np.empty((0,) + trail, dtype=np_dtype)
+        ends = np.cumsum(np.clip(lens, 0, f.shape[1]))
+        items = [whole[end - n:end] for end, n in zip(ends, np.clip(lens, 0, f.shape[1]))]
+        out.append([item.squeeze() for item in items] if squeeze else items)
+    return out
+
+
+def detach_batched_seqs(*sequence_features, seq_len=None, squeeze=True):
+    """Converts ``torch.Tensor`` to ``np.ndarray``: moves data to the host, detaches gradients and removes padding.
+    morgana/utils.py:66-102 - same arguments and return structure (a single feature comes back unwrapped; a feature whose items have
+    ``ndim <= 1`` comes back whole; ``seq_len=None`` crops nothing; ``squeeze`` is ``np.squeeze`` of every cropped item).
+
+    The reference copies every padded tensor to the host whole and slices there.  Here device tensors (B, T, ...) with a ``seq_len``
+    are packed on the device first (``_detach_on_device``): only the valid frames cross PCIe, in one copy for all features; a
+    ``seq_len`` that lives on the device is read once.  CPU tensors and NumPy inputs are sliced on the host: there is nothing to
+    compute.  On both paths a length above T counts as T and a negative one as 0 (the reference's slice would crop a negative
+    length from the end).  Any batch size works: above ``_lib.UNPAD_MAX_ITEMS`` items the pack takes several launches."""
+    seq_len_tensor = seq_len if isinstance(seq_len, torch.Tensor) else None
+    if seq_len_tensor is not None:
+        seq_len = seq_len_tensor.cpu().detach().numpy()
+
+    packed = {}
+    if seq_len is not None:
+        lens = np.asarray(seq_len).reshape(-1).astype(np.int64)
+        by_device = {}
+        for k, feature in enumerate(sequence_features):
+            if isinstance(feature, torch.Tensor) and feature.is_cuda and feature.ndim >= 3 and feature.numel() > 0:
+                if feature.shape[0] != lens.shape[0]:
+                    raise ValueError('detach_batched_seqs: feature %d has %d items, seq_len has %d' % (k, feature.shape[0], lens.shape[0]))
+                by_device.setdefault(feature.device, []).append(k)
+        for ks in by_device.values():
+            for k, items in zip(ks, _detach_on_device([sequence_features[k] for k in ks], lens, seq_len_tensor, squeeze)):
+                packed[k] = items
+
+    results = []
+    for k, feature in enumerate(sequence_features):
+        if k in packed:
+            results.append(packed[k])
+            continue
+        # host path: CPU tensors and NumPy inputs (and device tensors that are not padded sequences) - nothing to compute
+        array = feature.detach().cpu().numpy() if isinstance(feature, torch.Tensor) else feature
+        if seq_len is None or array[0].ndim <= 1:
+            results.append(array)                      # no lengths, or items that are scalars / vectors: returned whole
+            continue
+        items = [item[:max(int(n), 0)] for item, n in zip(array, seq_len)]
+        results.append([np.squeeze(item) for item in items] if squeeze else items)
+    return results[0] if len(results) == 1 else results
+
+
+def batched_masked_select(sequence_feature, seq_len):
+    """The feature vectors of all batch items that lie within their sequence length: (B, T, D) -> (sum_b min(seq_len[b], T), D), of
+    the input's dtype.  morgana/utils.py:147-166 (there: a mask, ``nonzero`` and an index).  One ragged-pack launch
+    (ops.unpad_rows; several above ``_lib.UNPAD_MAX_ITEMS`` items); ``seq_len`` is read once for the size of the result, as the
+    reference's ``nonzero`` does.  Differentiable for float32 inputs (backward: the zero-padded scatter)."""
+    if not isinstance(sequence_feature, torch.Tensor):
+        raise TypeError('sequence_feature must be a torch.Tensor, got %s' % type(sequence_feature))
+    sequence_feature = ops._require(sequence_feature, sequence_feature.dtype, 'sequence_feature')
+    seq_len_tensor = seq_len if isinstance(seq_len, torch.Tensor) else None
+    lens = np.asarray(seq_len_tensor.cpu().detach().numpy() if seq_len_tensor is not None else seq_len).reshape(-1).astype(np.int64)
+    with torch.cuda.device(sequence_feature.device):
+        seq_dev = _seq_len_on(seq_len_tensor, lens, sequence_feature.device)
+        if sequence_feature.dtype == torch.float32 and sequence_feature.requires_grad:
+            return F_hip.MaskedSelectFn.apply(sequence_feature, seq_dev, lens)
+        return F_hip.masked_select_rows(sequence_feature.detach(), seq_dev, lens)
+
+
+def both_voiced_mask(*sequence_features, dtype=torch.ByteTensor):
+    """Whether the sequence features are non-zero at the same time (NaN is non-zero, -0.0 is zero).  morgana/utils.py:169-172.
+    ``dtype`` as for ``sequence_mask``.  One launch for up to eight float32 device tensors (ops.all_nonzero)."""
+    return ops.all_nonzero(list(sequence_features), _as_dtype(dtype))
 
 
 class UpsampledSequence(object):
