@@ -1121,6 +1121,28 @@ int mg_adam_step_plan_f32(float* param, float* grad, float* exp_avg, float* exp_
 /* shadow -= (1 - decay) * (shadow - param). */
 int mg_ema_update_f32(float* shadow, const float* param, int64_t n, float decay, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * K21 (csrc/clip.hip)  global gradient-norm clipping over flat fp32 gradient buffers:
+ *                      torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2, error_if_nonfinite=False)
+ * Two launches per buffer and step, the norm never read by the host.  A buffer of n floats is cut into mg_grad_clip_blocks(n)
+ * contiguous chunks of mg_grad_clip_chunk(n) floats (from n alone: at most MG_CLIP_MAX_BLOCKS chunks, a multiple of 1024 floats
+ * each, at least 4096), one workgroup per chunk in both launches.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define MG_CLIP_MAX_BLOCKS 1024
+#define MG_CLIP_MAX_PARTIALS 16384
+int64_t mg_grad_clip_chunk(int64_t n);
+int mg_grad_clip_blocks(int64_t n);
+/* partials[offset + c] = sum of squares of chunk c of grad, accumulated in float64 in a fixed order (no atomics: the same bits on
+ * every call).  partials holds n_partials doubles - one array for all buffers that share a norm, each with its own offset.  grad
+ * need only be 4-byte aligned (a view into a larger allocation): each chunk reaches 16-byte loads behind a scalar head. */
+int mg_grad_sumsq_f32(const float* grad, int64_t n, double* partials, int offset, int n_partials, void* stream);
+/* norm = sqrt(sum of all n_partials partials) * inv_world, coef = min(1, max_norm / (norm + 1e-6)), both formed in float64 by every
+ * workgroup in the same order and rounded to fp32; grad *= coef in place (not written at all when coef == 1; a NaN norm gives a NaN
+ * coef and NaN gradients, an infinite one coef 0, as torch).  out (may be NULL): out[0] = norm, out[1] = coef.  inv_world in
+ * (0, 1]: grad holds the SUM over the ranks whose mean the threshold applies to; max_norm > 0. */
+int mg_grad_clip_scale_f32(float* grad, int64_t n, const double* partials, int n_partials, double inv_world, double max_norm, float* out,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

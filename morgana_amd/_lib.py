@@ -260,6 +260,10 @@ SIGNATURES = {
     'mg_adam_step_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
                                  c_float, c_int64, c_float, c_void_p]),
     'mg_ema_update_f32': (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),
+    'mg_grad_clip_chunk': (c_int64, [c_int64]),
+    'mg_grad_clip_blocks': (c_int, [c_int64]),
+    'mg_grad_sumsq_f32': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p]),
+    'mg_grad_clip_scale_f32': (c_int, [c_void_p, c_int64, c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p]),
 }
 
 
@@ -366,6 +370,7 @@ SPLIT3_MAX = 16
 STREAMS_MAX = 8
 LOSS_MSE, LOSS_SIGMOID_BCE = 0, 1
 CE_MAX_CLASSES = 65536       # MG_CE_MAX_CLASSES
+CLIP_MAX_PARTIALS = 16384    # MG_CLIP_MAX_PARTIALS
 _lib = None
 
 

@@ -24,7 +24,8 @@ from .optim import Adam
 class ExperimentBuilder(object):
     def __init__(self, model_class, model_kwargs=None, learning_rate=0.01, weight_decay=0., lr_schedule_name='constant',
                  lr_schedule_kwargs=None, ema_decay=0., device='cuda:0', start_epoch=1, end_epoch=50,
-                 experiment_dir=None, model_checkpoint_interval=1, checkpoint_path=None, use_graphs=False, graph_group=10, **unused):
+                 experiment_dir=None, model_checkpoint_interval=1, checkpoint_path=None, use_graphs=False, graph_group=10, max_grad_norm=None,
+                 **unused):
         self.model_class = model_class
         self.model_kwargs = model_kwargs or {}
         self.learning_rate = learning_rate
@@ -43,6 +44,8 @@ class ExperimentBuilder(object):
         # use_graphs with a RESIDENT loader (a list / tuple of device batches kept from epoch to epoch): this many consecutive batches are
         # captured into one graph that reads them in place (graphs.GraphedStepCache.step_group); 1 = a graph launch and a load per batch
         self.graph_group = int(graph_group)
+        # clip the global gradient norm before every update (optim.Adam(max_grad_norm=)); None = the reference's loop, unclipped
+        self.max_grad_norm = max_grad_norm
         self._graph_cache = None
         self._lr_schedule = lr_schedules.init_lr_schedule(lr_schedule_name, **self.lr_schedule_kwargs)
 
@@ -61,6 +64,7 @@ class ExperimentBuilder(object):
     def make_optimizer(self, **kwargs):
         # fused_loop: train_epoch below is the reference's loop body (zero_grad, forward, backward, step) and nothing else touches .grad
         kwargs.setdefault('fused_loop', True)
+        kwargs.setdefault('max_grad_norm', self.max_grad_norm)
         return Adam(self.model.parameters(), lr=self.learning_rate, weight_decay=self.weight_decay, **kwargs)  # :516
 
     def _cache_for(self, optimizer):

@@ -119,6 +119,10 @@ class GraphedTrainStep(object):
         graph launch (8-9 us measured) and runs the launch that stages Adam's step-dependent scalars (4.7 us): at a 0.17 ms step
         that is 8 % of the time, and it is paid once per replay, not once per step.  The update of step j reads scalar slot j
         (``optim.Adam.advance(K)`` stages all K with one launch); results are bit-identical to K single-step replays."""
+        if getattr(optimizer, 'max_grad_norm', None) is not None:
+            # refused before a warm-up step or a capture begins (GraphedStepCache then keeps such steps on ordinary launches)
+            raise RuntimeError('GraphedTrainStep: a step that clips its gradient norm (optim.Adam(max_grad_norm=)) is not captured into a '
+                               'HIP graph - it runs as ordinary launches')
         self.model, self.optimizer = model, optimizer
         self.steps_per_replay = int(steps_per_replay)
         if isinstance(features, (list, tuple)):

@@ -2390,6 +2390,39 @@ def adam_step_plan(param, grad, exp_avg, exp_avg_sq, betas, eps, weight_decay, s
                                          ctypes.byref(plan), _stream()), 'mg_adam_step_plan_f32')
 
 
+def grad_clip_blocks(n):
+    """(chunk floats, workgroups) of mg_grad_sumsq_f32 / mg_grad_clip_scale_f32 on a buffer of ``n`` floats: a function of n alone."""
+    lib = _lib.load()
+    return int(lib.mg_grad_clip_chunk(int(n))), int(lib.mg_grad_clip_blocks(int(n)))
+
+
+def _clip_buffer(grad, name):
+    if not (isinstance(grad, torch.Tensor) and grad.is_cuda and grad.dtype == torch.float32 and grad.dim() == 1 and grad.is_contiguous()):
+        raise ValueError('%s: grad must be a contiguous 1-D float32 device tensor' % name)
+
+
+def grad_sumsq(grad, partials, offset):
+    """partials[offset + c] = float64 sum of squares of chunk c of the flat gradient ``grad`` (mg_grad_sumsq_f32: fixed order, no
+    atomics).  ``partials``: the float64 device array that all buffers sharing one norm write into, each at its own offset."""
+    _clip_buffer(grad, 'grad_sumsq')
+    if not (partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous()):
+        raise ValueError('grad_sumsq: partials must be a contiguous float64 device tensor')
+    _lib.check(_lib.load().mg_grad_sumsq_f32(_p(grad), grad.numel(), _p(partials), int(offset), partials.numel(), _stream()),
+               'mg_grad_sumsq_f32')
+
+
+def grad_clip_scale(grad, partials, inv_world, max_norm, out=None):
+    """grad *= min(1, max_norm / (sqrt(sum(partials)) * inv_world + 1e-6)) in place (mg_grad_clip_scale_f32; not written when the
+    coefficient is exactly 1).  ``out``: 2 floats on the device that receive (norm, coefficient), or None."""
+    _clip_buffer(grad, 'grad_clip_scale')
+    if not (partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous()):
+        raise ValueError('grad_clip_scale: partials must be a contiguous float64 device tensor')
+    if out is not None and not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= 2):
+        raise ValueError('grad_clip_scale: out must hold two float32 on the device')
+    _lib.check(_lib.load().mg_grad_clip_scale_f32(_p(grad), grad.numel(), _p(partials), partials.numel(), float(inv_world), float(max_norm),
+                                                  _p(out), _stream()), 'mg_grad_clip_scale_f32')
+
+
 def ema_update(shadow, param, decay):
     lib = _lib.load()
     if not (shadow.is_cuda and shadow.is_contiguous() and param.is_contiguous()):

@@ -28,12 +28,23 @@ class Adam(torch.optim.Optimizer):
     gradient buffer zeroed and the following ``zero_grad`` is free, (b) on one rank the backward pass may leave split-M partial
     results of its weight-gradient GEMMs for ``step`` to sum (``defer_slabs``) instead of reducing them into ``.grad`` itself.
     ``ExperimentBuilder`` and ``graphs.GraphedTrainStep`` own exactly that loop and switch it on; off (the default) keeps torch's
-    semantics to the letter (``.grad`` complete after ``backward``, untouched by ``step``)."""
+    semantics to the letter (``.grad`` complete after ``backward``, untouched by ``step``).
+
+    ``max_grad_norm``: None (default) = no clipping, nothing changes.  A positive float clips the global 2-norm of the gradient at
+    the top of the update, exactly as ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm)`` would on the finished MEAN gradient
+    (all parameters of all groups share one norm; after the exchange, 1 / world applied to the norm): two streaming launches per
+    group (csrc/clip.hip), the norm never read by the host and left, with the coefficient, in ``grad_norms()``.  A clipped step runs as
+    ordinary launches: ``graphs.GraphedTrainStep`` refuses it and ``GraphedStepCache`` keeps it eager.  The norm needs the finished gradient: with clipping on ``defers_slabs()`` is False and the weight-gradient
+    GEMMs reduce into ``.grad`` themselves, as they do in front of an exchange."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, process_group=None,
-                 kernel=None, exchange_always=False, fused_loop=False, exchange_never=False):
+                 kernel=None, exchange_always=False, fused_loop=False, exchange_never=False, max_grad_norm=None):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError('Adam: max_grad_norm must be None or a positive number, got %r' % (max_grad_norm,))
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super(Adam, self).__init__(params, defaults)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._clip, self._host_norms = None, None
         self.process_group = process_group
         # exchange_always: run the gradient exchange whenever a process group exists, also at world size 1 (where it is the
         # identity) - lets the one-GPU box exercise the multi-rank code path on a live RCCL communicator
@@ -102,8 +113,8 @@ class Adam(torch.optim.Optimizer):
     # ---- what the backward pass may leave for the update kernel -------------------------------------------------------------
     def defers_slabs(self):
         """May a weight-gradient GEMM leave its split-M slabs unreduced for ``step``?  Only in the fused loop, on the device,
-        and when no exchange needs the finished gradient first."""
-        return self.fused_loop and self._on_device() and not self.exchanging()
+        when no exchange needs the finished gradient first and no clipping needs its norm."""
+        return self.fused_loop and self._on_device() and not self.exchanging() and self.max_grad_norm is None
 
     def defer_slabs(self, first_param, count, slab, n_slabs, stride):
         """Register partial results: elements [offset of ``first_param``, + count) of the flat gradient are ADDITIONALLY the sum of
@@ -111,9 +122,10 @@ class Adam(torch.optim.Optimizer):
         for flat in self._flat:
             if flat is not None and id(first_param) in flat['offsets']:
                 off = flat['offsets'][id(first_param)]
-                if len(flat['pending']) >= _lib.ADAM_MAX_SLABS:
+                if len(flat['pending']) >= _lib.ADAM_MAX_SLABS or self.max_grad_norm is not None:
                     # the update kernel's plan holds ADAM_MAX_SLABS sources (a deep stack registers one per leading layer plus
-                    # the tail): any further one is summed now, by a reduce launch straight into the flat gradient
+                    # the tail): any further one is summed now, by a reduce launch straight into the flat gradient (as is every one
+                    # handed over although clipping is on - ``defers_slabs`` says no: the norm runs over the flat buffer alone)
                     ops.slab_reduce(slab, n_slabs, stride, count, flat['grad'][off:off + int(count)], accumulate=True)
                 else:
                     flat['pending'].append((off, int(count), slab, int(n_slabs), int(stride)))
@@ -149,6 +161,64 @@ class Adam(torch.optim.Optimizer):
         if 'scalars' not in flat:          # slot j (floats 2 j, 2 j + 1): the scalars of the j-th step of a multi-step graph replay
             flat['scalars'] = torch.zeros(2 * ops.STORE_PAIRS_MAX, dtype=torch.float32, device=flat['param'].device)
         return flat['scalars']
+
+    # ---- global gradient-norm clipping (max_grad_norm) ------------------------------------------------------------------------
+    def _clip_buffers(self):
+        """Device scratch of the clip: one float64 partial per workgroup of every group's sum-of-squares launch (all groups in one
+        array: one norm), and (norm, coefficient) slots laid out as ``_scalar_buffers`` (``step`` writes slot 0).  Allocated once;
+        holds nothing between steps."""
+        if self._clip is None:
+            flats = [f for f in self._flat if f is not None]
+            device = flats[0]['grad'].device
+            if any(f['grad'].device != device for f in flats):
+                raise ValueError('Adam: max_grad_norm needs all parameter groups on one device')
+            offsets, total = [], 0
+            for f in flats:
+                offsets.append(total)
+                total += ops.grad_clip_blocks(f['grad'].numel())[1]
+            if total > _lib.CLIP_MAX_PARTIALS:
+                raise ValueError('Adam: max_grad_norm over %d parameter groups needs %d partial sums (limit %d)'
+                                 % (len(flats), total, _lib.CLIP_MAX_PARTIALS))
+            self._clip = {'partials': torch.zeros(total, dtype=torch.float64, device=device), 'offsets': offsets,
+                          'norms': torch.zeros(ops.STORE_PAIRS_MAX, 2, dtype=torch.float32, device=device)}
+        return self._clip
+
+    def grad_norms(self):
+        """(STORE_PAIRS_MAX, 2) float32 tensor on the gradient's device: row ``slot`` = (global 2-norm of the mean gradient before
+        clipping, coefficient applied) of the last update with that slot; ``step`` and ``step_captured()`` write row 0.  Reading it
+        synchronises - the optimiser itself never does.  None without ``max_grad_norm``."""
+        if self.max_grad_norm is None:
+            return None
+        if self._kernel is not None or not self._on_device():
+            if self._host_norms is None:
+                self._host_norms = torch.zeros(ops.STORE_PAIRS_MAX, 2, dtype=torch.float32)
+            return self._host_norms
+        return self._clip_buffers()['norms']
+
+    def _clip_gradients(self, world, slot=0):
+        """Clip the finished gradient of all groups to ``max_grad_norm`` (after any exchange, ahead of the update): launch 1 for every
+        group, then launch 2 for every group.  The flat buffers hold the SUM over ranks (the update folds 1 / world into its read), so
+        the norm is scaled by 1 / world and the sum by the coefficient; every rank reduces the same all-reduced buffer in the same
+        order and arrives at the same coefficient without another collective."""
+        flats = [f for f in self._flat if f is not None]
+        if not flats:
+            return
+        if self._kernel is not None or not self._on_device():
+            # the test seam's side of it (see ``kernel``): the same formula with torch ops in float64
+            total = sum(f['grad'].double().pow(2).sum() for f in flats)
+            norm = total.sqrt() / world
+            coef = torch.clamp(self.max_grad_norm / (norm + 1e-6), max=1.0)
+            self.grad_norms()[slot] = torch.stack((norm, coef)).float()
+            for f in flats:
+                f['grad'].mul_(coef.float())
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('Adam: max_grad_norm inside a stream capture is not supported - run the step as ordinary launches')
+        clip = self._clip_buffers()
+        for f, off in zip(flats, clip['offsets']):
+            ops.grad_sumsq(f['grad'], clip['partials'], off)
+        for i, f in enumerate(flats):
+            ops.grad_clip_scale(f['grad'], clip['partials'], 1.0 / world, self.max_grad_norm, clip['norms'][slot] if i == 0 else None)
 
     def exchanging(self):
         """True when ``step`` has a gradient exchange to do."""
@@ -243,7 +313,9 @@ class Adam(torch.optim.Optimizer):
     def forget_capture(self):
         """A capture of the step failed (graphs.GraphedTrainStep): what it registered here was recorded, never run - slabs and a
         deferred tail nobody computed, an update that "zeroed" the gradient and "refreshed" operand copies.  Drop them; the next
-        ``zero_grad`` clears the gradient itself.  (The copies' stamps are the caller's: ops.invalidate_operand_copies.)"""
+        ``zero_grad`` clears the gradient itself.  (The copies' stamps are the caller's: ops.invalidate_operand_copies.)  The clip of
+        ``max_grad_norm`` keeps no host state between steps - its partial sums and norm slots are rewritten by every step: nothing
+        of it to forget."""
         for flat in self._flat:
             if flat is not None:
                 flat['pending'] = []
@@ -278,6 +350,8 @@ class Adam(torch.optim.Optimizer):
         """The parameter update alone, from device-resident scalars (call ``advance`` before each replay; ``slot`` = which of the
         staged pairs: the position of this step inside a multi-step replay).  No all-reduce here."""
         world = self._world()
+        if self.max_grad_norm is not None:
+            self._clip_gradients(world, slot)
         for group, flat in zip(self.param_groups, self._flat):
             if flat is not None:
                 self._launch(group, flat, world, slot)
@@ -289,10 +363,18 @@ class Adam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         world = self._world()
+        clipping = self.max_grad_norm is not None
+        if clipping:
+            # one norm over all groups: every group's exchange comes first, then the clip, then the updates
+            if self.exchanging():
+                for flat in self._flat:
+                    if flat is not None:
+                        dist.all_reduce(flat['grad'], op=dist.ReduceOp.SUM, group=self.process_group)
+            self._clip_gradients(world)
         for group, flat in zip(self.param_groups, self._flat):
             if flat is None:
                 continue
-            if self.exchanging():
+            if self.exchanging() and not clipping:
                 # the single gradient exchange of the step: sum over ranks, mean folded into the kernel below
                 dist.all_reduce(flat['grad'], op=dist.ReduceOp.SUM, group=self.process_group)
             flat['step'] += 1
