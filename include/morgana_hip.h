@@ -1143,6 +1143,29 @@ int mg_grad_sumsq_f32(const float* grad, int64_t n, double* partials, int offset
 int mg_grad_clip_scale_f32(float* grad, int64_t n, const double* partials, int n_partials, double inv_world, double max_norm, float* out,
                            void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * K22 (csrc/colstats.hip)  per-column corpus statistics for the normaliser parameter files ({name}_mvn.json, {name}_minmax.json,
+ *                          their _deltas and per-speaker twins; the reference takes them from the un-vendored tts_data_tools)
+ * state (S, MG_COLSTATS_FIELDS, D) float64: count, mean, M2 = sum (x - mean)^2, min, max of every column of every group, updated in
+ * place batch after batch; all zeros is the empty state (count == 0: the other fields are ignored).  Shifted float64 chunk sums
+ * merged by Chan's update in a fixed order, no float atomics: the same input and state give the same bits.  A NaN or an infinity
+ * makes its column's mean and M2 non-finite and is counted; min / max skip NaNs.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define MG_COLSTATS_FIELDS 5
+#define MG_COLSTATS_MAX_D 2048
+/* Bytes of the job records of one call on B items of at most max_rows rows (0 for B <= 0, D outside 1..MG_COLSTATS_MAX_D). */
+size_t mg_column_stats_workspace_bytes(int B, int64_t max_rows, int D);
+/* x: float32 rows of D columns, row stride ld >= D floats (16-byte loads when ld == D).  Exactly one of
+ *   offsets (B + 1, int64): packed - the rows of item b are [offsets[b], offsets[b + 1]); T is unused and the items are cut into
+ *                           as many chunks as the workspace holds records for: size it for the longest item
+ *                           (any size from mg_column_stats_workspace_bytes(B, 1, D) up is valid),
+ *   seq_len (B, int64):     padded (B, T, D) - item b is rows [b T, b T + min(max(seq_len[b], 0), T))
+ * is non-NULL.  item_row (B, int32, may be NULL when S == 1): the group of item b; an index outside [0, S) is never used as one -
+ * that item contributes to nothing.  Two launches: job records into `workspace`, then the records and the state in job order.
+ * B == 0: MG_OK, nothing launched.  MG_EWORKSPACE when the workspace is too small. */
+int mg_column_stats_f32(const float* x, int64_t ld, int D, int B, int T, const int64_t* offsets, const int64_t* seq_len,
+                        const int32_t* item_row, int S, double* state, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

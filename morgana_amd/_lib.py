@@ -264,6 +264,9 @@ SIGNATURES = {
     'mg_grad_clip_blocks': (c_int, [c_int64]),
     'mg_grad_sumsq_f32': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p]),
     'mg_grad_clip_scale_f32': (c_int, [c_void_p, c_int64, c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p]),
+    'mg_column_stats_workspace_bytes': (c_size_t, [c_int, c_int64, c_int]),
+    'mg_column_stats_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_size_t, c_void_p]),
 }
 
 
@@ -371,6 +374,8 @@ STREAMS_MAX = 8
 LOSS_MSE, LOSS_SIGMOID_BCE = 0, 1
 CE_MAX_CLASSES = 65536       # MG_CE_MAX_CLASSES
 CLIP_MAX_PARTIALS = 16384    # MG_CLIP_MAX_PARTIALS
+COLSTATS_FIELDS = 5          # MG_COLSTATS_FIELDS
+COLSTATS_MAX_D = 2048        # MG_COLSTATS_MAX_D
 _lib = None
 
 

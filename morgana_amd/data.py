@@ -130,6 +130,12 @@ class _ParamGroup(object):
             return cls(kind, json.load(f), device=device)
 
 
+def _write_params_json(path, host_params):
+    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    with open(path, 'w') as f:
+        json.dump({name: [float(v) for v in np.asarray(values).reshape(-1)] for name, values in host_params.items()}, f)
+
+
 class FeatureNormaliser(object):
     """A named feature's normaliser: ``kind`` (a row of ``_KINDS``) + up to two parameter groups (the feature itself; its deltas when
     ``use_deltas``).  Public surface of the reference's normalisers (data.py:252-386): ``normalise`` / ``denormalise`` on NumPy arrays
@@ -169,6 +175,18 @@ class FeatureNormaliser(object):
         for deltas in ((False, True) if self.use_deltas else (False,)):
             file_name = pattern.format(name=self.name + ('_deltas' if deltas else ''))
             self._groups[deltas] = _ParamGroup.from_json(self.kind, os.path.join(data_root, data_dir, file_name), device=device)
+
+    def save_params(self, data_dir, data_root='.'):
+        """The inverse of ``load_params``: ``{name}_<kind>.json`` (and ``{name}_deltas_<kind>.json``) under ``data_root/data_dir``, the
+        same keys, plain lists of numbers.  A float32 written as its exact decimal value comes back bit for bit."""
+        pattern = _KINDS[self.kind]['file']
+        for deltas in ((False, True) if self.use_deltas else (False,)):
+            group = self._groups.get(deltas)
+            if group is None:
+                raise RuntimeError('normaliser %r has no %sparameters to save: call set_params or fit_normalisers first' % (
+                    self.name, 'delta ' if deltas else ''))
+            file_name = pattern.format(name=self.name + ('_deltas' if deltas else ''))
+            _write_params_json(os.path.join(data_root, data_dir, file_name), group.host)
 
     # -- the map ---------------------------------------------------------------------------------------------------------------------
     def _map(self, feature, deltas, inverse):
@@ -254,6 +272,18 @@ class _SpeakerDependentNormaliser(FeatureNormaliser):
             file_name = pattern.format(name=self.name + ('_deltas' if deltas else ''))
             self._install(deltas, {spk: _ParamGroup.from_json(self.kind, os.path.join(data_root, data_dir, spk, file_name), device=device)
                                    for spk in self.speaker_ids})
+
+    def save_params(self, data_dir, data_root='.'):
+        """The inverse of ``load_params``: ``{speaker_id}/{name}_<kind>.json`` (and its ``_deltas`` twin) for every speaker."""
+        pattern = _KINDS[self.kind]['file']
+        for deltas in ((False, True) if self.use_deltas else (False,)):
+            groups = self._groups.get(deltas)
+            if not groups:
+                raise RuntimeError('normaliser %r has no %sparameters to save: call set_params or fit_normalisers first' % (
+                    self.name, 'delta ' if deltas else ''))
+            file_name = pattern.format(name=self.name + ('_deltas' if deltas else ''))
+            for spk in self.speaker_ids:
+                _write_params_json(os.path.join(data_root, data_dir, spk, file_name), groups[spk].host)
 
     def _names(self, speaker_ids):
         """Speaker names of the batch items from a name, a list of names or an integer index array / tensor (host side)."""
@@ -822,3 +852,153 @@ class DeviceBatches(object):
             fetch = self.utterances.raw if isinstance(self.utterances, FilesDataset) else self.utterances.__getitem__
             batch = [fetch(int(i)) for i in order[start:start + self.batch_size]]
             yield collate_to_device(batch, self.normalisers, self.device, bf16_tables=self.bf16_tables)
+
+
+class ColumnStats(object):
+    """Running per-column statistics of one feature on the device: the (groups, 5, dim) float64 state of ``ops.column_stats`` -
+    count, mean, M2 = sum (x - mean)^2, min, max - updated in place batch after batch and read by the host once, in ``result``.
+    ``groups`` > 1: one row per speaker, every item assigned by ``item_row``.  There is no CPU path: ``device`` must be a HIP device.
+
+    Two states of disjoint data merge by the same Chan update the kernel uses (a multi-rank fit would do that on the host; not
+    built here)."""
+
+    FIELDS = ('count', 'mean', 'M2', 'mmin', 'mmax')
+
+    def __init__(self, dim, groups=1, device='cuda:0'):
+        from ._lib import MorganaHipError
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise MorganaHipError('ColumnStats accumulates on an MI355X device, got %s (there is no CPU fallback)' % device)
+        if dim <= 0 or groups <= 0:
+            raise ValueError('ColumnStats: dim=%r and groups=%r must be positive' % (dim, groups))
+        self.dim, self.groups = int(dim), int(groups)
+        self.state = torch.zeros((self.groups, len(self.FIELDS), self.dim), dtype=torch.float64, device=device)
+
+    @classmethod
+    def from_state(cls, state):
+        """A ColumnStats around an existing (groups, 5, dim) float64 state (a tensor on any device, or an array): for reading it."""
+        self = cls.__new__(cls)
+        state = state if isinstance(state, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(state, dtype=np.float64))
+        if state.dim() != 3 or state.shape[1] != len(cls.FIELDS) or state.dtype != torch.float64:
+            raise ValueError('ColumnStats state must be float64 (groups, %d, dim), got %s %s' % (
+                len(cls.FIELDS), state.dtype, tuple(state.shape)))
+        self.groups, self.dim, self.state = int(state.shape[0]), int(state.shape[2]), state
+        return self
+
+    def update_packed(self, packed, offsets, item_row=None, max_rows=None):
+        """Rows (N, dim) float32 of B items back to back and their ``offsets`` (B + 1,) int64, as ``_pack_pinned`` makes them."""
+        ops.column_stats(self.state, packed, offsets=offsets, item_row=item_row, max_rows=max_rows)
+        return self
+
+    def update_padded(self, x, seq_len, item_row=None):
+        """A padded (B, T, dim) float32 batch and its ``seq_len`` (B,) int64 - what a resident batch holds; frames past the length
+        are not read."""
+        ops.column_stats(self.state, x, seq_len=seq_len, item_row=item_row)
+        return self
+
+    def result(self, ddof=0):
+        """The one device-to-host read.  float64 arrays ``count``, ``mean``, ``var``, ``std_dev``, ``mmin``, ``mmax``, each
+        (groups, dim); ``var = M2 / (count - ddof)`` floored at 0.  A group that saw no frame (count == 0) has NaN everywhere else,
+        and so has ``var`` where ``count - ddof <= 0``.
+
+        ``ddof=0`` (population variance) is the default because that is what the parameter files of ``tts_data_tools`` are
+        believed to hold; this could not be verified - the package is not vendored with the reference - so it stays an argument."""
+        host = self.state.detach().cpu().numpy()
+        count, mean, m2, mmin, mmax = (host[:, i].copy() for i in range(len(self.FIELDS)))
+        seen = count > 0
+        nan = np.full_like(mean, np.nan)
+        denom = count - ddof
+        with np.errstate(divide='ignore', invalid='ignore'):
+            var = np.where(seen & (denom > 0), np.maximum(m2 / np.where(denom > 0, denom, 1.0), 0.0), nan)
+        return {'count': count, 'mean': np.where(seen, mean, nan), 'var': var, 'std_dev': np.sqrt(var),
+                'mmin': np.where(seen, mmin, nan), 'mmax': np.where(seen, mmax, nan)}
+
+    def params(self, kind, group=0, ddof=0, result=None):
+        """The parameter vectors of a normaliser of ``kind`` ('mvn': mean, std_dev; 'minmax': mmin, mmax) for one group, rounded once
+        from float64 to float32."""
+        result = self.result(ddof) if result is None else result
+        return {name: result[name][group].astype(np.float32) for name in _KINDS[kind]['params']}
+
+
+def _fit_rows(utterance, key):
+    value = np.asarray(utterance[key])
+    if value.ndim == 1:
+        value = value.reshape(-1, 1)
+    if value.ndim != 2:
+        raise ValueError('fit_normalisers: feature %r of utterance %r is not a (frames, features) array' % (key, utterance.get('name')))
+    return value
+
+
+def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out_dir=None, data_root='.', ddof=0):
+    """Fit the parameters of ``normalisers`` (a ``Normalisers`` or a dict name -> normaliser of any of the four classes) to a corpus:
+    the step that produces the ``{name}_mvn.json`` / ``{name}_minmax.json`` files (the reference gets them from ``tts_data_tools``).
+
+    ``utterances``: a ``FilesDataset`` (read through ``raw``: its normalisers need no parameters yet) or a sequence of raw utterance
+    dicts.  Batch by batch every named feature - and ``name + '_deltas'`` where ``use_deltas`` - is packed (``_pack_pinned``; integer
+    arrays such as ``dur`` go through float32, exact below 2^24) and one ``ColumnStats`` per feature is updated on ``device``;
+    speaker-dependent normalisers get one state row per speaker of their id list.  One read per feature at the end, then
+    ``set_params`` on every normaliser and, with ``out_dir``, ``save_params(out_dir, data_root)``.
+
+    Raises ValueError before anything is set or written if a listed speaker has no frame or a fitted parameter is not finite.
+    ``ddof``: see ``ColumnStats.result``.  Returns {feature: ColumnStats.result()} (the ``_deltas`` features under their own names)."""
+    from ._lib import MorganaHipError
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise MorganaHipError('fit_normalisers runs on an MI355X device, got %s (there is no CPU fallback)' % device)
+    if batch_size <= 0:
+        raise ValueError('batch_size must be positive, got %r' % (batch_size,))
+    for normaliser in normalisers.values():
+        if isinstance(normaliser, _SpeakerDependentNormaliser) and normaliser.speaker_ids is None:
+            normaliser.speaker_ids = _read_id_list(os.path.join(data_root, normaliser.speaker_id_list))
+    order = _speaker_order(normalisers)
+    features = []                                         # (feature key, normaliser, is the deltas group)
+    for name, normaliser in normalisers.items():
+        features.append((name, normaliser, False))
+        if normaliser.use_deltas:
+            features.append((name + '_deltas', normaliser, True))
+    from_files = isinstance(utterances, FilesDataset)
+    fetch = utterances.raw if from_files else utterances.__getitem__
+    stats = {}
+    for start in range(0, len(utterances), batch_size):
+        items = [fetch(i) for i in range(start, min(start + batch_size, len(utterances)))]
+        item_row = None
+        if order is not None:
+            if SPEAKER_ID_KEY not in items[0]:
+                raise KeyError("speaker-dependent normalisers need a '%s' entry in every utterance" % SPEAKER_ID_KEY)
+            index = torch.from_numpy(speaker_index_of([item[SPEAKER_ID_KEY] for item in items], order))
+            item_row = _small_to_device({SPEAKER_INDEX_KEY: index}, device)[SPEAKER_INDEX_KEY]
+        for key, normaliser, _ in features:
+            rows = [_fit_rows(item, key) for item in items]
+            by_speaker = isinstance(normaliser, _SpeakerDependentNormaliser)
+            if key not in stats:
+                stats[key] = ColumnStats(rows[0].shape[1], groups=len(order) if by_speaker else 1, device=device)
+            packed, offsets, lens = _pack_pinned(rows, device, 'fit:' + key)
+            stats[key].update_packed(packed, offsets, item_row if by_speaker else None, max_rows=int(lens.max()))
+    if not stats:
+        raise ValueError('fit_normalisers: no utterances')
+    results = {key: stats[key].result(ddof) for key, _, _ in features}
+    for key, normaliser, _ in features:                   # refuse before anything is installed or written
+        result = results[key]
+        if isinstance(normaliser, _SpeakerDependentNormaliser):
+            absent = [spk for row, spk in enumerate(order) if not result['count'][row].any()]
+            if absent:
+                raise ValueError('fit_normalisers: feature %r has no frame of the listed speakers %s' % (key, absent))
+        for name in _KINDS[normaliser.kind]['params']:
+            bad = np.argwhere(~np.isfinite(result[name]))
+            if bad.size:
+                raise ValueError('fit_normalisers: %s of feature %r is not finite in columns %s%s' % (
+                    name, key, sorted(set(int(c) for c in bad[:, 1])),
+                    '' if order is None or result[name].shape[0] == 1 else ' (speakers %s)' % sorted(set(order[int(r)] for r in bad[:, 0]))))
+    for name, normaliser in normalisers.items():
+        if isinstance(normaliser, _SpeakerDependentNormaliser):
+            own = {spk: stats[name].params(normaliser.kind, row, result=results[name]) for row, spk in enumerate(order)}
+            deltas = ({spk: stats[name + '_deltas'].params(normaliser.kind, row, result=results[name + '_deltas'])
+                       for row, spk in enumerate(order)} if normaliser.use_deltas else None)
+        else:
+            own = stats[name].params(normaliser.kind, result=results[name])
+            deltas = stats[name + '_deltas'].params(normaliser.kind, result=results[name + '_deltas']) if normaliser.use_deltas else None
+        normaliser.set_params(own, deltas, device=device)
+    if out_dir is not None:
+        for normaliser in normalisers.values():
+            normaliser.save_params(out_dir, data_root)
+    return results

@@ -588,6 +588,51 @@ def item_rows(table, item_row):
     return out
 
 
+def column_stats(state, x, *, offsets=None, seq_len=None, item_row=None, max_rows=None):
+    """state (S, 5, D) float64 += the per-column count / mean / M2 / min / max of the valid rows of one batch (mg_column_stats_f32:
+    shifted float64 chunks merged by Chan's update in a fixed order, updated in place, nothing read back).  Exactly one layout:
+    ``offsets`` (B + 1,) int64 with x the packed rows (N, D), or ``seq_len`` (B,) int64 with x padded (B, T, D).  ``item_row`` (B,)
+    int32 names the group (state row) of every item; an index outside [0, S) contributes to nothing.  ``max_rows``: the longest
+    item of a packed batch when the host knows it (it only sets how many workgroups share an item; default: one chunk per item)."""
+    lib = _lib.load()
+    if isinstance(state, torch.Tensor) and not state.is_contiguous():
+        raise ValueError('column_stats: state is updated in place and must be contiguous')
+    state = _require(state, torch.float64, 'state')
+    x = _require(x, torch.float32, 'feature')
+    if (offsets is None) == (seq_len is None):
+        raise ValueError('column_stats: give exactly one of offsets (packed rows) and seq_len (padded batch)')
+    if state.dim() != 3 or state.shape[1] != _lib.COLSTATS_FIELDS:
+        raise ValueError('column_stats: state %s must be (groups, %d, features)' % (tuple(state.shape), _lib.COLSTATS_FIELDS))
+    groups, d = state.shape[0], state.shape[2]
+    if offsets is not None:
+        offsets = _require(offsets, torch.int64, 'offsets')
+        if x.dim() != 2 or x.shape[1] != d or offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError('column_stats: packed rows %s must be (rows, %d) and offsets %s (items + 1,)' % (
+                tuple(x.shape), d, tuple(offsets.shape)))
+        b, t = offsets.numel() - 1, 0
+        rows = max(1, min(int(max_rows), x.shape[0])) if max_rows is not None else 1
+    else:
+        seq_len = _require(seq_len, torch.int64, 'seq_len')
+        if x.dim() != 3 or x.shape[2] != d or seq_len.dim() != 1 or seq_len.numel() != x.shape[0]:
+            raise ValueError('column_stats: padded batch %s must be (items, frames, %d) and seq_len %s (items,)' % (
+                tuple(x.shape), d, tuple(seq_len.shape)))
+        b, t = x.shape[0], x.shape[1]
+        rows = t
+    if item_row is not None:
+        item_row = _require(item_row, torch.int32, 'item_row')
+        if item_row.dim() != 1 or item_row.numel() != b:
+            raise ValueError('column_stats: item_row %s must hold one group for each of the %d items' % (tuple(item_row.shape), b))
+    elif groups != 1:
+        raise ValueError('column_stats: a state of %d groups needs item_row' % groups)
+    if b == 0 or x.numel() == 0:
+        return state
+    need = int(lib.mg_column_stats_workspace_bytes(b, rows, d))
+    buf = workspace(need, x.device)
+    _lib.check(lib.mg_column_stats_f32(_p(x), d, d, b, int(t), _p(offsets), _p(seq_len), _p(item_row), groups, _p(state), _p(buf), need,
+                                       _stream()), 'mg_column_stats_f32')
+    return state
+
+
 def normalise(x, p0, p1, kind):
     lib = _lib.load()
     x = _require(x, torch.float32, 'feature')

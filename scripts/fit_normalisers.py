@@ -1,0 +1,62 @@
+#!/usr/bin/env python
+"""Fit normaliser parameter files to a corpus of ``.npy`` features (``data.fit_normalisers``: per-column statistics on the device,
+csrc/colstats.hip) - the files ``data.Normalisers`` and ``load_params`` read, which the reference takes from ``tts_data_tools``.
+
+    python scripts/fit_normalisers.py DATA_ROOT DATA_DIR ID_LIST NAME:KIND[:deltas] [NAME:KIND[:deltas] ...]
+                                      [--speaker-id-list FILE] [--out-dir DIR] [--batch-size 64] [--ddof 0] [--device cuda:0]
+
+``KIND`` is ``mvn`` or ``minmax``; ``:deltas`` also fits ``{NAME}_deltas``.  Features are read from ``DATA_ROOT/DATA_DIR/NAME/*.npy``
+for the ids of ``DATA_ROOT/ID_LIST``.  With ``--speaker-id-list`` (relative to DATA_ROOT) every normaliser is speaker dependent: the
+speaker of an utterance is read from ``DATA_ROOT/DATA_DIR/speaker_id/*.txt`` and the files go to ``{speaker}/``.  The files are
+written under ``DATA_ROOT/OUT_DIR`` (default: DATA_DIR, where the reference's ``--normalisation_dir train`` looks for them).
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from morgana_amd import data  # noqa: E402
+
+CLASSES = {('mvn', False): data.MeanVarianceNormaliser, ('minmax', False): data.MinMaxNormaliser,
+           ('mvn', True): data.SpeakerDependentMeanVarianceNormaliser, ('minmax', True): data.SpeakerDependentMinMaxNormaliser}
+
+
+def parse_spec(spec, speaker_id_list):
+    name, _, rest = spec.partition(':')
+    kind, _, deltas = rest.partition(':')
+    if not name or kind not in ('mvn', 'minmax') or deltas not in ('', 'deltas'):
+        raise SystemExit('cannot read %r: expected NAME:mvn, NAME:minmax, NAME:mvn:deltas or NAME:minmax:deltas' % spec)
+    cls = CLASSES[kind, speaker_id_list is not None]
+    extra = (speaker_id_list,) if speaker_id_list is not None else ()
+    return name, cls(name, *extra, use_deltas=bool(deltas))
+
+
+def main():
+    parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    parser.add_argument('data_root')
+    parser.add_argument('data_dir')
+    parser.add_argument('id_list')
+    parser.add_argument('features', nargs='+', metavar='NAME:KIND[:deltas]')
+    parser.add_argument('--speaker-id-list', default=None)
+    parser.add_argument('--out-dir', default=None)
+    parser.add_argument('--batch-size', type=int, default=64)
+    parser.add_argument('--ddof', type=int, default=0)
+    parser.add_argument('--device', default='cuda:0')
+    args = parser.parse_args()
+    normalisers = dict(parse_spec(spec, args.speaker_id_list) for spec in args.features)
+    sources = {name: data.NumpyBinarySource(name, use_deltas=normaliser.use_deltas) for name, normaliser in normalisers.items()}
+    if args.speaker_id_list is not None:
+        sources[data.SPEAKER_ID_KEY] = data.StringSource(data.SPEAKER_ID_KEY)
+    dataset = data.FilesDataset(sources, args.data_dir, args.id_list, normalisers, data_root=args.data_root)
+    out_dir = args.data_dir if args.out_dir is None else args.out_dir
+    results = data.fit_normalisers(dataset, normalisers, device=args.device, batch_size=args.batch_size, out_dir=out_dir,
+                                   data_root=args.data_root, ddof=args.ddof)
+    print(json.dumps({'utterances': len(dataset), 'out_dir': os.path.join(args.data_root, out_dir),
+                      'frames': {key: int(result['count'][:, 0].sum()) for key, result in results.items()},
+                      'features': {key: int(result['count'].shape[1]) for key, result in results.items()}}))
+
+
+if __name__ == '__main__':
+    main()
