@@ -1,386 +1,129 @@
-"""ctypes binding of ``libmorgana_hip.so`` (C ABI declared in ``include/morgana_hip.h``).
+"""ctypes binding of ``libmorgana_hip.so``, derived from ``include/morgana_hip.h`` at import.
 
 This is the stub a maintainer of the reference would add: the reference has no FFI of its own, its
-hot path is PyTorch eager.  There is NO fallback: if the shared library is missing or a call fails, an exception is
-raised.  Nothing here imports the oracle.
+hot path is PyTorch eager.  The header is the single definition of the C ABI: ``parse_header`` turns its text into the
+``MG_*`` constants, one ``ctypes.Structure`` per ``typedef struct`` (named as in the header: ``mg_cast_desc``) and the
+``SIGNATURES`` table, and this module exposes all three under the header's own names.  Nothing is restated by hand.
+There is NO fallback: if the shared library is missing or a call fails, an exception is raised.  Nothing here imports
+the oracle.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libmorgana_hip.so')
-
-c_void_p, c_int, c_int64, c_float, c_size_t, c_char_p = (
-    ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t, ctypes.c_char_p)
-
-# name -> (restype, argtypes); must list every symbol of include/morgana_hip.h (checked by tests/test_abi.py).
-SIGNATURES = {
-    'mg_last_error': (c_char_p, []),
-    'mg_set_tuning': (c_int, [c_int, c_int]),
-    'mg_version': (c_int, []),
-    'mg_build_arch': (c_char_p, []),
-    'mg_upsample_lengths': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    'mg_upsample_index': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    'mg_gather_rows_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
-    'mg_gather_rows_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
-    'mg_segment_index': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    'mg_scatter_rows_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
-    'mg_frame_layout': (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'mg_unpad_rows': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
-    'mg_all_nonzero_f32': (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_void_p]),
-    'mg_pad_rows_colsum_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
-    'mg_pad_rows_colsum_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_gather_concat_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
-    'mg_gather_concat_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
-    'mg_upsample_backward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    'mg_sequence_mask': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
-    'mg_masked_mse_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
-    'mg_masked_mse_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
-                                  c_void_p, c_size_t, c_void_p]),
-    'mg_masked_bce_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
-                                  c_void_p, c_size_t, c_void_p]),
-    'mg_stream_loss_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
-    'mg_stream_loss_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_masked_ce_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
-    'mg_masked_ce_f32': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p,
-                                 c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_pad_normalise_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                     c_void_p]),
-    'mg_pad_normalise_bf16_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                          c_void_p, c_int, c_int, c_void_p]),
-    'mg_normalise_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
-    'mg_normalise_items_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int,
-                                       c_void_p]),
-    'mg_pad_normalise_items_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                           c_void_p, c_void_p, c_void_p]),
-    'mg_item_rows_f32': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
-    'mg_linear_fwd_f32': (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                                  c_int, c_int, c_void_p]),
-    'mg_linear_dgrad_f32': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    'mg_linear_dgrad_act_f32': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
-    'mg_linear_wgrad_workspace_bytes': (c_size_t, [c_int64, c_int, c_int]),
-    'mg_linear_wgrad_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
-                                    c_int, c_void_p, c_size_t, c_void_p]),
-    'mg_linear_fwd_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int,
-                                   c_void_p, c_int, c_int, c_int, c_void_p]),
-    'mg_linear_dgrad_bf16': (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
-                                     c_void_p, c_int, c_int, c_void_p]),
-    'mg_linear_dgrad_act_bf16': (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
-                                         c_void_p, c_int, c_int, c_void_p]),
-    'mg_linear_wgrad_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                     c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
-    'mg_linear_wgrad_rows_bf16': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                          c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
-    'mg_linear_bwd_fused_workspace_bytes': (c_size_t, [c_int64, c_int, c_int]),
-    'mg_linear_bwd_fused_bf16': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                                         c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
-    'mg_linear_wgrad_slabs_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t,
-                                           c_void_p, c_void_p, c_void_p]),
-    'mg_linear_wgrad_dgrad_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
-                                           c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
-    'mg_linear_wgrad_dgrad_expand_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
-                                                  c_void_p, c_size_t, c_void_p, c_void_p,
-                                                  c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64,
-                                                  c_int, c_void_p, c_int, c_void_p]),
-    'mg_slab_reduce_f32': (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_void_p]),
-    'mg_adam_step_plan_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_void_p,
-                                      c_float, c_void_p, c_void_p]),
-    'mg_cast_pad_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_void_p]),
-    'mg_cast_transpose_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
-    'mg_cast_params_bf16': (c_int, [c_void_p, c_int, c_void_p]),
-    'mg_cast_bf16_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_void_p]),
-    'mg_copy_many': (c_int, [c_void_p, c_int, c_void_p]),
-    'mg_host_pack': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int]),
-    'mg_split3_bf16': (c_int, [c_void_p, c_int, c_void_p]),
-    'mg_phone_front_linear_fwd_x3': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int64, c_int, c_void_p,
-                                             c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
-    'mg_linear_fwd_x3_f32': (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
-    'mg_f0_tail_rows_x3_workspace_bytes': (c_size_t, [c_int64]),
-    'mg_f0_tail_rows_x3': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
-                                   c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
-    'mg_f0_l2tail_x3_workspace_bytes': (c_size_t, [c_int64]),
-    'mg_f0_l2tail_x3': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
-                                c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
-    'mg_linear_wgrad_dgrad_x3_colsum_floats': (c_size_t, [c_int64, c_int]),
-    'mg_linear_wgrad_dgrad_x3': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
-                                         c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
-    'mg_linear_wgrad_slabs_x3': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
-                                         c_void_p]),
-    'mg_dropout': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p]),
-    'mg_dropout_advance': (c_int, [c_void_p, c_void_p, c_void_p]),
-    'mg_philox4x32_10': (None, [c_void_p, c_void_p, c_void_p]),
-    'mg_vae_sample_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p,
-                                  c_void_p, c_void_p]),
-    'mg_vae_sample_bwd_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
-    'mg_kld_standard_normal_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p]),
-    'mg_kld_standard_normal_bwd_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
-    'mg_gather_concat_latent_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int64, c_int,
-                                            c_void_p]),
-    'mg_gather_concat_latent_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int64, c_int,
-                                             c_void_p]),
-    'mg_rows_add_per_item_f32': (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int64, c_void_p]),
-    'mg_rows_sum_per_item': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p]),
-    'mg_sphere_sample_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p,
-                                     c_void_p]),
-    'mg_sphere_sample_bwd_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
-    'mg_ellipsoid_sample_f32': (c_int, [c_void_p, c_int64, c_int, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'mg_ellipsoid_angles_f32': (c_int, [c_int64, c_int, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p]),
-    'mg_ellipsoid_sample_bwd_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
-    'mg_calib_mfma_bf16': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    'mg_sigmoid_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
-    'mg_sigmoid_grad_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    'mg_act_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
-    'mg_act_grad_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
-    'mg_f0_tail_workspace_bytes': (c_size_t, [c_int64]),
-    'mg_f0_tail_bf16': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
-                                c_void_p]),
-    'mg_linear_bwd_fused_slabs_bf16': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                                               c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
-    'mg_linear_bwd_fused2_workspace_bytes': (c_size_t, [c_int64, c_int, c_int]),
-    'mg_linear_bwd_fused2_slabs_bf16': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                                                c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                c_void_p]),
-    'mg_f0_l2tail_slabs_bf16': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p,
-                                        c_void_p]),
-    'mg_f0_l2tail_rows_slabs_bf16': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                             c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_int, c_void_p,
-                                             c_size_t, c_void_p, c_void_p]),
-    'mg_expand_column_reduce_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64,
-                                            c_int, c_void_p, c_void_p]),
-    'mg_f0_l2tail_workspace_bytes': (c_size_t, [c_int64]),
-    'mg_f0_l2tail_slab_stride': (c_int64, []),
-    'mg_f0_l2tail_bf16': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                  c_void_p, c_size_t, c_void_p]),
-    'mg_f0_l2tail_rows_bf16': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_int,
-                                       c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
-    'mg_gru_fwd_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
-                               c_void_p, c_void_p]),
-    'mg_gru_fwd_bf16': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                c_void_p, c_void_p]),
-    'mg_gru_bwd_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_lstm_persist_f32_supported': (c_int, [c_int, c_int, c_int]),
-    'mg_lstm_fwd_persist_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_size_t, c_void_p]),
-    'mg_lstm_bwd_persist_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
-                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_gru_persist_workspace_bytes': (c_size_t, [c_int, c_int]),
-    'mg_gru_persist_supported': (c_int, [c_int, c_int, c_int]),
-    'mg_gru_persist_status': (c_int, [c_void_p, c_void_p]),
-    'mg_gru_fwd_persist_bf16': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_gru_fwd_persist_rows_bf16': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
-                                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_gru_fwd_persist_out_bf16': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
-                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_gru_bwd_persist_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
-                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_lstm_persist_supported': (c_int, [c_int, c_int, c_int]),
-    'mg_lstm_fwd_persist_bf16': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_lstm_bwd_persist_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
-                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_metric_workspace_bytes': (c_size_t, []),
-    'mg_metric_accumulate_f32': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                         c_void_p, c_size_t, c_void_p]),
-    'mg_store_pair_f32': (c_int, [c_void_p, c_float, c_float, c_void_p]),
-    'mg_store_pairs_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
-    'mg_adam_scalars': (None, [c_float, c_float, c_float, c_int64, c_void_p]),
-    'mg_adam_step_dev_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_void_p,
-                                     c_float, c_void_p]),
-    'mg_f0_tail_rows_bf16': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
-                                     c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
-    'mg_expand_column_loss_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    'mg_expand_column_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    'mg_phone_loss_const_add': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    'mg_phone_target_stats_workspace_bytes': (c_size_t, [c_int, c_int]),
-    'mg_phone_target_stats': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_upsample_index_maps': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    'mg_phone_front': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_phone_front_linear_fwd_bf16': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int64, c_int, c_void_p,
-                                               c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
-    'mg_segment_bounds': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    'mg_linear_dgrad_gathered_bf16': (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                              c_int, c_int, c_void_p]),
-    'mg_segment_sum': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
-                               c_void_p]),
-    'mg_segment_sum_feat_workspace_bytes': (c_size_t, [c_int, c_int]),
-    'mg_segment_sum_feat_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
-                                         c_int, c_void_p, c_size_t, c_void_p]),
-    'mg_feat_wgrad_reduce': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
-    'mg_f0_tail_rows_f32_workspace_bytes': (c_size_t, [c_int64]),
-    'mg_f0_tail_rows_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64,
-                                    c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_phone_mse_rows_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    'mg_phone_concat_layer_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
-                                           c_void_p, c_int, c_int, c_void_p]),
-    'mg_mlpg_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    'mg_mlpg_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                            c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
-    'mg_gru_small_supported': (c_int, [c_int]),
-    'mg_gru_fwd_small_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'mg_gru_bwd_small_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
-                                     c_void_p, c_void_p]),
-    'mg_gru_persist_f32_supported': (c_int, [c_int, c_int, c_int]),
-    'mg_gru_fwd_persist_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_size_t, c_void_p]),
-    'mg_gru_bwd_persist_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_gru_bwd_workspace_bytes': (c_size_t, [c_int, c_int]),
-    'mg_gru_bwd_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_lstm_fwd_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                c_void_p, c_void_p]),
-    'mg_lstm_bwd_workspace_bytes': (c_size_t, [c_int, c_int]),
-    'mg_lstm_bwd_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'mg_gru_stack_small_supported': (c_int, [c_int, c_int, c_int, c_int]),
-    'mg_gru_stack_small_workspace_bytes': (c_size_t, []),
-    'mg_gru_stack_fwd_small_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    'mg_gru_stack_fwd_small_fast_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    'mg_gru_stack_bwd_small_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    'mg_gru_stack_bwd_small_fast_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    'mg_lstm_pstack_supported': (c_int, [c_int, c_int, c_int, c_int]),
-    'mg_lstm_pstack_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
-    'mg_lstm_pstack_fwd_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    'mg_lstm_pstack_bwd_supported': (c_int, [c_int, c_int, c_int, c_int]),
-    'mg_lstm_pstack_bwd_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
-    'mg_lstm_pstack_bwd_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    'mg_lstm_stack_fwd_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    'mg_lstm_stack_bwd_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    'mg_adam_step_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
-                                 c_float, c_int64, c_float, c_void_p]),
-    'mg_ema_update_f32': (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),
-    'mg_grad_clip_chunk': (c_int64, [c_int64]),
-    'mg_grad_clip_blocks': (c_int, [c_int64]),
-    'mg_grad_sumsq_f32': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p]),
-    'mg_grad_clip_scale_f32': (c_int, [c_void_p, c_int64, c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p]),
-    'mg_column_stats_workspace_bytes': (c_size_t, [c_int, c_int64, c_int]),
-    'mg_column_stats_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                    c_size_t, c_void_p]),
-}
-
-
-
-class CastDesc(ctypes.Structure):
-    """mg_cast_desc of include/morgana_hip.h."""
-    _fields_ = [('src', c_void_p), ('rows', c_int), ('cols', c_int), ('dst', c_void_p), ('ldd', c_int),
-                ('dst_t', c_void_p), ('ldt', c_int)]
-
-
-class CopyDesc(ctypes.Structure):
-    """mg_copy_desc of include/morgana_hip.h."""
-    _fields_ = [('src', c_void_p), ('dst', c_void_p), ('bytes', c_int64)]
-
-
-COPY_MAX = 16
-
-
-class UnpadDesc(ctypes.Structure):
-    """mg_unpad_desc of include/morgana_hip.h."""
-    _fields_ = [('src', c_void_p), ('T', c_int64), ('row_bytes', c_int64), ('dst_offset', c_int64), ('block_bytes', c_int64)]
-
-
-UNPAD_MAX = 16                # MG_UNPAD_MAX
-UNPAD_MAX_ITEMS = 4096        # MG_UNPAD_MAX_ITEMS
-ALL_NONZERO_MAX = 8           # MG_ALL_NONZERO_MAX
-
-
-class Split3Desc(ctypes.Structure):
-    """mg_split3_desc of include/morgana_hip.h."""
-    _fields_ = [('src', c_void_p), ('rows', c_int64), ('cols', c_int), ('lds', c_int), ('dst', c_void_p), ('ldp', c_int),
-                ('order', c_int), ('transpose', c_int), ('plane_rows', c_int64), ('sig', c_void_p), ('ldsig', c_int), ('colsum', c_void_p),
-                ('colsum_blocks', c_int)]
-
-
-class StreamDesc(ctypes.Structure):
-    """mg_stream_desc of include/morgana_hip.h."""
-    _fields_ = [('target', c_void_p), ('ldt', c_int), ('col0', c_int), ('width', c_int), ('kind', c_int)]
-
-
-class LstmFwdLayer(ctypes.Structure):
-    """mg_lstm_fwd_layer of include/morgana_hip.h."""
-    _fields_ = [('xproj', c_void_p), ('x_T', c_int), ('x_t0', c_int), ('w_hh', c_void_p), ('b_hh', c_void_p),
-                ('hstate', c_void_p), ('cstate', c_void_p), ('out', c_void_p), ('saved', c_void_p)]
-
-
-class LstmPStackLayer(ctypes.Structure):
-    """mg_lstm_pstack_layer of include/morgana_hip.h."""
-    _fields_ = [('xproj', c_void_p), ('w_ih_bf', c_void_p), ('b_ih', c_void_p), ('w_hh_bf', c_void_p), ('b_hh', c_void_p),
-                ('hstate', c_void_p), ('cstate', c_void_p), ('hstate_bf', c_void_p), ('out', c_void_p), ('saved', c_void_p),
-                ('ldwi', c_int), ('ldwh', c_int)]
-
-
-class GruStackLayer(ctypes.Structure):
-    """mg_gru_stack_layer of include/morgana_hip.h."""
-    _fields_ = [('xproj', c_void_p), ('w_ih', c_void_p), ('b_ih', c_void_p), ('w_hh', c_void_p), ('b_hh', c_void_p),
-                ('hstate', c_void_p), ('out', c_void_p), ('saved', c_void_p), ('grad_out', c_void_p), ('grad_hn', c_void_p),
-                ('dxin', c_void_p), ('dxproj', c_void_p), ('dhproj', c_void_p), ('dh0', c_void_p)]
-
-
-class LstmPStackBwdLayer(ctypes.Structure):
-    """mg_lstm_pstack_bwd_layer of include/morgana_hip.h."""
-    _fields_ = [('grad_out', c_void_p), ('grad_hn', c_void_p), ('grad_cn', c_void_p), ('cstate', c_void_p), ('saved', c_void_p),
-                ('w_hh_t_bf', c_void_p), ('w_ih_up_t_bf', c_void_p), ('dgates', c_void_p), ('dgates_bf', c_void_p),
-                ('dh0', c_void_p), ('dc0', c_void_p), ('ldt', c_int), ('ldt_up', c_int)]
-
-
-class LstmBwdLayer(ctypes.Structure):
-    """mg_lstm_bwd_layer of include/morgana_hip.h."""
-    _fields_ = [('grad_out', c_void_p), ('g_T', c_int), ('g_t0', c_int), ('cstate', c_void_p), ('saved', c_void_p),
-                ('w_hh', c_void_p), ('dgates', c_void_p), ('carry_h', c_void_p), ('carry_c', c_void_p), ('dh0', c_void_p),
-                ('dc0', c_void_p)]
-
-
-class AdamSlabSrc(ctypes.Structure):
-    """mg_adam_slab_src of include/morgana_hip.h."""
-    _fields_ = [('begin', c_int64), ('count', c_int64), ('slab', c_void_p), ('n_slabs', c_int), ('stride', c_int64)]
-
-
-class AdamShadow(ctypes.Structure):
-    """mg_adam_shadow of include/morgana_hip.h."""
-    _fields_ = [('offset', c_int64), ('rows', c_int), ('cols', c_int), ('dst', c_void_p), ('ldd', c_int), ('dst_t', c_void_p),
-                ('ldt', c_int), ('pair', c_int)]
-
-
-ADAM_MAX_SLABS, ADAM_MAX_SHADOWS = 4, 8
-
-
-class AdamTail(ctypes.Structure):
-    """mg_adam_tail of include/morgana_hip.h."""
-    _fields_ = [('table', c_void_p), ('rows', c_void_p), ('frames', c_int64), ('out', c_void_p), ('partial', c_void_p),
-                ('n_partial', c_int), ('slab', c_void_p), ('n', c_int64), ('stride', c_int64), ('n_slabs', c_int), ('dst', c_void_p)]
-
-
-class AdamPlan(ctypes.Structure):
-    """mg_adam_plan of include/morgana_hip.h."""
-    _fields_ = [('n_slab_srcs', c_int), ('slabs', AdamSlabSrc * ADAM_MAX_SLABS), ('n_shadows', c_int),
-                ('shadows', AdamShadow * ADAM_MAX_SHADOWS), ('clear_grad', c_int), ('tail', AdamTail)]
-
-
-LSTM_MAX_LAYERS = 8
-CAST_MAX = 16
-SPLIT3_MAX = 16
-STREAMS_MAX = 8
-LOSS_MSE, LOSS_SIGMOID_BCE = 0, 1
-CE_MAX_CLASSES = 65536       # MG_CE_MAX_CLASSES
-CLIP_MAX_PARTIALS = 16384    # MG_CLIP_MAX_PARTIALS
-COLSTATS_FIELDS = 5          # MG_COLSTATS_FIELDS
-COLSTATS_MAX_D = 2048        # MG_COLSTATS_MAX_D
-_lib = None
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'morgana_hip.h'))
 
 
 class MorganaHipError(RuntimeError):
     pass
+
+
+# The whole type mapping.  Every pointer and every array parameter, whatever it points to, is a c_void_p: call sites pass
+# c_void_p, None, integers (tensor.data_ptr()) and cast ctypes arrays.  Anything else in the header is refused, not guessed.
+_SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float,
+            'double': ctypes.c_double, 'uint32_t': ctypes.c_uint32, 'uint64_t': ctypes.c_uint64}
+_DIRECTIVE = re.compile(r'#\s*(include\s*<\w+\.h>|ifndef\s+\w+_H|define\s+\w+_H|ifdef\s+__cplusplus|endif)\s*$')
+_DEFINE = re.compile(r'#\s*define\s+(MG_\w+)\s+(\(\s*-?\s*\w+\s*\)|-?\s*\w+)\s*$')
+_STRUCT = re.compile(r'typedef\s+struct\s*\{([^{}]*)\}\s*(\w+)\s*;')
+_DECLARATOR = re.compile(r'(.*?[\s*])(\w+)\s*(?:\[\s*(\w+)\s*\])?$', re.S)      # type, name, array length
+_PROTOTYPE = re.compile(r'(.*?[\s*])(\w+)\s*\(([^()]*)\)$', re.S)                  # return type, name, parameters
+
+
+def _refuse(text):
+    raise MorganaHipError('morgana_hip.h: no ctypes binding for %r' % ' '.join(text.split()))
+
+
+def _integer(word, constants, text):
+    try:
+        return constants[word] if word in constants else int(word.replace(' ', ''), 0)
+    except ValueError:
+        _refuse(text)
+
+
+def _ctype(spec, structs, text):
+    """'const float* const*' -> c_void_p, 'int64_t' -> c_int64, 'mg_adam_tail' -> that Structure; anything else is refused."""
+    words = [w for w in spec.replace('*', ' * ').split() if w != 'const']
+    if not words or not re.fullmatch(r'\w+', words[0]) or any(w != '*' for w in words[1:]):
+        _refuse(text)
+    if len(words) > 1:
+        return ctypes.c_void_p
+    ctype = _SCALARS.get(words[0], structs.get(words[0]))
+    return ctype if ctype is not None else _refuse(text)
+
+
+def _fields(body, constants, structs):
+    fields = []
+    for statement in filter(None, (s.strip() for s in body.split(';'))):
+        base = ''
+        for declarator in statement.split(','):      # `int rows, cols;`: later declarators share the type up to its first `*`
+            spec, name, length = (_DECLARATOR.match(base + declarator.strip()) or _refuse(statement)).groups()
+            base = base or spec.split('*')[0].strip() + ' '
+            ctype = _ctype(spec, structs, statement)
+            fields.append((name, ctype if length is None else ctype * _integer(length, constants, statement)))
+    return fields
+
+
+def _signature(statement):
+    returns, name, params = (_PROTOTYPE.match(statement) or _refuse(statement)).groups()
+    if returns.split() == ['void']:
+        restype = None
+    elif returns.replace('*', ' * ').split() == ['const', 'char', '*']:
+        restype = ctypes.c_char_p
+    else:
+        restype = _ctype(returns, {}, statement)
+        if restype is ctypes.c_void_p:
+            _refuse(statement)
+    argtypes = []
+    for param in ([] if params.split() in ([], ['void']) else params.split(',')):
+        spec, _, length = (_DECLARATOR.match(param.strip()) or _refuse(statement)).groups()
+        ctype = _ctype(spec, {}, statement)      # scalars and pointers only: no entry point takes a struct by value
+        argtypes.append(ctype if length is None else ctypes.c_void_p)      # `const uint32_t counter[4]` is a pointer
+    return name, (restype, argtypes)
+
+
+def parse_header(text):
+    """The C ABI of include/morgana_hip.h as (constants, structs, signatures): {'MG_X': int}, {'mg_x_desc': ctypes.Structure
+    subclass} and {'mg_x': (restype, argtypes)}.  Raises MorganaHipError, quoting the text, on anything it has no mapping for."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    constants, structs, signatures, code = {}, {}, {}, []
+    for line in text.split('\n'):
+        if not line.lstrip().startswith('#'):
+            code.append(line)
+        elif _DEFINE.match(line.strip()):
+            name, value = _DEFINE.match(line.strip()).groups()
+            constants[name] = _integer(value.strip('() '), constants, line)
+        elif not _DIRECTIVE.match(line.strip()):
+            _refuse(line)
+    code = re.sub(r'extern\s+"C"\s*\{(.*)\}', r'\1', '\n'.join(code), flags=re.S)
+
+    def struct(match):      # in the header's order: a struct may hold an earlier one by value
+        body, name = match.groups()
+        structs[name] = type(name, (ctypes.Structure,), {'_fields_': _fields(body, constants, structs),
+                                                         '__doc__': '%s of include/morgana_hip.h.' % name})
+        return ''
+
+    for statement in filter(None, (s.strip() for s in _STRUCT.sub(struct, code).split(';'))):
+        name, signature = _signature(statement)
+        signatures[name] = signature
+    return constants, structs, signatures
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise MorganaHipError('the C ABI header is missing (%s): %s.  The binding is derived from it.' % (HEADER_PATH, e))
+
+
+# MG_* constants, mg_* descriptor structs and SIGNATURES = name -> (restype, argtypes) of every entry point: include/morgana_hip.h
+# parsed under the mapping above (tests/test_abi.py holds it against the C compiler's layouts and the library's exports).
+CONSTANTS, STRUCTS, SIGNATURES = parse_header(_read_header())
+globals().update(CONSTANTS)      # _lib.MG_CAST_MAX, ...
+globals().update(STRUCTS)        # _lib.mg_cast_desc, ...
+_lib = None
 
 
 def load():
@@ -417,6 +160,6 @@ def check(rc, what):
         CALL_LOG.append(what)
     if rc != 0:
         msg = last_error()
-        if rc == -1:
+        if rc == MG_EINVAL:
             raise ValueError('%s: %s' % (what, msg))
         raise MorganaHipError('%s failed (code %d): %s' % (what, rc, msg))

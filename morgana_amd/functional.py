@@ -1854,7 +1854,7 @@ class LSTMStackFn(torch.autograd.Function):
         saved = [torch.empty((b, t, 4 * hid), dtype=torch.float32, device=dev) for _ in range(n_layers)]
         rows = LSTMStackFn._chunk_rows(b, t, lag, dev)
         n_chunks = len(rows)
-        descs = (_lib.LstmFwdLayer * n_layers)()
+        descs = (_lib.mg_lstm_fwd_layer * n_layers)()
         for l in range(n_layers):
             d = descs[l]
             d.w_hh, d.b_hh = w_hh[l].data_ptr(), b_hh[l].data_ptr()
@@ -1914,7 +1914,7 @@ class LSTMStackFn(torch.autograd.Function):
         rows = LSTMStackFn._chunk_rows(b, t, lag, dev)
         n_chunks = len(rows)
         w_t_bf = [ops.cast_transpose_bf16(w) for w in w_ih] if precision == 'bf16' else None
-        descs = (_lib.LstmBwdLayer * n_layers)()
+        descs = (_lib.mg_lstm_bwd_layer * n_layers)()
         for l in range(n_layers):
             d = descs[l]
             d.cstate, d.saved, d.w_hh, d.dgates = cstate[l].data_ptr(), saved[l].data_ptr(), w_hh[l].data_ptr(), dgates[l].data_ptr()

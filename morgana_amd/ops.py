@@ -9,8 +9,9 @@ import torch
 
 from . import _lib
 
-ACT_NONE, ACT_SIGMOID, ACT_TANH, ACT_RELU = 0, 1, 2, 3      # MG_ACT_* of include/morgana_hip.h
-NORM_MVN, DENORM_MVN, NORM_MINMAX, DENORM_MINMAX = 0, 1, 2, 3
+# the header's MG_ACT_* / MG_NORM_* (include/morgana_hip.h through _lib), under the names the host layer uses
+ACT_NONE, ACT_SIGMOID, ACT_TANH, ACT_RELU = _lib.MG_ACT_NONE, _lib.MG_ACT_SIGMOID, _lib.MG_ACT_TANH, _lib.MG_ACT_RELU
+NORM_MVN, DENORM_MVN, NORM_MINMAX, DENORM_MINMAX = _lib.MG_NORM_MVN, _lib.MG_DENORM_MVN, _lib.MG_NORM_MINMAX, _lib.MG_DENORM_MINMAX
 
 _workspaces = {}
 SIDE_STREAM_IDS = set()      # raw handles of the side streams functional._Beside launches on (their scratch is their own)
@@ -235,11 +236,11 @@ def sequence_mask(seq_len, max_len, dtype):
 
 
 def all_nonzero(tensors, dtype):
-    """out = all_k (tensors[k] != 0) in ``dtype`` for up to ``_lib.ALL_NONZERO_MAX`` float32 device tensors of one shape
+    """out = all_k (tensors[k] != 0) in ``dtype`` for up to ``_lib.MG_ALL_NONZERO_MAX`` float32 device tensors of one shape
     (mg_all_nonzero_f32): NaN counts as non-zero, -0.0 as zero."""
     lib = _lib.load()
-    if not 1 <= len(tensors) <= _lib.ALL_NONZERO_MAX:
-        raise ValueError('all_nonzero: %d inputs, the kernel takes 1..%d' % (len(tensors), _lib.ALL_NONZERO_MAX))
+    if not 1 <= len(tensors) <= _lib.MG_ALL_NONZERO_MAX:
+        raise ValueError('all_nonzero: %d inputs, the kernel takes 1..%d' % (len(tensors), _lib.MG_ALL_NONZERO_MAX))
     if dtype not in _MASK_TYPES:
         raise TypeError('all_nonzero: unsupported mask dtype %s' % dtype)
     tensors = [_require(t, torch.float32, 'sequence_feature') for t in tensors]
@@ -280,7 +281,7 @@ def unpad_layout(shapes_and_sizes, lens_host):
 
 def unpad_rows(tensors, seq_len, lens_host):
     """The valid frames of padded device features, utterance after utterance, as ONE byte buffer (mg_unpad_rows: one launch per
-    ``_lib.UNPAD_MAX`` features; beyond ``_lib.UNPAD_MAX_ITEMS`` items one launch per feature and group of that many items).  tensors: contiguous device tensors (B, T_f, ...) of any dtype; seq_len: int64 (B,) on the same device
+    ``_lib.MG_UNPAD_MAX`` features; beyond ``_lib.MG_UNPAD_MAX_ITEMS`` items one launch per feature and group of that many items).  tensors: contiguous device tensors (B, T_f, ...) of any dtype; seq_len: int64 (B,) on the same device
     - the kernel reads the lengths there; lens_host: the same lengths on the host, which size the blocks (a frame beyond a block is
     dropped, never written).  Returns (uint8 device buffer, [(byte offset, rows)] per feature)."""
     lib = _lib.load()
@@ -298,12 +299,12 @@ def unpad_rows(tensors, seq_len, lens_host):
         feats.append((t, int(t.shape[1]), row_bytes(t)))
     blocks, size = unpad_layout([(t_len, rb) for _, t_len, rb in feats], lens_host)
     buf = torch.empty(max(size, 1), dtype=torch.uint8, device=seq_len.device)
-    if b > _lib.UNPAD_MAX_ITEMS:
+    if b > _lib.MG_UNPAD_MAX_ITEMS:
         _unpad_rows_in_item_groups(lib, feats, blocks, seq_len, lens_host, buf)
         return buf, blocks
-    for first in range(0, len(feats), _lib.UNPAD_MAX):
-        chunk = feats[first:first + _lib.UNPAD_MAX]
-        descs = (_lib.UnpadDesc * len(chunk))()
+    for first in range(0, len(feats), _lib.MG_UNPAD_MAX):
+        chunk = feats[first:first + _lib.MG_UNPAD_MAX]
+        descs = (_lib.mg_unpad_desc * len(chunk))()
         for i, (t, t_len, rb) in enumerate(chunk):
             offset, rows = blocks[first + i]
             descs[i].src, descs[i].T, descs[i].row_bytes = t.data_ptr(), t_len, rb
@@ -314,16 +315,16 @@ def unpad_rows(tensors, seq_len, lens_host):
 
 
 def _unpad_rows_in_item_groups(lib, feats, blocks, seq_len, lens_host, buf):
-    """``unpad_rows`` for more items than one launch scans (``_lib.UNPAD_MAX_ITEMS``): per feature, one launch per group of that many
+    """``unpad_rows`` for more items than one launch scans (``_lib.MG_UNPAD_MAX_ITEMS``): per feature, one launch per group of that many
     items, each writing behind the rows of the groups before it.  A group's first byte is wherever those rows end, so the launch gets
     the destination pointer moved there and a block at offset 0 (the kernel aligns by address, only ``dst_offset`` must be a
     multiple of 16)."""
     b = seq_len.numel()
-    desc = (_lib.UnpadDesc * 1)()
+    desc = (_lib.mg_unpad_desc * 1)()
     for (t, t_len, rb), (offset, _) in zip(feats, blocks):
         done = 0                                                           # rows of the groups already packed
-        for b0 in range(0, b, _lib.UNPAD_MAX_ITEMS):
-            b1 = min(b0 + _lib.UNPAD_MAX_ITEMS, b)
+        for b0 in range(0, b, _lib.MG_UNPAD_MAX_ITEMS):
+            b1 = min(b0 + _lib.MG_UNPAD_MAX_ITEMS, b)
             rows = sum(min(max(int(n), 0), t_len) for n in lens_host[b0:b1])
             desc[0].src, desc[0].T, desc[0].row_bytes = t.data_ptr() + b0 * t_len * rb, t_len, rb
             desc[0].dst_offset, desc[0].block_bytes = 0, rows * rb
@@ -358,14 +359,14 @@ def stream_loss(pred, targets, kinds, seq_len, want_grad, want_prob=False, grad_
     in column order, kinds[k] in {'mse', 'sigmoid_bce'}.  Returns (loss 0-d, grad or None, prob or None)."""
     lib = _lib.load()
     pred = _require(pred, torch.float32, 'predictions')
-    if pred.dim() != 3 or len(targets) != len(kinds) or not 1 <= len(targets) <= _lib.STREAMS_MAX:
-        raise ValueError('stream_loss: predictions must be (B, T, D) with 1..%d streams' % _lib.STREAMS_MAX)
+    if pred.dim() != 3 or len(targets) != len(kinds) or not 1 <= len(targets) <= _lib.MG_STREAMS_MAX:
+        raise ValueError('stream_loss: predictions must be (B, T, D) with 1..%d streams' % _lib.MG_STREAMS_MAX)
     b, t, d = pred.shape
     if sum(int(y.shape[-1]) for y in targets) != d:
         raise ValueError('stream_loss: stream widths %s do not add up to D=%d' % ([int(y.shape[-1]) for y in targets], d))
     if seq_len is not None:
         seq_len = _require(seq_len, torch.int64, 'seq_len')
-    descs = (_lib.StreamDesc * len(targets))()
+    descs = (_lib.mg_stream_desc * len(targets))()
     keep, col0, prob = [], 0, None
     for k, (y, kind) in enumerate(zip(targets, kinds)):
         y = _require(y, torch.float32, 'targets[%d]' % k)
@@ -374,7 +375,7 @@ def stream_loss(pred, targets, kinds, seq_len, want_grad, want_prob=False, grad_
         keep.append(y)
         w = int(y.shape[2])
         descs[k].target, descs[k].ldt, descs[k].col0, descs[k].width = y.data_ptr(), w, col0, w
-        descs[k].kind = {'mse': _lib.LOSS_MSE, 'sigmoid_bce': _lib.LOSS_SIGMOID_BCE}[kind]
+        descs[k].kind = {'mse': _lib.MG_LOSS_MSE, 'sigmoid_bce': _lib.MG_LOSS_SIGMOID_BCE}[kind]
         if kind == 'sigmoid_bce' and want_prob:
             prob = torch.empty((b, t, w), dtype=torch.float32, device=pred.device)
         col0 += w
@@ -454,8 +455,8 @@ def stream_loss_ce(pred, targets, kinds, widths, seq_len, want_grad, want_prob=F
     (loss 0-d, grad or None, prob or None, [argmax per stream or None])."""
     lib = _lib.load()
     pred = _require(pred, torch.float32, 'predictions')
-    if pred.dim() != 3 or len(targets) != len(kinds) or not 1 <= len(targets) <= _lib.STREAMS_MAX:
-        raise ValueError('stream_loss: predictions must be (B, T, D) with 1..%d streams' % _lib.STREAMS_MAX)
+    if pred.dim() != 3 or len(targets) != len(kinds) or not 1 <= len(targets) <= _lib.MG_STREAMS_MAX:
+        raise ValueError('stream_loss: predictions must be (B, T, D) with 1..%d streams' % _lib.MG_STREAMS_MAX)
     b, t, d = pred.shape
     if seq_len is not None:
         seq_len = _require(seq_len, torch.int64, 'seq_len')
@@ -464,7 +465,7 @@ def stream_loss_ce(pred, targets, kinds, widths, seq_len, want_grad, want_prob=F
     if len(widths) != n or min(widths) < 1 or sum(widths) != d:
         raise ValueError('stream_loss: stream widths %s do not add up to D=%d' % (widths, d))
     rest = [k for k in range(n) if kinds[k] != 'ce']
-    descs = (_lib.StreamDesc * max(len(rest), 1))()
+    descs = (_lib.mg_stream_desc * max(len(rest), 1))()
     keep, prob, col0s = [], None, [sum(widths[:k]) for k in range(n)]
     for j, k in enumerate(rest):
         y = _require(targets[k], torch.float32, 'targets[%d]' % k)
@@ -472,7 +473,7 @@ def stream_loss_ce(pred, targets, kinds, widths, seq_len, want_grad, want_prob=F
             raise ValueError('stream_loss: targets[%d] %s does not match predictions (%d, %d, *)' % (k, tuple(y.shape), b, t))
         keep.append(y)
         descs[j].target, descs[j].ldt, descs[j].col0, descs[j].width = y.data_ptr(), widths[k], col0s[k], widths[k]
-        descs[j].kind = {'mse': _lib.LOSS_MSE, 'sigmoid_bce': _lib.LOSS_SIGMOID_BCE}[kinds[k]]
+        descs[j].kind = {'mse': _lib.MG_LOSS_MSE, 'sigmoid_bce': _lib.MG_LOSS_SIGMOID_BCE}[kinds[k]]
         if kinds[k] == 'sigmoid_bce' and want_prob:
             prob = torch.empty((b, t, widths[k]), dtype=torch.float32, device=pred.device)
     loss = torch.empty((), dtype=torch.float32, device=pred.device)
@@ -601,8 +602,8 @@ def column_stats(state, x, *, offsets=None, seq_len=None, item_row=None, max_row
     x = _require(x, torch.float32, 'feature')
     if (offsets is None) == (seq_len is None):
         raise ValueError('column_stats: give exactly one of offsets (packed rows) and seq_len (padded batch)')
-    if state.dim() != 3 or state.shape[1] != _lib.COLSTATS_FIELDS:
-        raise ValueError('column_stats: state %s must be (groups, %d, features)' % (tuple(state.shape), _lib.COLSTATS_FIELDS))
+    if state.dim() != 3 or state.shape[1] != _lib.MG_COLSTATS_FIELDS:
+        raise ValueError('column_stats: state %s must be (groups, %d, features)' % (tuple(state.shape), _lib.MG_COLSTATS_FIELDS))
     groups, d = state.shape[0], state.shape[2]
     if offsets is not None:
         offsets = _require(offsets, torch.int64, 'offsets')
@@ -712,7 +713,7 @@ def cast_bf16_f32(x_bf16, cols):
     return out
 
 
-ACT_ROWS_RUNS = 0x100      # MG_ACT_ROWS_RUNS: `rows` is a frame map of upsample_to_repetitions (runs of equal indices); a hint only
+ACT_ROWS_RUNS = _lib.MG_ACT_ROWS_RUNS      # `rows` is a frame map of upsample_to_repetitions (runs of equal indices); a hint only
 
 
 def linear_fwd_bf16(a, rows, m, k, w_bf16, bias, n, act, out_f32=False, rows_runs=False):
@@ -921,9 +922,9 @@ def copy_many(pairs):
     the tensors of a new batch into a captured step's static buffers as one launch instead of one per tensor."""
     lib = _lib.load()
     pairs = list(pairs)
-    for i in range(0, len(pairs), _lib.COPY_MAX):
-        chunk = pairs[i:i + _lib.COPY_MAX]
-        descs = (_lib.CopyDesc * len(chunk))()
+    for i in range(0, len(pairs), _lib.MG_COPY_MAX):
+        chunk = pairs[i:i + _lib.MG_COPY_MAX]
+        descs = (_lib.mg_copy_desc * len(chunk))()
         for j, (dst, src) in enumerate(chunk):
             if (not dst.is_cuda or not src.is_cuda or dst.device != src.device or not dst.is_contiguous() or not src.is_contiguous()
                     or dst.dtype != src.dtype or dst.numel() != src.numel()):
@@ -936,9 +937,9 @@ def cast_params_bf16(weights, want_plain=True, want_t=()):
     """One launch: bf16 copies [N, pad_ld(K)] of every fp32 weight and, for the indices in `want_t`, the transposed
     copies [K, pad_ld(N)].  Returns (plain list, transposed list with None where not requested)."""
     lib = _lib.load()
-    if len(weights) > _lib.CAST_MAX:
-        raise ValueError('cast_params_bf16: at most %d matrices per call' % _lib.CAST_MAX)
-    descs = (_lib.CastDesc * len(weights))()
+    if len(weights) > _lib.MG_CAST_MAX:
+        raise ValueError('cast_params_bf16: at most %d matrices per call' % _lib.MG_CAST_MAX)
+    descs = (_lib.mg_cast_desc * len(weights))()
     plain, trans = [], []
     for i, w in enumerate(weights):
         w = _require(w, torch.float32, 'weight')
@@ -966,8 +967,8 @@ def weight_operands(weights, transposed=False):
     if not WEIGHT_SHADOWS:
         return [cast_transpose_bf16(w) if transposed else cast_pad_bf16(_require(w, torch.float32, 'weight')) for w in weights]
     out = []
-    for i in range(0, len(weights), _lib.CAST_MAX):      # mg_cast_params_bf16 takes at most MG_CAST_MAX descriptors per launch
-        part = weights[i:i + _lib.CAST_MAX]
+    for i in range(0, len(weights), _lib.MG_CAST_MAX):      # mg_cast_params_bf16 takes at most MG_CAST_MAX descriptors per launch
+        part = weights[i:i + _lib.MG_CAST_MAX]
         plain, trans = param_shadows(part, want_t=tuple(range(len(part))) if transposed else ())
         out += trans if transposed else plain
     return out
@@ -993,7 +994,7 @@ def param_shadows(weights, want_t=()):
         if not ok:
             stale.append(i)
     if stale:
-        descs = (_lib.CastDesc * len(stale))()
+        descs = (_lib.mg_cast_desc * len(stale))()
         for j, i in enumerate(stale):
             w = _require(weights[i], torch.float32, 'weight')
             n, k = w.shape
@@ -1028,9 +1029,9 @@ def refresh_shadows(params):
     ``optim.Adam`` for the copies its update kernel's plan has no room for, so that EVERY copy is current when an update ends -
     inside a captured step as well, where nothing on the host can notice a stale copy later."""
     lib = _lib.load()
-    for i in range(0, len(params), _lib.CAST_MAX):
-        chunk = params[i:i + _lib.CAST_MAX]
-        descs = (_lib.CastDesc * len(chunk))()
+    for i in range(0, len(params), _lib.MG_CAST_MAX):
+        chunk = params[i:i + _lib.MG_CAST_MAX]
+        descs = (_lib.mg_cast_desc * len(chunk))()
         for j, w in enumerate(chunk):
             sh = w._mg_shadow
             n, k = w.shape
@@ -1292,9 +1293,9 @@ def split3(jobs):
     sixth element True (plain layouts) returns (planes, slabs): the per-workgroup column sums of the split values (``slab_reduce``)."""
     lib = _lib.load()
     outs = []
-    for i in range(0, len(jobs), _lib.SPLIT3_MAX):
-        chunk = jobs[i:i + _lib.SPLIT3_MAX]
-        descs = (_lib.Split3Desc * len(chunk))()
+    for i in range(0, len(jobs), _lib.MG_SPLIT3_MAX):
+        chunk = jobs[i:i + _lib.MG_SPLIT3_MAX]
+        descs = (_lib.mg_split3_desc * len(chunk))()
         for j, job in enumerate(chunk):
             x, order, transpose = job[:3]
             extra = int(job[3]) if len(job) > 3 else 0          # zero rows appended behind the split (not with transpose)
@@ -1437,7 +1438,7 @@ def linear_wgrad_x3(g2, a2, rows, m, n, k, out_w=None, out_b=None, accumulate=Fa
 
 # ------------------------------------------------------------------------------- precision 'bf16x3', the FUSED step on pair planes
 # (include/morgana_hip.h, "The FUSED step of precision mode 'bf16x3' on PAIR PLANES").  A pair is a bf16 (rows, 2 ldp) buffer [hi | lo].
-F0_TAIL_X3_SLAB = 4292                 # MG_F0_TAIL_X3_SLAB: db2 128 | dW3 4096 | db3 32 | dW4 32 | db4 | loss | 2 unused
+F0_TAIL_X3_SLAB = _lib.MG_F0_TAIL_X3_SLAB      # db2 128 | dW3 4096 | db3 32 | dW4 32 | db4 | loss | 2 unused
 F0_TAIL_X3_N = F0_TAIL_X3_SLAB - 2     # ... up to and including the loss
 
 
@@ -1455,7 +1456,7 @@ def split_pair(x2d, transpose=False, extra_rows=0):
     out = torch.empty(((cols if transpose else rows) + extra_rows, 2 * ldp), dtype=torch.bfloat16, device=x2d.device)
     if extra_rows:
         out[rows:].zero_()
-    descs = (_lib.Split3Desc * 1)()
+    descs = (_lib.mg_split3_desc * 1)()
     d = descs[0]
     d.src, d.rows, d.cols, d.lds = x2d.data_ptr(), rows, cols, x2d.stride(0)
     d.dst, d.ldp, d.order, d.transpose, d.plane_rows = out.data_ptr(), ldp, 5, int(bool(transpose)), 0
@@ -2154,7 +2155,7 @@ def lstm_pstack_fwd(xproj0, w_ih, w_hh, b_ih, b_hh, seq_len, h0s, c0s, b, t, h):
     dev = xproj0.device
     n_layers = len(w_hh)
     hstate, cstate, saved, hstate_bf, keep, o = [], [], [], [], [], None
-    descs = (_lib.LstmPStackLayer * n_layers)()
+    descs = (_lib.mg_lstm_pstack_layer * n_layers)()
     # the state arrays of all layers in three allocations: their initial rows are set by three launches, not three per layer
     if os.environ.get('MORGANA_LSTM_BATCH_STATES', '1') != '0':
         hs_all = torch.empty((n_layers, b, t + 1, h), dtype=torch.float32, device=dev)
@@ -2231,7 +2232,7 @@ def gru_stack_small_fwd(xproj0, w_ih, w_hh, b_ih, b_hh, seq_len, h0s, b, t, h, f
     lib = _lib.load()
     dev = xproj0.device
     n_layers = len(w_hh)
-    descs = (_lib.GruStackLayer * n_layers)()
+    descs = (_lib.mg_gru_stack_layer * n_layers)()
     outs, hstates, saveds = [], [], []
     for l in range(n_layers):
         hs = torch.empty((b, t + 1, h), dtype=torch.float32, device=dev)
@@ -2262,7 +2263,7 @@ def gru_stack_small_bwd(grad_out, grad_hn, hstate, saved, w_ih, w_hh, seq_len, b
     lib = _lib.load()
     dev = grad_out.device
     n_layers = len(w_hh)
-    descs = (_lib.GruStackLayer * n_layers)()
+    descs = (_lib.mg_gru_stack_layer * n_layers)()
     dxprojs, dhprojs, keep = [], [], []
     dh0 = torch.empty((n_layers, b, h), dtype=torch.float32, device=dev)
     for l in range(n_layers):
@@ -2304,7 +2305,7 @@ def lstm_pstack_bwd(grad_out, grad_hn, grad_cn, cstate, saved, w_ih, w_hh, seq_l
     lib = _lib.load()
     dev = grad_out.device
     n_layers = len(w_hh)
-    descs = (_lib.LstmPStackBwdLayer * n_layers)()
+    descs = (_lib.mg_lstm_pstack_bwd_layer * n_layers)()
     dgates, dgates_bf, keep = [], [], []
     dh0 = torch.empty((n_layers, b, h), dtype=torch.float32, device=dev)
     dc0 = torch.empty((n_layers, b, h), dtype=torch.float32, device=dev)
@@ -2381,7 +2382,7 @@ def store_pair(dst, a, b):
     _lib.check(_lib.load().mg_store_pair_f32(_p(dst), float(a), float(b), _stream()), 'mg_store_pair_f32')
 
 
-STORE_PAIRS_MAX = 32
+STORE_PAIRS_MAX = _lib.MG_STORE_PAIRS_MAX
 
 
 def store_pairs(dst, pairs):
@@ -2405,9 +2406,9 @@ def adam_step_plan(param, grad, exp_avg, exp_avg_sq, betas, eps, weight_decay, s
     ``shadows`` = [(offset, rows, cols, bf16 [rows, ldd] or None, bf16 transpose [cols, ldt] or None)] are refreshed from the
     updated weights, ``clear_grad`` zeroes the flat gradient behind the read."""
     lib = _lib.load()
-    if len(slab_srcs) > _lib.ADAM_MAX_SLABS or len(shadows) > _lib.ADAM_MAX_SHADOWS:
-        raise ValueError('adam_step_plan: at most %d slab sources and %d shadows' % (_lib.ADAM_MAX_SLABS, _lib.ADAM_MAX_SHADOWS))
-    plan = _lib.AdamPlan()
+    if len(slab_srcs) > _lib.MG_ADAM_MAX_SLABS or len(shadows) > _lib.MG_ADAM_MAX_SHADOWS:
+        raise ValueError('adam_step_plan: at most %d slab sources and %d shadows' % (_lib.MG_ADAM_MAX_SLABS, _lib.MG_ADAM_MAX_SHADOWS))
+    plan = _lib.mg_adam_plan()
     plan.n_slab_srcs, plan.n_shadows, plan.clear_grad = len(slab_srcs), len(shadows), int(bool(clear_grad))
     for i, (begin, count, slab, n_slabs, stride) in enumerate(slab_srcs):
         src = plan.slabs[i]
@@ -2477,7 +2478,9 @@ def ema_update(shadow, param, decay):
 
 
 # ----------------------------------------------------------------------------------------------------------- metrics
-METRIC_MEAN, METRIC_SQDIFF, METRIC_ABSDIFF, METRIC_ROOT_SQ, METRIC_SQDIFF_VOICED, METRIC_SQDIFF_VOICED_EXP = range(6)
+METRIC_MEAN, METRIC_SQDIFF, METRIC_ABSDIFF, METRIC_ROOT_SQ, METRIC_SQDIFF_VOICED, METRIC_SQDIFF_VOICED_EXP = (
+    _lib.MG_METRIC_MEAN, _lib.MG_METRIC_SQDIFF, _lib.MG_METRIC_ABSDIFF, _lib.MG_METRIC_ROOT_SQ, _lib.MG_METRIC_SQDIFF_VOICED,
+    _lib.MG_METRIC_SQDIFF_VOICED_EXP)
 
 
 def metric_accumulate(kind, accum, target, pred=None, voiced=None, seq_len=None, col0=0, width=None):
@@ -2500,7 +2503,7 @@ def metric_accumulate(kind, accum, target, pred=None, voiced=None, seq_len=None,
 
 
 MLPG_MAX_WINDOWS, MLPG_MAX_COEFF = 4, 5
-MLPG_VAR_ITEM = 2           # MG_MLPG_VAR_ITEM: variances (B, W*D), one row per utterance
+MLPG_VAR_ITEM = _lib.MG_MLPG_VAR_ITEM      # variances (B, W*D), one row per utterance
 
 
 def mlpg(means, variances, windows, padding_size=0, seq_len=None, out_dtype=torch.float32):

@@ -122,7 +122,7 @@ class Adam(torch.optim.Optimizer):
         for flat in self._flat:
             if flat is not None and id(first_param) in flat['offsets']:
                 off = flat['offsets'][id(first_param)]
-                if len(flat['pending']) >= _lib.ADAM_MAX_SLABS or self.max_grad_norm is not None:
+                if len(flat['pending']) >= _lib.MG_ADAM_MAX_SLABS or self.max_grad_norm is not None:
                     # the update kernel's plan holds ADAM_MAX_SLABS sources (a deep stack registers one per leading layer plus
                     # the tail): any further one is summed now, by a reduce launch straight into the flat gradient (as is every one
                     # handed over although clipping is on - ``defers_slabs`` says no: the norm runs over the flat buffer alone)
@@ -176,9 +176,9 @@ class Adam(torch.optim.Optimizer):
             for f in flats:
                 offsets.append(total)
                 total += ops.grad_clip_blocks(f['grad'].numel())[1]
-            if total > _lib.CLIP_MAX_PARTIALS:
+            if total > _lib.MG_CLIP_MAX_PARTIALS:
                 raise ValueError('Adam: max_grad_norm over %d parameter groups needs %d partial sums (limit %d)'
-                                 % (len(flats), total, _lib.CLIP_MAX_PARTIALS))
+                                 % (len(flats), total, _lib.MG_CLIP_MAX_PARTIALS))
             self._clip = {'partials': torch.zeros(total, dtype=torch.float64, device=device), 'offsets': offsets,
                           'norms': torch.zeros(ops.STORE_PAIRS_MAX, 2, dtype=torch.float32, device=device)}
         return self._clip
@@ -289,7 +289,7 @@ class Adam(torch.optim.Optimizer):
         every = self._shadows(flat)
         pairs = [sh for sh in every if sh[6]]               # pair planes have no batched re-split launch: they go first
         every = pairs + [sh for sh in every if not sh[6]]
-        shadows, rest = every[:_lib.ADAM_MAX_SHADOWS], every[_lib.ADAM_MAX_SHADOWS:]
+        shadows, rest = every[:_lib.MG_ADAM_MAX_SHADOWS], every[_lib.MG_ADAM_MAX_SHADOWS:]
         stale_pairs = [sh for sh in rest if sh[6]]
         rest = [sh for sh in rest if not sh[6]]
         pending, flat['pending'] = flat['pending'], []

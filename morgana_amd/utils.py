@@ -132,7 +132,7 @@ def detach_batched_seqs(*sequence_features, seq_len=None, squeeze=True):
     are packed on the device first (``_detach_on_device``): only the valid frames cross PCIe, in one copy for all features; a
     ``seq_len`` that lives on the device is read once.  CPU tensors and NumPy inputs are sliced on the host: there is nothing to
     compute.  On both paths a length above T counts as T and a negative one as 0 (the reference's slice would crop a negative
-    length from the end).  Any batch size works: above ``_lib.UNPAD_MAX_ITEMS`` items the pack takes several launches."""
+    length from the end).  Any batch size works: above ``_lib.MG_UNPAD_MAX_ITEMS`` items the pack takes several launches."""
     seq_len_tensor = seq_len if isinstance(seq_len, torch.Tensor) else None
     if seq_len_tensor is not None:
         seq_len = seq_len_tensor.cpu().detach().numpy()
@@ -168,7 +168,7 @@ def detach_batched_seqs(*sequence_features, seq_len=None, squeeze=True):
 def batched_masked_select(sequence_feature, seq_len):
     """The feature vectors of all batch items that lie within their sequence length: (B, T, D) -> (sum_b min(seq_len[b], T), D), of
     the input's dtype.  morgana/utils.py:147-166 (there: a mask, ``nonzero`` and an index).  One ragged-pack launch
-    (ops.unpad_rows; several above ``_lib.UNPAD_MAX_ITEMS`` items); ``seq_len`` is read once for the size of the result, as the
+    (ops.unpad_rows; several above ``_lib.MG_UNPAD_MAX_ITEMS`` items); ``seq_len`` is read once for the size of the result, as the
     reference's ``nonzero`` does.  Differentiable for float32 inputs (backward: the zero-padded scatter)."""
     if not isinstance(sequence_feature, torch.Tensor):
         raise TypeError('sequence_feature must be a torch.Tensor, got %s' % type(sequence_feature))

@@ -1,5 +1,6 @@
 """CPU-only checks of the drop-in boundary: the C-ABI library loads and exports exactly what include/morgana_hip.h
-declares, the ctypes signature table covers it, and the product path refuses to run without a device / library."""
+declares, the binding parsed from that header (signatures, struct layouts, constants) is what the C compiler sees, and the product
+path refuses to run without a device / library."""
 import os
 import re
 
@@ -26,6 +27,111 @@ def test_header_symbols_are_exported_and_bound():
     for name in declared:
         assert hasattr(lib, name), 'libmorgana_hip.so does not export %s' % name
     assert sorted(_lib.SIGNATURES) == declared
+
+
+def test_pinned_signatures_cover_every_type_mapping():
+    """parse_header against (restype, argtypes) pairs written out by hand; between them: c_char_p and (void), a void return and array
+    parameters, double, float / uint64_t / uint32_t / int64_t, an int64_t and a size_t return, `const void* const*`."""
+    from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
+    pinned = {
+        'mg_last_error': (c_char_p, []),
+        'mg_philox4x32_10': (None, [c_void_p, c_void_p, c_void_p]),
+        'mg_grad_clip_scale_f32': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p]),
+        'mg_dropout': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_uint64, c_uint32, c_void_p, c_void_p]),
+        'mg_f0_l2tail_slab_stride': (c_int64, []),
+        'mg_column_stats_workspace_bytes': (c_size_t, [c_int, c_int64, c_int]),
+        'mg_host_pack': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int]),
+        'mg_upsample_index': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    }
+    for name, signature in pinned.items():
+        assert tuple(_lib.SIGNATURES[name]) == signature, name
+
+
+def _host_c_compiler():
+    """cc, or the clang that hipcc drives (what builds the library itself)."""
+    import shutil
+    hipcc = shutil.which('hipcc')
+    roots = [os.path.dirname(os.path.dirname(os.path.realpath(hipcc)))] if hipcc else []
+    roots += [os.environ.get('ROCM_PATH', '/opt/rocm')]
+    found = [shutil.which(c) for c in ('cc', 'gcc', 'clang')] + [os.path.join(r, 'lib', 'llvm', 'bin', 'clang') for r in roots]
+    found = [c for c in found if c and os.path.exists(c)]
+    assert found, 'no host C compiler: neither cc nor the clang behind hipcc'
+    return found[0]
+
+
+def test_struct_layouts_match_the_c_compiler(tmp_path):
+    """Every descriptor struct ctypes builds from the parsed header has the size and the field offsets the C compiler gives the header
+    itself: a C program generated from the parsed field names prints sizeof / offsetof, compiled and run on the host."""
+    import ctypes
+    import subprocess
+    assert len(_lib.STRUCTS) == 14 and _lib.STRUCTS['mg_adam_plan'] is _lib.mg_adam_plan
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "morgana_hip.h"', 'int main(void) {']
+    want = {}
+    for name, struct in _lib.STRUCTS.items():
+        lines.append('    printf("%s %%zu\\n", sizeof(%s));' % (name, name))
+        want[name] = ctypes.sizeof(struct)
+        for field, _ in struct._fields_:
+            lines.append('    printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (name, field, name, field))
+            want['%s.%s' % (name, field)] = getattr(struct, field).offset
+    lines += ['    return 0;', '}']
+    source, program = tmp_path / 'layouts.c', tmp_path / 'layouts'
+    source.write_text('\n'.join(lines) + '\n')
+    subprocess.run([_host_c_compiler(), '-I', os.path.join(REPO, 'include'), str(source), '-o', str(program)], check=True)
+    out = subprocess.run([str(program)], check=True, stdout=subprocess.PIPE, universal_newlines=True).stdout
+    got = {key: int(value) for key, value in (line.split() for line in out.splitlines())}
+    assert got == want
+    assert want['mg_adam_plan'] == 656 and len(want) > 14 + 100
+
+
+def test_pinned_constants_and_their_python_names():
+    assert _lib.MG_ADAM_MAX_SLABS == 4
+    assert _lib.MG_ADAM_MAX_SHADOWS == 8
+    assert _lib.MG_CE_MAX_CLASSES == 65536
+    assert _lib.MG_ACT_ROWS_RUNS == 0x100
+    assert _lib.MG_EINVAL == -1
+    for name in ('ACT_NONE', 'ACT_SIGMOID', 'ACT_TANH', 'ACT_RELU', 'ACT_ROWS_RUNS', 'NORM_MVN', 'DENORM_MVN', 'NORM_MINMAX',
+                 'DENORM_MINMAX', 'F0_TAIL_X3_SLAB', 'STORE_PAIRS_MAX', 'MLPG_VAR_ITEM', 'METRIC_MEAN', 'METRIC_SQDIFF_VOICED_EXP'):
+        assert getattr(ops, name) == getattr(_lib, 'MG_' + name), name
+    assert (ops.ACT_NONE, ops.ACT_SIGMOID, ops.ACT_TANH, ops.ACT_RELU) == (0, 1, 2, 3)
+    assert (ops.NORM_MVN, ops.DENORM_MVN, ops.NORM_MINMAX, ops.DENORM_MINMAX) == (0, 1, 2, 3)
+
+
+@pytest.mark.parametrize('text, quoted', [
+    ('int mg_f(long double x);', 'long double x'),                       # a scalar type without a mapping
+    ('typedef struct { int a : 3; } mg_bits;', 'int a : 3'),             # a bit-field
+    ('#define MG_X (1 << 3)', '(1 << 3)'),                               # a constant that is not an integer literal
+    ('int mg_f(void (*callback)(int));', 'callback'),                    # a function-pointer parameter
+    ('typedef union { int a; float b; } mg_u;', 'union'),
+    ('typedef struct { float v[MG_UNKNOWN]; } mg_arr;', 'MG_UNKNOWN'),   # an array length that no #define gives
+    ('mg_cast_desc mg_f(void);', 'mg_cast_desc'),                        # nothing is guessed for an unknown return type
+])
+def test_parse_header_refuses_what_it_cannot_bind(text, quoted):
+    with pytest.raises(_lib.MorganaHipError) as refusal:
+        _lib.parse_header(text)
+    assert quoted in str(refusal.value)
+
+
+def test_missing_header_is_named(monkeypatch, tmp_path):
+    monkeypatch.setattr(_lib, 'HEADER_PATH', str(tmp_path / 'include' / 'morgana_hip.h'))
+    with pytest.raises(_lib.MorganaHipError) as refusal:
+        _lib._read_header()
+    assert _lib.HEADER_PATH in str(refusal.value)
+
+
+def test_parse_header_forms():
+    """The declaration forms the header uses, on a small text: parenthesised / negative / hex constants, several declarators on a
+    line, arrays sized by a literal or a constant, an earlier struct by value, every pointer flavour as c_void_p."""
+    import ctypes
+    constants, structs, signatures = _lib.parse_header(
+        '#define MG_A (-3)\n#define MG_B 0x10 /* hex */\n#define MG_C ( 7 )\n'
+        'typedef struct { int rows, cols; const void* p; } mg_in;\n'
+        'typedef struct { mg_in one; mg_in many[MG_C]; double d[2]; const float* const* pp; uint64_t u; } mg_out;\n'
+        'size_t mg_f(const mg_out* o, const uint32_t counter[4], float x,\n    void* stream);  // trailing\n')
+    assert constants == {'MG_A': -3, 'MG_B': 16, 'MG_C': 7}
+    assert [(n, getattr(structs['mg_in'], n).offset) for n, _ in structs['mg_in']._fields_] == [('rows', 0), ('cols', 4), ('p', 8)]
+    out = structs['mg_out']
+    assert ctypes.sizeof(out) == 16 + 7 * 16 + 16 + 8 + 8 and out.many.offset == 16 and out.pp.size == 8 and out.u.offset == 152
+    assert signatures == {'mg_f': (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p])}
 
 
 def test_library_identity_calls():
@@ -66,7 +172,7 @@ def test_new_entry_points_validate_their_arguments_without_a_gpu():
     message), as every other entry point does."""
     import ctypes
     lib = _lib.load()
-    desc = (_lib.Split3Desc * 1)()
+    desc = (_lib.mg_split3_desc * 1)()
     desc[0].src, desc[0].rows, desc[0].cols, desc[0].lds = 16, 4, 8, 8
     desc[0].dst, desc[0].ldp, desc[0].order, desc[0].transpose = 32, 8, 7, 0           # order 7 does not exist
     assert lib.mg_split3_bf16(ctypes.cast(desc, ctypes.c_void_p), 1, None) == -1 and 'order 7' in _lib.last_error()

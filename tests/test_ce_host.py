@@ -100,7 +100,7 @@ def test_masked_ce_validates_its_arguments_without_a_gpu():
     assert call(c=-3) == -1 and 'mg_masked_ce_f32' in _lib.last_error()
     assert call(pred=None) == -1 and 'NULL' in _lib.last_error()
     assert call(target=None) == -1 and call(loss=None) == -1
-    assert call(c=_lib.CE_MAX_CLASSES + 1, ldp=_lib.CE_MAX_CLASSES + 1) == -1 and 'cap' in _lib.last_error()
+    assert call(c=_lib.MG_CE_MAX_CLASSES + 1, ldp=_lib.MG_CE_MAX_CLASSES + 1) == -1 and 'cap' in _lib.last_error()
     assert call(b=0) == -1 and call(t=0) == -1 and call(b=65536) == -1
     assert call(ldp=7) == -1 and 'ldp=7' in _lib.last_error()                      # the row stride must cover col0 + C
     assert call(ldp=10, col0=3) == -1 and call(col0=-1) == -1

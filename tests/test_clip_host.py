@@ -140,7 +140,7 @@ def test_clip_entry_points_validate_their_arguments_without_a_gpu():
     assert lib.mg_grad_sumsq_f32(fake_g, 16, fake_p, 4, 4, None) == -1 and 'do not fit' in _lib.last_error()
     assert lib.mg_grad_sumsq_f32(fake_g, 3 * 4096, fake_p, 2, 4, None) == -1 and 'do not fit' in _lib.last_error()
     assert lib.mg_grad_sumsq_f32(fake_g, 16, fake_p, -1, 4, None) == -1
-    assert lib.mg_grad_sumsq_f32(fake_g, 16, fake_p, 0, _lib.CLIP_MAX_PARTIALS + 1, None) == -1 and 'n_partials' in _lib.last_error()
+    assert lib.mg_grad_sumsq_f32(fake_g, 16, fake_p, 0, _lib.MG_CLIP_MAX_PARTIALS + 1, None) == -1 and 'n_partials' in _lib.last_error()
     assert lib.mg_grad_clip_scale_f32(fake_g, 0, fake_p, 1, 1.0, 1.0, fake_o, None) == -1 and 'n=0' in _lib.last_error()
     assert lib.mg_grad_clip_scale_f32(None, 16, fake_p, 1, 1.0, 1.0, fake_o, None) == -1
     assert lib.mg_grad_clip_scale_f32(fake_g, 16, None, 1, 1.0, 1.0, fake_o, None) == -1

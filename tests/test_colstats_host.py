@@ -73,7 +73,7 @@ def test_column_stats_validates_its_arguments_without_a_gpu():
 
     for rc in (call(offsets=fake, seq_len=fake), call(offsets=None, seq_len=None)):
         assert rc == -1 and 'mg_column_stats_f32' in _lib.last_error() and 'exactly one' in _lib.last_error()
-    for d in (0, -3, _lib.COLSTATS_MAX_D + 1):
+    for d in (0, -3, _lib.MG_COLSTATS_MAX_D + 1):
         assert call(d=d, ld=max(d, 1)) == -1 and 'mg_column_stats_f32: D=' in _lib.last_error()
     for s in (0, -1):
         assert call(s=s) == -1 and 'mg_column_stats_f32: S=' in _lib.last_error()

@@ -125,7 +125,7 @@ def test_save_batched_seqs_on_cpu_tensors(tmp_path, g19):
 
 # ------------------------------------------------------------------------------------------------------------ argument validation
 def _descs(n=1, **fields):
-    descs = (_lib.UnpadDesc * n)()
+    descs = (_lib.mg_unpad_desc * n)()
     for i in range(n):
         descs[i].src, descs[i].T, descs[i].row_bytes, descs[i].dst_offset, descs[i].block_bytes = 4096, 8, 4, 128 * i, 64
     for key, value in fields.items():
@@ -139,7 +139,7 @@ def _unpad(descs, count, seq_len=8192, b=2, dst=16384, dst_bytes=4096):
 
 
 def test_unpad_rows_validates_its_arguments_without_a_gpu():
-    assert ctypes.sizeof(_lib.UnpadDesc) == 40 and _lib.UNPAD_MAX == 16
+    assert ctypes.sizeof(_lib.mg_unpad_desc) == 40 and _lib.MG_UNPAD_MAX == 16
     for count in (0, 17, -1):
         assert _unpad(_descs(1), count) == -1 and 'count %d' % count in _lib.last_error()
     assert _unpad(_descs(1, row_bytes=0), 1) == -1 and 'row_bytes=0' in _lib.last_error()
@@ -154,7 +154,7 @@ def test_unpad_rows_validates_its_arguments_without_a_gpu():
     assert _unpad(_descs(1), 1, dst=None) == -1 and 'dst is NULL' in _lib.last_error()
     assert _unpad(_descs(1), 1, seq_len=None) == -1 and 'seq_len is NULL' in _lib.last_error()
     assert _unpad(_descs(1), 1, b=-1) == -1 and 'B=-1' in _lib.last_error()
-    assert _unpad(_descs(1), 1, b=_lib.UNPAD_MAX_ITEMS + 1) == -1 and 'B=4097' in _lib.last_error()
+    assert _unpad(_descs(1), 1, b=_lib.MG_UNPAD_MAX_ITEMS + 1) == -1 and 'B=4097' in _lib.last_error()
     assert _unpad(_descs(1, T=1 << 40, row_bytes=1 << 40), 1) == -1 and 'overflows' in _lib.last_error()
     with pytest.raises(ValueError, match='row_bytes=0'):
         _lib.check(_unpad(_descs(1, row_bytes=0), 1), 'mg_unpad_rows')

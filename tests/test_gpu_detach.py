@@ -103,7 +103,7 @@ def test_unpad_rows_more_items_than_one_launch_scans():
     """B = 4100 > MG_UNPAD_MAX_ITEMS: ops.unpad_rows packs in groups of 4096 items, each behind the rows of the groups before it;
     detach_batched_seqs and batched_masked_select work at any batch size, as the reference does."""
     rng = np.random.RandomState(18)
-    b = _lib.UNPAD_MAX_ITEMS + 4
+    b = _lib.MG_UNPAD_MAX_ITEMS + 4
     lens = rng.randint(0, 5, size=b).tolist()
     lens[-3:] = [3, 0, 2]
     arrays = [_array(rng, np.float32, (b, 4, 3)), _array(rng, np.bool_, (b, 4, 5))]
@@ -126,7 +126,7 @@ def test_unpad_rows_never_writes_outside_its_blocks():
     tensors = [torch.from_numpy(a).to(DEV) for a in arrays]
     dst = torch.full((size,), 0xA5, dtype=torch.uint8, device=DEV)
     seq_len = torch.tensor(on_device, dtype=torch.int64, device=DEV)
-    descs = (_lib.UnpadDesc * len(arrays))()
+    descs = (_lib.mg_unpad_desc * len(arrays))()
     for i, (t, a, (off, rows)) in enumerate(zip(tensors, arrays, blocks)):
         descs[i].src, descs[i].T, descs[i].row_bytes = t.data_ptr(), a.shape[1], detach_ref.row_bytes(a)
         descs[i].dst_offset, descs[i].block_bytes = off, rows * detach_ref.row_bytes(a)

@@ -504,7 +504,7 @@ def test_lstm_skewed_stack(lag):
     ds = [_make('lstm', b, t, h, 111 + l) for l in range(n_layers)]
     seq, seq_d = ds[0]['seq_len'], ds[0]['dev']['seq_len']
     keep = []
-    fd = (_lib.LstmFwdLayer * n_layers)()
+    fd = (_lib.mg_lstm_fwd_layer * n_layers)()
     bufs = []
     for l, d in enumerate(ds):
         v = d['dev']
@@ -518,7 +518,7 @@ def test_lstm_skewed_stack(lag):
         fd[l].hstate, fd[l].cstate, fd[l].out, fd[l].saved = hs.data_ptr(), cs.data_ptr(), out.data_ptr(), sv.data_ptr()
         bufs.append((hs, cs, out, sv))
     ops.lstm_stack_fwd(fd, n_layers, seq_d, b, t, h, lag, 0, t + (n_layers - 1) * lag)
-    bd = (_lib.LstmBwdLayer * n_layers)()
+    bd = (_lib.mg_lstm_bwd_layer * n_layers)()
     grads = []
     for l, d in enumerate(ds):
         v = d['dev']
