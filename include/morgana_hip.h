@@ -272,6 +272,8 @@ int mg_metric_accumulate_f32(int kind, const float* target, const float* pred, c
 /* var_per_frame selects the layout of `variances`: 0 = global [W*D], MG_MLPG_VAR_ITEM = one row per utterance [B, W*D] (speaker-dependent
  * variances: the same values as the per-frame form fed that row T times, bit for bit), any other value = per frame [B,T,W*D]. */
 #define MG_MLPG_VAR_ITEM 2
+#define MG_MLPG_MAX_WINDOWS 4 /* n_windows <= this */
+#define MG_MLPG_MAX_COEFF 5   /* the row length of win_coeff: l + u + 1 <= this */
 size_t mg_mlpg_workspace_bytes(int B, int T, int D, int padding, int n_windows, const int* win_l, const int* win_u);
 int mg_mlpg_f32(const float* means, const float* variances, int var_per_frame, const int64_t* seq_len, int B, int T, int D,
                 int n_windows, const int* win_l, const int* win_u, const double* win_coeff, int padding, void* out, int out_f64,
@@ -1165,6 +1167,42 @@ size_t mg_column_stats_workspace_bytes(int B, int64_t max_rows, int D);
  * B == 0: MG_OK, nothing launched.  MG_EWORKSPACE when the workspace is too small. */
 int mg_column_stats_f32(const float* x, int64_t ld, int D, int B, int T, const int64_t* offsets, const int64_t* seq_len,
                         const int32_t* item_row, int S, double* state, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------------------
+ * K23 (csrc/deltas.hip)  delta features: the forward of MLPG's window operator    reference: morgana/viz/synthesis.py:8-36
+ *                        (_build_win_mats: output column w*D + d at frame t is row t of W_w applied to column d) - applied nowhere in
+ *                        the reference, whose {name}_deltas files come from the un-vendored tts_data_tools (data.py:135-150 loads
+ *                        and normalises them); here computed on the device inside the loader's pad-and-normalise pass.
+ * Windows as in mg_mlpg_f32: win_l / win_u [W] ints, win_coeff [W][MG_MLPG_MAX_COEFF] doubles, l + u + 1 <= MG_MLPG_MAX_COEFF,
+ * 1 <= W <= MG_MLPG_MAX_WINDOWS (host arrays).  out[t, w*D + d] = sum_k coeff[w][k] x[t - l_w + k, d], accumulated in float64,
+ * taps in ascending k, rounded once to float32.  A tap outside [0, len) reads the item's first / last frame
+ * (MG_DELTAS_EDGE_REPLICATE) or contributes nothing (MG_DELTAS_EDGE_ZERO: exactly W_w of MLPG).
+ * Input x, exactly one of
+ *   offsets (B + 1, int64): packed [N, D] - the rows of item b are [offsets[b], offsets[b + 1]); T_in is unused,
+ *   seq_len (B, int64):     padded [B, T_in, D] - item b is rows [b T_in, b T_in + min(max(seq_len[b], 0), T_in)); later frames are
+ *                           never read.
+ * Output, raw_out and / or norm_out (either may be NULL), both of the form out_form:
+ *   MG_DELTAS_OUT_PADDED  [B, out_rows, W*D]: an item longer than out_rows frames is cut to out_rows frames first (as
+ *                         mg_pad_normalise_f32 cuts it); frames past the length are written as zeros by the same launch,
+ *   MG_DELTAS_OUT_PACKED  [out_rows, W*D]: packed input - row r of the output belongs to row r of the input; padded input - the valid
+ *                         frames of the items back to back (B <= MG_DELTAS_MAX_SCAN_ITEMS).  Rows that belong to no item, and rows
+ *                         from out_rows on, are not written.
+ * norm_out = kind (MG_NORM_MVN or MG_NORM_MINMAX) with p0 / p1 [W*D] applied to the rounded float32 value, the arithmetic of
+ * mg_normalise_f32; with item_row (B, int32) non-NULL p0 / p1 are tables [S, W*D] and item b takes row item_row[b], as in
+ * mg_pad_normalise_items_f32: an index outside [0, S) is never used as one and gives NaN in that item's valid frames.
+ * Lengths 0, 1 and 2 are legal.  B == 0: MG_OK, nothing launched.  One launch, no workspace, no atomics; 16-byte accesses when
+ * D % 4 == 0 and x, the outputs and the parameters are 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define MG_DELTAS_EDGE_REPLICATE 0
+#define MG_DELTAS_EDGE_ZERO 1
+#define MG_DELTAS_OUT_PADDED 0
+#define MG_DELTAS_OUT_PACKED 1
+#define MG_DELTAS_MAX_SCAN_ITEMS 4096
+/* Destination rows of one chunk of the launch for features of D columns (0 for D <= 0): what a test needs to cross a chunk. */
+int mg_deltas_chunk_rows(int D);
+int mg_deltas_f32(const float* x, int D, int B, const int64_t* offsets, const int64_t* seq_len, int T_in, int n_windows, const int* win_l,
+                  const int* win_u, const double* win_coeff, int edge, const float* p0, const float* p1, const int32_t* item_row, int S,
+                  int kind, int out_form, int64_t out_rows, float* raw_out, float* norm_out, void* stream);
 
 #ifdef __cplusplus
 }

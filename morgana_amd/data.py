@@ -521,6 +521,108 @@ def load_utterance(features, normalisers):
     return out
 
 
+DELTAS_SUFFIX = '_deltas'
+
+
+def _default_windows():
+    from .viz import synthesis                            # (imported here: viz imports this package's ops on its own)
+    return synthesis.DEFAULT_WINDOWS
+
+
+class DeltaSpec(object):
+    """How the delta features of one named feature are computed: ``windows`` - [(l, u, coefficients)], as ``viz.synthesis.MLPG`` takes
+    them, default ``viz.synthesis.DEFAULT_WINDOWS`` (static, delta, delta-delta) - and ``edge``, see ``compute_deltas``."""
+
+    def __init__(self, windows=None, edge='replicate'):
+        if edge not in ops.DELTAS_EDGES:
+            raise ValueError("edge must be 'replicate' or 'zero', got %r" % (edge,))
+        windows = _default_windows() if windows is None else windows
+        self.windows = tuple((int(l), int(u), tuple(float(c) for c in coeff)) for l, u, coeff in windows)
+        for w, (l, u, coeff) in enumerate(self.windows):
+            if l < 0 or u < 0 or len(coeff) != l + u + 1:
+                raise ValueError('window %d: %d coefficients for extents l=%d, u=%d' % (w, len(coeff), l, u))
+        self.edge = edge
+
+    def __repr__(self):
+        return 'DeltaSpec(windows=%r, edge=%r)' % (self.windows, self.edge)
+
+
+def _host_deltas(feature, spec):
+    """The arithmetic of mg_deltas_f32 in NumPy for one (len, D) item: per window the products coefficient * x in float64, taps in
+    ascending order, the first product starting the sum, each later one added with one rounding; the sum rounded once to float32."""
+    x = np.asarray(feature)
+    if x.ndim != 2:
+        raise ValueError('compute_deltas: a host feature must be one (frames, features) array, got shape %s' % (x.shape,))
+    n, d = x.shape
+    wide = x.astype(np.float32).astype(np.float64)
+    out = np.zeros((n, len(spec.windows) * d), dtype=np.float32)
+    if n == 0:
+        return out
+    frames = np.arange(n)
+    for w, (l, u, coeff) in enumerate(spec.windows):
+        acc, opened = np.zeros((n, d)), np.zeros(n, dtype=bool)
+        for k, c in enumerate(coeff):
+            taps = frames - l + k
+            inside = (taps >= 0) & (taps < n)
+            use = np.ones(n, dtype=bool) if spec.edge == 'replicate' else inside
+            with np.errstate(all='ignore'):
+                term = np.float64(c) * wide[np.clip(taps, 0, n - 1)]
+                summed = np.where(opened[:, None], acc + term, term)
+            acc = np.where(use[:, None], summed, acc)
+            opened |= use
+        with np.errstate(all='ignore'):
+            out[:, w * d:(w + 1) * d] = acc.astype(np.float32)
+    return out
+
+
+def compute_deltas(feature, windows=None, edge='replicate', seq_len=None):
+    """Delta features ``[window 0 | window 1 | ...]`` of a feature: column ``w*D + d`` at frame t is ``sum_k coeff[w][k] x[t - l_w + k, d]``,
+    row t of the window matrix ``W_w`` that MLPG inverts (morgana/viz/synthesis.py:8-36).  ``windows`` defaults to
+    ``viz.synthesis.DEFAULT_WINDOWS``: the result is then ``[static | delta | delta-delta]``, the layout of the ``{name}_deltas`` files.
+
+    A NumPy ``(len, D)`` array is computed on the host; a device tensor ``(B, T, D)`` - with ``seq_len`` (B,), frames past it are not
+    read and come back as zeros - or ``(T, D)`` goes through the HIP kernel (csrc/deltas.hip).  Both accumulate every element in
+    float64, taps in ascending order, and round once to float32: the same bits.  There is no backward: a tensor that requires grad is
+    refused.
+
+    ``edge``: what a tap outside the item reads.  'replicate' (default): the item's first / last frame, the Merlin convention;
+    'zero': nothing, which is exactly ``W_w`` (MLPG of the result with unit variances gives the feature back).  Which of the two the
+    ``{name}_deltas`` files of ``tts_data_tools`` were written with could not be verified - the package is not vendored with the
+    reference - so it stays an argument."""
+    spec = DeltaSpec(windows, edge)
+    if isinstance(feature, np.ndarray):
+        if seq_len is not None:
+            raise ValueError('compute_deltas: seq_len goes with a batched device tensor; a host array is one whole item')
+        return _host_deltas(feature, spec)
+    if not isinstance(feature, torch.Tensor):
+        raise TypeError('compute_deltas takes a NumPy array or a device tensor, got %s' % type(feature))
+    if feature.requires_grad:
+        raise RuntimeError('compute_deltas has no backward: detach the feature first')
+    if feature.dim() not in (2, 3):
+        raise ValueError('compute_deltas: a tensor must be (frames, features) or (batch, frames, features), got %s' % (tuple(feature.shape),))
+    single = feature.dim() == 2
+    if single and seq_len is not None:
+        raise ValueError('compute_deltas: seq_len goes with a batched (batch, frames, features) tensor')
+    batched = feature[None] if single else feature
+    if not batched.is_cuda:
+        from ._lib import MorganaHipError
+        raise MorganaHipError('compute_deltas takes NumPy arrays (host) or device tensors; got a tensor on %s (no CPU fallback for the '
+                              'device path)' % feature.device)
+    if seq_len is None:
+        seq_len = torch.full((batched.shape[0],), batched.shape[1], dtype=torch.int64, device=batched.device)
+    else:
+        seq_len = seq_len.to(device=batched.device, dtype=torch.int64).reshape(-1)
+    out, _ = ops.deltas(batched, spec.windows, seq_len=seq_len, edge=spec.edge, t=batched.shape[1])
+    return out[0] if single else out
+
+
+def _delta_specs_of(utterances, delta_specs):
+    """The {feature name: DeltaSpec} a loader applies: the argument, or what the data sources of a ``FilesDataset`` ask for."""
+    if delta_specs is None:
+        return utterances.delta_specs() if isinstance(utterances, FilesDataset) else {}
+    return dict(delta_specs)
+
+
 class _Staging(object):
     """Pinned host staging for the loader's packed features: per (device, feature) TWO buffers used in turn - the copy of the batch
     before last has certainly been issued when a buffer comes round again, and its event says when it has finished - grown
@@ -616,7 +718,26 @@ def _small_to_device(plain, device):
     return out
 
 
-def collate_to_device(batch, normalisers, device, bf16_tables=()):
+def _device_deltas(out, key, packed, offsets, t, spec, normaliser, device):
+    """``out[key + '_deltas']`` (and its ``normalised_`` twin when ``normaliser`` normalises deltas) from the packed statics of ``key``
+    that are on the device already: one mg_deltas_f32 launch, nothing more crosses PCIe."""
+    kind = p0 = p1 = item_row = None
+    if normaliser is not None and normaliser.use_deltas:
+        kind = _KINDS[normaliser.kind]['forward']
+        if isinstance(normaliser, _SpeakerDependentNormaliser):
+            (p0, p1), item_row = normaliser.tables(device, deltas=True), out[SPEAKER_INDEX_KEY]
+        else:
+            prm = normaliser.fetch_params(torch.Tensor, deltas=True)
+            if prm is None:
+                raise RuntimeError('normaliser %r has no delta parameters: call load_params, set_params or fit_normalisers first' % key)
+            p0, p1 = (prm[n].to(device) for n in _KINDS[normaliser.kind]['params'])
+    raw, norm = ops.deltas(packed, spec.windows, offsets=offsets, edge=spec.edge, t=t, p0=p0, p1=p1, kind=kind, item_row=item_row)
+    out[key + DELTAS_SUFFIX] = raw
+    if norm is not None:
+        out['normalised_' + key + DELTAS_SUFFIX] = norm
+
+
+def collate_to_device(batch, normalisers, device, bf16_tables=(), delta_specs=None):
     """``load_utterance`` + ``collate_fn`` + ``to_device`` for a list of RAW per-utterance feature dicts, with the float
     sequence features normalised and zero padded on the device (reference: data.py:119-127, 159-224, 648-663).
 
@@ -628,9 +749,21 @@ def collate_to_device(batch, normalisers, device, bf16_tables=()):
 
     ``bf16_tables``: names of normalised phone-level features (``'normalised_lab'``) whose bf16 operand table the SAME pass writes
     (``mg_pad_normalise_bf16_f32``): the batch then carries ``name + '__bf16_table'`` and a bf16-precision model's training step
-    launches no cast of the phone table (reference: the float32 cast on load, data.py:127)."""
+    launches no cast of the phone table (reference: the float32 cast on load, data.py:127).
+
+    ``delta_specs``: {feature name: ``DeltaSpec``}.  The packed statics uploaded for such a feature also give ``name_deltas`` and -
+    where its normaliser has ``use_deltas`` - ``normalised_name_deltas``, computed on the device by one more launch
+    (mg_deltas_f32, csrc/deltas.hip): no ``{name}_deltas`` file is read and nothing is uploaded twice.  A batch that already
+    carries ``name_deltas`` is refused (ValueError): it is one or the other."""
     device = torch.device(device)
     bf16_tables = tuple(bf16_tables or ())
+    delta_specs = dict(delta_specs or {})
+    for name in delta_specs:
+        if name + DELTAS_SUFFIX in batch[0]:
+            raise ValueError('%r is in the utterances and in delta_specs: deltas are read from files or computed, not both' % (
+                name + DELTAS_SUFFIX))
+        if name not in batch[0]:
+            raise KeyError('delta_specs names %r, which the utterances do not have' % name)
     out, rest = {}, []
     order = _speaker_order(normalisers)
     if order is not None:
@@ -660,6 +793,8 @@ def collate_to_device(batch, normalisers, device, bf16_tables=()):
             p0, p1 = normaliser.tables(device)
             out[key], out['normalised_' + key] = ops.pad_normalise_items(packed, offsets, int(lens.max()), p0, p1, out[SPEAKER_INDEX_KEY],
                                                                          _KINDS[normaliser.kind]['forward'])
+            if key in delta_specs:
+                _device_deltas(out, key, packed, offsets, int(lens.max()), delta_specs[key], normaliser, device)
             continue
         if isinstance(normaliser, FeatureNormaliser):
             spec, prm = _KINDS[normaliser.kind], normaliser.fetch_params(torch.Tensor)
@@ -672,6 +807,12 @@ def collate_to_device(batch, normalisers, device, bf16_tables=()):
         out[key] = raw
         if norm is not None:
             out['normalised_' + key] = norm
+        if key in delta_specs:
+            _device_deltas(out, key, packed, offsets, int(lens.max()), delta_specs[key], normaliser, device)
+    for name in delta_specs:
+        if name + DELTAS_SUFFIX not in out:
+            raise TypeError('delta_specs names %r, which is not a float32 (frames, features) array: its deltas are computed by the '
+                            'device pass of such features' % name)
     if rest:
         plain = collate_fn([{key: item[key] for key in rest} for item in batch])
         total = _host_total(plain.get(FRAME_COUNT_KEY))
@@ -697,17 +838,29 @@ class NumpyBinarySource(object):
     ``tts_data_tools.data_sources.NumpyBinarySource`` the reference's models name in ``train_data_sources``
     (models/f0_test_model.py:60-69).  ``FilesDataset`` only needs a ``use_deltas`` attribute and a call
     ``(base_name, data_dir) -> dict`` (data.py:93, :135, :142).  Arrays come back as stored: float32 ``(len, D)`` sequence
-    features, integer ``(P, 1)`` durations.  ``use_deltas`` additionally loads ``{name}_deltas``."""
+    features, integer ``(P, 1)`` durations.
 
-    def __init__(self, name, use_deltas=False, ext='npy'):
-        self.name, self.use_deltas, self.ext = name, use_deltas, ext
+    ``use_deltas`` says that the feature has a delta stream ``{name}_deltas``; ``deltas`` says where it comes from.  ``'file'`` (the
+    default, the reference's behaviour): ``{data_dir}/{name}_deltas/{base_name}.npy`` is loaded next to the statics - a file
+    ``tts_data_tools`` wrote.  ``'compute'``: only ``{name}`` is loaded and the source carries a ``DeltaSpec(windows, edge)`` in
+    ``delta_spec``; ``FilesDataset.__getitem__`` then computes the deltas on the host (``compute_deltas``) and the device loaders
+    (``DeviceBatches``, ``collate_to_device``, ``fit_normalisers``) compute them on the device from the statics they upload anyway, so
+    no ``_deltas`` file is needed and a quarter of the bytes is read, packed and copied.  ``windows`` / ``edge``: see ``compute_deltas``."""
+
+    def __init__(self, name, use_deltas=False, ext='npy', deltas='file', windows=None, edge='replicate'):
+        if deltas not in ('file', 'compute'):
+            raise ValueError("deltas must be 'file' or 'compute', got %r" % (deltas,))
+        if deltas == 'compute' and not use_deltas:
+            raise ValueError("deltas='compute' goes with use_deltas=True")
+        self.name, self.use_deltas, self.ext, self.deltas = name, use_deltas, ext, deltas
+        self.delta_spec = DeltaSpec(windows, edge) if deltas == 'compute' else None
 
     def file_path(self, base_name, data_dir, name=None):
         return os.path.join(data_dir, name or self.name, '{}.{}'.format(base_name, self.ext))
 
     def __call__(self, base_name, data_dir):
         features = {self.name: np.load(self.file_path(base_name, data_dir))}
-        if self.use_deltas:
+        if self.use_deltas and self.delta_spec is None:
             deltas = self.name + '_deltas'
             features[deltas] = np.load(self.file_path(base_name, data_dir, deltas))
         return features
@@ -753,7 +906,11 @@ class FilesDataset(object):
     normaliser, its ``normalised_`` twin computed on the host in NumPy and cast to float32 (:119-127, :144-150).
     ``dataset.raw(i)`` is the same utterance WITHOUT the twins - what ``DeviceBatches`` takes, because ``collate_to_device`` pads
     and normalises on the device in one pass.  With a speaker-dependent normaliser a data source named ``speaker_id`` must exist
-    (:88-91); it is read first and its value handed to those normalisers (:119-136)."""
+    (:88-91); it is read first and its value handed to those normalisers (:119-136).
+
+    A data source that computes its deltas (``NumpyBinarySource(..., deltas='compute')``) yields statics only: ``raw`` has no
+    ``name_deltas``, ``__getitem__`` adds it (and its normalised twin) with the host form of ``compute_deltas``, and the device
+    loaders take ``delta_specs()`` and compute it on the device."""
 
     def __init__(self, data_sources, data_dir, id_list, normalisers, data_root='.'):
         for name, normaliser in normalisers.items():
@@ -772,6 +929,10 @@ class FilesDataset(object):
     def __len__(self):
         return len(self.file_ids)
 
+    def delta_specs(self):
+        """{feature name: DeltaSpec} of the data sources that compute their deltas."""
+        return {name: source.delta_spec for name, source in self.data_sources.items() if getattr(source, 'delta_spec', None) is not None}
+
     def raw(self, index):
         base_name = self.file_ids[index]
         features = {'name': base_name}
@@ -784,6 +945,8 @@ class FilesDataset(object):
 
     def __getitem__(self, index):
         features = self.raw(index)
+        for name, spec in self.delta_specs().items():
+            features[name + DELTAS_SUFFIX] = compute_deltas(features[name], spec.windows, spec.edge)
         for name in self.data_sources:
             normaliser = self.normalisers.get(name)
             if normaliser is None or name == SPEAKER_ID_KEY:
@@ -798,12 +961,13 @@ class FilesDataset(object):
     collate_fn = staticmethod(collate_fn)
 
 
-def batch(data_generator, batch_size=32, shuffle=True, num_data_threads=0, device='cuda:0', bf16_tables=()):
+def batch(data_generator, batch_size=32, shuffle=True, num_data_threads=0, device='cuda:0', bf16_tables=(), delta_specs=None):
     """The reference's ``data.batch`` (data.py:29-57) for a ``FilesDataset``: a loader of device-resident batches.  Files are read
     on the calling thread as each batch is formed (``num_data_threads`` is accepted for signature compatibility; worker
     subprocesses are the reference's answer to a host-bound collate, which here runs on the device)."""
     rng = np.random.RandomState(torch.initial_seed() % (2 ** 32)) if shuffle else None
-    return DeviceBatches(data_generator, batch_size, data_generator.normalisers, device, shuffle=rng, bf16_tables=bf16_tables)
+    return DeviceBatches(data_generator, batch_size, data_generator.normalisers, device, shuffle=rng, bf16_tables=bf16_tables,
+                         delta_specs=delta_specs)
 
 
 class DeviceBatches(object):
@@ -811,13 +975,14 @@ class DeviceBatches(object):
     each batch padded and normalised there by ``collate_to_device``.  ``utterances`` is a ``FilesDataset`` (read lazily, batch by
     batch, through ``raw``) or a sequence of utterances that are already in host memory.
 
-    ``bf16_tables``: see ``collate_to_device``.  ``utterances`` is a sequence of RAW per-utterance feature dicts (what a ``_DataSource`` returns: float32 ``(len, D)``
+    ``bf16_tables``, ``delta_specs``: see ``collate_to_device``; ``delta_specs=None`` takes what the data sources of a ``FilesDataset``
+    ask for (``FilesDataset.delta_specs``).  ``utterances`` is a sequence of RAW per-utterance feature dicts (what a ``_DataSource`` returns: float32 ``(len, D)``
     arrays, integer ``dur``, python ints, the name); ``normalisers`` maps feature names to normalisers (``Normalisers`` or a
     dict).  Batches are contiguous slices in the given order, or a fresh permutation per epoch from ``shuffle`` = a
     ``numpy.random.RandomState`` (the reference shuffles with torch's global generator, data.py:50); the last, smaller batch
     is kept, as ``DataLoader`` does by default.  ``ExperimentBuilder.train_epoch`` takes it like any other loader."""
 
-    def __init__(self, utterances, batch_size, normalisers, device, shuffle=None, bf16_tables=()):
+    def __init__(self, utterances, batch_size, normalisers, device, shuffle=None, bf16_tables=(), delta_specs=None):
         if batch_size <= 0:
             raise ValueError('batch_size must be positive, got %r' % (batch_size,))
         self.utterances = utterances if isinstance(utterances, FilesDataset) else list(utterances)
@@ -826,6 +991,7 @@ class DeviceBatches(object):
         self.device = torch.device(device)
         self.shuffle = shuffle
         self.bf16_tables = tuple(bf16_tables or ())
+        self.delta_specs = _delta_specs_of(self.utterances, delta_specs)
 
     def use_bf16_tables(self, names):
         """The loader half of bf16 mode: every batch from now on carries the bf16 operand tables of these (normalised, phone-level)
@@ -851,7 +1017,7 @@ class DeviceBatches(object):
         for start in range(0, len(order), self.batch_size):
             fetch = self.utterances.raw if isinstance(self.utterances, FilesDataset) else self.utterances.__getitem__
             batch = [fetch(int(i)) for i in order[start:start + self.batch_size]]
-            yield collate_to_device(batch, self.normalisers, self.device, bf16_tables=self.bf16_tables)
+            yield collate_to_device(batch, self.normalisers, self.device, bf16_tables=self.bf16_tables, delta_specs=self.delta_specs)
 
 
 class ColumnStats(object):
@@ -929,7 +1095,7 @@ def _fit_rows(utterance, key):
     return value
 
 
-def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out_dir=None, data_root='.', ddof=0):
+def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out_dir=None, data_root='.', ddof=0, delta_specs=None):
     """Fit the parameters of ``normalisers`` (a ``Normalisers`` or a dict name -> normaliser of any of the four classes) to a corpus:
     the step that produces the ``{name}_mvn.json`` / ``{name}_minmax.json`` files (the reference gets them from ``tts_data_tools``).
 
@@ -938,6 +1104,10 @@ def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out
     arrays such as ``dur`` go through float32, exact below 2^24) and one ``ColumnStats`` per feature is updated on ``device``;
     speaker-dependent normalisers get one state row per speaker of their id list.  One read per feature at the end, then
     ``set_params`` on every normaliser and, with ``out_dir``, ``save_params(out_dir, data_root)``.
+
+    ``delta_specs``: {feature name: ``DeltaSpec``}, default what the data sources of a ``FilesDataset`` ask for.  ``name + '_deltas'`` of
+    such a feature is not read from the utterances: mg_deltas_f32 (csrc/deltas.hip) writes it, packed as the statics are, from the
+    statics uploaded for ``name``, and ``ColumnStats.update_packed`` reads that.  An utterance that carries it anyway is refused.
 
     Raises ValueError before anything is set or written if a listed speaker has no frame or a fitted parameter is not finite.
     ``ddof``: see ``ColumnStats.result``.  Returns {feature: ColumnStats.result()} (the ``_deltas`` features under their own names)."""
@@ -958,6 +1128,10 @@ def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out
             features.append((name + '_deltas', normaliser, True))
     from_files = isinstance(utterances, FilesDataset)
     fetch = utterances.raw if from_files else utterances.__getitem__
+    delta_specs = _delta_specs_of(utterances, delta_specs)
+    for name in delta_specs:
+        if name not in normalisers or not normalisers[name].use_deltas:
+            raise ValueError('delta_specs names %r, which has no normaliser with use_deltas' % name)
     stats = {}
     for start in range(0, len(utterances), batch_size):
         items = [fetch(i) for i in range(start, min(start + batch_size, len(utterances)))]
@@ -967,12 +1141,22 @@ def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out
                 raise KeyError("speaker-dependent normalisers need a '%s' entry in every utterance" % SPEAKER_ID_KEY)
             index = torch.from_numpy(speaker_index_of([item[SPEAKER_ID_KEY] for item in items], order))
             item_row = _small_to_device({SPEAKER_INDEX_KEY: index}, device)[SPEAKER_INDEX_KEY]
-        for key, normaliser, _ in features:
-            rows = [_fit_rows(item, key) for item in items]
+        uploaded = {}                                     # the packed statics of this batch, for the features whose deltas are computed
+        for key, normaliser, is_deltas in features:
             by_speaker = isinstance(normaliser, _SpeakerDependentNormaliser)
+            base = key[:-len(DELTAS_SUFFIX)] if is_deltas else key
+            if is_deltas and base in delta_specs:
+                if key in items[0]:
+                    raise ValueError('%r is in the utterances and in delta_specs: deltas are read from files or computed, not both' % key)
+                spec, (statics, offsets, lens) = delta_specs[base], uploaded[base]
+                packed, _ = ops.deltas(statics, spec.windows, offsets=offsets, edge=spec.edge, packed_rows=statics.shape[0])
+            else:
+                rows = [_fit_rows(item, key) for item in items]
+                packed, offsets, lens = _pack_pinned(rows, device, 'fit:' + key)
+                if key in delta_specs:
+                    uploaded[key] = (packed, offsets, lens)
             if key not in stats:
-                stats[key] = ColumnStats(rows[0].shape[1], groups=len(order) if by_speaker else 1, device=device)
-            packed, offsets, lens = _pack_pinned(rows, device, 'fit:' + key)
+                stats[key] = ColumnStats(packed.shape[1], groups=len(order) if by_speaker else 1, device=device)
             stats[key].update_packed(packed, offsets, item_row if by_speaker else None, max_rows=int(lens.max()))
     if not stats:
         raise ValueError('fit_normalisers: no utterances')

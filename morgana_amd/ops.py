@@ -2502,7 +2502,7 @@ def metric_accumulate(kind, accum, target, pred=None, voiced=None, seq_len=None,
                                             ws.numel(), _stream()), 'mg_metric_accumulate_f32')
 
 
-MLPG_MAX_WINDOWS, MLPG_MAX_COEFF = 4, 5
+MLPG_MAX_WINDOWS, MLPG_MAX_COEFF = _lib.MG_MLPG_MAX_WINDOWS, _lib.MG_MLPG_MAX_COEFF
 MLPG_VAR_ITEM = _lib.MG_MLPG_VAR_ITEM      # variances (B, W*D), one row per utterance
 
 
@@ -2528,18 +2528,7 @@ def mlpg(means, variances, windows, padding_size=0, seq_len=None, out_dtype=torc
         per_frame = MLPG_VAR_ITEM
     else:
         raise ValueError('variances %s fit neither (%d,) nor %s nor (%d, %d)' % (tuple(variances.shape), width, tuple(means.shape), b, width))
-    win_l = (ctypes.c_int * n_win)()
-    win_u = (ctypes.c_int * n_win)()
-    win_c = (ctypes.c_double * (n_win * MLPG_MAX_COEFF))()
-    for w, (l, u, coeff) in enumerate(windows):
-        l, u = int(l), int(u)
-        if l < 0 or u < 0 or len(coeff) != l + u + 1:                 # the asserts of synthesis.py:30-31
-            raise ValueError('window %d: %d coefficients for extents l=%d, u=%d' % (w, len(coeff), l, u))
-        if l + u + 1 > MLPG_MAX_COEFF:
-            raise ValueError('window %d is wider than %d coefficients' % (w, MLPG_MAX_COEFF))
-        win_l[w], win_u[w] = l, u
-        for k, c in enumerate(coeff):
-            win_c[w * MLPG_MAX_COEFF + k] = float(c)
+    win_l, win_u, win_c = _window_arrays(windows)
     if seq_len is not None:
         seq_len = _require(seq_len, torch.int64, 'seq_len')
     if out_dtype not in (torch.float32, torch.float64):
@@ -2550,6 +2539,96 @@ def mlpg(means, variances, windows, padding_size=0, seq_len=None, out_dtype=torc
     _lib.check(lib.mg_mlpg_f32(_p(means), _p(variances), per_frame, _p(seq_len), b, t, d, n_win, win_l, win_u, win_c, int(padding_size),
                                _p(out), int(out_dtype == torch.float64), _p(ws), ws.numel(), _stream()), 'mg_mlpg_f32')
     return out
+
+
+DELTAS_EDGE_REPLICATE, DELTAS_EDGE_ZERO = _lib.MG_DELTAS_EDGE_REPLICATE, _lib.MG_DELTAS_EDGE_ZERO
+DELTAS_EDGES = {'replicate': DELTAS_EDGE_REPLICATE, 'zero': DELTAS_EDGE_ZERO}
+
+
+def _window_arrays(windows):
+    """[(l, u, coeffs)] -> the parallel host arrays of mg_mlpg_f32 / mg_deltas_f32 (checked as synthesis.py:30-31 asserts)."""
+    n_win = len(windows)
+    if n_win == 0 or n_win > _lib.MG_MLPG_MAX_WINDOWS:
+        raise ValueError('%d windows (1..%d supported)' % (n_win, _lib.MG_MLPG_MAX_WINDOWS))
+    win_l = (ctypes.c_int * n_win)()
+    win_u = (ctypes.c_int * n_win)()
+    win_c = (ctypes.c_double * (n_win * _lib.MG_MLPG_MAX_COEFF))()
+    for w, (l, u, coeff) in enumerate(windows):
+        l, u = int(l), int(u)
+        if l < 0 or u < 0 or len(coeff) != l + u + 1:
+            raise ValueError('window %d: %d coefficients for extents l=%d, u=%d' % (w, len(coeff), l, u))
+        if l + u + 1 > _lib.MG_MLPG_MAX_COEFF:
+            raise ValueError('window %d is wider than %d coefficients' % (w, _lib.MG_MLPG_MAX_COEFF))
+        win_l[w], win_u[w] = l, u
+        for k, c in enumerate(coeff):
+            win_c[w * _lib.MG_MLPG_MAX_COEFF + k] = float(c)
+    return win_l, win_u, win_c
+
+
+def deltas(x, windows, *, offsets=None, seq_len=None, edge='replicate', t=None, packed_rows=None, p0=None, p1=None, kind=None,
+           item_row=None, want_raw=True):
+    """Delta features of a float32 feature (csrc/deltas.hip, mg_deltas_f32): column w*D + d of the result at frame t is
+    sum_k coeff[w][k] x[t - l_w + k, d], float64 accumulation rounded once - the forward of the operator ``mlpg`` inverts.
+
+    Input, exactly one of: ``offsets`` (B + 1,) int64 with x the packed rows (N, D), or ``seq_len`` (B,) int64 with x padded (B, T, D)
+    (frames past the length are never read).  Output, exactly one of: ``t`` - padded (B, t, W*D), zeros past each length, an item
+    longer than t cut to t frames - or ``packed_rows`` - packed (packed_rows, W*D): the rows of a packed input, or the valid frames of
+    a padded input back to back.  ``edge``: 'replicate' (a tap outside the item reads its first / last frame) or 'zero' (it
+    contributes nothing: MLPG's window matrix).  ``kind`` (NORM_MVN / NORM_MINMAX) with p0 / p1 (W*D,) adds the normalised twin; with
+    ``item_row`` (B,) int32 they are tables (S, W*D) and item b takes row item_row[b] (NaN for an index outside [0, S)).
+    Returns (raw or None, normalised or None)."""
+    lib = _lib.load()
+    x = _require(x, torch.float32, 'feature')
+    if (offsets is None) == (seq_len is None):
+        raise ValueError('deltas: give exactly one of offsets (packed rows) and seq_len (padded batch)')
+    if (t is None) == (packed_rows is None):
+        raise ValueError('deltas: give exactly one of t (padded output) and packed_rows (packed output)')
+    if edge not in DELTAS_EDGES:
+        raise ValueError("deltas: edge must be 'replicate' or 'zero', got %r" % (edge,))
+    win_l, win_u, win_c = _window_arrays(windows)
+    n_win = len(windows)
+    if offsets is not None:
+        offsets = _require(offsets, torch.int64, 'offsets')
+        if x.dim() != 2 or offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError('deltas: packed rows %s must be (rows, features) and offsets %s (items + 1,)' % (
+                tuple(x.shape), tuple(offsets.shape)))
+        b, t_in, d = offsets.numel() - 1, 0, x.shape[1]
+    else:
+        seq_len = _require(seq_len, torch.int64, 'seq_len')
+        if x.dim() != 3 or seq_len.dim() != 1 or seq_len.numel() != x.shape[0]:
+            raise ValueError('deltas: padded batch %s must be (items, frames, features) and seq_len %s (items,)' % (
+                tuple(x.shape), tuple(seq_len.shape)))
+        b, t_in, d = x.shape
+    width = n_win * d
+    if d == 0:
+        raise ValueError('deltas: the feature has no columns')
+    if kind is None and (want_raw is False or p0 is not None or p1 is not None or item_row is not None):
+        raise ValueError('deltas: normaliser parameters, item_row and want_raw=False go with a kind (NORM_MVN or NORM_MINMAX)')
+    s = 0
+    if kind is not None:
+        if kind not in (NORM_MVN, NORM_MINMAX):
+            raise ValueError('deltas: kind %r is not NORM_MVN or NORM_MINMAX' % (kind,))
+        if item_row is not None:
+            p0, p1, item_row = _item_tables(p0, p1, item_row, b, width, 'deltas')
+            s = p0.shape[0]
+        else:
+            p0 = _require(p0, torch.float32, 'param0')
+            p1 = _require(p1, torch.float32, 'param1')
+            if p0.numel() != width or p1.numel() != width:
+                raise ValueError('normaliser parameters have %d / %d entries, %d windows of %d columns need %d' % (
+                    p0.numel(), p1.numel(), n_win, d, width))
+    if t is not None:
+        form, rows, shape = _lib.MG_DELTAS_OUT_PADDED, int(t), (b, int(t), width)
+    else:
+        form, rows, shape = _lib.MG_DELTAS_OUT_PACKED, int(packed_rows), (int(packed_rows), width)
+    if rows < 0:
+        raise ValueError('deltas: a negative output size %d' % rows)
+    raw = torch.empty(shape, dtype=torch.float32, device=x.device) if want_raw else None
+    norm = torch.empty(shape, dtype=torch.float32, device=x.device) if kind is not None else None
+    _lib.check(lib.mg_deltas_f32(_p(x), d, b, _p(offsets), _p(seq_len), int(t_in), n_win, win_l, win_u, win_c, DELTAS_EDGES[edge], _p(p0),
+                                 _p(p1), _p(item_row), s, -1 if kind is None else kind, form, rows, _p(raw), _p(norm), _stream()),
+               'mg_deltas_f32')
+    return raw, norm
 
 
 # ---------------------------------------------------------------------------------------------- phone-rate first layer

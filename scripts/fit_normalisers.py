@@ -2,10 +2,12 @@
 """Fit normaliser parameter files to a corpus of ``.npy`` features (``data.fit_normalisers``: per-column statistics on the device,
 csrc/colstats.hip) - the files ``data.Normalisers`` and ``load_params`` read, which the reference takes from ``tts_data_tools``.
 
-    python scripts/fit_normalisers.py DATA_ROOT DATA_DIR ID_LIST NAME:KIND[:deltas] [NAME:KIND[:deltas] ...]
+    python scripts/fit_normalisers.py DATA_ROOT DATA_DIR ID_LIST NAME:KIND[:deltas[=compute]] [NAME:KIND[:deltas[=compute]] ...]
                                       [--speaker-id-list FILE] [--out-dir DIR] [--batch-size 64] [--ddof 0] [--device cuda:0]
 
-``KIND`` is ``mvn`` or ``minmax``; ``:deltas`` also fits ``{NAME}_deltas``.  Features are read from ``DATA_ROOT/DATA_DIR/NAME/*.npy``
+``KIND`` is ``mvn`` or ``minmax``; ``:deltas`` also fits ``{NAME}_deltas`` from the files of ``DATA_ROOT/DATA_DIR/NAME_deltas``;
+``:deltas=compute`` fits it without such files: the deltas are computed on the device from the statics (csrc/deltas.hip; default
+windows, replicated edges - ``data.compute_deltas``).  Features are read from ``DATA_ROOT/DATA_DIR/NAME/*.npy``
 for the ids of ``DATA_ROOT/ID_LIST``.  With ``--speaker-id-list`` (relative to DATA_ROOT) every normaliser is speaker dependent: the
 speaker of an utterance is read from ``DATA_ROOT/DATA_DIR/speaker_id/*.txt`` and the files go to ``{speaker}/``.  The files are
 written under ``DATA_ROOT/OUT_DIR`` (default: DATA_DIR, where the reference's ``--normalisation_dir train`` looks for them).
@@ -26,11 +28,11 @@ CLASSES = {('mvn', False): data.MeanVarianceNormaliser, ('minmax', False): data.
 def parse_spec(spec, speaker_id_list):
     name, _, rest = spec.partition(':')
     kind, _, deltas = rest.partition(':')
-    if not name or kind not in ('mvn', 'minmax') or deltas not in ('', 'deltas'):
-        raise SystemExit('cannot read %r: expected NAME:mvn, NAME:minmax, NAME:mvn:deltas or NAME:minmax:deltas' % spec)
+    if not name or kind not in ('mvn', 'minmax') or deltas not in ('', 'deltas', 'deltas=compute'):
+        raise SystemExit('cannot read %r: expected NAME:KIND, NAME:KIND:deltas or NAME:KIND:deltas=compute, KIND mvn or minmax' % spec)
     cls = CLASSES[kind, speaker_id_list is not None]
     extra = (speaker_id_list,) if speaker_id_list is not None else ()
-    return name, cls(name, *extra, use_deltas=bool(deltas))
+    return name, cls(name, *extra, use_deltas=bool(deltas)), 'compute' if deltas == 'deltas=compute' else 'file'
 
 
 def main():
@@ -38,15 +40,16 @@ def main():
     parser.add_argument('data_root')
     parser.add_argument('data_dir')
     parser.add_argument('id_list')
-    parser.add_argument('features', nargs='+', metavar='NAME:KIND[:deltas]')
+    parser.add_argument('features', nargs='+', metavar='NAME:KIND[:deltas[=compute]]')
     parser.add_argument('--speaker-id-list', default=None)
     parser.add_argument('--out-dir', default=None)
     parser.add_argument('--batch-size', type=int, default=64)
     parser.add_argument('--ddof', type=int, default=0)
     parser.add_argument('--device', default='cuda:0')
     args = parser.parse_args()
-    normalisers = dict(parse_spec(spec, args.speaker_id_list) for spec in args.features)
-    sources = {name: data.NumpyBinarySource(name, use_deltas=normaliser.use_deltas) for name, normaliser in normalisers.items()}
+    specs = [parse_spec(spec, args.speaker_id_list) for spec in args.features]
+    normalisers = {name: normaliser for name, normaliser, _ in specs}
+    sources = {name: data.NumpyBinarySource(name, use_deltas=normaliser.use_deltas, deltas=deltas) for name, normaliser, deltas in specs}
     if args.speaker_id_list is not None:
         sources[data.SPEAKER_ID_KEY] = data.StringSource(data.SPEAKER_ID_KEY)
     dataset = data.FilesDataset(sources, args.data_dir, args.id_list, normalisers, data_root=args.data_root)
