@@ -1204,6 +1204,31 @@ int mg_deltas_f32(const float* x, int D, int B, const int64_t* offsets, const in
                   const int* win_u, const double* win_coeff, int edge, const float* p0, const float* p1, const int32_t* item_row, int S,
                   int kind, int out_form, int64_t out_rows, float* raw_out, float* norm_out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * K24 (csrc/seqmean.hip)  masked sequence mean of a feature loss: the reduction of losses.sequence_loss
+ *                         reference: morgana/losses.py:29-46 (mask from morgana/utils.py:115-144)
+ * loss[0] = (1 / (B D)) sum_b ( sum_{t < T, d} x[b,t,d] m[b,t] ) / n_b,  m[b,t] = (t < n_b),  n_b = min(max(seq_len[b], 0), T), or
+ * T when seq_len is NULL (the rules of mg_masked_mse_f32).  x is float32, element (b, t, d) at x[b stride_b + t stride_t +
+ * d stride_d] (element strides, not negative; 0 = an expanded operand): a column slice, a misaligned base and a stride-0 operand are
+ * read in place.  Every frame is read and multiplied by its mask value: a NaN or Inf in a pad frame makes the loss NaN, and n_b == 0
+ * gives NaN.  Accumulated in float64: one partial per (utterance, chunk of the (t, d) index space) in the workspace, summed in a
+ * fixed order by a one-workgroup finish, divided by n_b in float64, rounded to float32 once.  The order depends on the logical index
+ * alone: the same bits on every call, for every stride pattern and alignment of the same values.  No atomics, no host read.  Rows with
+ * stride_d == 1 and stride_t == D take 16-byte loads at aligned addresses behind a scalar head and tail; anything else takes one
+ * element per load.  workspace: mg_seq_mean_workspace_bytes(B, T, D) bytes (0 for a shape that is not positive), 8-byte aligned;
+ * MG_EWORKSPACE when it is NULL or too small.
+ *
+ * Backward, one launch: grad [B, T, D] float32, contiguous; grad[b,t,d] = (float)((double)grad_loss[0] / ((double)n_b B D)) for
+ * t < n_b, 0 for the pad frames of an utterance with n_b > 0, NaN on every frame of an utterance with n_b == 0 (the reference's
+ * 0 * inf).  grad_loss is the upstream gradient, one float32 ON THE DEVICE.  16-byte stores behind a scalar head and tail.
+ * mg_seq_mean_chunk(): elements of one utterance per workgroup, what a test needs to cross a chunk.
+ * ---------------------------------------------------------------------------------------------------------------- */
+int mg_seq_mean_chunk(void);
+size_t mg_seq_mean_workspace_bytes(int B, int T, int D);
+int mg_seq_mean_f32(const float* x, int64_t stride_b, int64_t stride_t, int64_t stride_d, const int64_t* seq_len, int B, int T, int D,
+                    float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int mg_seq_mean_bwd_f32(const float* grad_loss, const int64_t* seq_len, int B, int T, int D, float* grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

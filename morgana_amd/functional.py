@@ -1988,6 +1988,27 @@ class MaskedMSEFn(torch.autograd.Function):
         return grad * grad_loss, None, None, None
 
 
+class SeqMeanFn(torch.autograd.Function):
+    """The reduction of ``losses.sequence_loss`` (losses.py:29-46): feature loss (B, T, D) float32 -> masked per-utterance mean over
+    the valid frames, then the mean over (batch, feature), a 0-d device tensor (ops.masked_seq_mean).  The gradient does not depend on
+    the feature loss, so only ``seq_len`` and the shape are kept; the backward writes it in one launch from the upstream gradient on
+    the device (ops.masked_seq_mean_bwd).  Double backward is NOT supported: the backward is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, feature_loss, seq_len):
+        ctx.save_for_backward(seq_len)
+        ctx.shape = tuple(feature_loss.shape)
+        return ops.masked_seq_mean(feature_loss, seq_len)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        (seq_len,) = ctx.saved_tensors
+        if grad_loss.dtype != torch.float32:
+            grad_loss = grad_loss.float()
+        return ops.masked_seq_mean_bwd(grad_loss, seq_len, ctx.shape), None
+
+
 class StreamLossFn(torch.autograd.Function):
     """Multi-stream loss of models/RNN_SPSS.py:120-139 in one pass: returns (loss, sigmoid of the BCE stream or None)."""
 

@@ -1,8 +1,49 @@
 """Mirror of ``morgana.losses`` for the hot path.  Reference: morgana/losses.py:9-51 (``sequence_loss`` / ``mse``), :54-56 (``bce``),
 :59-61 (``ce``) and :64-67 (``KLD_standard_normal``)."""
+import functools
+
 import torch
 
 from . import functional as F_hip
+
+
+def sequence_loss(loss_fn):
+    r"""Sequence loss wrapper of the reference (losses.py:9-46): turns ``loss_fn(predictions, targets)``, which returns the loss of
+    every frame and feature, into ``wrapped(predictions, targets, seq_len=None)``: the per-utterance mean over the valid frames, then
+    the mean over (batch, feature).  The extension point for a model's own loss::
+
+        @losses.sequence_loss
+        def l1(predictions, targets):
+            return F.l1_loss(predictions, targets, reduction='none')
+
+    ``loss_fn`` runs as the torch ops it is written in, and autograd flows through them.  Its result - a (B, T, D') float32 device
+    tensor; D' need not be the predictions' width - is reduced by one HIP pass in float64 and a one-workgroup finish, read in place
+    whatever its strides, and the backward writes d loss / d feature loss in one launch (csrc/seqmean.hip through
+    ``functional.SeqMeanFn``; the reference runs a host-built mask, mul, two sums, div and mean, then their autograd mirrors).  Every
+    frame is read and multiplied by its mask value, so a NaN in a pad frame gives NaN, and ``seq_len[b] == 0`` gives NaN, both as in
+    the reference.  ``seq_len``: (B,) integers or None (every frame valid).  No double backward through the reduction."""
+
+    @functools.wraps(loss_fn)
+    def wrapped_loss(predictions, targets, seq_len=None):
+        feature_loss = loss_fn(predictions, targets)
+        name = getattr(loss_fn, '__name__', 'loss_fn')
+        if not isinstance(feature_loss, torch.Tensor):
+            raise TypeError('sequence_loss: %s must return a torch.Tensor, got %s' % (name, type(feature_loss)))
+        if feature_loss.dim() != 3:
+            raise ValueError('sequence_loss: %s must return a (B, T, D) feature loss, got shape %s' % (name, tuple(feature_loss.shape)))
+        if feature_loss.dtype != torch.float32:
+            raise TypeError('sequence_loss: %s must return a torch.float32 feature loss, got %s' % (name, feature_loss.dtype))
+        if seq_len is not None:
+            if not isinstance(seq_len, torch.Tensor) or seq_len.is_floating_point() or seq_len.is_complex() or seq_len.dtype == torch.bool:
+                raise TypeError('sequence_loss: seq_len must be a tensor of integers, got %s'
+                                % (seq_len.dtype if isinstance(seq_len, torch.Tensor) else type(seq_len)))
+            if tuple(seq_len.shape) != (feature_loss.shape[0],):
+                raise ValueError('sequence_loss: seq_len must be (B,) = (%d,), got %s' % (feature_loss.shape[0], tuple(seq_len.shape)))
+            if seq_len.dtype != torch.int64:
+                seq_len = seq_len.long()
+        return F_hip.SeqMeanFn.apply(feature_loss, seq_len)
+
+    return wrapped_loss
 
 
 def mse(predictions, targets, seq_len=None):

@@ -167,7 +167,9 @@ class Stream(object):
     ``normalised_<name>_deltas`` (a delta stream: static + delta + delta-delta, denormalised and turned into a trajectory by MLPG)
     or 'sigmoid_bce' against ``<name>`` (a probability stream) or 'ce' against ``<name>`` as integer class indices, (B, T) or
     (B, T, 1) (a categorical stream of ``dim`` classes, losses.ce: the logits go out as ``<name>_logits``, the predicted class as
-    ``<name>``, (B, T) int64).  ``metric`` = (registered name, factory, kind): kind 'trajectory'
+    ``<name>``, (B, T) int64) or any callable ``(predictions, targets, seq_len)`` - typically a ``losses.sequence_loss``-wrapped
+    function - which makes a delta stream exactly as 'mse' does (target, output key, normaliser, trajectory, metrics) and is called
+    where ``losses.mse`` would be.  ``metric`` = (registered name, factory, kind): kind 'trajectory'
     feeds (target, trajectory, n_frames), 'voiced_trajectory' adds a voicing mask (the predicted probability stream ``voicing`` >
     0.5, or the feature of that name when the model predicts none), 'accuracy' feeds the hit rate of a probability or categorical
     stream."""
@@ -177,7 +179,7 @@ class Stream(object):
 
     @property
     def is_delta(self):
-        return self.loss == 'mse'
+        return self.loss == 'mse' or callable(self.loss)
 
     @property
     def is_categorical(self):
@@ -207,7 +209,8 @@ class StreamModel(BaseSPSS):
     ``predict`` / ``loss`` / ``forward`` as the shipped models define them: input = upsampled labels concatenated with the frame
     counters, per-stream outputs under the reference's keys, loss = mean of the streams' masked losses, trajectories and metrics on
     the device whenever the normalisers carry delta parameters (i.e. under ``ExperimentBuilder``; ``generate=False`` turns both off).
-    ``fused_loss``: the split, the sigmoid and all masked losses as one pass over the prediction (``losses.multi_stream``).
+    ``fused_loss``: the split, the sigmoid and all masked losses as one pass over the prediction (``losses.multi_stream``); refused
+    for a table with a callable loss, which that kernel cannot run.
     ``speaker_id_list`` (a file of speaker names): the delta streams are normalised PER SPEAKER
     (``data.SpeakerDependentMeanVarianceNormaliser``); trajectories are then denormalised with ``features['speaker_index']`` and MLPG
     runs under each utterance's own delta variances (``ops.mlpg``'s per-item mode).  None changes nothing."""
@@ -216,6 +219,10 @@ class StreamModel(BaseSPSS):
         super(StreamModel, self).__init__()
         self.layers = layers
         self.streams = tuple(streams)
+        custom = [st.name for st in self.streams if callable(st.loss)]
+        if fused_loss and custom:
+            raise ValueError('StreamModel: fused_loss=True cannot score the stream(s) %s with a callable loss: the one-pass multi-stream '
+                             'kernel runs no user code (use fused_loss=False)' % ', '.join(custom))
         self.speaker_id_list = speaker_id_list
         self.fused_upsample, self.fused_loss, self.generate = fused_upsample, fused_loss, generate
         registered = {st.metric[0]: st.metric[1]() for st in self.streams if st.metric is not None}
@@ -338,7 +345,8 @@ class StreamModel(BaseSPSS):
         total = 0.
         for st in self.streams:                           # delta streams first, then the probability streams: the reference's order
             if st.is_delta:
-                total = total + losses.mse(output_features[st.output_key], self._target(features, st), n_frames)
+                stream_loss = st.loss if callable(st.loss) else losses.mse
+                total = total + stream_loss(output_features[st.output_key], self._target(features, st), n_frames)
         for st in self.streams:
             if not st.is_delta and not st.is_categorical:
                 total = total + losses.bce(output_features[st.output_key].type(torch.float), self._target(features, st).type(torch.float),

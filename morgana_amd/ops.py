@@ -354,6 +354,61 @@ def masked_mse(pred, target, seq_len, want_grad, grad_scale=1.0, kind='mse'):
     return loss, grad
 
 
+def _require_in_place(t, dtype, name):
+    """``_require`` without the contiguous copy: for the entry points that take strides."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('%s must be a torch.Tensor, got %s' % (name, type(t)))
+    if not t.is_cuda:
+        raise _lib.MorganaHipError('%s is on %s: the morgana_amd ops run only on an MI355X device (no CPU fallback)'
+                                   % (name, t.device))
+    if t.dtype != dtype:
+        raise TypeError('%s must be %s, got %s' % (name, dtype, t.dtype))
+    return t
+
+
+def _seq_mean_lengths(seq_len, b):
+    if seq_len is None:
+        return None
+    seq_len = _require(seq_len, torch.int64, 'seq_len')
+    if tuple(seq_len.shape) != (b,):
+        raise ValueError('seq_len must be (B,) = (%d,), got %s' % (b, tuple(seq_len.shape)))
+    return seq_len
+
+
+def masked_seq_mean(x, seq_len):
+    """Masked sequence mean of a feature loss (mg_seq_mean_f32, csrc/seqmean.hip): x (B, T, D) float32, read in place through its
+    strides (a column slice, a misaligned base, an expanded operand); seq_len (B,) int64 or None.  Returns the 0-d float32 loss
+    ``mean_{b,d}( sum_{t} x[b,t,d] [t < n_b] / n_b )`` on the device, accumulated in float64 in a fixed order."""
+    lib = _lib.load()
+    x = _require_in_place(x, torch.float32, 'feature loss')
+    if x.dim() != 3 or 0 in x.shape:
+        raise ValueError('feature loss must be a non-empty (B, T, D) tensor, got %s' % (tuple(x.shape),))
+    b, t, d = x.shape
+    seq_len = _seq_mean_lengths(seq_len, b)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    ws = workspace(lib.mg_seq_mean_workspace_bytes(b, t, d), x.device)
+    _lib.check(lib.mg_seq_mean_f32(_p(x), x.stride(0), x.stride(1), x.stride(2), _p(seq_len), b, t, d, _p(loss), _p(ws), ws.numel(),
+                                   _stream()), 'mg_seq_mean_f32')
+    return loss
+
+
+def masked_seq_mean_bwd(grad_loss, seq_len, shape):
+    """d masked_seq_mean / d x for a feature loss of ``shape`` (B, T, D) (mg_seq_mean_bwd_f32): a dense float32 tensor, grad_loss / (n_b
+    B D) on valid frames, 0 on pad frames, NaN on an utterance without a valid frame.  ``grad_loss``: the upstream gradient, a
+    one-element float32 device tensor that the kernel reads (no host read)."""
+    lib = _lib.load()
+    grad_loss = _require(grad_loss, torch.float32, 'grad_loss')
+    if grad_loss.numel() != 1:
+        raise ValueError('grad_loss must hold one element, got %s' % (tuple(grad_loss.shape),))
+    if len(shape) != 3 or min(shape) <= 0:
+        raise ValueError('shape must be a non-empty (B, T, D), got %s' % (tuple(shape),))
+    b, t, d = (int(v) for v in shape)
+    seq_len = _seq_mean_lengths(seq_len, b)
+    grad = torch.empty((b, t, d), dtype=torch.float32, device=grad_loss.device)
+    _lib.check(lib.mg_seq_mean_bwd_f32(_p(grad_loss), _p(seq_len), b, t, d, _p(grad), _stream()), 'mg_seq_mean_bwd_f32')
+    return grad
+
+
 def stream_loss(pred, targets, kinds, seq_len, want_grad, want_prob=False, grad_scale=1.0):
     """Multi-stream loss (mg_stream_loss_f32): pred (B, T, sum of widths), targets[k] (B, T, width_k) scored side by side
     in column order, kinds[k] in {'mse', 'sigmoid_bce'}.  Returns (loss 0-d, grad or None, prob or None)."""
