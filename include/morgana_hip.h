@@ -278,9 +278,18 @@ size_t mg_mlpg_workspace_bytes(int B, int T, int D, int padding, int n_windows, 
 int mg_mlpg_f32(const float* means, const float* variances, int var_per_frame, const int64_t* seq_len, int B, int T, int D,
                 int n_windows, const int* win_l, const int* win_u, const double* win_coeff, int padding, void* out, int out_f64,
                 void* workspace, size_t workspace_bytes, void* stream);
+/* The gradient of mg_mlpg_f32's trajectory with respect to `means` (trajectory training; the reference's host MLPG has none).
+ * grad_out f32 [B,T,D] (frames past seq_len are never read); variances, var_per_frame, seq_len, windows and padding as in the
+ * forward, with the same checks.  Per (b, d): P lambda = g~ (grad_out on the output rows, zero on the 2 x padding rows; the forward's
+ * band and LDL^T, lambda float64 for all rows), then grad_means[b, f, w*D + d] = sum over the padded rows s that read frame f of
+ * (1/var_w) (W_w lambda)[s], float64 in increasing s, rounded once: f32 [B,T,W*D], or f64 if out_f64; zero past seq_len.  The
+ * variances get no gradient.  No atomics, deterministic.  workspace: mg_mlpg_workspace_bytes(...) bytes, as the forward. */
+int mg_mlpg_grad_f32(const float* grad_out, const float* variances, int var_per_frame, const int64_t* seq_len, int B, int T, int D,
+                     int n_windows, const int* win_l, const int* win_u, const double* win_coeff, int padding, void* grad_means,
+                     int out_f64, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
- * K5  mvn / minmax normalisers            reference: morgana/data.py:533-538, 579-590
+ * K5  mvn / minmax normalisers           reference: morgana/data.py:533-538, 579-590
  * ---------------------------------------------------------------------------------------------------------------- */
 #define MG_NORM_MVN 0         /* (x - mean) / (std_dev + 1e-8)       p0 = mean, p1 = std_dev */
 #define MG_DENORM_MVN 1       /* x * std_dev + mean                                             */

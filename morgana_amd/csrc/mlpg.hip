@@ -23,6 +23,20 @@
 // one row per utterance; only the address the band kernel reads them from differs, the systems and the solve are the same.
 // Summation order differs from bandmat's (which adds the windows band by band), so results agree to float64 rounding, not bit
 // for bit: tests hold the float32 trajectories to 1e-6 relative against the float64 CPU restatement.
+//
+// The gradient with respect to the means (mg_mlpg_grad_f32; trajectory / minimum-generation-error training).  x is linear in mu:
+// x = P^-1 sum_w W_w^T (tau_w o mu_w), so for an upstream gradient g on the output rows [padding, N - padding)
+//     P lambda = g~ (g on the output rows, zero on the padding rows),    v_w = tau_w o (W_w lambda),
+//     dL/dmu[b, f, w D + d] = sum over the padded rows s that read frame f of v_w[s]
+// (one row for an inner frame, padding + 1 rows for the first and the last frame, all N rows when len = 1).  P is symmetric: the band,
+// the factorisation and both sweeps are the forward's, instantiated with GRAD / KEEP:
+//   mlpg_band_kernel<HB, true>          the same band rows; the right-hand-side plane holds g~ (frames >= len are never read)
+//   mlpg_solve_kernel<HB, double, true> the same sweeps; x_i = lambda_i goes over z_i in plane HB + 1 for ALL N rows (by then z_i is
+//                                       in registers, and the prefetch reads lower rows only) instead of to the output
+//   mlpg_scatter_kernel                 one thread per (inner frame, system): tau (W_w lambda) at the frame's one padded row, float64,
+//                                       one rounding at the store.  No atomics: a frame has one owner.
+//   mlpg_scatter_edge_kernel            one thread per (first / last frame, system): the same over its padding + 1 rows in increasing s
+// The variances get no gradient (normaliser constants at every call site).
 #include "common.h"
 
 #define MLPG_MAX_WINDOWS 4
@@ -34,7 +48,8 @@ struct MlpgWindows {
     double c[MLPG_MAX_WINDOWS][MLPG_MAX_COEFF];
 };
 
-template <int HB>
+// GRAD: `means` is the upstream gradient [B, T, D] and the right-hand side is g~ (see the header comment); the band is the same
+template <int HB, bool GRAD = false>
 __global__ __launch_bounds__(256) void mlpg_band_kernel(const float* __restrict__ means, const float* __restrict__ variances,
                                                         int var_per_frame, const int64_t* __restrict__ seq_len, int B, int T, int D,
                                                         MlpgWindows win, int padding, double* __restrict__ planes) {
@@ -61,9 +76,12 @@ __global__ __launch_bounds__(256) void mlpg_band_kernel(const float* __restrict_
             const size_t at = ((size_t)b * T + f) * width + (size_t)w * D + d;
             const float var = var_per_frame == MG_MLPG_VAR_ITEM ? variances[(size_t)b * width + w * D + d]
                               : var_per_frame ? variances[at] : variances[w * D + d];
-            const float mu_tau = means[at] / var, tau = 1.0f / var;           // float32, as numpy does on the model's arrays
+            const float tau = 1.0f / var;                                     // float32, as numpy does on the model's arrays
             const double ck = win.c[w][l + k];
-            rhs += ck * (double)mu_tau;
+            if constexpr (!GRAD) {
+                const float mu_tau = means[at] / var;
+                rhs += ck * (double)mu_tau;
+            }
 #pragma unroll
             for (int m = 0; m <= HB; ++m) {
                 const int k2 = l + k - m;
@@ -71,6 +89,8 @@ __global__ __launch_bounds__(256) void mlpg_band_kernel(const float* __restrict_
             }
         }
     }
+    if constexpr (GRAD)
+        if (t >= padding && t < n - padding) rhs = (double)means[((size_t)b * T + (t - padding)) * D + d];       // frame t - padding < len
 #pragma unroll
     for (int m = 0; m <= HB; ++m) planes[((size_t)m * n_max + t) * S + sys] = band[m];
     planes[((size_t)(HB + 1) * n_max + t) * S + sys] = rhs;
@@ -88,7 +108,8 @@ __device__ __forceinline__ double mlpg_rcp(double d) {
     return __builtin_fma(y, e, y);
 }
 
-template <int HB, typename OutT>
+// KEEP: the solution of all n rows stays in the workspace, float64, over z in plane HB + 1; `out` is not used
+template <int HB, typename OutT, bool KEEP = false>
 __global__ __launch_bounds__(64) void mlpg_solve_kernel(const int64_t* __restrict__ seq_len, int B, int T, int D, int padding,
                                                        double* __restrict__ planes, OutT* __restrict__ out) {
     const int S = B * D, n_max = T + 2 * padding;
@@ -175,7 +196,10 @@ __global__ __launch_bounds__(64) void mlpg_solve_kernel(const int64_t* __restric
         double x = a[HB];
 #pragma unroll
         for (int k = 0; k < HB; ++k) x -= a[k] * xn[k];
-        if (i >= padding && i < n - padding) o[(size_t)(i - padding) * D] = (OutT)x;
+        if constexpr (KEEP)
+            p[(HB + 1) * plane + (size_t)i * S] = x;
+        else if (i >= padding && i < n - padding)
+            o[(size_t)(i - padding) * D] = (OutT)x;
 #pragma unroll
         for (int k = HB - 1; k > 0; --k) xn[k] = xn[k - 1];
         xn[0] = x;
@@ -203,6 +227,107 @@ __global__ __launch_bounds__(64) void mlpg_solve_kernel(const int64_t* __restric
 #pragma unroll
     for (int r = 0; r < MLPG_ROWS - 1; ++r)
         if (i0 - r >= 0) bwd_row(bc[r], i0 - r);
+}
+
+#define MLPG_SPAN (MLPG_MAX_COEFF - 1)      // a window reaches at most this many rows to either side of its own
+
+// grad_means[b, f, w D + d] of the INNER frames 0 < f < len - 1, one (frame, system) per thread, gid / S = f as in the band kernel: one
+// padded row each, its taps read directly; lambda loads coalesce over the systems and the W stores of neighbouring threads are
+// contiguous over d.  Rows past len stay as the memset left them; the first and the last frame are the edge kernel's.
+template <typename OutT>
+__global__ __launch_bounds__(256) void mlpg_scatter_kernel(const float* __restrict__ variances, int var_per_frame,
+                                                           const int64_t* __restrict__ seq_len, int B, int T, int D, MlpgWindows win,
+                                                           int padding, const double* __restrict__ lambda, OutT* __restrict__ grad_means) {
+    const int S = B * D;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= (int64_t)T * S) return;
+    const int f = (int)(gid / S), sys = (int)(gid - (int64_t)f * S);
+    const int b = sys / D, d = sys - b * D;
+    const int len = (int)(seq_len ? (seq_len[b] < T ? seq_len[b] : (int64_t)T) : (int64_t)T);
+    if (f <= 0 || f >= len - 1) return;
+    const int n = len + 2 * padding, width = win.n * D, s = f + padding;
+    const double* lam = lambda + sys;
+    for (int w = 0; w < win.n; ++w) {
+        const int l = win.l[w], u = win.u[w];
+        const size_t at = ((size_t)b * T + f) * width + (size_t)w * D + d;
+        const float var = var_per_frame == MG_MLPG_VAR_ITEM ? variances[(size_t)b * width + w * D + d]
+                          : var_per_frame ? variances[at] : variances[w * D + d];
+        double dot = 0.0;
+        for (int k = -l; k <= u; ++k)
+            if (s + k >= 0 && s + k < n) dot += win.c[w][l + k] * lam[(size_t)(s + k) * S];
+        grad_means[at] = (OutT)((double)(1.0f / var) * dot);
+    }
+}
+
+// The first (e = 0) and the last (e = 1) frame of every system, one (e, system) per thread: padding + 1 padded rows each, or all n rows
+// for the one frame of an utterance of length 1.  A chain of dependent additions but NOT of dependent loads: lambda slides through a
+// register window of 2 SPAN + 1 rows, one new row per step, fetched MLPG_ROWS at a time with unconditional (clamped) loads that fly
+// together - a load per tap and row, waited for one by one, cost 0.1 ms for 101 rows.  Taps outside a window's [-l, u] carry a zero
+// coefficient and rows outside [0, n) a zero lambda, so every sum keeps its order: rows in increasing s, taps in increasing k.
+template <typename OutT>
+__global__ __launch_bounds__(64) void mlpg_scatter_edge_kernel(const float* __restrict__ variances, int var_per_frame,
+                                                              const int64_t* __restrict__ seq_len, int B, int T, int D, MlpgWindows win,
+                                                              int padding, const double* __restrict__ lambda,
+                                                              OutT* __restrict__ grad_means) {
+    const int S = B * D;
+    const int gid = blockIdx.x * 64 + threadIdx.x;
+    if (gid >= 2 * S) return;
+    const int e = gid / S, sys = gid - e * S;
+    const int b = sys / D, d = sys - b * D;
+    const int len = (int)(seq_len ? (seq_len[b] < T ? seq_len[b] : (int64_t)T) : (int64_t)T);
+    if (len <= 0 || (e && len == 1)) return;
+    const int f = e ? len - 1 : 0;
+    const int n = len + 2 * padding, width = win.n * D;
+    const int s_lo = f == 0 ? 0 : f + padding, s_hi = f == len - 1 ? n - 1 : f + padding;      // the padded rows that read frame f
+    const double* lam = lambda + sys;
+    const size_t at0 = ((size_t)b * T + f) * width + d;
+    double coeff[MLPG_MAX_WINDOWS][2 * MLPG_SPAN + 1], tau[MLPG_MAX_WINDOWS], acc[MLPG_MAX_WINDOWS];
+#pragma unroll
+    for (int w = 0; w < MLPG_MAX_WINDOWS; ++w) {
+        tau[w] = 0.0; acc[w] = 0.0;
+        const int l = w < win.n ? win.l[w] : 0, u = w < win.n ? win.u[w] : -1;
+#pragma unroll
+        for (int k = -MLPG_SPAN; k <= MLPG_SPAN; ++k) {
+            const double c = win.c[w < win.n ? w : 0][min(max(l + k, 0), MLPG_MAX_COEFF - 1)];
+            coeff[w][k + MLPG_SPAN] = (k >= -l && k <= u) ? c : 0.0;
+        }
+        if (w < win.n) {
+            const size_t at = at0 + (size_t)w * D;
+            const float var = var_per_frame == MG_MLPG_VAR_ITEM ? variances[(size_t)b * width + w * D + d]
+                              : var_per_frame ? variances[at] : variances[w * D + d];
+            tau[w] = (double)(1.0f / var);
+        }
+    }
+    auto fetch = [&](int r) __attribute__((always_inline)) {       // lambda[r], zero outside [0, n); the address is clamped into it
+        const double v = lam[(size_t)min(max(r, 0), n - 1) * S];
+        return r >= 0 && r < n ? v : 0.0;
+    };
+    double rows[2 * MLPG_SPAN + 1];              // before row s: rows[j + 1] = lambda[s - SPAN + j], j = 0 .. 2 SPAN - 1
+    rows[0] = 0.0;
+#pragma unroll
+    for (int j = 0; j < 2 * MLPG_SPAN; ++j) rows[j + 1] = fetch(s_lo - MLPG_SPAN + j);
+    for (int s0 = s_lo; s0 <= s_hi; s0 += MLPG_ROWS) {
+        double nxt[MLPG_ROWS];
+#pragma unroll
+        for (int j = 0; j < MLPG_ROWS; ++j) nxt[j] = fetch(s0 + j + MLPG_SPAN);
+#pragma unroll
+        for (int j = 0; j < MLPG_ROWS; ++j) {
+            if (s0 + j > s_hi) break;
+#pragma unroll
+            for (int i = 0; i < 2 * MLPG_SPAN; ++i) rows[i] = rows[i + 1];
+            rows[2 * MLPG_SPAN] = nxt[j];
+#pragma unroll
+            for (int w = 0; w < MLPG_MAX_WINDOWS; ++w) {
+                double dot = 0.0;
+#pragma unroll
+                for (int i = 0; i <= 2 * MLPG_SPAN; ++i) dot += coeff[w][i] * rows[i];
+                acc[w] += tau[w] * dot;
+            }
+        }
+    }
+#pragma unroll
+    for (int w = 0; w < MLPG_MAX_WINDOWS; ++w)
+        if (w < win.n) grad_means[at0 + (size_t)w * D] = (OutT)acc[w];
 }
 
 static int mlpg_half_bandwidth(int n_windows, const int* win_l, const int* win_u) {
@@ -268,6 +393,66 @@ int mg_mlpg_f32(const float* means, const float* variances, int var_per_frame, c
     else
         MLPG_RUN(4);
     MG_CHECK_LAUNCH("mg_mlpg_f32");
+    return MG_OK;
+}
+
+int mg_mlpg_grad_f32(const float* grad_out, const float* variances, int var_per_frame, const int64_t* seq_len, int B, int T, int D,
+                     int n_windows, const int* win_l, const int* win_u, const double* win_coeff, int padding, void* grad_means,
+                     int out_f64, void* workspace, size_t workspace_bytes, void* stream) {
+    MG_CHECK_ARG(grad_out && variances && grad_means && win_l && win_u && win_coeff, "mg_mlpg_grad_f32: null argument");
+    MG_CHECK_ARG(B > 0 && T > 0 && D > 0 && padding >= 0, "mg_mlpg_grad_f32: bad shape (B=%d T=%d D=%d padding=%d)", B, T, D, padding);
+    MG_CHECK_ARG(n_windows > 0 && n_windows <= MLPG_MAX_WINDOWS, "mg_mlpg_grad_f32: 1..%d windows supported, got %d", MLPG_MAX_WINDOWS,
+                 n_windows);
+    MlpgWindows win = {};
+    win.n = n_windows;
+    for (int w = 0; w < n_windows; ++w) {
+        MG_CHECK_ARG(win_l[w] >= 0 && win_u[w] >= 0 && win_l[w] + win_u[w] + 1 <= MLPG_MAX_COEFF,
+                     "mg_mlpg_grad_f32: window %d (l=%d, u=%d) is wider than %d coefficients", w, win_l[w], win_u[w], MLPG_MAX_COEFF);
+        win.l[w] = win_l[w];
+        win.u[w] = win_u[w];
+        for (int k = 0; k <= win_l[w] + win_u[w]; ++k) win.c[w][k] = win_coeff[w * MLPG_MAX_COEFF + k];
+    }
+    const size_t need = mg_mlpg_workspace_bytes(B, T, D, padding, n_windows, win_l, win_u);
+    MG_CHECK_ARG((size_t)(T + 2 * padding) * (size_t)B * D < ((size_t)1 << 31), "mg_mlpg_grad_f32: too many unknowns for 32-bit frame x system ids");
+    if (!workspace || workspace_bytes < need) {
+        mg_set_error("mg_mlpg_grad_f32: workspace of %zu bytes needed, got %zu", need, workspace_bytes);
+        return MG_EWORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t out_bytes = (size_t)B * T * n_windows * D * (out_f64 ? sizeof(double) : sizeof(float));
+    if (hipMemsetAsync(grad_means, 0, out_bytes, st) != hipSuccess) {    // frames past seq_len get no gradient
+        mg_set_error("mg_mlpg_grad_f32: memset failed");
+        return MG_ELAUNCH;
+    }
+    const int hb = mlpg_half_bandwidth(n_windows, win_l, win_u);
+    const int n_max = T + 2 * padding;
+    const unsigned grid_a = (unsigned)mg_ceil_div((int64_t)n_max * B * D, 256), grid_b = (unsigned)mg_ceil_div((int64_t)B * D, 64);
+    const unsigned grid_c = (unsigned)mg_ceil_div((int64_t)T * B * D, 256), grid_d = (unsigned)mg_ceil_div((int64_t)2 * B * D, 64);
+    double* planes = (double*)workspace;
+    const double* lambda = planes + (size_t)(hb + 1) * n_max * B * D;
+#define MLPG_GRAD_RUN(HB)                                                                                                             \
+    do {                                                                                                                              \
+        hipLaunchKernelGGL((mlpg_band_kernel<HB, true>), dim3(grid_a), dim3(256), 0, st, grad_out, variances, var_per_frame, seq_len,  \
+                           B, T, D, win, padding, planes);                                                                            \
+        hipLaunchKernelGGL((mlpg_solve_kernel<HB, double, true>), dim3(grid_b), dim3(64), 0, st, seq_len, B, T, D, padding, planes,    \
+                           (double*)nullptr);                                                                                         \
+    } while (0)
+    if (hb == 2)
+        MLPG_GRAD_RUN(2);
+    else
+        MLPG_GRAD_RUN(4);
+#define MLPG_SCATTER(OutT)                                                                                                            \
+    do {                                                                                                                              \
+        hipLaunchKernelGGL((mlpg_scatter_kernel<OutT>), dim3(grid_c), dim3(256), 0, st, variances, var_per_frame, seq_len, B, T, D,    \
+                           win, padding, lambda, (OutT*)grad_means);                                                                  \
+        hipLaunchKernelGGL((mlpg_scatter_edge_kernel<OutT>), dim3(grid_d), dim3(64), 0, st, variances, var_per_frame, seq_len, B, T,   \
+                           D, win, padding, lambda, (OutT*)grad_means);                                                               \
+    } while (0)
+    if (out_f64)
+        MLPG_SCATTER(double);
+    else
+        MLPG_SCATTER(float);
+    MG_CHECK_LAUNCH("mg_mlpg_grad_f32");
     return MG_OK;
 }
 

@@ -2009,6 +2009,29 @@ class SeqMeanFn(torch.autograd.Function):
         return ops.masked_seq_mean_bwd(grad_loss, seq_len, ctx.shape), None
 
 
+class MLPGFn(torch.autograd.Function):
+    """``ops.mlpg`` with a gradient for ``means`` (trajectory training): the backward is one more solve with the forward's matrix and a
+    window pass (``ops.mlpg_backward``).  Only ``variances`` and ``seq_len`` are kept; the factorisation is recomputed in the backward -
+    kept, it would be (HB + 2) (T + 2 padding) B D doubles, about 150 MB for the shipped acoustic model's mcep stream.  The variances are
+    constants (normaliser parameters): one that requires grad is refused.  Double backward is NOT supported."""
+
+    @staticmethod
+    def forward(ctx, means, variances, windows, padding_size, seq_len):
+        if ctx.needs_input_grad[1]:
+            raise ValueError('MLPG has no gradient for its variances (they are normaliser constants): detach them')
+        ctx.windows, ctx.padding_size = windows, padding_size
+        ctx.save_for_backward(variances, seq_len)
+        return ops.mlpg(means, variances, windows, padding_size=padding_size, seq_len=seq_len)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        variances, seq_len = ctx.saved_tensors
+        if grad_out.dtype != torch.float32:
+            grad_out = grad_out.float()
+        return ops.mlpg_backward(grad_out, variances, ctx.windows, padding_size=ctx.padding_size, seq_len=seq_len), None, None, None, None
+
+
 class StreamLossFn(torch.autograd.Function):
     """Multi-stream loss of models/RNN_SPSS.py:120-139 in one pass: returns (loss, sigmoid of the BCE stream or None)."""
 

@@ -172,10 +172,21 @@ class Stream(object):
     where ``losses.mse`` would be.  ``metric`` = (registered name, factory, kind): kind 'trajectory'
     feeds (target, trajectory, n_frames), 'voiced_trajectory' adds a voicing mask (the predicted probability stream ``voicing`` >
     0.5, or the feature of that name when the model predicts none), 'accuracy' feeds the hit rate of a probability or categorical
-    stream."""
+    stream.  ``trajectory_weight`` > 0 (delta streams only) adds a loss on what is listened to, the MLPG trajectory (trajectory /
+    minimum-generation-error training): the stream's loss becomes ``delta loss + trajectory_weight * trajectory_loss(normalised
+    trajectory, normalised_<name>, n_frames)`` with the gradient flowing through MLPG (``viz.synthesis.mlpg_trajectory``);
+    ``trajectory_loss`` is a callable ``(predictions, targets, seq_len)``, default ``losses.mse``."""
 
-    def __init__(self, name, dim, loss='mse', metric=None, voicing='vuv'):
+    def __init__(self, name, dim, loss='mse', metric=None, voicing='vuv', trajectory_weight=0., trajectory_loss=None):
         self.name, self.dim, self.loss, self.metric, self.voicing = name, dim, loss, metric, voicing
+        self.trajectory_weight, self.trajectory_loss = float(trajectory_weight), trajectory_loss
+        if self.trajectory_weight < 0.:
+            raise ValueError('stream %r: trajectory_weight must not be negative, got %r' % (name, trajectory_weight))
+        if (self.trajectory_weight > 0. or trajectory_loss is not None) and not self.is_delta:
+            raise ValueError('stream %r: a trajectory loss needs a delta stream (loss \'mse\' or a callable): a %r stream has no '
+                             'MLPG trajectory' % (name, loss))
+        if trajectory_loss is not None and not callable(trajectory_loss):
+            raise TypeError('stream %r: trajectory_loss must be a callable (predictions, targets, seq_len), got %r' % (name, trajectory_loss))
 
     @property
     def is_delta(self):
@@ -190,6 +201,10 @@ class Stream(object):
         if self.is_categorical:
             return self.name + '_logits'
         return 'normalised_%s_deltas' % self.name if self.is_delta else self.name
+
+    @property
+    def trains_trajectory(self):
+        return self.trajectory_weight > 0.
 
 
 # The delta streams' MLPG launches on streams of their own (StreamModel._with_trajectories); 0 = one after the other on the current stream
@@ -210,7 +225,9 @@ class StreamModel(BaseSPSS):
     counters, per-stream outputs under the reference's keys, loss = mean of the streams' masked losses, trajectories and metrics on
     the device whenever the normalisers carry delta parameters (i.e. under ``ExperimentBuilder``; ``generate=False`` turns both off).
     ``fused_loss``: the split, the sigmoid and all masked losses as one pass over the prediction (``losses.multi_stream``); refused
-    for a table with a callable loss, which that kernel cannot run.
+    for a table with a callable loss or a trajectory loss, which that kernel cannot run.
+    A stream with ``trajectory_weight`` > 0 gets its trajectory from the differentiable MLPG (one forward solve, on the current stream)
+    and a trajectory term in ``loss``; metrics read the detached trajectory.
     ``speaker_id_list`` (a file of speaker names): the delta streams are normalised PER SPEAKER
     (``data.SpeakerDependentMeanVarianceNormaliser``); trajectories are then denormalised with ``features['speaker_index']`` and MLPG
     runs under each utterance's own delta variances (``ops.mlpg``'s per-item mode).  None changes nothing."""
@@ -223,6 +240,10 @@ class StreamModel(BaseSPSS):
         if fused_loss and custom:
             raise ValueError('StreamModel: fused_loss=True cannot score the stream(s) %s with a callable loss: the one-pass multi-stream '
                              'kernel runs no user code (use fused_loss=False)' % ', '.join(custom))
+        weighted = [st.name for st in self.streams if st.trains_trajectory]
+        if fused_loss and weighted:
+            raise ValueError('StreamModel: fused_loss=True cannot score the stream(s) %s with a trajectory loss: the one-pass multi-stream '
+                             'kernel has no trajectory term (use fused_loss=False)' % ', '.join(weighted))
         self.speaker_id_list = speaker_id_list
         self.fused_upsample, self.fused_loss, self.generate = fused_upsample, fused_loss, generate
         registered = {st.metric[0]: st.metric[1]() for st in self.streams if st.metric is not None}
@@ -267,20 +288,28 @@ class StreamModel(BaseSPSS):
     def _generating(self):
         return self.generate and all(_has_delta_params(self.normalisers, st.name) for st in self.streams if st.is_delta)
 
-    def _trajectory(self, name, pred_norm_deltas, seq_len=None, speaker_index=None):
+    def _trajectory(self, name, pred_norm_deltas, seq_len=None, speaker_index=None, differentiable=False):
         """Denormalised deltas -> most probable static trajectory under the global delta variances, padding 100
         (models/RNN_SPSS.py:107-118, models/f0_test_model.py:83-89), without leaving the device.  With a speaker-dependent
-        normaliser: each utterance under the delta variances of its own speaker (row ``speaker_index[b]`` of the tables)."""
+        normaliser: each utterance under the delta variances of its own speaker (row ``speaker_index[b]`` of the tables).
+        ``differentiable``: the same solve with the gradient flowing back to ``pred_norm_deltas`` (a stream with a trajectory loss)."""
         normaliser = self.normalisers[name]
+        if not differentiable:
+            pred_norm_deltas = pred_norm_deltas.detach()
         if isinstance(normaliser, data._SpeakerDependentNormaliser):
             if speaker_index is None:
                 raise KeyError("the normaliser of %r is speaker-dependent: the batch needs features['%s'] (the loaders write it)"
                                % (name, data.SPEAKER_INDEX_KEY))
-            pred_deltas = normaliser.denormalise(pred_norm_deltas.detach(), speaker_index, deltas=True)
+            pred_deltas = normaliser.denormalise(pred_norm_deltas, speaker_index, deltas=True)
             index = normaliser.speaker_index(speaker_index, pred_deltas.device)
             std_dev = ops.item_rows(normaliser.tables(pred_deltas.device, deltas=True)[1], index)
+            if differentiable:
+                return viz.synthesis.mlpg_trajectory(pred_deltas, std_dev ** 2, padding_size=100, seq_len=seq_len)
             return ops.mlpg(pred_deltas, std_dev ** 2, viz.synthesis.DEFAULT_WINDOWS, padding_size=100, seq_len=seq_len)
-        pred_deltas = normaliser.denormalise(pred_norm_deltas.detach(), deltas=True)
+        pred_deltas = normaliser.denormalise(pred_norm_deltas, deltas=True)
+        if differentiable:
+            std_dev = normaliser.delta_params_torch['std_dev'].to(device=pred_deltas.device, dtype=torch.float32)
+            return viz.synthesis.mlpg_trajectory(pred_deltas, std_dev ** 2, padding_size=100, seq_len=seq_len)
         return viz.synthesis.MLPG(means=pred_deltas, variances=normaliser.delta_params_torch['std_dev'] ** 2, padding_size=100,
                                   seq_len=seq_len)
 
@@ -288,7 +317,11 @@ class StreamModel(BaseSPSS):
 
     def _with_trajectories(self, outputs, n_frames, speaker_index=None):
         if self._generating():
-            delta = [st for st in self.streams if st.is_delta]
+            # a stream with a trajectory loss: the differentiable solve, on the current stream (its backward runs where autograd puts it)
+            for st in self.streams:
+                if st.is_delta and st.trains_trajectory:
+                    outputs[st.name] = self._trajectory(st.name, outputs[st.output_key], n_frames, speaker_index, differentiable=True)
+            delta = [st for st in self.streams if st.is_delta and not st.trains_trajectory]
             first = outputs[delta[0].output_key] if delta else None
             if len(delta) > 1 and TRAJECTORY_STREAMS and torch.is_tensor(first) and first.is_cuda:
                 # The streams' trajectories are independent, and each MLPG launch is ONE dependent chain per (utterance, dimension) over
@@ -326,13 +359,30 @@ class StreamModel(BaseSPSS):
                 calls[metric_name] = ((features[st.name] == (outputs[st.name] > 0.5)).type(torch.float), n_frames)
             elif kind == 'voiced_trajectory':
                 voiced = (outputs[st.voicing] > 0.5) if st.voicing in predicted else features[st.voicing]
-                calls[metric_name] = (features[st.name], outputs[st.name], voiced, n_frames)
+                calls[metric_name] = (features[st.name], outputs[st.name].detach(), voiced, n_frames)
             else:
-                calls[metric_name] = (features[st.name], outputs[st.name], n_frames)
+                calls[metric_name] = (features[st.name], outputs[st.name].detach(), n_frames)
         self.metrics.accumulate(self.mode, **calls)
 
     def _target(self, features, st):
         return features[st.name] if st.is_categorical else features[st.output_key]
+
+    def _trajectory_loss(self, features, output_features, st):
+        """``trajectory_loss(normalise(trajectory), normalised target, n_frames)`` of a delta stream: both sides through the stream's
+        STATIC normaliser (per speaker when it is speaker-dependent), so the term is on the scale of the delta loss next to it."""
+        normaliser = self.normalisers[st.name]
+        args = ()
+        if isinstance(normaliser, data._SpeakerDependentNormaliser):
+            speaker_index = features.get(data.SPEAKER_INDEX_KEY)
+            if speaker_index is None:
+                raise KeyError("the normaliser of %r is speaker-dependent: the batch needs features['%s'] (the loaders write it)"
+                               % (st.name, data.SPEAKER_INDEX_KEY))
+            args = (speaker_index,)
+        target = features.get('normalised_' + st.name)
+        if target is None:
+            target = normaliser.normalise(features[st.name], *args)
+        score = st.trajectory_loss if st.trajectory_loss is not None else losses.mse
+        return score(normaliser.normalise(output_features[st.name], *args), target, features['n_frames'])
 
     # -- the plugin surface ----------------------------------------------------------------------------------------------------------
     def predict(self, features):
@@ -341,12 +391,19 @@ class StreamModel(BaseSPSS):
 
     def loss(self, features, output_features):
         n_frames = features['n_frames']
+        for st in self.streams:
+            if st.trains_trajectory and not self._generating():
+                raise RuntimeError("stream %r has trajectory_weight=%g, but there is no trajectory to score: the normaliser %r has no "
+                                   "delta parameters (%s_deltas_mvn.json, or set_params(..., delta_params)) or the model was built with "
+                                   "generate=False" % (st.name, st.trajectory_weight, st.name, st.name))
         self._accumulate_metrics(features, output_features)
         total = 0.
         for st in self.streams:                           # delta streams first, then the probability streams: the reference's order
             if st.is_delta:
                 stream_loss = st.loss if callable(st.loss) else losses.mse
                 total = total + stream_loss(output_features[st.output_key], self._target(features, st), n_frames)
+                if st.trains_trajectory:
+                    total = total + st.trajectory_weight * self._trajectory_loss(features, output_features, st)
         for st in self.streams:
             if not st.is_delta and not st.is_categorical:
                 total = total + losses.bce(output_features[st.output_key].type(torch.float), self._target(features, st).type(torch.float),
@@ -417,19 +474,23 @@ class LSTMAcousticModel(StreamModel):
     """The reference's shipped acoustic model (models/RNN_SPSS.py:20-139) as a stream table: lf0 / mcep / bap delta streams with
     masked MSE, a vuv probability stream with masked BCE, loss = their mean; LF0 RMSE in Hz over the frames the model calls voiced,
     V/UV accuracy, mel-cepstral and band-aperiodicity distortion (:44-48, :120-129).  Same constructor arguments and state_dict keys
-    (``layers.0.weight`` ... ``layers.{3+k}.layer.weight_ih_l0`` ...)."""
+    (``layers.0.weight`` ... ``layers.{3+k}.layer.weight_ih_l0`` ...).  ``trajectory_weight`` > 0 adds the trajectory loss of ``Stream``
+    to the three delta streams; it needs ``fused_loss=False``."""
 
     STREAMS = ('lf0', 'vuv', 'mcep', 'bap')
 
     def __init__(self, input_dim=600 + 9, output_dims=None, dropout_prob=0., num_layers=8, hidden_dim=512, post_dim=256,
-                 precision=None, fused_upsample=True, fused_loss=True, generate=True, speaker_id_list=None):
+                 precision=None, fused_upsample=True, fused_loss=True, generate=True, speaker_id_list=None, trajectory_weight=0.):
         if output_dims is None:
             output_dims = {'lf0': 1 * 3, 'vuv': 1, 'mcep': 60 * 3, 'bap': 5 * 3}
         self.input_dim, self.output_dims, self.dropout_prob, self.num_layers = input_dim, output_dims, dropout_prob, num_layers
-        table = {'lf0': Stream('lf0', output_dims['lf0'], 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory')),
+        table = {'lf0': Stream('lf0', output_dims['lf0'], 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'),
+                               trajectory_weight=trajectory_weight),
                  'vuv': Stream('vuv', output_dims['vuv'], 'sigmoid_bce', ('VUV_accuracy', metrics.Mean, 'accuracy')),
-                 'mcep': Stream('mcep', output_dims['mcep'], 'mse', ('MCEP_distortion', metrics.MelCepDistortion, 'trajectory')),
-                 'bap': Stream('bap', output_dims['bap'], 'mse', ('BAP_distortion', metrics.Distortion, 'trajectory'))}
+                 'mcep': Stream('mcep', output_dims['mcep'], 'mse', ('MCEP_distortion', metrics.MelCepDistortion, 'trajectory'),
+                                trajectory_weight=trajectory_weight),
+                 'bap': Stream('bap', output_dims['bap'], 'mse', ('BAP_distortion', metrics.Distortion, 'trajectory'),
+                               trajectory_weight=trajectory_weight)}
         layers = _lstm_stack(input_dim, hidden_dim, post_dim, sum(output_dims.values()), num_layers, dropout_prob, precision)
         super(LSTMAcousticModel, self).__init__(layers, [table[name] for name in self.STREAMS], fused_upsample=fused_upsample,
                                                 fused_loss=fused_loss, generate=generate, speaker_id_list=speaker_id_list)
@@ -441,10 +502,11 @@ class GRUF0Model(StreamModel):
     state_dict keys (``layers.0.weight``, ``layers.3.layer.weight_ih_l0`` ...)."""
 
     def __init__(self, dropout_prob=0., input_dim=600 + 9, output_dim=1 * 3, precision=None, fused_upsample=True, generate=True,
-                 speaker_id_list=None):
+                 speaker_id_list=None, trajectory_weight=0.):
         self.input_dim, self.output_dim = input_dim, output_dim
         layers = _gru_f0_stack(input_dim, output_dim, dropout_prob, precision)
-        streams = [Stream('lf0', output_dim, 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'))]
+        streams = [Stream('lf0', output_dim, 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'),
+                          trajectory_weight=trajectory_weight)]
         super(GRUF0Model, self).__init__(layers, streams, fused_upsample=fused_upsample, fused_loss=False, generate=generate,
                                          speaker_id_list=speaker_id_list)
 
@@ -458,10 +520,11 @@ class VAEF0Model(StreamModel, BaseVAE):
     ``encoder.0.layer.*`` and ``encoder_projection.0.*``."""
 
     def __init__(self, z_dim=16, kld_weight=1., encoder_hidden=64, dropout_prob=0., input_dim=600 + 9, output_dim=1 * 3, precision=None,
-                 fused_upsample=True, generate=True, speaker_id_list=None):
+                 fused_upsample=True, generate=True, speaker_id_list=None, trajectory_weight=0.):
         self.input_dim, self.output_dim = input_dim, output_dim
         layers = _gru_f0_stack(input_dim + z_dim, output_dim, dropout_prob, precision)
-        streams = [Stream('lf0', output_dim, 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'))]
+        streams = [Stream('lf0', output_dim, 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'),
+                          trajectory_weight=trajectory_weight)]
         super(VAEF0Model, self).__init__(layers, streams, fused_upsample=fused_upsample, fused_loss=False, generate=generate,
                                          speaker_id_list=speaker_id_list)
         self.z_dim, self.kld_weight = z_dim, kld_weight

@@ -2596,7 +2596,43 @@ def mlpg(means, variances, windows, padding_size=0, seq_len=None, out_dtype=torc
     return out
 
 
-DELTAS_EDGE_REPLICATE, DELTAS_EDGE_ZERO = _lib.MG_DELTAS_EDGE_REPLICATE, _lib.MG_DELTAS_EDGE_ZERO
+def mlpg_backward(grad_out, variances, windows, padding_size=0, seq_len=None, out_dtype=torch.float32):
+    """The gradient of ``mlpg``'s trajectory with respect to its means (csrc/mlpg.hip, mg_mlpg_grad_f32): grad_out (B, T, D) f32 ->
+    (B, T, W*D), zero past seq_len (whose frames of grad_out are never read).  One more solve with the forward's matrix and a window
+    pass; variances (all three layouts), windows, padding_size and seq_len as given to ``mlpg``.  The variances get no gradient."""
+    lib = _lib.load()
+    grad_out = _require(grad_out, torch.float32, 'grad_out')
+    variances = _require(variances, torch.float32, 'variances')
+    if grad_out.dim() != 3:
+        raise ValueError('grad_out must have shape (batch, time, features), got %s' % (tuple(grad_out.shape),))
+    b, t, d = grad_out.shape
+    n_win = len(windows)
+    if n_win == 0 or n_win > MLPG_MAX_WINDOWS:
+        raise ValueError('%d windows (1..%d supported)' % (n_win, MLPG_MAX_WINDOWS))
+    width = n_win * d
+    if variances.dim() == 1 and variances.shape[0] == width:
+        per_frame = 0
+    elif tuple(variances.shape) == (b, t, width):
+        per_frame = 1
+    elif variances.dim() == 2 and tuple(variances.shape) == (b, width):
+        per_frame = MLPG_VAR_ITEM
+    else:
+        raise ValueError('variances %s fit neither (%d,) nor %s nor (%d, %d)' % (tuple(variances.shape), width, (b, t, width), b, width))
+    win_l, win_u, win_c = _window_arrays(windows)
+    if seq_len is not None:
+        seq_len = _require(seq_len, torch.int64, 'seq_len')
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError('out_dtype must be torch.float32 or torch.float64')
+    grad_means = torch.empty((b, t, width), dtype=out_dtype, device=grad_out.device)
+    nbytes = lib.mg_mlpg_workspace_bytes(b, t, d, int(padding_size), n_win, win_l, win_u)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=grad_out.device)
+    _lib.check(lib.mg_mlpg_grad_f32(_p(grad_out), _p(variances), per_frame, _p(seq_len), b, t, d, n_win, win_l, win_u, win_c,
+                                    int(padding_size), _p(grad_means), int(out_dtype == torch.float64), _p(ws), ws.numel(), _stream()),
+               'mg_mlpg_grad_f32')
+    return grad_means
+
+
+DELTAS_EDGE_REPLICATE, DELTAS_EDGE_ZERO =_lib.MG_DELTAS_EDGE_REPLICATE, _lib.MG_DELTAS_EDGE_ZERO
 DELTAS_EDGES = {'replicate': DELTAS_EDGE_REPLICATE, 'zero': DELTAS_EDGE_ZERO}
 
 

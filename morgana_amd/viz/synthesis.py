@@ -4,11 +4,13 @@ device (``csrc/mlpg.hip``) instead of on the host with ``bandmat``.
 The reference calls this from ``predict`` of its shipped models (``models/f0_test_model.py:86-89``, ``models/RNN_SPSS.py:107-118``)
 on every training step - a device -> host copy, B x D banded float64 solves in a Python loop, a host -> device copy - to feed the
 LF0 / MCD metrics of ``loss``.  Here the delta streams never leave the device and nothing synchronises.
+
+``mlpg_trajectory`` is the same solve as a differentiable layer (device tensors only), for losses taken on the trajectory itself.
 """
 import numpy as np
 import torch
 
-from .. import _lib, ops
+from .. import _lib, functional, ops
 
 DEFAULT_WINDOWS = (                                  # synthesis.py:122-127
     (0, 0, np.array([1.0])),
@@ -64,3 +66,27 @@ def MLPG(means, variances, windows=None, padding_size=0, seq_len=None):
     if not using_batches:
         out = out.squeeze(0)                          # :173-174
     return out if as_tensor else out.cpu().numpy()    # :176-178
+
+
+def mlpg_trajectory(means, variances, windows=None, padding_size=0, seq_len=None):
+    r"""``MLPG`` as a differentiable layer (trajectory / minimum-generation-error training; the reference's host MLPG has no gradient).
+
+    means : (batch_size, seq_len, feat_dim) float32 device tensor; variances : (feat_dim,) global, the same shape as ``means`` or
+    (batch_size, feat_dim) per item, float32 on the same device - constants: one that requires grad is a ValueError; windows,
+    padding_size, seq_len as for ``MLPG``.  Device tensors only, always batched.
+
+    Returns the most probable trajectory (batch_size, seq_len, feat_dim // len(windows)), float32, zero past ``seq_len``, with a
+    gradient for ``means``: one more banded solve with the forward's matrix and a window pass (``csrc/mlpg.hip``).
+    """
+    for name, value in (('means', means), ('variances', variances)):
+        if not isinstance(value, torch.Tensor):
+            raise TypeError('mlpg_trajectory takes device tensors; %s is %s (MLPG takes arrays)' % (name, type(value)))
+    if variances.requires_grad:
+        raise ValueError('mlpg_trajectory has no gradient for its variances (they are normaliser constants): detach them')
+    if windows is None:
+        windows = DEFAULT_WINDOWS
+    if seq_len is not None:
+        if not isinstance(seq_len, torch.Tensor):
+            raise TypeError('mlpg_trajectory takes device tensors; seq_len is %s' % type(seq_len))
+        seq_len = seq_len.reshape(-1).to(device=means.device, dtype=torch.int64)
+    return functional.MLPGFn.apply(means, variances, windows, padding_size, seq_len)
