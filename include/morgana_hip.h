@@ -242,6 +242,34 @@ int mg_masked_ce_f32(const float* pred, int ldp, int col0, const int64_t* target
                      float grad_scale, float loss_weight, float loss_keep, float* loss, float* grad, int ldg, int gcol0,
                      int64_t* argmax, void* workspace, size_t workspace_bytes, void* stream);
 
+/* seq_len-masked mixture-density negative log likelihood, forward + backward (no counterpart in the reference: a K-component
+ * diagonal-Gaussian output layer over a stream's static + delta + delta-delta vector; Zen & Senior, ICASSP 2014).
+ * A frame's row holds W = K (1 + 2 D) columns: [ a_0 .. a_{K-1} | mu_{0,0} .. mu_{0,D-1}, mu_{1,0} .. mu_{K-1,D-1} | s_{0,0} ..
+ * s_{K-1,D-1} ] = logits, means (component-major), log standard deviations; target [B,T,D] f32 with row stride ldt.
+ *   z_kd = (y_d - mu_kd) exp(-s_kd),   q_k = log_softmax(a)_k - sum_d (0.5 z_kd^2 + s_kd) - D * 0.9189385332046727,
+ *   l[b,t] = -logsumexp_k(q_k) / D  (nats per dimension),   L = mean_b( sum_{t < n_b} l[b,t] / n_b ),  n_b = seq_len[b] clamped to
+ *   [0, T] (T when seq_len == NULL; n_b == 0 gives NaN),   loss[0] = loss_weight * L + loss_keep * loss[0]  (loss_keep == 0: loss[0]
+ *   is not read).  With r_k = exp(q_k - logsumexp q) and c = grad_scale / (D n_b B):
+ *   grad a_k = c (softmax(a)_k - r_k),   grad mu_kd = -c r_k z_kd exp(-s_kd),   grad s_kd = c r_k (1 - z_kd^2)
+ * for t < n_b and exactly 0 for pad frames (written, not skipped); pad frames of pred and target are never read.  has_floor != 0:
+ * s is replaced by max(s, min_log_std) and an s below the floor gets gradient 0 (torch.clamp's rule).  A -inf logit removes its
+ * component exactly; all logits -inf give NaN.  pred: frame (b,t) at pred + (b T + t) ldp + col0 - a column slice of a wider
+ * prediction is read in place; grad (may be NULL) likewise with ldg / gcol0: only those W columns of each row are written.
+ * 1 <= K <= MG_MDN_MAX_COMPONENTS, K * D <= MG_MDN_MAX_ROW, B <= 65535 (MG_EINVAL otherwise, before any launch).  Per-workgroup
+ * partials in a fixed layout and a one-workgroup finishing pass: no atomics, the same bits on every call.
+ * workspace: mg_masked_mdn_workspace_bytes(B,T,K,D) bytes.
+ * mg_mdn_select_f32 (generation, forward only, one launch): component[b,t] = the lowest index among the largest logits,
+ * mean[b,t,:] = mu of that component (exact copies), variance[b,t,:] = exp(2 max(s, floor)) of that component; pad frames are
+ * written as 0, 0 and 1.  component [B,T] int64, mean / variance [B,T,D] f32, contiguous. */
+#define MG_MDN_MAX_COMPONENTS 64
+#define MG_MDN_MAX_ROW 16384
+size_t mg_masked_mdn_workspace_bytes(int B, int T, int K, int D);
+int mg_masked_mdn_f32(const float* pred, int ldp, int col0, const float* target, int ldt, const int64_t* seq_len, int B, int T, int K,
+                      int D, float min_log_std, int has_floor, float grad_scale, float loss_weight, float loss_keep, float* loss,
+                      float* grad, int ldg, int gcol0, void* workspace, size_t workspace_bytes, void* stream);
+int mg_mdn_select_f32(const float* pred, int ldp, int col0, const int64_t* seq_len, int B, int T, int K, int D, float min_log_std,
+                      int has_floor, int64_t* component, float* mean, float* variance, void* stream);
+
 /* Streaming metrics (reference: morgana/metrics.py:359-695; accumulated inside the shipped model's loss() every step,
  * models/RNN_SPSS.py:120-129): accum[0] += sum, accum[1] += count on the device - no host read-back (the reference calls .item()
  * per accumulate).  kind: MG_METRIC_MEAN (target only), _SQDIFF (RMSE / MelCepDistortion), _ABSDIFF (MAE), _ROOT_SQ (Distortion:

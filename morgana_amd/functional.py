@@ -2077,6 +2077,27 @@ class MaskedCEFn(torch.autograd.Function):
         return grad * grad_loss, None, None, None
 
 
+class MaskedMDNFn(torch.autograd.Function):
+    """Masked mixture-density negative log likelihood (ops.masked_mdn) in one pass.  The gradient is computed in the forward and
+    saved; the targets get none, and there is no double backward."""
+
+    @staticmethod
+    def forward(ctx, predictions, targets, seq_len, n_components, min_log_std=None):
+        loss, grad = ops.masked_mdn(predictions, targets, seq_len, n_components, want_grad=ctx.needs_input_grad[0], min_log_std=min_log_std)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        (grad,) = ctx.saved_tensors
+        if grad is None:
+            return None, None, None, None, None
+        if _is_unit_grad(grad_loss):
+            return grad, None, None, None, None
+        return grad * grad_loss, None, None, None, None
+
+
 class StreamLossCEFn(torch.autograd.Function):
     """``StreamLossFn`` for a stream table with categorical streams (ops.stream_loss_ce): returns (loss, sigmoid of the BCE stream or
     None, the predicted class of every 'ce' stream)."""

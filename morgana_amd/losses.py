@@ -5,6 +5,7 @@ import functools
 import torch
 
 from . import functional as F_hip
+from . import ops
 
 
 def sequence_loss(loss_fn):
@@ -105,6 +106,60 @@ def ce(predictions, targets, seq_len=None, want_argmax=False):
         raise ValueError('ce: predictions must be a (B, T, C) tensor')
     loss, argmax = F_hip.MaskedCEFn.apply(predictions, _class_targets(predictions, targets), seq_len, want_argmax)
     return (loss, argmax) if want_argmax else loss
+
+
+def mdn_width(n_components, dim):
+    """Prediction columns of a mixture-density stream: K logits, K D means, K D log standard deviations."""
+    return int(n_components) * (1 + 2 * int(dim))
+
+
+def _mdn_predictions(what, predictions, n_components, dim):
+    if not isinstance(predictions, torch.Tensor) or predictions.dim() != 3:
+        raise ValueError('%s: predictions must be a (B, T, K (1 + 2 D)) tensor' % what)
+    if predictions.dtype != torch.float32:
+        raise TypeError('%s: predictions must be torch.float32, got %s' % (what, predictions.dtype))
+    if int(n_components) < 1 or predictions.shape[2] != mdn_width(n_components, dim):
+        raise ValueError('%s: predictions %s are not n_components * (1 + 2 D) = %d * (1 + 2 * %d) = %d columns wide'
+                         % (what, tuple(predictions.shape), n_components, dim, mdn_width(n_components, dim)))
+
+
+def mdn(predictions, targets, seq_len=None, n_components=1, min_log_std=None):
+    r"""Masked negative log likelihood of a mixture density network's output (Zen & Senior 2014) with the per-utterance averaging of
+    ``mse``, in nats per target dimension.  The reference has no such loss.
+
+    predictions (B, T, K (1 + 2 D)) float32, K = ``n_components``: ``[K logits a | K D means mu, component-major | K D log standard
+    deviations s]`` - a column slice of a wider tensor is read in place; targets (B, T, D) float32.  Per frame
+
+        z_kd = (y_d - mu_kd) exp(-s_kd),   q_k = log_softmax(a)_k - sum_d (0.5 z_kd^2 + s_kd) - D log sqrt(2 pi),
+        l = -logsumexp_k(q_k) / D
+
+    and the loss is ``mean_b( sum_{t < n_b} l[b,t] / n_b )``; ``seq_len[b] == 0`` gives NaN.  ``min_log_std`` puts a floor under s
+    (``torch.clamp``'s rule: a floored s gets gradient 0).  Pad frames are not read: a NaN there does not reach the loss.  A -inf
+    logit removes its component.  One HIP pass computes the loss and d loss / d predictions (csrc/mdn.hip); composed of torch ops it
+    is about 15 launches over (B, T, K, D) temporaries plus their autograd mirrors.  No gradient for the targets, no double backward."""
+    if not isinstance(targets, torch.Tensor) or targets.dim() != 3:
+        raise ValueError('mdn: targets must be a (B, T, D) tensor')
+    _mdn_predictions('mdn', predictions, n_components, targets.shape[2])
+    if targets.shape[1] != predictions.shape[1]:
+        raise RuntimeError('The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton dimension 1'
+                           % (predictions.shape[1], targets.shape[1]))
+    if seq_len is not None and seq_len.dtype != torch.int64:
+        seq_len = seq_len.long()
+    if targets.dtype != torch.float32:
+        targets = targets.float()
+    return F_hip.MaskedMDNFn.apply(predictions, targets.detach(), seq_len, int(n_components),
+                                   None if min_log_std is None else float(min_log_std))
+
+
+def mdn_select(predictions, n_components, dim, seq_len=None, min_log_std=None):
+    """Generation from a mixture-density stream (the layout of ``mdn``, D = ``dim``): per frame the most probable component (the
+    lowest index among the largest logits), its means and its variances ``exp(2 max(s, min_log_std))`` - what MLPG takes as per-frame
+    means and variances.  Returns (component (B, T) int64, mean (B, T, D), variance (B, T, D)), detached; pad frames hold 0, 0 and 1.
+    One launch (csrc/mdn.hip).  Sampling a component instead of taking the largest is not provided."""
+    _mdn_predictions('mdn_select', predictions, n_components, dim)
+    if seq_len is not None and seq_len.dtype != torch.int64:
+        seq_len = seq_len.long()
+    return ops.mdn_select(predictions.detach(), seq_len, int(n_components), int(dim), min_log_std=min_log_std)
 
 
 def multi_stream(predictions, targets, kinds, seq_len=None, want_prob=False, widths=None, want_argmax=False):

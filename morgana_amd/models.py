@@ -175,11 +175,28 @@ class Stream(object):
     stream.  ``trajectory_weight`` > 0 (delta streams only) adds a loss on what is listened to, the MLPG trajectory (trajectory /
     minimum-generation-error training): the stream's loss becomes ``delta loss + trajectory_weight * trajectory_loss(normalised
     trajectory, normalised_<name>, n_frames)`` with the gradient flowing through MLPG (``viz.synthesis.mlpg_trajectory``);
-    ``trajectory_loss`` is a callable ``(predictions, targets, seq_len)``, default ``losses.mse``."""
+    ``trajectory_loss`` is a callable ``(predictions, targets, seq_len)``, default ``losses.mse``.
+    ``loss='mdn'`` (with ``n_components`` = K and an optional floor ``min_log_std`` under the log standard deviations) makes a
+    mixture-density delta stream: it owns ``width`` = K (1 + 2 dim) prediction columns (``losses.mdn``'s layout), is scored by
+    ``losses.mdn`` against ``normalised_<name>_deltas`` and is a delta stream for target, normaliser, trajectory and metrics.  Its raw
+    parameters go out as ``<name>_mdn``, the most probable component's mean as ``normalised_<name>_deltas`` and its per-frame
+    variance as ``normalised_<name>_deltas_variance`` (``losses.mdn_select``, both detached); MLPG then runs on the denormalised mean
+    under the PER-FRAME variances ``variance * std_dev^2``.  Such a stream takes no trajectory loss."""
 
-    def __init__(self, name, dim, loss='mse', metric=None, voicing='vuv', trajectory_weight=0., trajectory_loss=None):
+    def __init__(self, name, dim, loss='mse', metric=None, voicing='vuv', trajectory_weight=0., trajectory_loss=None, n_components=1,
+                 min_log_std=None):
         self.name, self.dim, self.loss, self.metric, self.voicing = name, dim, loss, metric, voicing
         self.trajectory_weight, self.trajectory_loss = float(trajectory_weight), trajectory_loss
+        self.n_components, self.min_log_std = int(n_components), None if min_log_std is None else float(min_log_std)
+        if self.is_mdn and self.n_components < 1:
+            raise ValueError('stream %r: an \'mdn\' stream needs n_components >= 1, got %r' % (name, n_components))
+        if not self.is_mdn and (self.n_components != 1 or min_log_std is not None):
+            raise ValueError('stream %r: n_components and min_log_std belong to an \'mdn\' stream: a %r stream has no mixture'
+                             % (name, loss))
+        if self.is_mdn and (self.trajectory_weight > 0. or trajectory_loss is not None):
+            raise ValueError('stream %r: a trajectory loss needs a delta stream with a differentiable prediction (loss \'mse\' or a '
+                             'callable): the selected mean of an \'mdn\' stream is not a differentiable function of the weights'
+                             % (name,))
         if self.trajectory_weight < 0.:
             raise ValueError('stream %r: trajectory_weight must not be negative, got %r' % (name, trajectory_weight))
         if (self.trajectory_weight > 0. or trajectory_loss is not None) and not self.is_delta:
@@ -190,7 +207,16 @@ class Stream(object):
 
     @property
     def is_delta(self):
-        return self.loss == 'mse' or callable(self.loss)
+        return self.loss == 'mse' or self.loss == 'mdn' or callable(self.loss)
+
+    @property
+    def is_mdn(self):
+        return self.loss == 'mdn'
+
+    @property
+    def width(self):
+        """Columns of the prediction the stream owns: ``dim``, or K (1 + 2 dim) for a mixture-density stream."""
+        return losses.mdn_width(self.n_components, self.dim) if self.is_mdn else self.dim
 
     @property
     def is_categorical(self):
@@ -244,6 +270,10 @@ class StreamModel(BaseSPSS):
         if fused_loss and weighted:
             raise ValueError('StreamModel: fused_loss=True cannot score the stream(s) %s with a trajectory loss: the one-pass multi-stream '
                              'kernel has no trajectory term (use fused_loss=False)' % ', '.join(weighted))
+        mixtures = [st.name for st in self.streams if st.is_mdn]
+        if fused_loss and mixtures:
+            raise ValueError('StreamModel: fused_loss=True cannot score the stream(s) %s with a mixture-density loss: the one-pass '
+                             'multi-stream kernel has no MDN term (use fused_loss=False)' % ', '.join(mixtures))
         self.speaker_id_list = speaker_id_list
         self.fused_upsample, self.fused_loss, self.generate = fused_upsample, fused_loss, generate
         registered = {st.metric[0]: st.metric[1]() for st in self.streams if st.metric is not None}
@@ -270,13 +300,18 @@ class StreamModel(BaseSPSS):
         prediction, _ = self.layers(model_inputs, seq_len=features['n_frames'], max_len=norm_counters.shape[1])
         return prediction
 
-    def _split(self, prediction, probabilities=None, classes=None):
+    def _split(self, prediction, probabilities=None, classes=None, seq_len=None):
         """Per-stream outputs under the reference's keys; ``probabilities``: the sigmoid of the probability streams when a fused
-        loss pass has computed it already; ``classes``: {stream name: predicted class} of the categorical streams likewise."""
-        parts = torch.split(prediction, [st.dim for st in self.streams], dim=-1) if len(self.streams) > 1 else (prediction,)
+        loss pass has computed it already; ``classes``: {stream name: predicted class} of the categorical streams likewise;
+        ``seq_len``: the valid frames a mixture-density stream's selection reads (None: all of them)."""
+        parts = torch.split(prediction, [st.width for st in self.streams], dim=-1) if len(self.streams) > 1 else (prediction,)
         outputs = {}
         for st, part in zip(self.streams, parts):
-            if st.is_delta:
+            if st.is_mdn:
+                outputs[st.name + '_mdn'] = part          # what the loss reads (the column slice, in place)
+                _, outputs[st.output_key], outputs[st.output_key + '_variance'] = losses.mdn_select(
+                    part, st.n_components, st.dim, seq_len=seq_len, min_log_std=st.min_log_std)
+            elif st.is_delta:
                 outputs[st.output_key] = part
             elif st.is_categorical:
                 outputs[st.output_key] = part
@@ -288,12 +323,16 @@ class StreamModel(BaseSPSS):
     def _generating(self):
         return self.generate and all(_has_delta_params(self.normalisers, st.name) for st in self.streams if st.is_delta)
 
-    def _trajectory(self, name, pred_norm_deltas, seq_len=None, speaker_index=None, differentiable=False):
+    def _trajectory(self, name, pred_norm_deltas, seq_len=None, speaker_index=None, differentiable=False, norm_variance=None):
         """Denormalised deltas -> most probable static trajectory under the global delta variances, padding 100
         (models/RNN_SPSS.py:107-118, models/f0_test_model.py:83-89), without leaving the device.  With a speaker-dependent
         normaliser: each utterance under the delta variances of its own speaker (row ``speaker_index[b]`` of the tables).
-        ``differentiable``: the same solve with the gradient flowing back to ``pred_norm_deltas`` (a stream with a trajectory loss)."""
+        ``differentiable``: the same solve with the gradient flowing back to ``pred_norm_deltas`` (a stream with a trajectory loss).
+        ``norm_variance`` (B, T, D): per-frame variances in the normalised space (a mixture-density stream's selected component);
+        MLPG then runs under ``norm_variance * std_dev^2`` per frame instead of the global ``std_dev^2``."""
         normaliser = self.normalisers[name]
+        if norm_variance is not None and differentiable:
+            raise ValueError('stream %r: per-frame variances have no differentiable trajectory' % (name,))
         if not differentiable:
             pred_norm_deltas = pred_norm_deltas.detach()
         if isinstance(normaliser, data._SpeakerDependentNormaliser):
@@ -305,8 +344,13 @@ class StreamModel(BaseSPSS):
             std_dev = ops.item_rows(normaliser.tables(pred_deltas.device, deltas=True)[1], index)
             if differentiable:
                 return viz.synthesis.mlpg_trajectory(pred_deltas, std_dev ** 2, padding_size=100, seq_len=seq_len)
-            return ops.mlpg(pred_deltas, std_dev ** 2, viz.synthesis.DEFAULT_WINDOWS, padding_size=100, seq_len=seq_len)
+            variances = std_dev ** 2 if norm_variance is None else norm_variance.detach() * (std_dev ** 2)[:, None, :]
+            return ops.mlpg(pred_deltas, variances, viz.synthesis.DEFAULT_WINDOWS, padding_size=100, seq_len=seq_len)
         pred_deltas = normaliser.denormalise(pred_norm_deltas, deltas=True)
+        if norm_variance is not None:
+            std_dev = normaliser.delta_params_torch['std_dev'].to(device=pred_deltas.device, dtype=torch.float32)
+            return ops.mlpg(pred_deltas, norm_variance.detach() * std_dev ** 2, viz.synthesis.DEFAULT_WINDOWS, padding_size=100,
+                            seq_len=seq_len)
         if differentiable:
             std_dev = normaliser.delta_params_torch['std_dev'].to(device=pred_deltas.device, dtype=torch.float32)
             return viz.synthesis.mlpg_trajectory(pred_deltas, std_dev ** 2, padding_size=100, seq_len=seq_len)
@@ -333,13 +377,15 @@ class StreamModel(BaseSPSS):
                 for st, side in zip(delta, pool):
                     side.wait_stream(main)
                     with torch.cuda.stream(side):
-                        outputs[st.name] = self._trajectory(st.name, outputs[st.output_key], n_frames, speaker_index)
+                        outputs[st.name] = self._trajectory(st.name, outputs[st.output_key], n_frames, speaker_index,
+                                                            norm_variance=outputs.get(st.output_key + '_variance'))
                 for st, side in zip(delta, pool):
                     main.wait_stream(side)
                     outputs[st.name].record_stream(main)
             else:
                 for st in delta:
-                    outputs[st.name] = self._trajectory(st.name, outputs[st.output_key], n_frames, speaker_index)
+                    outputs[st.name] = self._trajectory(st.name, outputs[st.output_key], n_frames, speaker_index,
+                                                        norm_variance=outputs.get(st.output_key + '_variance'))
         return outputs
 
     def _accumulate_metrics(self, features, outputs):
@@ -386,7 +432,7 @@ class StreamModel(BaseSPSS):
 
     # -- the plugin surface ----------------------------------------------------------------------------------------------------------
     def predict(self, features):
-        return self._with_trajectories(self._split(self._run_layers(features)), features['n_frames'],
+        return self._with_trajectories(self._split(self._run_layers(features), seq_len=features['n_frames']), features['n_frames'],
                                        features.get(data.SPEAKER_INDEX_KEY))
 
     def loss(self, features, output_features):
@@ -399,7 +445,10 @@ class StreamModel(BaseSPSS):
         self._accumulate_metrics(features, output_features)
         total = 0.
         for st in self.streams:                           # delta streams first, then the probability streams: the reference's order
-            if st.is_delta:
+            if st.is_mdn:
+                total = total + losses.mdn(output_features[st.name + '_mdn'], self._target(features, st), n_frames,
+                                           n_components=st.n_components, min_log_std=st.min_log_std)
+            elif st.is_delta:
                 stream_loss = st.loss if callable(st.loss) else losses.mse
                 total = total + stream_loss(output_features[st.output_key], self._target(features, st), n_frames)
                 if st.trains_trajectory:
@@ -436,7 +485,7 @@ class StreamModel(BaseSPSS):
         classes = None
         if 'ce' in kinds:
             loss, probabilities, by_index = losses.multi_stream(prediction, targets, kinds, features['n_frames'],
-                                                                want_prob='sigmoid_bce' in kinds, widths=[st.dim for st in self.streams],
+                                                                want_prob='sigmoid_bce' in kinds, widths=[st.width for st in self.streams],
                                                                 want_argmax=True)
             classes = {self.streams[k].name: argmax for k, argmax in by_index.items()}
         else:
@@ -499,14 +548,21 @@ class LSTMAcousticModel(StreamModel):
 class GRUF0Model(StreamModel):
     """The reference's shipped F0 model (models/f0_test_model.py:21-107) as a one-row stream table: the lf0 delta stream with masked
     MSE and the LF0 RMSE in Hz over the frames the DATA calls voiced (``features['vuv']``, :101-103).  Same constructor arguments and
-    state_dict keys (``layers.0.weight``, ``layers.3.layer.weight_ih_l0`` ...)."""
+    state_dict keys (``layers.0.weight``, ``layers.3.layer.weight_ih_l0`` ...).  ``n_components`` > 0 makes the lf0 stream a
+    mixture-density stream of that many components (``Stream(loss='mdn')``; ``min_log_std``: its floor) and the last Linear
+    ``n_components * (1 + 2 * output_dim)`` wide; 0 is the reference's model."""
 
     def __init__(self, dropout_prob=0., input_dim=600 + 9, output_dim=1 * 3, precision=None, fused_upsample=True, generate=True,
-                 speaker_id_list=None, trajectory_weight=0.):
+                 speaker_id_list=None, trajectory_weight=0., n_components=0, min_log_std=None):
         self.input_dim, self.output_dim = input_dim, output_dim
-        layers = _gru_f0_stack(input_dim, output_dim, dropout_prob, precision)
-        streams = [Stream('lf0', output_dim, 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'),
-                          trajectory_weight=trajectory_weight)]
+        if n_components > 0:
+            stream = Stream('lf0', output_dim, 'mdn', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'),
+                            trajectory_weight=trajectory_weight, n_components=n_components, min_log_std=min_log_std)
+        else:
+            stream = Stream('lf0', output_dim, 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'),
+                            trajectory_weight=trajectory_weight, min_log_std=min_log_std)
+        layers = _gru_f0_stack(input_dim, stream.width, dropout_prob, precision)
+        streams = [stream]
         super(GRUF0Model, self).__init__(layers, streams, fused_upsample=fused_upsample, fused_loss=False, generate=generate,
                                          speaker_id_list=speaker_id_list)
 
@@ -550,7 +606,8 @@ class VAEF0Model(StreamModel, BaseVAE):
                                                                phone_rate=self.phone_rate)
         model_inputs = utils.concat_frame_features(norm_lab_at_frame_rate, norm_counters, latent)
         prediction, _ = self.layers(model_inputs, seq_len=features['n_frames'], max_len=norm_counters.shape[1])
-        return self._with_trajectories(self._split(prediction), features['n_frames'], features.get(data.SPEAKER_INDEX_KEY))
+        return self._with_trajectories(self._split(prediction, seq_len=features['n_frames']), features['n_frames'],
+                                       features.get(data.SPEAKER_INDEX_KEY))
 
     forward = BaseVAE.forward
     predict = BaseVAE.predict

@@ -502,6 +502,85 @@ def masked_ce(pred, target, seq_len, want_grad, grad_scale=1.0, want_argmax=Fals
     return loss, grad, argmax
 
 
+def _mdn_shape(what, pred, n_components, dim, col0):
+    """(B, T, D_total) predictions whose columns [col0, col0 + K (1 + 2 dim)) are one mixture-density stream -> that width, after the
+    caps of include/morgana_hip.h (refused here, before anything is allocated or launched)."""
+    k, d = int(n_components), int(dim)
+    if k < 1 or d < 1:
+        raise ValueError('%s: n_components=%d and a target width of %d must both be positive' % (what, k, d))
+    if k > _lib.MG_MDN_MAX_COMPONENTS:
+        raise _lib.MorganaHipError('%s: n_components=%d exceeds the cap of %d components (MG_MDN_MAX_COMPONENTS)'
+                                   % (what, k, _lib.MG_MDN_MAX_COMPONENTS))
+    if k * d > _lib.MG_MDN_MAX_ROW:
+        raise _lib.MorganaHipError('%s: n_components * D = %d exceeds the cap of %d means per frame (MG_MDN_MAX_ROW)'
+                                   % (what, k * d, _lib.MG_MDN_MAX_ROW))
+    w = k * (1 + 2 * d)
+    if col0 < 0 or col0 + w > pred.shape[2]:
+        raise ValueError('%s: columns [%d, %d) = %d components x (1 + 2 x %d) do not fit predictions %s'
+                         % (what, col0, col0 + w, k, d, tuple(pred.shape)))
+    return k, d, w
+
+
+def masked_mdn(pred, target, seq_len, n_components, want_grad, min_log_std=None, grad_scale=1.0, col0=0, grad_out=None, loss_out=None,
+               loss_weight=1.0, loss_keep=0.0):
+    """Masked mixture-density negative log likelihood (mg_masked_mdn_f32, csrc/mdn.hip) of columns [col0, col0 + K (1 + 2 D)) of
+    ``pred`` (B, T, *) f32 - K = ``n_components`` logits, K D means (component-major), K D log standard deviations - against
+    ``target`` (B, T, D) f32, in nats per dimension.  Returns (loss 0-d f32, grad or None).
+
+    ``pred`` is read in place when its last dimension is contiguous (a column slice of a wider prediction).  ``min_log_std``: a floor
+    under the log standard deviations (None = none); a floored one gets gradient 0.  ``grad_out``: a (B, T, *) f32 buffer shaped
+    like ``pred`` whose columns [col0, col0 + K (1 + 2 D)) receive the gradient (the other columns are not touched) instead of a new
+    (B, T, K (1 + 2 D)) tensor.  ``loss_out`` / ``loss_weight`` / ``loss_keep``: loss_out = loss_weight * loss + loss_keep *
+    loss_out on the device (``loss_keep == 0``: loss_out is only written)."""
+    lib = _lib.load()
+    pred, ldp = _rows_in_place(pred, 'predictions')
+    target, ldt = _rows_in_place(target, 'targets')
+    b, t, width = pred.shape
+    if target.shape[0] != b or target.shape[1] != t:
+        raise ValueError('mdn: targets %s do not match predictions %s: (B, T, D) wanted' % (tuple(target.shape), tuple(pred.shape)))
+    k, d, w = _mdn_shape('mdn', pred, n_components, target.shape[2], col0)
+    if seq_len is not None:
+        seq_len = _require(seq_len, torch.int64, 'seq_len')
+        if tuple(seq_len.shape) != (b,):
+            raise ValueError('mdn: seq_len must be (B,) = (%d,), got %s' % (b, tuple(seq_len.shape)))
+    loss = torch.empty((), dtype=torch.float32, device=pred.device) if loss_out is None else loss_out
+    grad, g, ldg, gcol0 = None, None, 0, 0
+    if want_grad and grad_out is not None:
+        g, ldg = _rows_in_place(grad_out, 'grad_out')
+        if g is not grad_out or tuple(g.shape) != (b, t, width):
+            raise ValueError('mdn: grad_out must be a (B, T, D) tensor with evenly spaced rows, shaped like predictions')
+        grad, gcol0 = grad_out, col0
+    elif want_grad:
+        grad = g = torch.empty((b, t, w), dtype=torch.float32, device=pred.device)
+        ldg = w
+    ws = workspace(lib.mg_masked_mdn_workspace_bytes(b, t, k, d), pred.device)
+    _lib.check(lib.mg_masked_mdn_f32(_p(pred), ldp, col0, _p(target), ldt, _p(seq_len), b, t, k, d,
+                                     0.0 if min_log_std is None else float(min_log_std), int(min_log_std is not None), float(grad_scale),
+                                     float(loss_weight), float(loss_keep), _p(loss), _p(g), ldg, gcol0, _p(ws), ws.numel(), _stream()),
+               'mg_masked_mdn_f32')
+    return loss, grad
+
+
+def mdn_select(pred, seq_len, n_components, dim, min_log_std=None, col0=0):
+    """The most probable component of every frame of a mixture-density stream (mg_mdn_select_f32; the column layout of
+    ``masked_mdn``, D = ``dim``): (component (B, T) int64 - the lowest index among the largest logits, mean (B, T, D) - that
+    component's means, copied, variance (B, T, D) = exp(2 max(log std, min_log_std)) of that component).  Pad frames hold 0, 0 and 1."""
+    lib = _lib.load()
+    pred, ldp = _rows_in_place(pred, 'predictions')
+    b, t, _ = pred.shape
+    k, d, _ = _mdn_shape('mdn_select', pred, n_components, dim, col0)
+    if seq_len is not None:
+        seq_len = _require(seq_len, torch.int64, 'seq_len')
+        if tuple(seq_len.shape) != (b,):
+            raise ValueError('mdn_select: seq_len must be (B,) = (%d,), got %s' % (b, tuple(seq_len.shape)))
+    component = torch.empty((b, t), dtype=torch.int64, device=pred.device)
+    mean = torch.empty((b, t, d), dtype=torch.float32, device=pred.device)
+    variance = torch.empty((b, t, d), dtype=torch.float32, device=pred.device)
+    _lib.check(lib.mg_mdn_select_f32(_p(pred), ldp, col0, _p(seq_len), b, t, k, d, 0.0 if min_log_std is None else float(min_log_std),
+                                     int(min_log_std is not None), _p(component), _p(mean), _p(variance), _stream()), 'mg_mdn_select_f32')
+    return component, mean, variance
+
+
 def stream_loss_ce(pred, targets, kinds, widths, seq_len, want_grad, want_prob=False, want_argmax=False):
     """``stream_loss`` for a stream table that holds 'ce' streams: the mse / sigmoid_bce streams take ONE mg_stream_loss_f32 launch
     over a descriptor table of their own (gradient weight n_rest / n through ``grad_scale``), every 'ce' stream (``targets[k]`` (B, T) int64, ``widths[k]`` classes) one mg_masked_ce_f32
