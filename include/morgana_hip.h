@@ -1266,6 +1266,49 @@ int mg_seq_mean_f32(const float* x, int64_t stride_b, int64_t stride_t, int64_t 
                     float* loss, void* workspace, size_t workspace_bytes, void* stream);
 int mg_seq_mean_bwd_f32(const float* grad_loss, const int64_t* seq_len, int B, int T, int D, float* grad, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * K26 (csrc/gv.hip)  global-variance loss: the per-utterance variance of a trajectory against that of the natural one
+ *                    (Toda & Tokuda 2007); the reference has no such loss.
+ * With n_b = min(max(seq_len[b], 0), T) (T when seq_len is NULL), over the valid frames t < n_b of utterance b and column d:
+ *     m[b,d] = mean_t x[b,t,d],   v[b,d] = mean_t (x[b,t,d] - m[b,d])^2   (biased),
+ *     f(v) = log(v + eps) if log_variance else v,
+ *     loss[0] = (1 / (B D)) sum_{b,d} ( f(v_pred[b,d]) - f(v_tgt[b,d]) )^2.
+ * pred / tgt are float32, element (b, t, d) at p[b stride_b + t stride_t + d stride_d] (element strides, not negative; 0 = an
+ * expanded operand), read in place.  PAD FRAMES ARE NEVER READ: a NaN there changes nothing.  n_b == 1 gives v == 0; n_b == 0 gives
+ * a NaN loss.
+ *
+ * Forward, two launches.  (1) grid (ceil(T / mg_gv_chunk_frames()), B, 2 operands): one workgroup streams the valid frames of its
+ * chunk of pred or of tgt once, as a flat array in steps of W = R D elements (R whole frames, W near 1024 whatever D, so narrow features
+ * fill the lanes), and leaves per column (mean - anchor, M2) in float64 in the workspace: shifted chunks of at most 32 values (sum
+ * of x - k and of (x - k)^2, k the chunk's first value) folded by Chan's update, the anchor being x[b,0,d].  No sum of raw squares,
+ * no atomics.  Rows with stride_d == 1 and stride_t == D whose step is a multiple of 4 take 16-byte loads at aligned addresses
+ * whatever the base alignment; anything else takes one element per load.  The order of every sum is a function of (b, t, d) alone:
+ * the same bits on every call and for every stride pattern and alignment of the same values.  (2) the finish, one thread per
+ * (b, d): merges the chunks in ascending order for both operands, evaluates f in float64, writes state [B, D, 2] float64 =
+ * (m_pred, c) with
+ *     c[b,d] = (2 / (B D)) (f(v_pred) - f(v_tgt)) f'(v_pred) (2 / n_b)          (NaN for n_b == 0),
+ * and sums the loss over (b, d) in a fixed tree: per workgroup of 256 items, then - by the workgroup that arrives last, found by one
+ * integer ticket per workgroup, nobody waiting - over the workgroups in index order; rounded to float32 once.  v_pred / v_tgt [B, D] float32 (either may be NULL)
+ * receive the variances.  tgt == NULL: only v_pred is computed (it must be given); loss and state are not touched.
+ * D <= MG_GV_MAX_D.  workspace: mg_gv_workspace_bytes(B, T, D) bytes (0 for a shape that is not positive), 8-byte aligned;
+ * MG_EWORKSPACE when it is NULL or too small.  No host read; capturable.
+ *
+ * Backward, one launch: grad [B, T, D] float32, contiguous; grad[b,t,d] = (float)(g c[b,d] (x[b,t,d] - m_pred[b,d])) in float64
+ * with one rounding for t < n_b, 0 on the pad frames of an utterance with n_b > 0 (they are not read), NaN on every frame of an
+ * utterance with n_b == 0.  g = grad_loss[0], one float32 ON THE DEVICE; pred is read in place through its strides.  16-byte
+ * stores behind a scalar head and tail.
+ * mg_gv_chunk_frames(): frames of one utterance per workgroup of launch (1), what a test needs to cross a chunk.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define MG_GV_MAX_D 2048
+int mg_gv_chunk_frames(void);
+size_t mg_gv_workspace_bytes(int B, int T, int D);
+int mg_gv_f32(const float* pred, int64_t pred_stride_b, int64_t pred_stride_t, int64_t pred_stride_d, const float* tgt,
+              int64_t tgt_stride_b, int64_t tgt_stride_t, int64_t tgt_stride_d, const int64_t* seq_len, int B, int T, int D,
+              int log_variance, double eps, float* loss, double* state, float* v_pred, float* v_tgt, void* workspace,
+              size_t workspace_bytes, void* stream);
+int mg_gv_bwd_f32(const float* grad_loss, const double* state, const float* pred, int64_t pred_stride_b, int64_t pred_stride_t,
+                  int64_t pred_stride_d, const int64_t* seq_len, int B, int T, int D, float* grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

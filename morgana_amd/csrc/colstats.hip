@@ -23,6 +23,7 @@
 // [first, last) is read.  Wide odd features (lcm(D, 4) > 1024: D = 609 -> W = 2436) take several quads per thread, one after the
 // other.  Launch 2 reads the job records (8 + 24 D bytes each, at most COLSTATS_MAX_JOBS of them) and the state.
 #include "common.h"
+#include "moments.h"      // mg_chan_merge: Chan's update, b folded into a
 
 #define COLSTATS_THREADS 256
 #define COLSTATS_FLUSH 32          // values per shifted chunk (a multiple of 4)
@@ -73,22 +74,6 @@ static inline int colstats_chunks(int B, int64_t max_rows, int D) {
     const int64_t cap = COLSTATS_MAX_JOBS / B > 1 ? COLSTATS_MAX_JOBS / B : 1;
     if (ch > cap) ch = cap;
     return ch < 1 ? 1 : (int)ch;
-}
-
-// Chan's update, b folded into a; counts as doubles (exact below 2^53)
-__device__ __forceinline__ void colstats_merge(double& na, double& ma, double& Ma, double nb, double mb, double Mb) {
-    if (nb == 0.0) return;
-    if (na == 0.0) {
-        na = nb;
-        ma = mb;
-        Ma = Mb;
-        return;
-    }
-    const double n = na + nb;
-    const double delta = mb - ma;
-    ma = ma + delta * (nb / n);
-    Ma = Ma + Mb + delta * delta * (na * nb / n);
-    na = n;
 }
 
 // order-preserving key of a float (not a NaN) and back
@@ -152,7 +137,7 @@ __device__ __forceinline__ void colstats_flush(colstats_acc& a) {
     const double mean = (a.k - a.anchor) + a.s1 / n;
     double m2 = a.s2 - a.s1 * a.s1 / n;
     if (m2 < 0.0) m2 = 0.0;                                  // rounding only; a NaN stays
-    colstats_merge(a.rn, a.rmean, a.rm2, n, mean, m2);
+    mg_chan_merge(a.rn, a.rmean, a.rm2, n, mean, m2);
     a.s1 = a.s2 = 0.0;
     a.cnt = 0;
 }
@@ -320,7 +305,7 @@ __global__ __launch_bounds__(COLSTATS_THREADS) void colstats_partial_kernel(cons
         for (int i = tid; i < n_pairs; i += COLSTATS_THREADS) {
             const int o = i + half * D;
             double na = (double)s_n[i], ma = s_mean[i], Ma = s_m2[i];
-            colstats_merge(na, ma, Ma, (double)s_n[o], s_mean[o], s_m2[o]);
+            mg_chan_merge(na, ma, Ma, (double)s_n[o], s_mean[o], s_m2[o]);
             s_n[i] = (int)na;
             s_mean[i] = ma;
             s_m2[i] = Ma;
@@ -379,7 +364,7 @@ __global__ __launch_bounds__(COLSTATS_THREADS) void colstats_merge_kernel(const 
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (n[u] == 0.0) continue;                        // an empty job's other fields were never written
-            colstats_merge(rn, rmean, rm2, n[u], me[u], m2[u]);
+            mg_chan_merge(rn, rmean, rm2, n[u], me[u], m2[u]);
             rmn = fminf(rmn, mn[u]);
             rmx = fmaxf(rmx, mx[u]);
         }
@@ -393,7 +378,7 @@ __global__ __launch_bounds__(COLSTATS_THREADS) void colstats_merge_kernel(const 
     for (int st = 1; st < COLSTATS_MERGE_LANES; st <<= 1) {
         if (lane % (2 * st) == 0) {
             double na = s_n[lane][cl], ma = s_mean[lane][cl], Ma = s_m2[lane][cl];
-            colstats_merge(na, ma, Ma, s_n[lane + st][cl], s_mean[lane + st][cl], s_m2[lane + st][cl]);
+            mg_chan_merge(na, ma, Ma, s_n[lane + st][cl], s_mean[lane + st][cl], s_m2[lane + st][cl]);
             s_n[lane][cl] = na;
             s_mean[lane][cl] = ma;
             s_m2[lane][cl] = Ma;

@@ -2009,6 +2009,26 @@ class SeqMeanFn(torch.autograd.Function):
         return ops.masked_seq_mean_bwd(grad_loss, seq_len, ctx.shape), None
 
 
+class GVFn(torch.autograd.Function):
+    """The global-variance loss of ``losses.gv`` (ops.gv): two launches forward, one backward (ops.gv_backward).  Kept between them:
+    the (B, D, 2) float64 state (the predictions' means and the gradient coefficients), the predictions themselves, which the
+    backward reads in place, and ``seq_len``.  The targets get no gradient.  Double backward is NOT supported."""
+
+    @staticmethod
+    def forward(ctx, predictions, targets, seq_len, log, eps):
+        loss, state, _, _ = ops.gv(predictions, targets, seq_len, log=log, eps=eps)
+        ctx.save_for_backward(state, predictions, seq_len)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        state, predictions, seq_len = ctx.saved_tensors
+        if grad_loss.dtype != torch.float32:
+            grad_loss = grad_loss.float()
+        return ops.gv_backward(grad_loss, state, predictions, seq_len), None, None, None, None
+
+
 class MLPGFn(torch.autograd.Function):
     """``ops.mlpg`` with a gradient for ``means`` (trajectory training): the backward is one more solve with the forward's matrix and a
     window pass (``ops.mlpg_backward``).  Only ``variances`` and ``seq_len`` are kept; the factorisation is recomputed in the backward -

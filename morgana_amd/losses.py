@@ -162,6 +162,47 @@ def mdn_select(predictions, n_components, dim, seq_len=None, min_log_std=None):
     return ops.mdn_select(predictions.detach(), seq_len, int(n_components), int(dim), min_log_std=min_log_std)
 
 
+def _gv_seq_len(what, x, seq_len):
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError('%s: a (B, T, D) tensor is wanted, got %s' % (what, tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)))
+    if seq_len is not None and seq_len.dtype != torch.int64:
+        seq_len = seq_len.long()
+    return seq_len
+
+
+def gv(predictions, targets, seq_len=None, log=True, eps=1e-6):
+    r"""Global-variance loss (Toda & Tokuda 2007): the squared gap between the per-utterance variance of a generated trajectory and
+    that of the natural one - the usual companion of trajectory training against over-smoothing.  The reference has no such loss.
+
+    predictions and targets (B, T, D) float32 on the device, both read in place whatever their strides (a column slice, a
+    transposed view, an expanded operand).  With n_b = ``seq_len[b]`` clamped to [0, T] (T without ``seq_len``):
+
+        m[b,d] = mean_{t < n_b} x[b,t,d],   v[b,d] = mean_{t < n_b} (x[b,t,d] - m[b,d])^2    (biased),
+        loss = mean_{b,d} ( f(v_pred[b,d]) - f(v_tgt[b,d]) )^2,    f(v) = log(v + eps) if ``log`` else v.
+
+    Returns a 0-d float32 device tensor, differentiable in ``predictions``; the targets get no gradient.  One utterance of one frame
+    has v = 0: the loss is finite and its gradient 0.  ``seq_len[b] == 0`` gives NaN, as for ``mse``.  Pad frames are NOT read, so a
+    NaN there changes nothing: this is ``mdn``'s rule, not ``sequence_loss``'s, which multiplies every frame by its mask value.
+    Targets of another dtype are refused as ``mse`` refuses them.  The variances are accumulated in float64 from shifted chunks
+    merged by Chan's update - no sum of raw squares, so a column far from 0 (a spectral coefficient at 16384 +- 2^-6) keeps its
+    variance - in an order that depends on (b, t, d) alone: the same bits on every call and for every layout of the same values.
+    Two launches forward, one backward (csrc/gv.hip through ``functional.GVFn``); composed of torch ops it is about a dozen
+    launches plus their autograd mirrors.  No CPU fallback, no double backward."""
+    seq_len = _gv_seq_len('gv', predictions, seq_len)
+    if not isinstance(targets, torch.Tensor) or targets.shape != predictions.shape:
+        raise ValueError('gv: targets must be a tensor shaped like the predictions %s, got %s'
+                         % (tuple(predictions.shape), tuple(targets.shape) if isinstance(targets, torch.Tensor) else type(targets)))
+    return F_hip.GVFn.apply(predictions, targets.detach(), seq_len, bool(log), float(eps))
+
+
+def global_variance(x, seq_len=None):
+    """Per-utterance variance of every column over the valid frames (biased, as ``gv`` defines it): x (B, T, D) float32 on the device
+    -> (B, D) float32, detached, from ``gv``'s kernel.  What one plots against the natural features' to see over-smoothing; a
+    constant column gives exactly 0, an utterance without a valid frame NaN."""
+    seq_len = _gv_seq_len('global_variance', x, seq_len)
+    return ops.gv(x.detach(), None, seq_len, want_variances=True)[2]
+
+
 def multi_stream(predictions, targets, kinds, seq_len=None, want_prob=False, widths=None, want_argmax=False):
     """Mean over streams of ``mse`` / ``bce(sigmoid(.))`` / ``ce`` on column slices of one prediction tensor - the loss of the
     reference's LSTM acoustic model (models/RNN_SPSS.py:120-139: three ``losses.mse`` + one ``losses.bce``, ``/ 4.``) in one

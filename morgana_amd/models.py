@@ -181,12 +181,16 @@ class Stream(object):
     ``losses.mdn`` against ``normalised_<name>_deltas`` and is a delta stream for target, normaliser, trajectory and metrics.  Its raw
     parameters go out as ``<name>_mdn``, the most probable component's mean as ``normalised_<name>_deltas`` and its per-frame
     variance as ``normalised_<name>_deltas_variance`` (``losses.mdn_select``, both detached); MLPG then runs on the denormalised mean
-    under the PER-FRAME variances ``variance * std_dev^2``.  Such a stream takes no trajectory loss."""
+    under the PER-FRAME variances ``variance * std_dev^2``.  Such a stream takes no trajectory loss.
+    ``gv_weight`` > 0 (delta streams only) adds a global-variance term on the same differentiable trajectory, against over-smoothing:
+    ``gv_weight * losses.gv(normalised trajectory, normalised_<name>, n_frames, log=gv_log)``; with ``trajectory_weight`` as well the
+    trajectory is solved and normalised once."""
 
     def __init__(self, name, dim, loss='mse', metric=None, voicing='vuv', trajectory_weight=0., trajectory_loss=None, n_components=1,
-                 min_log_std=None):
+                 min_log_std=None, gv_weight=0., gv_log=True):
         self.name, self.dim, self.loss, self.metric, self.voicing = name, dim, loss, metric, voicing
         self.trajectory_weight, self.trajectory_loss = float(trajectory_weight), trajectory_loss
+        self.gv_weight, self.gv_log = float(gv_weight), bool(gv_log)
         self.n_components, self.min_log_std = int(n_components), None if min_log_std is None else float(min_log_std)
         if self.is_mdn and self.n_components < 1:
             raise ValueError('stream %r: an \'mdn\' stream needs n_components >= 1, got %r' % (name, n_components))
@@ -204,6 +208,15 @@ class Stream(object):
                              'MLPG trajectory' % (name, loss))
         if trajectory_loss is not None and not callable(trajectory_loss):
             raise TypeError('stream %r: trajectory_loss must be a callable (predictions, targets, seq_len), got %r' % (name, trajectory_loss))
+        if self.gv_weight < 0. or self.gv_weight != self.gv_weight:
+            raise ValueError('stream %r: gv_weight must not be negative, got %r' % (name, gv_weight))
+        if self.gv_weight > 0. and self.is_mdn:
+            raise ValueError('stream %r: a global-variance loss needs a delta stream with a differentiable prediction (loss \'mse\' or a '
+                             'callable): the selected mean of an \'mdn\' stream is not a differentiable function of the weights'
+                             % (name,))
+        if self.gv_weight > 0. and not self.is_delta:
+            raise ValueError('stream %r: a global-variance loss needs a delta stream (loss \'mse\' or a callable): a %r stream has no '
+                             'MLPG trajectory' % (name, loss))
 
     @property
     def is_delta(self):
@@ -232,6 +245,15 @@ class Stream(object):
     def trains_trajectory(self):
         return self.trajectory_weight > 0.
 
+    @property
+    def trains_gv(self):
+        return self.gv_weight > 0.
+
+    @property
+    def differentiable_trajectory(self):
+        """The stream's trajectory feeds a loss term: it comes from the differentiable MLPG solve."""
+        return self.trains_trajectory or self.trains_gv
+
 
 # The delta streams' MLPG launches on streams of their own (StreamModel._with_trajectories); 0 = one after the other on the current stream
 TRAJECTORY_STREAMS = os.environ.get('MORGANA_TRAJECTORY_STREAMS', '1') != '0'
@@ -252,8 +274,8 @@ class StreamModel(BaseSPSS):
     the device whenever the normalisers carry delta parameters (i.e. under ``ExperimentBuilder``; ``generate=False`` turns both off).
     ``fused_loss``: the split, the sigmoid and all masked losses as one pass over the prediction (``losses.multi_stream``); refused
     for a table with a callable loss or a trajectory loss, which that kernel cannot run.
-    A stream with ``trajectory_weight`` > 0 gets its trajectory from the differentiable MLPG (one forward solve, on the current stream)
-    and a trajectory term in ``loss``; metrics read the detached trajectory.
+    A stream with ``trajectory_weight`` > 0 or ``gv_weight`` > 0 gets its trajectory from the differentiable MLPG (one forward solve,
+    on the current stream) and a trajectory and / or global-variance term in ``loss``; metrics read the detached trajectory.
     ``speaker_id_list`` (a file of speaker names): the delta streams are normalised PER SPEAKER
     (``data.SpeakerDependentMeanVarianceNormaliser``); trajectories are then denormalised with ``features['speaker_index']`` and MLPG
     runs under each utterance's own delta variances (``ops.mlpg``'s per-item mode).  None changes nothing."""
@@ -270,6 +292,10 @@ class StreamModel(BaseSPSS):
         if fused_loss and weighted:
             raise ValueError('StreamModel: fused_loss=True cannot score the stream(s) %s with a trajectory loss: the one-pass multi-stream '
                              'kernel has no trajectory term (use fused_loss=False)' % ', '.join(weighted))
+        varied = [st.name for st in self.streams if st.trains_gv]
+        if fused_loss and varied:
+            raise ValueError('StreamModel: fused_loss=True cannot score the stream(s) %s with a global-variance loss: the one-pass '
+                             'multi-stream kernel has no global-variance term (use fused_loss=False)' % ', '.join(varied))
         mixtures = [st.name for st in self.streams if st.is_mdn]
         if fused_loss and mixtures:
             raise ValueError('StreamModel: fused_loss=True cannot score the stream(s) %s with a mixture-density loss: the one-pass '
@@ -363,9 +389,9 @@ class StreamModel(BaseSPSS):
         if self._generating():
             # a stream with a trajectory loss: the differentiable solve, on the current stream (its backward runs where autograd puts it)
             for st in self.streams:
-                if st.is_delta and st.trains_trajectory:
+                if st.is_delta and st.differentiable_trajectory:
                     outputs[st.name] = self._trajectory(st.name, outputs[st.output_key], n_frames, speaker_index, differentiable=True)
-            delta = [st for st in self.streams if st.is_delta and not st.trains_trajectory]
+            delta = [st for st in self.streams if st.is_delta and not st.differentiable_trajectory]
             first = outputs[delta[0].output_key] if delta else None
             if len(delta) > 1 and TRAJECTORY_STREAMS and torch.is_tensor(first) and first.is_cuda:
                 # The streams' trajectories are independent, and each MLPG launch is ONE dependent chain per (utterance, dimension) over
@@ -414,8 +440,9 @@ class StreamModel(BaseSPSS):
         return features[st.name] if st.is_categorical else features[st.output_key]
 
     def _trajectory_loss(self, features, output_features, st):
-        """``trajectory_loss(normalise(trajectory), normalised target, n_frames)`` of a delta stream: both sides through the stream's
-        STATIC normaliser (per speaker when it is speaker-dependent), so the term is on the scale of the delta loss next to it."""
+        """``trajectory_weight * trajectory_loss(normalise(trajectory), normalised target, n_frames) + gv_weight * losses.gv(the same
+        three, log=gv_log)`` of a delta stream, whichever of the two weights is set: both sides through the stream's STATIC normaliser
+        (per speaker when it is speaker-dependent), once, so the terms are on the scale of the delta loss next to them."""
         normaliser = self.normalisers[st.name]
         args = ()
         if isinstance(normaliser, data._SpeakerDependentNormaliser):
@@ -427,8 +454,15 @@ class StreamModel(BaseSPSS):
         target = features.get('normalised_' + st.name)
         if target is None:
             target = normaliser.normalise(features[st.name], *args)
-        score = st.trajectory_loss if st.trajectory_loss is not None else losses.mse
-        return score(normaliser.normalise(output_features[st.name], *args), target, features['n_frames'])
+        trajectory = normaliser.normalise(output_features[st.name], *args)
+        total = None
+        if st.trains_trajectory:
+            score = st.trajectory_loss if st.trajectory_loss is not None else losses.mse
+            total = st.trajectory_weight * score(trajectory, target, features['n_frames'])
+        if st.trains_gv:
+            term = st.gv_weight * losses.gv(trajectory, target, features['n_frames'], log=st.gv_log)
+            total = term if total is None else total + term
+        return total
 
     # -- the plugin surface ----------------------------------------------------------------------------------------------------------
     def predict(self, features):
@@ -442,6 +476,10 @@ class StreamModel(BaseSPSS):
                 raise RuntimeError("stream %r has trajectory_weight=%g, but there is no trajectory to score: the normaliser %r has no "
                                    "delta parameters (%s_deltas_mvn.json, or set_params(..., delta_params)) or the model was built with "
                                    "generate=False" % (st.name, st.trajectory_weight, st.name, st.name))
+            if st.trains_gv and not self._generating():
+                raise RuntimeError("stream %r has gv_weight=%g, but there is no trajectory to score: the normaliser %r has no "
+                                   "delta parameters (%s_deltas_mvn.json, or set_params(..., delta_params)) or the model was built with "
+                                   "generate=False" % (st.name, st.gv_weight, st.name, st.name))
         self._accumulate_metrics(features, output_features)
         total = 0.
         for st in self.streams:                           # delta streams first, then the probability streams: the reference's order
@@ -451,8 +489,8 @@ class StreamModel(BaseSPSS):
             elif st.is_delta:
                 stream_loss = st.loss if callable(st.loss) else losses.mse
                 total = total + stream_loss(output_features[st.output_key], self._target(features, st), n_frames)
-                if st.trains_trajectory:
-                    total = total + st.trajectory_weight * self._trajectory_loss(features, output_features, st)
+                if st.differentiable_trajectory:
+                    total = total + self._trajectory_loss(features, output_features, st)
         for st in self.streams:
             if not st.is_delta and not st.is_categorical:
                 total = total + losses.bce(output_features[st.output_key].type(torch.float), self._target(features, st).type(torch.float),
@@ -524,22 +562,23 @@ class LSTMAcousticModel(StreamModel):
     masked MSE, a vuv probability stream with masked BCE, loss = their mean; LF0 RMSE in Hz over the frames the model calls voiced,
     V/UV accuracy, mel-cepstral and band-aperiodicity distortion (:44-48, :120-129).  Same constructor arguments and state_dict keys
     (``layers.0.weight`` ... ``layers.{3+k}.layer.weight_ih_l0`` ...).  ``trajectory_weight`` > 0 adds the trajectory loss of ``Stream``
-    to the three delta streams; it needs ``fused_loss=False``."""
+    to the three delta streams, ``gv_weight`` > 0 its global-variance loss; either needs ``fused_loss=False``."""
 
     STREAMS = ('lf0', 'vuv', 'mcep', 'bap')
 
     def __init__(self, input_dim=600 + 9, output_dims=None, dropout_prob=0., num_layers=8, hidden_dim=512, post_dim=256,
-                 precision=None, fused_upsample=True, fused_loss=True, generate=True, speaker_id_list=None, trajectory_weight=0.):
+                 precision=None, fused_upsample=True, fused_loss=True, generate=True, speaker_id_list=None, trajectory_weight=0.,
+                 gv_weight=0.):
         if output_dims is None:
             output_dims = {'lf0': 1 * 3, 'vuv': 1, 'mcep': 60 * 3, 'bap': 5 * 3}
         self.input_dim, self.output_dims, self.dropout_prob, self.num_layers = input_dim, output_dims, dropout_prob, num_layers
         table = {'lf0': Stream('lf0', output_dims['lf0'], 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'),
-                               trajectory_weight=trajectory_weight),
+                               trajectory_weight=trajectory_weight, gv_weight=gv_weight),
                  'vuv': Stream('vuv', output_dims['vuv'], 'sigmoid_bce', ('VUV_accuracy', metrics.Mean, 'accuracy')),
                  'mcep': Stream('mcep', output_dims['mcep'], 'mse', ('MCEP_distortion', metrics.MelCepDistortion, 'trajectory'),
-                                trajectory_weight=trajectory_weight),
+                                trajectory_weight=trajectory_weight, gv_weight=gv_weight),
                  'bap': Stream('bap', output_dims['bap'], 'mse', ('BAP_distortion', metrics.Distortion, 'trajectory'),
-                               trajectory_weight=trajectory_weight)}
+                               trajectory_weight=trajectory_weight, gv_weight=gv_weight)}
         layers = _lstm_stack(input_dim, hidden_dim, post_dim, sum(output_dims.values()), num_layers, dropout_prob, precision)
         super(LSTMAcousticModel, self).__init__(layers, [table[name] for name in self.STREAMS], fused_upsample=fused_upsample,
                                                 fused_loss=fused_loss, generate=generate, speaker_id_list=speaker_id_list)
@@ -553,14 +592,15 @@ class GRUF0Model(StreamModel):
     ``n_components * (1 + 2 * output_dim)`` wide; 0 is the reference's model."""
 
     def __init__(self, dropout_prob=0., input_dim=600 + 9, output_dim=1 * 3, precision=None, fused_upsample=True, generate=True,
-                 speaker_id_list=None, trajectory_weight=0., n_components=0, min_log_std=None):
+                 speaker_id_list=None, trajectory_weight=0., n_components=0, min_log_std=None, gv_weight=0.):
         self.input_dim, self.output_dim = input_dim, output_dim
         if n_components > 0:
             stream = Stream('lf0', output_dim, 'mdn', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'),
-                            trajectory_weight=trajectory_weight, n_components=n_components, min_log_std=min_log_std)
+                            trajectory_weight=trajectory_weight, n_components=n_components, min_log_std=min_log_std,
+                            gv_weight=gv_weight)
         else:
             stream = Stream('lf0', output_dim, 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'),
-                            trajectory_weight=trajectory_weight, min_log_std=min_log_std)
+                            trajectory_weight=trajectory_weight, min_log_std=min_log_std, gv_weight=gv_weight)
         layers = _gru_f0_stack(input_dim, stream.width, dropout_prob, precision)
         streams = [stream]
         super(GRUF0Model, self).__init__(layers, streams, fused_upsample=fused_upsample, fused_loss=False, generate=generate,
@@ -576,11 +616,11 @@ class VAEF0Model(StreamModel, BaseVAE):
     ``encoder.0.layer.*`` and ``encoder_projection.0.*``."""
 
     def __init__(self, z_dim=16, kld_weight=1., encoder_hidden=64, dropout_prob=0., input_dim=600 + 9, output_dim=1 * 3, precision=None,
-                 fused_upsample=True, generate=True, speaker_id_list=None, trajectory_weight=0.):
+                 fused_upsample=True, generate=True, speaker_id_list=None, trajectory_weight=0., gv_weight=0.):
         self.input_dim, self.output_dim = input_dim, output_dim
         layers = _gru_f0_stack(input_dim + z_dim, output_dim, dropout_prob, precision)
         streams = [Stream('lf0', output_dim, 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'),
-                          trajectory_weight=trajectory_weight)]
+                          trajectory_weight=trajectory_weight, gv_weight=gv_weight)]
         super(VAEF0Model, self).__init__(layers, streams, fused_upsample=fused_upsample, fused_loss=False, generate=generate,
                                          speaker_id_list=speaker_id_list)
         self.z_dim, self.kld_weight = z_dim, kld_weight

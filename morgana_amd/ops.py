@@ -409,6 +409,64 @@ def masked_seq_mean_bwd(grad_loss, seq_len, shape):
     return grad
 
 
+def _gv_operand(x, name):
+    x = _require_in_place(x, torch.float32, name)
+    if x.dim() != 3 or 0 in x.shape:
+        raise ValueError('%s must be a non-empty (B, T, D) tensor, got %s' % (name, tuple(x.shape)))
+    if min(x.stride()) < 0:
+        x = x.contiguous()
+    return x
+
+
+def gv(pred, target, seq_len=None, log=True, eps=1e-6, want_variances=False):
+    """Global-variance loss (mg_gv_f32, csrc/gv.hip): pred and target (B, T, D) float32, both read in place through their strides;
+    seq_len (B,) int64 or None.  Returns (loss 0-d float32, state (B, D, 2) float64 = (mean of pred, gradient coefficient) for
+    ``gv_backward``, v_pred, v_target): the (B, D) float32 per-utterance variances when ``want_variances``, else None.
+    ``target`` None: only the variances of ``pred`` are computed, (None, None, v_pred, None)."""
+    lib = _lib.load()
+    pred = _gv_operand(pred, 'predictions')
+    b, t, d = pred.shape
+    if target is not None:
+        target = _gv_operand(target, 'targets')
+        if target.shape != pred.shape:
+            raise ValueError('gv: predictions %s and targets %s must both be (B, T, D)' % (tuple(pred.shape), tuple(target.shape)))
+    seq_len = _seq_mean_lengths(seq_len, b)
+    dev = pred.device
+    loss = state = v_pred = v_tgt = None
+    if target is not None:
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        state = torch.empty((b, d, 2), dtype=torch.float64, device=dev)
+    if want_variances or target is None:
+        v_pred = torch.empty((b, d), dtype=torch.float32, device=dev)
+        v_tgt = torch.empty((b, d), dtype=torch.float32, device=dev) if target is not None else None
+    ws = workspace(lib.mg_gv_workspace_bytes(b, t, d), dev)
+    ts = target.stride() if target is not None else (0, 0, 0)
+    _lib.check(lib.mg_gv_f32(_p(pred), pred.stride(0), pred.stride(1), pred.stride(2), _p(target), ts[0], ts[1], ts[2], _p(seq_len), b, t, d,
+                             1 if log else 0, float(eps), _p(loss), _p(state), _p(v_pred), _p(v_tgt), _p(ws), ws.numel(), _stream()),
+               'mg_gv_f32')
+    return loss, state, v_pred, v_tgt
+
+
+def gv_backward(grad_loss, state, pred, seq_len=None):
+    """d gv / d pred (mg_gv_bwd_f32): a dense (B, T, D) float32 tensor, ``grad_loss * c * (pred - mean)`` on valid frames, 0 on pad
+    frames, NaN on an utterance without a valid frame.  ``grad_loss``: the upstream gradient, a one-element float32 device tensor
+    that the kernel reads (no host read); ``state``: what ``gv`` returned; ``pred`` is read in place through its strides."""
+    lib = _lib.load()
+    grad_loss = _require(grad_loss, torch.float32, 'grad_loss')
+    if grad_loss.numel() != 1:
+        raise ValueError('grad_loss must hold one element, got %s' % (tuple(grad_loss.shape),))
+    pred = _gv_operand(pred, 'predictions')
+    b, t, d = pred.shape
+    state = _require(state, torch.float64, 'state')
+    if tuple(state.shape) != (b, d, 2):
+        raise ValueError('state must be (B, D, 2) = (%d, %d, 2), got %s' % (b, d, tuple(state.shape)))
+    seq_len = _seq_mean_lengths(seq_len, b)
+    grad = torch.empty((b, t, d), dtype=torch.float32, device=pred.device)
+    _lib.check(lib.mg_gv_bwd_f32(_p(grad_loss), _p(state), _p(pred), pred.stride(0), pred.stride(1), pred.stride(2), _p(seq_len), b, t, d,
+                                 _p(grad), _stream()), 'mg_gv_bwd_f32')
+    return grad
+
+
 def stream_loss(pred, targets, kinds, seq_len, want_grad, want_prob=False, grad_scale=1.0):
     """Multi-stream loss (mg_stream_loss_f32): pred (B, T, sum of widths), targets[k] (B, T, width_k) scored side by side
     in column order, kinds[k] in {'mse', 'sigmoid_bce'}.  Returns (loss 0-d, grad or None, prob or None)."""
