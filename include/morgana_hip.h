@@ -315,9 +315,23 @@ int mg_mlpg_f32(const float* means, const float* variances, int var_per_frame, c
 int mg_mlpg_grad_f32(const float* grad_out, const float* variances, int var_per_frame, const int64_t* seq_len, int B, int T, int D,
                      int n_windows, const int* win_l, const int* win_u, const double* win_coeff, int padding, void* grad_means,
                      int out_f64, void* workspace, size_t workspace_bytes, void* stream);
+/* Both gradients of mg_mlpg_f32's trajectory, for PER-FRAME variances a model predicts: means and variances f32 [B,T,W*D] as given
+ * to the forward (var_per_frame = 1; the other layouts are expanded by the caller), grad_out, seq_len, windows and padding as in
+ * mg_mlpg_grad_f32, with the same checks.  Per (b, d) the forward's system P x~ = rhs and the adjoint P lambda = g~ are built and
+ * solved side by side (one launch each of the band and the solve kernels over two sets of planes), then for every frame f, over
+ * the padded rows s that read it in increasing s:
+ *   grad_means[b,f,w*D+d]     = sum_s  (1/var_w) (W_w lambda)[s]                                  (bit-equal to mg_mlpg_grad_f32's)
+ *   grad_variances[b,f,w*D+d] = sum_s -(1/var_w)^2 (W_w lambda)[s] (mean_w - (W_w x~)[s])
+ * with 1/var and mean/var formed in float32 as in the forward and everything after that in float64, rounded once: f32 [B,T,W*D]
+ * each, or f64 if out_f64; zero past seq_len, whose frames are read in no input.  No atomics, deterministic.
+ * workspace: mg_mlpg_grad_mv_workspace_bytes(...) bytes = twice mg_mlpg_workspace_bytes(...). */
+size_t mg_mlpg_grad_mv_workspace_bytes(int B, int T, int D, int padding, int n_windows, const int* win_l, const int* win_u);
+int mg_mlpg_grad_mv_f32(const float* grad_out, const float* means, const float* variances, const int64_t* seq_len, int B, int T, int D,
+                        int n_windows, const int* win_l, const int* win_u, const double* win_coeff, int padding, void* grad_means,
+                        void* grad_variances, int out_f64, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
- * K5  mvn / minmax normalisers           reference: morgana/data.py:533-538, 579-590
+ * K5 mvn / minmax normalisers           reference: morgana/data.py:533-538, 579-590
  * ---------------------------------------------------------------------------------------------------------------- */
 #define MG_NORM_MVN 0         /* (x - mean) / (std_dev + 1e-8)       p0 = mean, p1 = std_dev */
 #define MG_DENORM_MVN 1       /* x * std_dev + mean                                             */

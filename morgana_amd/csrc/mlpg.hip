@@ -36,7 +36,17 @@
 //   mlpg_scatter_kernel                 one thread per (inner frame, system): tau (W_w lambda) at the frame's one padded row, float64,
 //                                       one rounding at the store.  No atomics: a frame has one owner.
 //   mlpg_scatter_edge_kernel            one thread per (first / last frame, system): the same over its padding + 1 rows in increasing s
-// The variances get no gradient (normaliser constants at every call site).
+// The variances get no gradient there (normaliser constants at those call sites).
+//
+// Both gradients (mg_mlpg_grad_mv_f32; per-frame variances a model predicts - a 'gaussian' stream under a trajectory or global-variance
+// loss).  x~ = P^-1 rhs on ALL n rows is needed next to lambda:
+//     dL/dvar[b, f, w D + d] = sum over the padded rows s that read frame f of -tau_w[s]^2 (W_w lambda)[s] (mu_w[s] - (W_w x~)[s])
+// so the forward's system and the adjoint one are built and solved SIDE BY SIDE, grid.y = 2 picking a set of planes:
+//   mlpg_band_pair_kernel<HB>     y = 0: the forward's band rows and rhs; y = 1: the GRAD rows (the same band, g~)
+//   mlpg_solve_pair_kernel<HB>    the KEEP solve of either set: two independent chains on waves of their own, so the chain latency
+//                                 of one solve, not of two; x~ and lambda stay in plane HB + 1 of their sets
+//   mlpg_fold_mv_kernel / mlpg_fold_mv_edge_kernel   the scatter kernels with a second tap pass / register window over x~; grad_means
+//                                 bit for bit what mg_mlpg_grad_f32 writes
 #include "common.h"
 
 #define MLPG_MAX_WINDOWS 4
@@ -53,47 +63,28 @@ template <int HB, bool GRAD = false>
 __global__ __launch_bounds__(256) void mlpg_band_kernel(const float* __restrict__ means, const float* __restrict__ variances,
                                                         int var_per_frame, const int64_t* __restrict__ seq_len, int B, int T, int D,
                                                         MlpgWindows win, int padding, double* __restrict__ planes) {
-    const int S = B * D, n_max = T + 2 * padding;
-    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= (int64_t)n_max * S) return;
-    const int t = (int)(gid / S), sys = (int)(gid - (int64_t)t * S);
-    const int b = sys / D, d = sys - b * D;
-    const int len = (int)(seq_len ? (seq_len[b] < T ? seq_len[b] : (int64_t)T) : (int64_t)T);
-    if (len <= 0) return;
-    const int n = len + 2 * padding;
-    if (t >= n) return;
-    const int width = win.n * D;
-    double band[HB + 1], rhs = 0.0;
-#pragma unroll
-    for (int m = 0; m <= HB; ++m) band[m] = 0.0;
-    for (int w = 0; w < win.n; ++w) {
-        const int l = win.l[w], u = win.u[w];
-        for (int k = -l; k <= u; ++k) {                       // row s = t - k of W_w has a coefficient in column t
-            const int s = t - k;
-            if (s < 0 || s >= n) continue;
-            int f = s - padding;
-            f = f < 0 ? 0 : (f >= len ? len - 1 : f);
-            const size_t at = ((size_t)b * T + f) * width + (size_t)w * D + d;
-            const float var = var_per_frame == MG_MLPG_VAR_ITEM ? variances[(size_t)b * width + w * D + d]
-                              : var_per_frame ? variances[at] : variances[w * D + d];
-            const float tau = 1.0f / var;                                     // float32, as numpy does on the model's arrays
-            const double ck = win.c[w][l + k];
-            if constexpr (!GRAD) {
-                const float mu_tau = means[at] / var;
-                rhs += ck * (double)mu_tau;
-            }
-#pragma unroll
-            for (int m = 0; m <= HB; ++m) {
-                const int k2 = l + k - m;
-                if (t - m >= 0 && k2 >= 0 && k2 <= l + u) band[m] += (double)tau * ck * win.c[w][k2];
-            }
-        }
+#include "mlpg_band_body.inc"
+}
+
+// The two systems of mg_mlpg_grad_mv_f32 side by side, blockIdx.y picks one: 0 = the forward's (right-hand side mu tau, per-frame
+// variances) into the first set of planes, 1 = the adjoint's (right-hand side g~) into the second, `set_stride` doubles further on
+template <int HB>
+__global__ __launch_bounds__(256) void mlpg_band_pair_kernel(const float* __restrict__ fwd_means, const float* __restrict__ grad_out,
+                                                             const float* __restrict__ variances, const int64_t* __restrict__ seq_len,
+                                                             int B, int T, int D, MlpgWindows win, int padding,
+                                                             double* __restrict__ both, size_t set_stride) {
+    constexpr int var_per_frame = 1;
+    if (blockIdx.y == 0) {
+        constexpr bool GRAD = false;
+        const float* __restrict__ means = fwd_means;
+        double* __restrict__ planes = both;
+#include "mlpg_band_body.inc"
+    } else {
+        constexpr bool GRAD = true;
+        const float* __restrict__ means = grad_out;
+        double* __restrict__ planes = both + set_stride;
+#include "mlpg_band_body.inc"
     }
-    if constexpr (GRAD)
-        if (t >= padding && t < n - padding) rhs = (double)means[((size_t)b * T + (t - padding)) * D + d];       // frame t - padding < len
-#pragma unroll
-    for (int m = 0; m <= HB; ++m) planes[((size_t)m * n_max + t) * S + sys] = band[m];
-    planes[((size_t)(HB + 1) * n_max + t) * S + sys] = rhs;
 }
 
 #define MLPG_ROWS 8      // rows fetched ahead per block: their loads fly while the previous block's chain is worked off
@@ -112,121 +103,19 @@ __device__ __forceinline__ double mlpg_rcp(double d) {
 template <int HB, typename OutT, bool KEEP = false>
 __global__ __launch_bounds__(64) void mlpg_solve_kernel(const int64_t* __restrict__ seq_len, int B, int T, int D, int padding,
                                                        double* __restrict__ planes, OutT* __restrict__ out) {
-    const int S = B * D, n_max = T + 2 * padding;
-    const int sys = blockIdx.x * 64 + threadIdx.x;
-    if (sys >= S) return;
-    const int b = sys / D, d = sys - b * D;
-    const int len = (int)(seq_len ? (seq_len[b] < T ? seq_len[b] : (int64_t)T) : (int64_t)T);
-    if (len <= 0) return;
-    const int n = len + 2 * padding;
-    const size_t plane = (size_t)n_max * S;
-    double* p = planes + sys;
+#include "mlpg_solve_body.inc"
+}
 
-    // forward: row i of L (unit lower band), d_i, y_i; L[i, i-1-k] goes to plane k + 1, z_i = y_i / d_i to plane HB + 1
-    double lprev[HB][HB];        // lprev[r][k]: L[i-1-r, i-1-r-(k+1)]
-    double yprev[HB], dinv[HB];
-#pragma unroll
-    for (int r = 0; r < HB; ++r) {
-        yprev[r] = 0.0; dinv[r] = 0.0;
-#pragma unroll
-        for (int k = 0; k < HB; ++k) lprev[r][k] = 0.0;
-    }
-    // one row of the factorisation from its band row a[0..HB] and right-hand side a[HB + 1]
-    auto fwd_row = [&](const double (&a)[HB + 2], int i) __attribute__((always_inline)) {
-        double lw[HB], ud[HB];       // lw[k] = L[i, i-1-k], ud[k] = lw[k] * d_{i-1-k}
-#pragma unroll
-        for (int m = HB - 1; m >= 0; --m) {           // columns i-HB .. i-1 in increasing order
-            double v = a[m + 1];
-#pragma unroll
-            for (int k = m + 1; k < HB; ++k) v -= ud[k] * lprev[m][k - m - 1];
-            ud[m] = v;
-            lw[m] = v * dinv[m];                      // dinv = 0 for rows before the first: those entries are 0 anyway
-        }
-        double di = a[0], yi = a[HB + 1];
-#pragma unroll
-        for (int k = 0; k < HB; ++k) {
-            di -= lw[k] * ud[k];
-            yi -= lw[k] * yprev[k];
-        }
-        const double inv = mlpg_rcp(di);
-#pragma unroll
-        for (int k = 0; k < HB; ++k) p[(k + 1) * plane + (size_t)i * S] = lw[k];
-        p[(HB + 1) * plane + (size_t)i * S] = yi * inv;
-#pragma unroll
-        for (int q = HB - 1; q > 0; --q) {
-            yprev[q] = yprev[q - 1]; dinv[q] = dinv[q - 1];
-#pragma unroll
-            for (int k = 0; k < HB; ++k) lprev[q][k] = lprev[q - 1][k];
-        }
-        yprev[0] = yi; dinv[0] = inv;
-#pragma unroll
-        for (int k = 0; k < HB; ++k) lprev[0][k] = lw[k];
-    };
-    // blocks of MLPG_ROWS rows; every load is unconditional (row index clamped) so that the block ahead is in flight while this
-    // one's chain runs - with per-row branches the compiler drains the memory queue (vmcnt(0)) before the first row
-    double cur[MLPG_ROWS][HB + 2], nxt[MLPG_ROWS][HB + 2];
-#pragma unroll
-    for (int r = 0; r < MLPG_ROWS; ++r)
-#pragma unroll
-        for (int m = 0; m < HB + 2; ++m) cur[r][m] = p[m * plane + (size_t)min(r, n - 1) * S];
-    int i0 = 0;
-    for (; i0 + MLPG_ROWS <= n; i0 += MLPG_ROWS) {
-#pragma unroll
-        for (int r = 0; r < MLPG_ROWS; ++r)
-#pragma unroll
-            for (int m = 0; m < HB + 2; ++m) nxt[r][m] = p[m * plane + (size_t)min(i0 + MLPG_ROWS + r, n - 1) * S];
-#pragma unroll
-        for (int r = 0; r < MLPG_ROWS; ++r) fwd_row(cur[r], i0 + r);
-#pragma unroll
-        for (int r = 0; r < MLPG_ROWS; ++r)
-#pragma unroll
-            for (int m = 0; m < HB + 2; ++m) cur[r][m] = nxt[r][m];
-    }
-#pragma unroll
-    for (int r = 0; r < MLPG_ROWS - 1; ++r)
-        if (i0 + r < n) fwd_row(cur[r], i0 + r);
-
-    // backward: x_i = z_i - sum_k L[i+1+k, i] x_{i+1+k}; per row z_i (plane HB + 1, row i) and L[i+1+k, i] (plane k + 1, row i+1+k,
-    // zero past the last row: those x are zero too, so the clamped load is harmless)
-    double xn[HB];
-#pragma unroll
-    for (int k = 0; k < HB; ++k) xn[k] = 0.0;
-    OutT* o = out + (size_t)b * T * D + d;
-    auto bwd_row = [&](const double (&a)[HB + 1], int i) __attribute__((always_inline)) {
-        double x = a[HB];
-#pragma unroll
-        for (int k = 0; k < HB; ++k) x -= a[k] * xn[k];
-        if constexpr (KEEP)
-            p[(HB + 1) * plane + (size_t)i * S] = x;
-        else if (i >= padding && i < n - padding)
-            o[(size_t)(i - padding) * D] = (OutT)x;
-#pragma unroll
-        for (int k = HB - 1; k > 0; --k) xn[k] = xn[k - 1];
-        xn[0] = x;
-    };
-    auto bwd_load = [&](double (&a)[HB + 1], int i) __attribute__((always_inline)) {
-        i = max(i, 0);
-        a[HB] = p[(HB + 1) * plane + (size_t)i * S];
-#pragma unroll
-        for (int k = 0; k < HB; ++k) a[k] = p[(k + 1) * plane + (size_t)min(i + 1 + k, n - 1) * S];
-    };
-    double bc[MLPG_ROWS][HB + 1], bn[MLPG_ROWS][HB + 1];
-#pragma unroll
-    for (int r = 0; r < MLPG_ROWS; ++r) bwd_load(bc[r], n - 1 - r);
-    i0 = n - 1;
-    for (; i0 - MLPG_ROWS >= -1; i0 -= MLPG_ROWS) {
-#pragma unroll
-        for (int r = 0; r < MLPG_ROWS; ++r) bwd_load(bn[r], i0 - MLPG_ROWS - r);
-#pragma unroll
-        for (int r = 0; r < MLPG_ROWS; ++r) bwd_row(bc[r], i0 - r);
-#pragma unroll
-        for (int r = 0; r < MLPG_ROWS; ++r)
-#pragma unroll
-            for (int k = 0; k <= HB; ++k) bc[r][k] = bn[r][k];
-    }
-#pragma unroll
-    for (int r = 0; r < MLPG_ROWS - 1; ++r)
-        if (i0 - r >= 0) bwd_row(bc[r], i0 - r);
+// Both sets of planes of mlpg_band_pair_kernel in one launch, blockIdx.y picks one: two independent chains on waves of their own,
+// each the KEEP solve (x~ resp. lambda of all n rows over z in its plane HB + 1)
+template <int HB>
+__global__ __launch_bounds__(64) void mlpg_solve_pair_kernel(const int64_t* __restrict__ seq_len, int B, int T, int D, int padding,
+                                                            double* __restrict__ both, size_t set_stride) {
+    using OutT = double;
+    constexpr bool KEEP = true;
+    double* __restrict__ planes = both + blockIdx.y * set_stride;
+    OutT* __restrict__ out = nullptr;
+#include "mlpg_solve_body.inc"
 }
 
 #define MLPG_SPAN (MLPG_MAX_COEFF - 1)      // a window reaches at most this many rows to either side of its own
@@ -328,6 +217,128 @@ __global__ __launch_bounds__(64) void mlpg_scatter_edge_kernel(const float* __re
 #pragma unroll
     for (int w = 0; w < MLPG_MAX_WINDOWS; ++w)
         if (w < win.n) grad_means[at0 + (size_t)w * D] = (OutT)acc[w];
+}
+
+// mg_mlpg_grad_mv_f32: both gradients of the INNER frames 0 < f < len - 1, one (frame, system) per thread as mlpg_scatter_kernel.  With
+// lambda and x~ (the forward's solution on ALL n rows) side by side: dL/dmu = tau (W_w lambda)[s] - the same expression, in the same
+// order, as mlpg_scatter_kernel, so the same bits - and dL/dvar = -tau^2 (W_w lambda)[s] (mu - (W_w x~)[s]), one rounding each.
+template <typename OutT>
+__global__ __launch_bounds__(256) void mlpg_fold_mv_kernel(const float* __restrict__ means, const float* __restrict__ variances,
+                                                           const int64_t* __restrict__ seq_len, int B, int T, int D, MlpgWindows win,
+                                                           int padding, const double* __restrict__ lambda, const double* __restrict__ xs,
+                                                           OutT* __restrict__ grad_means, OutT* __restrict__ grad_variances) {
+    const int S = B * D;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= (int64_t)T * S) return;
+    const int f = (int)(gid / S), sys = (int)(gid - (int64_t)f * S);
+    const int b = sys / D, d = sys - b * D;
+    const int len = (int)(seq_len ? (seq_len[b] < T ? seq_len[b] : (int64_t)T) : (int64_t)T);
+    if (f <= 0 || f >= len - 1) return;
+    const int n = len + 2 * padding, width = win.n * D, s = f + padding;
+    const double* lam = lambda + sys;
+    const double* xt = xs + sys;
+    for (int w = 0; w < win.n; ++w) {
+        const int l = win.l[w], u = win.u[w];
+        const size_t at = ((size_t)b * T + f) * width + (size_t)w * D + d;
+        const float var = variances[at];
+        const double tau = (double)(1.0f / var), mu = (double)means[at];
+        double dot = 0.0, wx = 0.0;
+        for (int k = -l; k <= u; ++k)
+            if (s + k >= 0 && s + k < n) {
+                dot += win.c[w][l + k] * lam[(size_t)(s + k) * S];
+                wx += win.c[w][l + k] * xt[(size_t)(s + k) * S];
+            }
+        grad_means[at] = (OutT)(tau * dot);
+        grad_variances[at] = (OutT)(-(tau * tau) * dot * (mu - wx));
+    }
+}
+
+// The first and the last frame, as mlpg_scatter_edge_kernel with a second register window for x~: per padded row s and window w
+// dot = (W_w lambda)[s], wx = (W_w x~)[s]; acc += tau dot (the means, bit for bit the edge kernel's) and accv += -tau^2 dot (mu - wx)
+// (mu and tau are the frame's, the same on every one of its rows).  Rows in increasing s, taps in increasing k.
+template <typename OutT>
+__global__ __launch_bounds__(64) void mlpg_fold_mv_edge_kernel(const float* __restrict__ means, const float* __restrict__ variances,
+                                                              const int64_t* __restrict__ seq_len, int B, int T, int D, MlpgWindows win,
+                                                              int padding, const double* __restrict__ lambda,
+                                                              const double* __restrict__ xs, OutT* __restrict__ grad_means,
+                                                              OutT* __restrict__ grad_variances) {
+    const int S = B * D;
+    const int gid = blockIdx.x * 64 + threadIdx.x;
+    if (gid >= 2 * S) return;
+    const int e = gid / S, sys = gid - e * S;
+    const int b = sys / D, d = sys - b * D;
+    const int len = (int)(seq_len ? (seq_len[b] < T ? seq_len[b] : (int64_t)T) : (int64_t)T);
+    if (len <= 0 || (e && len == 1)) return;
+    const int f = e ? len - 1 : 0;
+    const int n = len + 2 * padding, width = win.n * D;
+    const int s_lo = f == 0 ? 0 : f + padding, s_hi = f == len - 1 ? n - 1 : f + padding;      // the padded rows that read frame f
+    const double* lam = lambda + sys;
+    const double* xt = xs + sys;
+    const size_t at0 = ((size_t)b * T + f) * width + d;
+    double coeff[MLPG_MAX_WINDOWS][2 * MLPG_SPAN + 1], tau[MLPG_MAX_WINDOWS], ntau2[MLPG_MAX_WINDOWS], mu[MLPG_MAX_WINDOWS];
+    double acc[MLPG_MAX_WINDOWS], accv[MLPG_MAX_WINDOWS];
+#pragma unroll
+    for (int w = 0; w < MLPG_MAX_WINDOWS; ++w) {
+        tau[w] = 0.0; ntau2[w] = 0.0; mu[w] = 0.0; acc[w] = 0.0; accv[w] = 0.0;
+        const int l = w < win.n ? win.l[w] : 0, u = w < win.n ? win.u[w] : -1;
+#pragma unroll
+        for (int k = -MLPG_SPAN; k <= MLPG_SPAN; ++k) {
+            const double c = win.c[w < win.n ? w : 0][min(max(l + k, 0), MLPG_MAX_COEFF - 1)];
+            coeff[w][k + MLPG_SPAN] = (k >= -l && k <= u) ? c : 0.0;
+        }
+        if (w < win.n) {
+            const size_t at = at0 + (size_t)w * D;
+            tau[w] = (double)(1.0f / variances[at]);
+            ntau2[w] = -(tau[w] * tau[w]);
+            mu[w] = (double)means[at];
+        }
+    }
+    auto fetch = [&](const double* __restrict__ from, int r) __attribute__((always_inline)) {      // zero outside [0, n); address clamped
+        const double v = from[(size_t)min(max(r, 0), n - 1) * S];
+        return r >= 0 && r < n ? v : 0.0;
+    };
+    double rows[2 * MLPG_SPAN + 1], xrows[2 * MLPG_SPAN + 1];      // before row s: rows[j + 1] = lambda[s - SPAN + j], xrows likewise of x~
+    rows[0] = 0.0; xrows[0] = 0.0;
+#pragma unroll
+    for (int j = 0; j < 2 * MLPG_SPAN; ++j) {
+        rows[j + 1] = fetch(lam, s_lo - MLPG_SPAN + j);
+        xrows[j + 1] = fetch(xt, s_lo - MLPG_SPAN + j);
+    }
+    for (int s0 = s_lo; s0 <= s_hi; s0 += MLPG_ROWS) {
+        double nxt[MLPG_ROWS], xnxt[MLPG_ROWS];
+#pragma unroll
+        for (int j = 0; j < MLPG_ROWS; ++j) {
+            nxt[j] = fetch(lam, s0 + j + MLPG_SPAN);
+            xnxt[j] = fetch(xt, s0 + j + MLPG_SPAN);
+        }
+#pragma unroll
+        for (int j = 0; j < MLPG_ROWS; ++j) {
+            if (s0 + j > s_hi) break;
+#pragma unroll
+            for (int i = 0; i < 2 * MLPG_SPAN; ++i) {
+                rows[i] = rows[i + 1];
+                xrows[i] = xrows[i + 1];
+            }
+            rows[2 * MLPG_SPAN] = nxt[j];
+            xrows[2 * MLPG_SPAN] = xnxt[j];
+#pragma unroll
+            for (int w = 0; w < MLPG_MAX_WINDOWS; ++w) {
+                double dot = 0.0, wx = 0.0;
+#pragma unroll
+                for (int i = 0; i <= 2 * MLPG_SPAN; ++i) dot += coeff[w][i] * rows[i];
+#pragma unroll
+                for (int i = 0; i <= 2 * MLPG_SPAN; ++i) wx += coeff[w][i] * xrows[i];
+                acc[w] += tau[w] * dot;
+                accv[w] += ntau2[w] * dot * (mu[w] - wx);
+            }
+        }
+    }
+#pragma unroll
+    for (int w = 0; w < MLPG_MAX_WINDOWS; ++w)
+        if (w < win.n) {
+            grad_means[at0 + (size_t)w * D] = (OutT)acc[w];
+            grad_variances[at0 + (size_t)w * D] = (OutT)accv[w];
+        }
 }
 
 static int mlpg_half_bandwidth(int n_windows, const int* win_l, const int* win_u) {
@@ -453,6 +464,74 @@ int mg_mlpg_grad_f32(const float* grad_out, const float* variances, int var_per_
     else
         MLPG_SCATTER(float);
     MG_CHECK_LAUNCH("mg_mlpg_grad_f32");
+    return MG_OK;
+}
+
+// two sets of the forward's planes: the forward system (x~ of all rows in its plane HB + 1) and the adjoint one (lambda)
+size_t mg_mlpg_grad_mv_workspace_bytes(int B, int T, int D, int padding, int n_windows, const int* win_l, const int* win_u) {
+    return 2 * mg_mlpg_workspace_bytes(B, T, D, padding, n_windows, win_l, win_u);
+}
+
+int mg_mlpg_grad_mv_f32(const float* grad_out, const float* means, const float* variances, const int64_t* seq_len, int B, int T, int D,
+                        int n_windows, const int* win_l, const int* win_u, const double* win_coeff, int padding, void* grad_means,
+                        void* grad_variances, int out_f64, void* workspace, size_t workspace_bytes, void* stream) {
+    MG_CHECK_ARG(grad_out && means && variances && grad_means && grad_variances && win_l && win_u && win_coeff,
+                 "mg_mlpg_grad_mv_f32: null argument");
+    MG_CHECK_ARG(B > 0 && T > 0 && D > 0 && padding >= 0, "mg_mlpg_grad_mv_f32: bad shape (B=%d T=%d D=%d padding=%d)", B, T, D, padding);
+    MG_CHECK_ARG(n_windows > 0 && n_windows <= MLPG_MAX_WINDOWS, "mg_mlpg_grad_mv_f32: 1..%d windows supported, got %d", MLPG_MAX_WINDOWS,
+                 n_windows);
+    MlpgWindows win = {};
+    win.n = n_windows;
+    for (int w = 0; w < n_windows; ++w) {
+        MG_CHECK_ARG(win_l[w] >= 0 && win_u[w] >= 0 && win_l[w] + win_u[w] + 1 <= MLPG_MAX_COEFF,
+                     "mg_mlpg_grad_mv_f32: window %d (l=%d, u=%d) is wider than %d coefficients", w, win_l[w], win_u[w], MLPG_MAX_COEFF);
+        win.l[w] = win_l[w];
+        win.u[w] = win_u[w];
+        for (int k = 0; k <= win_l[w] + win_u[w]; ++k) win.c[w][k] = win_coeff[w * MLPG_MAX_COEFF + k];
+    }
+    const size_t need = mg_mlpg_grad_mv_workspace_bytes(B, T, D, padding, n_windows, win_l, win_u);
+    MG_CHECK_ARG((size_t)(T + 2 * padding) * (size_t)B * D < ((size_t)1 << 31), "mg_mlpg_grad_mv_f32: too many unknowns for 32-bit frame x system ids");
+    if (!workspace || workspace_bytes < need) {
+        mg_set_error("mg_mlpg_grad_mv_f32: workspace of %zu bytes needed, got %zu", need, workspace_bytes);
+        return MG_EWORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t out_bytes = (size_t)B * T * n_windows * D * (out_f64 ? sizeof(double) : sizeof(float));
+    if (hipMemsetAsync(grad_means, 0, out_bytes, st) != hipSuccess || hipMemsetAsync(grad_variances, 0, out_bytes, st) != hipSuccess) {
+        mg_set_error("mg_mlpg_grad_mv_f32: memset failed");                  // frames past seq_len get no gradient
+        return MG_ELAUNCH;
+    }
+    const int hb = mlpg_half_bandwidth(n_windows, win_l, win_u);
+    const int n_max = T + 2 * padding;
+    const unsigned grid_a = (unsigned)mg_ceil_div((int64_t)n_max * B * D, 256), grid_b = (unsigned)mg_ceil_div((int64_t)B * D, 64);
+    const unsigned grid_c = (unsigned)mg_ceil_div((int64_t)T * B * D, 256), grid_d = (unsigned)mg_ceil_div((int64_t)2 * B * D, 64);
+    double* planes = (double*)workspace;
+    const size_t set_stride = (size_t)(hb + 2) * n_max * B * D;             // doubles per set: mg_mlpg_workspace_bytes / 8
+    const double* xs = planes + (size_t)(hb + 1) * n_max * B * D;
+    const double* lambda = xs + set_stride;
+#define MLPG_PAIR_RUN(HB)                                                                                                             \
+    do {                                                                                                                              \
+        hipLaunchKernelGGL((mlpg_band_pair_kernel<HB>), dim3(grid_a, 2), dim3(256), 0, st, means, grad_out, variances, seq_len, B, T,  \
+                           D, win, padding, planes, set_stride);                                                                      \
+        hipLaunchKernelGGL((mlpg_solve_pair_kernel<HB>), dim3(grid_b, 2), dim3(64), 0, st, seq_len, B, T, D, padding, planes,          \
+                           set_stride);                                                                                               \
+    } while (0)
+    if (hb == 2)
+        MLPG_PAIR_RUN(2);
+    else
+        MLPG_PAIR_RUN(4);
+#define MLPG_FOLD_MV(OutT)                                                                                                            \
+    do {                                                                                                                              \
+        hipLaunchKernelGGL((mlpg_fold_mv_kernel<OutT>), dim3(grid_c), dim3(256), 0, st, means, variances, seq_len, B, T, D, win,       \
+                           padding, lambda, xs, (OutT*)grad_means, (OutT*)grad_variances);                                            \
+        hipLaunchKernelGGL((mlpg_fold_mv_edge_kernel<OutT>), dim3(grid_d), dim3(64), 0, st, means, variances, seq_len, B, T, D, win,   \
+                           padding, lambda, xs, (OutT*)grad_means, (OutT*)grad_variances);                                            \
+    } while (0)
+    if (out_f64)
+        MLPG_FOLD_MV(double);
+    else
+        MLPG_FOLD_MV(float);
+    MG_CHECK_LAUNCH("mg_mlpg_grad_mv_f32");
     return MG_OK;
 }
 

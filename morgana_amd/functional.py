@@ -2052,6 +2052,33 @@ class MLPGFn(torch.autograd.Function):
         return ops.mlpg_backward(grad_out, variances, ctx.windows, padding_size=ctx.padding_size, seq_len=seq_len), None, None, None, None
 
 
+class MLPGVarFn(torch.autograd.Function):
+    """``ops.mlpg`` with gradients for ``means`` AND per-frame ``variances`` (a stream that predicts its variance under a trajectory or
+    global-variance loss): the backward solves the forward's system again next to the adjoint one, in one launch, and folds both
+    solutions through the windows (``ops.mlpg_backward_mv``).  Means, variances and ``seq_len`` are kept, the factorisation is not (see
+    ``MLPGFn``, which stays the layer for constant variances).  Variances (B, T, W*D) only: a global or per-item table is expanded by the
+    caller and autograd sums the expansion.  Double backward is NOT supported."""
+
+    @staticmethod
+    def forward(ctx, means, variances, windows, padding_size, seq_len):
+        if variances.shape != means.shape:
+            raise ValueError('MLPGVarFn takes per-frame variances shaped like the means %s, got %s: expand them to (B, T, W*D)'
+                             % (tuple(means.shape), tuple(variances.shape)))
+        ctx.windows, ctx.padding_size = windows, padding_size
+        ctx.save_for_backward(means, variances, seq_len)
+        return ops.mlpg(means, variances, windows, padding_size=padding_size, seq_len=seq_len)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        means, variances, seq_len = ctx.saved_tensors
+        if grad_out.dtype != torch.float32:
+            grad_out = grad_out.float()
+        grad_means, grad_variances = ops.mlpg_backward_mv(grad_out, means, variances, ctx.windows, padding_size=ctx.padding_size,
+                                                          seq_len=seq_len)
+        return grad_means, grad_variances, None, None, None
+
+
 class StreamLossFn(torch.autograd.Function):
     """Multi-stream loss of models/RNN_SPSS.py:120-139 in one pass: returns (loss, sigmoid of the BCE stream or None)."""
 

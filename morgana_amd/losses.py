@@ -162,6 +162,56 @@ def mdn_select(predictions, n_components, dim, seq_len=None, min_log_std=None):
     return ops.mdn_select(predictions.detach(), seq_len, int(n_components), int(dim), min_log_std=min_log_std)
 
 
+_HALF_LOG_2PI = 0.9189385332046727
+
+
+def gaussian_nll(predictions, targets, min_log_std=None):
+    """The per-frame, per-dimension term of ``gaussian``: predictions (..., 2 D) = ``[means | log standard deviations]`` against
+    targets (..., D) -> ``0.5 ((y - mu) exp(-s'))^2 + s' + 0.5 log(2 pi)`` with ``s' = max(s, min_log_std)``, shaped like the targets.
+    Plain torch ops on whatever device and dtype the inputs have; autograd flows through them (a floored s gets gradient 0)."""
+    dim = targets.shape[-1]
+    if predictions.shape[-1] != 2 * dim:
+        raise ValueError('gaussian: predictions %s are not 2 D = 2 * %d columns wide ([means | log standard deviations])'
+                         % (tuple(predictions.shape), dim))
+    mean, log_std = predictions[..., :dim], predictions[..., dim:]
+    if min_log_std is not None:
+        log_std = torch.clamp(log_std, min=float(min_log_std))
+    z = (targets - mean) * torch.exp(-log_std)
+    return 0.5 * (z * z) + log_std + _HALF_LOG_2PI
+
+
+def gaussian(predictions, targets, seq_len=None, min_log_std=None):
+    r"""Masked negative log likelihood of a diagonal Gaussian whose mean AND standard deviation the model predicts per frame (the
+    single-Gaussian trajectory model of Hashimoto et al. 2016), with the per-utterance averaging of ``mse``, in nats per dimension:
+    the value of ``mdn`` at ``n_components=1``.  The reference has no such loss.
+
+    predictions (B, T, 2 D) float32 ``[means | log standard deviations s]`` - a column slice of a wider tensor is read in place;
+    targets (B, T, D) float32.  Per element ``0.5 ((y - mu) exp(-s'))^2 + s' + 0.5 log(2 pi)``, ``s' = max(s, min_log_std)``
+    (``torch.clamp``'s rule: a floored s gets gradient 0); the loss is ``mean_{b,d}( sum_{t < n_b} l[b,t,d] / n_b )``.  Built on
+    ``sequence_loss``: the per-element term runs as torch ops (``gaussian_nll``), the reduction and its backward on csrc/seqmean.hip -
+    and with ``sequence_loss``'s rule for pad frames (every frame is read: a NaN there gives NaN), not ``mdn``'s.  A fused one-pass
+    kernel for it is not provided."""
+    if not isinstance(predictions, torch.Tensor) or predictions.dim() != 3:
+        raise ValueError('gaussian: predictions must be a (B, T, 2 D) tensor')
+    if not isinstance(targets, torch.Tensor) or targets.dim() != 3:
+        raise ValueError('gaussian: targets must be a (B, T, D) tensor')
+    if predictions.dtype != torch.float32:
+        raise TypeError('gaussian: predictions must be torch.float32, got %s' % predictions.dtype)
+    if predictions.shape[2] != 2 * targets.shape[2]:
+        raise ValueError('gaussian: predictions %s are not 2 D = 2 * %d columns wide ([means | log standard deviations])'
+                         % (tuple(predictions.shape), targets.shape[2]))
+    if targets.shape[1] != predictions.shape[1]:
+        raise RuntimeError('The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton dimension 1'
+                           % (predictions.shape[1], targets.shape[1]))
+    if targets.dtype != torch.float32:
+        targets = targets.float()
+
+    def gaussian_feature_loss(p, y):
+        return gaussian_nll(p, y, min_log_std)
+
+    return sequence_loss(gaussian_feature_loss)(predictions, targets.detach(), seq_len)
+
+
 def _gv_seq_len(what, x, seq_len):
     if not isinstance(x, torch.Tensor) or x.dim() != 3:
         raise ValueError('%s: a (B, T, D) tensor is wanted, got %s' % (what, tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)))

@@ -184,7 +184,16 @@ class Stream(object):
     under the PER-FRAME variances ``variance * std_dev^2``.  Such a stream takes no trajectory loss.
     ``gv_weight`` > 0 (delta streams only) adds a global-variance term on the same differentiable trajectory, against over-smoothing:
     ``gv_weight * losses.gv(normalised trajectory, normalised_<name>, n_frames, log=gv_log)``; with ``trajectory_weight`` as well the
-    trajectory is solved and normalised once."""
+    trajectory is solved and normalised once.
+    ``loss='gaussian'`` (with an optional floor ``min_log_std``) makes a delta stream that predicts its own variance (the single
+    Gaussian per frame of Hashimoto et al. 2016): it owns ``width`` = 2 dim columns, ``[means | log standard deviations s]``, is
+    scored by ``losses.gaussian`` against ``normalised_<name>_deltas`` and is a delta stream for target, normaliser, trajectory and
+    metrics.  Its raw slice goes out as ``<name>_gaussian`` (what the loss reads), the means slice as ``normalised_<name>_deltas``
+    and ``exp(2 max(s, min_log_std))`` as ``normalised_<name>_deltas_variance``; MLPG runs on the denormalised means under the
+    per-frame variances ``variance * std_dev^2``, as for an 'mdn' stream.  Unlike that one it TAKES ``trajectory_weight`` and
+    ``gv_weight``: the mean and the variance are differentiable functions of the weights, and the trajectory then comes from
+    ``viz.synthesis.mlpg_trajectory(..., variance_grad=True)``, whose backward trains both (csrc/mlpg.hip, mg_mlpg_grad_mv_f32);
+    without a weight the two outputs are detached."""
 
     def __init__(self, name, dim, loss='mse', metric=None, voicing='vuv', trajectory_weight=0., trajectory_loss=None, n_components=1,
                  min_log_std=None, gv_weight=0., gv_log=True):
@@ -194,7 +203,10 @@ class Stream(object):
         self.n_components, self.min_log_std = int(n_components), None if min_log_std is None else float(min_log_std)
         if self.is_mdn and self.n_components < 1:
             raise ValueError('stream %r: an \'mdn\' stream needs n_components >= 1, got %r' % (name, n_components))
-        if not self.is_mdn and (self.n_components != 1 or min_log_std is not None):
+        if self.is_gaussian and self.n_components != 1:
+            raise ValueError('stream %r: n_components belongs to an \'mdn\' stream: a \'gaussian\' stream is one Gaussian per frame, got '
+                             'n_components=%r' % (name, n_components))
+        if not self.is_mdn and not self.is_gaussian and (self.n_components != 1 or min_log_std is not None):
             raise ValueError('stream %r: n_components and min_log_std belong to an \'mdn\' stream: a %r stream has no mixture'
                              % (name, loss))
         if self.is_mdn and (self.trajectory_weight > 0. or trajectory_loss is not None):
@@ -220,15 +232,21 @@ class Stream(object):
 
     @property
     def is_delta(self):
-        return self.loss == 'mse' or self.loss == 'mdn' or callable(self.loss)
+        return self.loss == 'mse' or self.loss == 'mdn' or self.loss == 'gaussian' or callable(self.loss)
 
     @property
     def is_mdn(self):
         return self.loss == 'mdn'
 
     @property
+    def is_gaussian(self):
+        return self.loss == 'gaussian'
+
+    @property
     def width(self):
-        """Columns of the prediction the stream owns: ``dim``, or K (1 + 2 dim) for a mixture-density stream."""
+        """Columns of the prediction the stream owns: ``dim``, K (1 + 2 dim) for a mixture-density stream, 2 dim for a 'gaussian' one."""
+        if self.is_gaussian:
+            return 2 * self.dim
         return losses.mdn_width(self.n_components, self.dim) if self.is_mdn else self.dim
 
     @property
@@ -300,6 +318,10 @@ class StreamModel(BaseSPSS):
         if fused_loss and mixtures:
             raise ValueError('StreamModel: fused_loss=True cannot score the stream(s) %s with a mixture-density loss: the one-pass '
                              'multi-stream kernel has no MDN term (use fused_loss=False)' % ', '.join(mixtures))
+        gaussians = [st.name for st in self.streams if st.is_gaussian]
+        if fused_loss and gaussians:
+            raise ValueError('StreamModel: fused_loss=True cannot score the stream(s) %s with a Gaussian likelihood: the one-pass '
+                             'multi-stream kernel has no such term (use fused_loss=False)' % ', '.join(gaussians))
         self.speaker_id_list = speaker_id_list
         self.fused_upsample, self.fused_loss, self.generate = fused_upsample, fused_loss, generate
         registered = {st.metric[0]: st.metric[1]() for st in self.streams if st.metric is not None}
@@ -337,6 +359,15 @@ class StreamModel(BaseSPSS):
                 outputs[st.name + '_mdn'] = part          # what the loss reads (the column slice, in place)
                 _, outputs[st.output_key], outputs[st.output_key + '_variance'] = losses.mdn_select(
                     part, st.n_components, st.dim, seq_len=seq_len, min_log_std=st.min_log_std)
+            elif st.is_gaussian:
+                outputs[st.name + '_gaussian'] = part     # what the loss reads (the column slice, in place)
+                mean, log_std = part[..., :st.dim], part[..., st.dim:]
+                if st.min_log_std is not None:
+                    log_std = torch.clamp(log_std, min=st.min_log_std)
+                variance = torch.exp(2. * log_std)
+                if not st.differentiable_trajectory:      # nothing downstream trains them: MLPG and the metrics read values
+                    mean, variance = mean.detach(), variance.detach()
+                outputs[st.output_key], outputs[st.output_key + '_variance'] = mean, variance
             elif st.is_delta:
                 outputs[st.output_key] = part
             elif st.is_categorical:
@@ -349,15 +380,18 @@ class StreamModel(BaseSPSS):
     def _generating(self):
         return self.generate and all(_has_delta_params(self.normalisers, st.name) for st in self.streams if st.is_delta)
 
-    def _trajectory(self, name, pred_norm_deltas, seq_len=None, speaker_index=None, differentiable=False, norm_variance=None):
+    def _trajectory(self, name, pred_norm_deltas, seq_len=None, speaker_index=None, differentiable=False, norm_variance=None,
+                    variance_grad=False):
         """Denormalised deltas -> most probable static trajectory under the global delta variances, padding 100
         (models/RNN_SPSS.py:107-118, models/f0_test_model.py:83-89), without leaving the device.  With a speaker-dependent
         normaliser: each utterance under the delta variances of its own speaker (row ``speaker_index[b]`` of the tables).
         ``differentiable``: the same solve with the gradient flowing back to ``pred_norm_deltas`` (a stream with a trajectory loss).
         ``norm_variance`` (B, T, D): per-frame variances in the normalised space (a mixture-density stream's selected component);
-        MLPG then runs under ``norm_variance * std_dev^2`` per frame instead of the global ``std_dev^2``."""
+        MLPG then runs under ``norm_variance * std_dev^2`` per frame instead of the global ``std_dev^2``.
+        ``variance_grad`` (a 'gaussian' stream, with ``differentiable`` and ``norm_variance``): the gradient flows back to
+        ``norm_variance`` as well (``viz.synthesis.mlpg_trajectory(..., variance_grad=True)``)."""
         normaliser = self.normalisers[name]
-        if norm_variance is not None and differentiable:
+        if norm_variance is not None and differentiable and not variance_grad:
             raise ValueError('stream %r: per-frame variances have no differentiable trajectory' % (name,))
         if not differentiable:
             pred_norm_deltas = pred_norm_deltas.detach()
@@ -368,11 +402,18 @@ class StreamModel(BaseSPSS):
             pred_deltas = normaliser.denormalise(pred_norm_deltas, speaker_index, deltas=True)
             index = normaliser.speaker_index(speaker_index, pred_deltas.device)
             std_dev = ops.item_rows(normaliser.tables(pred_deltas.device, deltas=True)[1], index)
+            if differentiable and variance_grad:
+                return viz.synthesis.mlpg_trajectory(pred_deltas, norm_variance * (std_dev ** 2)[:, None, :], padding_size=100,
+                                                     seq_len=seq_len, variance_grad=True)
             if differentiable:
                 return viz.synthesis.mlpg_trajectory(pred_deltas, std_dev ** 2, padding_size=100, seq_len=seq_len)
             variances = std_dev ** 2 if norm_variance is None else norm_variance.detach() * (std_dev ** 2)[:, None, :]
             return ops.mlpg(pred_deltas, variances, viz.synthesis.DEFAULT_WINDOWS, padding_size=100, seq_len=seq_len)
         pred_deltas = normaliser.denormalise(pred_norm_deltas, deltas=True)
+        if differentiable and variance_grad:
+            std_dev = normaliser.delta_params_torch['std_dev'].to(device=pred_deltas.device, dtype=torch.float32)
+            return viz.synthesis.mlpg_trajectory(pred_deltas, norm_variance * std_dev ** 2, padding_size=100, seq_len=seq_len,
+                                                 variance_grad=True)
         if norm_variance is not None:
             std_dev = normaliser.delta_params_torch['std_dev'].to(device=pred_deltas.device, dtype=torch.float32)
             return ops.mlpg(pred_deltas, norm_variance.detach() * std_dev ** 2, viz.synthesis.DEFAULT_WINDOWS, padding_size=100,
@@ -390,7 +431,11 @@ class StreamModel(BaseSPSS):
             # a stream with a trajectory loss: the differentiable solve, on the current stream (its backward runs where autograd puts it)
             for st in self.streams:
                 if st.is_delta and st.differentiable_trajectory:
-                    outputs[st.name] = self._trajectory(st.name, outputs[st.output_key], n_frames, speaker_index, differentiable=True)
+                    if st.is_gaussian:
+                        outputs[st.name] = self._trajectory(st.name, outputs[st.output_key], n_frames, speaker_index, differentiable=True,
+                                                            norm_variance=outputs[st.output_key + '_variance'], variance_grad=True)
+                    else:
+                        outputs[st.name] = self._trajectory(st.name, outputs[st.output_key], n_frames, speaker_index, differentiable=True)
             delta = [st for st in self.streams if st.is_delta and not st.differentiable_trajectory]
             first = outputs[delta[0].output_key] if delta else None
             if len(delta) > 1 and TRAJECTORY_STREAMS and torch.is_tensor(first) and first.is_cuda:
@@ -486,6 +531,11 @@ class StreamModel(BaseSPSS):
             if st.is_mdn:
                 total = total + losses.mdn(output_features[st.name + '_mdn'], self._target(features, st), n_frames,
                                            n_components=st.n_components, min_log_std=st.min_log_std)
+            elif st.is_gaussian:
+                total = total + losses.gaussian(output_features[st.name + '_gaussian'], self._target(features, st), n_frames,
+                                                min_log_std=st.min_log_std)
+                if st.differentiable_trajectory:
+                    total = total + self._trajectory_loss(features, output_features, st)
             elif st.is_delta:
                 stream_loss = st.loss if callable(st.loss) else losses.mse
                 total = total + stream_loss(output_features[st.output_key], self._target(features, st), n_frames)
@@ -589,12 +639,20 @@ class GRUF0Model(StreamModel):
     MSE and the LF0 RMSE in Hz over the frames the DATA calls voiced (``features['vuv']``, :101-103).  Same constructor arguments and
     state_dict keys (``layers.0.weight``, ``layers.3.layer.weight_ih_l0`` ...).  ``n_components`` > 0 makes the lf0 stream a
     mixture-density stream of that many components (``Stream(loss='mdn')``; ``min_log_std``: its floor) and the last Linear
-    ``n_components * (1 + 2 * output_dim)`` wide; 0 is the reference's model."""
+    ``n_components * (1 + 2 * output_dim)`` wide; 0 is the reference's model.  ``predict_variance=True`` makes it a 'gaussian' stream
+    (``Stream(loss='gaussian')``: mean and log standard deviation per frame, the last Linear ``2 * output_dim`` wide), which composes
+    with ``trajectory_weight``, ``gv_weight`` and ``min_log_std`` and is refused together with ``n_components`` > 0."""
 
     def __init__(self, dropout_prob=0., input_dim=600 + 9, output_dim=1 * 3, precision=None, fused_upsample=True, generate=True,
-                 speaker_id_list=None, trajectory_weight=0., n_components=0, min_log_std=None, gv_weight=0.):
+                 speaker_id_list=None, trajectory_weight=0., n_components=0, min_log_std=None, gv_weight=0., predict_variance=False):
         self.input_dim, self.output_dim = input_dim, output_dim
-        if n_components > 0:
+        if predict_variance and n_components > 0:
+            raise ValueError('GRUF0Model: predict_variance=True is one Gaussian per frame; it does not go with n_components=%r (a '
+                             'mixture-density stream)' % (n_components,))
+        if predict_variance:
+            stream = Stream('lf0', output_dim, 'gaussian', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'),
+                            trajectory_weight=trajectory_weight, min_log_std=min_log_std, gv_weight=gv_weight)
+        elif n_components > 0:
             stream = Stream('lf0', output_dim, 'mdn', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'),
                             trajectory_weight=trajectory_weight, n_components=n_components, min_log_std=min_log_std,
                             gv_weight=gv_weight)

@@ -2769,6 +2769,46 @@ def mlpg_backward(grad_out, variances, windows, padding_size=0, seq_len=None, ou
     return grad_means
 
 
+def mlpg_backward_mv(grad_out, means, variances, windows, padding_size=0, seq_len=None, out_dtype=torch.float32):
+    """The gradients of ``mlpg``'s trajectory with respect to its means AND its per-frame variances (csrc/mlpg.hip,
+    mg_mlpg_grad_mv_f32): grad_out (B, T, D), means and variances (B, T, W*D) f32 -> (grad_means, grad_variances), both (B, T, W*D),
+    zero past seq_len (whose frames are read in no input).  The forward's system and the adjoint one are solved side by side in one
+    launch, then one window pass; grad_means equals ``mlpg_backward``'s bit for bit.  Per-frame variances only: a global (W*D,) or
+    per-item (B, W*D) table is expanded by the caller, and autograd sums the expansion."""
+    lib = _lib.load()
+    for name, value in (('grad_out', grad_out), ('means', means), ('variances', variances)):
+        if not isinstance(value, torch.Tensor):
+            raise TypeError('%s must be a torch.Tensor, got %s' % (name, type(value)))
+    if grad_out.dim() != 3:
+        raise ValueError('grad_out must have shape (batch, time, features), got %s' % (tuple(grad_out.shape),))
+    b, t, d = grad_out.shape
+    n_win = len(windows)
+    if n_win == 0 or n_win > MLPG_MAX_WINDOWS:
+        raise ValueError('%d windows (1..%d supported)' % (n_win, MLPG_MAX_WINDOWS))
+    width = n_win * d
+    if tuple(means.shape) != (b, t, width):
+        raise ValueError('means %s do not fit grad_out %s under %d windows: %s wanted' % (tuple(means.shape), (b, t, d), n_win, (b, t, width)))
+    if tuple(variances.shape) != (b, t, width):
+        raise ValueError('mlpg_backward_mv: variances %s are not per frame %s: expand them to (B, T, W*D) (variances.expand(%d, %d, %d)) so '
+                         'that autograd sums the expansion' % (tuple(variances.shape), (b, t, width), b, t, width))
+    grad_out = _require(grad_out, torch.float32, 'grad_out')
+    means = _require(means, torch.float32, 'means')
+    variances = _require(variances, torch.float32, 'variances')
+    win_l, win_u, win_c = _window_arrays(windows)
+    if seq_len is not None:
+        seq_len = _require(seq_len, torch.int64, 'seq_len')
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError('out_dtype must be torch.float32 or torch.float64')
+    grad_means = torch.empty((b, t, width), dtype=out_dtype, device=grad_out.device)
+    grad_variances = torch.empty((b, t, width), dtype=out_dtype, device=grad_out.device)
+    nbytes = lib.mg_mlpg_grad_mv_workspace_bytes(b, t, d, int(padding_size), n_win, win_l, win_u)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=grad_out.device)
+    _lib.check(lib.mg_mlpg_grad_mv_f32(_p(grad_out), _p(means), _p(variances), _p(seq_len), b, t, d, n_win, win_l, win_u, win_c,
+                                       int(padding_size), _p(grad_means), _p(grad_variances), int(out_dtype == torch.float64), _p(ws),
+                                       ws.numel(), _stream()), 'mg_mlpg_grad_mv_f32')
+    return grad_means, grad_variances
+
+
 DELTAS_EDGE_REPLICATE, DELTAS_EDGE_ZERO =_lib.MG_DELTAS_EDGE_REPLICATE, _lib.MG_DELTAS_EDGE_ZERO
 DELTAS_EDGES = {'replicate': DELTAS_EDGE_REPLICATE, 'zero': DELTAS_EDGE_ZERO}
 

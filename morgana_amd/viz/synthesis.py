@@ -68,12 +68,15 @@ def MLPG(means, variances, windows=None, padding_size=0, seq_len=None):
     return out if as_tensor else out.cpu().numpy()    # :176-178
 
 
-def mlpg_trajectory(means, variances, windows=None, padding_size=0, seq_len=None):
+def mlpg_trajectory(means, variances, windows=None, padding_size=0, seq_len=None, variance_grad=False):
     r"""``MLPG`` as a differentiable layer (trajectory / minimum-generation-error training; the reference's host MLPG has no gradient).
 
     means : (batch_size, seq_len, feat_dim) float32 device tensor; variances : (feat_dim,) global, the same shape as ``means`` or
     (batch_size, feat_dim) per item, float32 on the same device - constants: one that requires grad is a ValueError; windows,
     padding_size, seq_len as for ``MLPG``.  Device tensors only, always batched.
+    variance_grad : True makes the variances a trained input as well (a stream that predicts its variance): they must be per frame,
+    the same shape as ``means`` - expand a global or per-item table, autograd sums the expansion - and the backward returns both
+    gradients from one pair of side-by-side solves (``functional.MLPGVarFn``).  The forward is the same launch either way.
 
     Returns the most probable trajectory (batch_size, seq_len, feat_dim // len(windows)), float32, zero past ``seq_len``, with a
     gradient for ``means``: one more banded solve with the forward's matrix and a window pass (``csrc/mlpg.hip``).
@@ -81,12 +84,18 @@ def mlpg_trajectory(means, variances, windows=None, padding_size=0, seq_len=None
     for name, value in (('means', means), ('variances', variances)):
         if not isinstance(value, torch.Tensor):
             raise TypeError('mlpg_trajectory takes device tensors; %s is %s (MLPG takes arrays)' % (name, type(value)))
-    if variances.requires_grad:
-        raise ValueError('mlpg_trajectory has no gradient for its variances (they are normaliser constants): detach them')
+    if variances.requires_grad and not variance_grad:
+        raise ValueError('mlpg_trajectory has no gradient for its variances (they are normaliser constants): detach them, or pass '
+                         'variance_grad=True with per-frame variances to train them')
+    if variance_grad and variances.shape != means.shape:
+        raise ValueError('mlpg_trajectory(variance_grad=True) takes per-frame variances shaped like the means %s, got %s: expand them to '
+                         '(B, T, W*D) so that autograd sums the expansion' % (tuple(means.shape), tuple(variances.shape)))
     if windows is None:
         windows = DEFAULT_WINDOWS
     if seq_len is not None:
         if not isinstance(seq_len, torch.Tensor):
             raise TypeError('mlpg_trajectory takes device tensors; seq_len is %s' % type(seq_len))
         seq_len = seq_len.reshape(-1).to(device=means.device, dtype=torch.int64)
+    if variance_grad:
+        return functional.MLPGVarFn.apply(means, variances, windows, padding_size, seq_len)
     return functional.MLPGFn.apply(means, variances, windows, padding_size, seq_len)
