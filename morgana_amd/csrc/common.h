@@ -37,6 +37,26 @@ extern int g_mg_tuning[];
 
 static inline size_t mg_align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
+// Write-through (sc1) stores for the bulk outputs of the phone-rate step's launches (the device helpers are below): a launch that
+// is one tile / split / row block per workgroup ends with everything it wrote dirty in the eight L2s, and the kernel boundary
+// behind it writes that back before the next launch starts; written through, the bytes leave during the epilogue's own work.
+// Same bytes either way.  One bit per launch; MG_WT_DEFAULT holds the launches where the same-box A/B showed a gain (DESIGN.md
+// section 4.1 has the table).  MG_TUNE_AB 85 (A/B): plain write-back stores everywhere; lab builds: 300 + mask (1, 4 or 5) picks the launches.
+#define MG_WT_FWD 1      // layer-1 forward in the phone-rate step's first launch (phone_front_gemm_kernel): H1
+#define MG_WT_PAIR 4     // wgrad_dgrad_pair_kernel: dZ1 and the layer-2 slabs
+// Measured one launch at a time (same box, three interleaved rounds, C2 step against 0.1057 ms with plain stores): FWD -1.5 us,
+// PAIR -2.3 us; the layer-1 weight gradient -0.2 us (inside the noise: its 4-byte lanes write partial lines through), the update
+// kernel +0.4 us, the layers 2-4 pass +24 us (4-byte slab values) - those three keep plain stores and carry no switch.
+#define MG_WT_DEFAULT (MG_WT_FWD | MG_WT_PAIR)
+static inline int mg_wt_mask(void) {
+    const int ab = g_mg_tuning[MG_TUNE_AB];
+    if (ab == 85) return 0;
+#ifdef MG_EXPERIMENTS
+    if (ab >= 300 && ab <= 300 + (MG_WT_FWD | MG_WT_PAIR)) return (ab - 300) & (MG_WT_FWD | MG_WT_PAIR);
+#endif
+    return MG_WT_DEFAULT;
+}
+
 #ifdef __HIPCC__
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -156,6 +176,27 @@ __device__ __forceinline__ void mg_glds16(const void* src, unsigned char* lds_wa
                  : "=&s"(keep)
                  : "v"(src), "s"(lds_uni)
                  : "memory");
+}
+
+// Write-through stores (mg_wt_mask above): the value goes to memory with the sc1 bit, the line does not stay dirty in L2.
+// 4 bytes per lane: a relaxed agent-scope atomic store (global_store_dword ... sc1), which hipcc counts in its vmcnt bookkeeping like
+// any store.  16 bytes per lane: inline asm on a flat 64-bit address (the raw-buffer builtin of the recurrent kernels needs a
+// wave-uniform base and 32-bit offsets: the outputs here may be larger than 4 GB), which hipcc does NOT count - the hardware's vmcnt
+// counts it like a plain store (a kernel that counts vmcnt by hand keeps its numbers), a compiler wait for an older load only becomes
+// conservative, and nothing reads the data back inside the launch.  s_nop 1: the next instruction must not overwrite the data
+// registers early.
+typedef unsigned int mg_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void mg_store_wt(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void mg_store_wt16(void* p, mg_u32x4 v) {
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
+// the form chosen by a wave-uniform flag (a kernel argument)
+template <typename T>
+__device__ __forceinline__ void mg_store_sel(bool wt, T* p, T v) {
+    if (wt) mg_store_wt(p, v); else *p = v;
+}
+__device__ __forceinline__ void mg_store16_sel(bool wt, void* p, mg_u32x4 v) {
+    if (wt) mg_store_wt16(p, v); else *reinterpret_cast<mg_u32x4*>(p) = v;
 }
 
 // Sum over each row of 16 lanes, in every lane of the row, on the DPP path (row_ror 8, 4, 2, 1: four VALU instructions, where four

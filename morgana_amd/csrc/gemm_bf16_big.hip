@@ -73,7 +73,8 @@ __device__ __forceinline__ void gemm_nt_big_body(unsigned char* __restrict__ sme
                                                  int lda, const int32_t* __restrict__ rows, int64_t M, int K, const uint16_t* __restrict__ Bm,
                                                  int ldb, int N, const float* __restrict__ bias_in, const uint16_t* __restrict__ H, int ldh,
                                                  const int32_t* __restrict__ h_rows, void* __restrict__ Cv_in, int ldc, int tiles_m, int tiles_n,
-                                                 int c_f32, float* __restrict__ colsum = nullptr) {
+                                                 int c_f32, float* __restrict__ colsum = nullptr, int wt = 0) {
+    // wt: the bf16 rows of the dgrad epilogues as write-through stores (common.h) - the shared grid of the phone-rate backward
     const float* bias = bias_in;
     void* Cv = Cv_in;
     constexpr int BM = 256;
@@ -286,8 +287,8 @@ __device__ __forceinline__ void gemm_nt_big_body(unsigned char* __restrict__ sme
                         o_lo[e] = (__bf16)(x - (float)o_hi[e]);
                     }
                     uint16_t* crow = reinterpret_cast<uint16_t*>(Cv) + (size_t)row * ldc + col;
-                    *reinterpret_cast<bfv8*>(crow) = o_hi;
-                    *reinterpret_cast<bfv8*>(crow + (ldc >> 1)) = o_lo;
+                    mg_store16_sel(wt, crow, __builtin_bit_cast(mg_u32x4, o_hi));
+                    mg_store16_sel(wt, crow + (ldc >> 1), __builtin_bit_cast(mg_u32x4, o_lo));
                     continue;
                 }
 #pragma unroll
@@ -300,7 +301,7 @@ __device__ __forceinline__ void gemm_nt_big_body(unsigned char* __restrict__ sme
                     bfv8 o;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
-                    *reinterpret_cast<bfv8*>(reinterpret_cast<uint16_t*>(Cv) + (size_t)row * ldc + col) = o;
+                    mg_store16_sel(wt, reinterpret_cast<uint16_t*>(Cv) + (size_t)row * ldc + col, __builtin_bit_cast(mg_u32x4, o));
                 }
             }
         }
@@ -481,7 +482,9 @@ template <int BN, int EPI, bool STAG, int BK, int MODE = 0, int BMV = 256, int X
 __device__ __forceinline__ void gemm_nt_persist_body(unsigned char* __restrict__ smem, const unsigned block_id, const unsigned n_blocks,
                                                      const uint16_t* __restrict__ A, int lda, const int32_t* __restrict__ rows, int64_t M,
                                                      int K, const uint16_t* __restrict__ Bm, int ldb, int N, const float* __restrict__ bias,
-                                                     uint16_t* __restrict__ C, int ldc, int tiles_m, int tiles_n, int probe) {
+                                                     uint16_t* __restrict__ C, int ldc, int tiles_m, int tiles_n, int probe,
+                                                     int wt = 0) {
+    // wt: the epilogue's row segments as write-through stores (common.h, mg_store_wt16) - one tile per workgroup, nothing reads C here
     constexpr bool PIPE = MODE == 1, ROLE = MODE == 5, SPREAD = MODE == 2;
     constexpr int BM = 256;
     constexpr int WAVES_N = BN / 64;              // 4 or 2
@@ -953,6 +956,26 @@ __device__ __forceinline__ void gemm_nt_persist_body(unsigned char* __restrict__
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int q = 0; q < 4; ++q) bv[j][q] = *reinterpret_cast<const f32x4*>(bias_lds + wn0 + j * 32 + 8 * q + 4 * lh);
+        // the patch's 32 rows leave as 128-byte segments: four LDS reads, then four stores in the launch's form (one branch per four
+        // stores; every wave issues all of them - the counted vmcnt waits rely on NST stores per wave - rows past M go to the sink)
+        auto store_rows = [&](int i, int plane_off) {
+            mg_u32x4 o[4];
+            uint16_t* dst[4];
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int rl = it * 8 + prow;
+                o[it] = *reinterpret_cast<const mg_u32x4*>(patch + rl * SP + ((pchunk ^ (rl & 7)) << 4));
+                const int64_t m = m0 + wm0 + i * 32 + rl;
+                dst[it] = (m < M) ? C + (size_t)m * ldc + plane_off + n0 + wn0 + pchunk * 8 : g_ntp_sink + lane * 8;
+            }
+            if (wt) {
+#pragma unroll
+                for (int it = 0; it < 4; ++it) mg_store_wt16(dst[it], o[it]);
+            } else {
+#pragma unroll
+                for (int it = 0; it < 4; ++it) *reinterpret_cast<mg_u32x4*>(dst[it]) = o[it];
+            }
+        };
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             typedef __bf16 bfv2 __attribute__((ext_vector_type(2)));
@@ -979,15 +1002,7 @@ __device__ __forceinline__ void gemm_nt_persist_body(unsigned char* __restrict__
                     const int chunk = 4 * j + q;                              // columns 32 j + 8 q .. + 7 of the 64-wide strip
                     *reinterpret_cast<u32x2_t*>(patch + lr * SP + ((chunk ^ (lr & 7)) << 4) + 8 * lh) = pk;
                 }
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-                const int rl = it * 8 + prow;
-                const u32x4_t o = *reinterpret_cast<const u32x4_t*>(patch + rl * SP + ((pchunk ^ (rl & 7)) << 4));
-                const int64_t m = m0 + wm0 + i * 32 + rl;
-                uint16_t* dst = (m < M) ? C + (size_t)m * ldc + n0 + wn0 + pchunk * 8 : g_ntp_sink + lane * 8;
-                *reinterpret_cast<u32x4_t*>(dst) = o;     // unconditional: the counted vmcnt waits rely on NST stores per wave
-            }
+            store_rows(i, 0);
             if (X3) {
                 // the lo plane through the same wave-private patch (a wave's LDS operations complete in order)
 #pragma unroll
@@ -995,15 +1010,7 @@ __device__ __forceinline__ void gemm_nt_persist_body(unsigned char* __restrict__
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
                         *reinterpret_cast<u32x2_t*>(patch + lr * SP + (((4 * j + q) ^ (lr & 7)) << 4) + 8 * lh) = pk_lo[X3 ? j : 0][q];
-#pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-                    const int rl = it * 8 + prow;
-                    const u32x4_t o = *reinterpret_cast<const u32x4_t*>(patch + rl * SP + ((pchunk ^ (rl & 7)) << 4));
-                    const int64_t m = m0 + wm0 + i * 32 + rl;
-                    uint16_t* dst = (m < M) ? C + (size_t)m * ldc + (ldc >> 1) + n0 + wn0 + pchunk * 8 : g_ntp_sink + lane * 8;
-                    *reinterpret_cast<u32x4_t*>(dst) = o;
-                }
+                store_rows(i, ldc >> 1);
             }
         }
         MG_STAMP(tb);
@@ -1046,7 +1053,7 @@ template <int EPI, int BMV = 256, int X3 = 0, int BK = 32>
 __global__ __launch_bounds__(512) void phone_front_gemm_kernel(unsigned side_blocks, int wave_ints, PhoneFrontArgs pf, const uint16_t* __restrict__ A, int lda,
                                                                int64_t M, int K, const uint16_t* __restrict__ Bm, int ldb, int N,
                                                                const float* __restrict__ bias, uint16_t* __restrict__ C, int ldc, int tiles_m,
-                                                               int tiles_n) {
+                                                               int tiles_n, int wt) {
     static_assert(ntp_lds_bytes<256, BK, 0>() == ntp_lds_bytes<256, 32, 0>(), "the front's jobs were sized for this LDS block");
     __shared__ __attribute__((aligned(16))) unsigned char smem[ntp_lds_bytes<256, BK, 0>()];
     if (blockIdx.x < side_blocks) {
@@ -1061,7 +1068,7 @@ __global__ __launch_bounds__(512) void phone_front_gemm_kernel(unsigned side_blo
     }
     if (pf.probe & 8) return;
     gemm_nt_persist_body<256, EPI, false, BK, 0, BMV, X3>(smem, blockIdx.x - side_blocks, gridDim.x - side_blocks, A, lda, nullptr, M, K, Bm, ldb, N, bias, C,
-                                                     ldc, tiles_m, tiles_n, 0);
+                                                     ldc, tiles_m, tiles_n, 0, wt);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1092,11 +1099,12 @@ MG_STAMP_DECL(g_stamps_wg);
 // X3 (pair planes, see gemm_nt_big_body): dY [M, lddy] and A [M, lda] are [hi | lo] pairs (planes lddy / 2 / lda / 2 apart); the
 // workgroup walks its row range three times - (dY hi, A hi), (dY lo, A hi), (dY hi, A lo) - into the same accumulators.  No bias sums
 // here (the column sums of the fp32 gradient come from the kernel that produced it).
-template <int TKW, bool DYR = false, int NW = 1, int X3 = 0>
+template <int TKW, bool DYR = false, int NW = 1, int X3 = 0, bool WT = false>
 __device__ __forceinline__ void wgrad_big_body(unsigned char* __restrict__ smem, const unsigned block_id, const uint16_t* __restrict__ dY,
                                                int lddy, const uint16_t* __restrict__ A, int lda, const int32_t* __restrict__ rows, int64_t M,
                                                int N, int K, int m_chunk, float* __restrict__ slab, float* __restrict__ bslab, int64_t sstride,
                                                int xcd_group, const int32_t* __restrict__ dy_rows = nullptr) {
+    // WT: the slab and bias-slab values as write-through stores (common.h) - the shared grid of the phone-rate backward
     static_assert(!X3 || !DYR, "X3: no gathered dY form");
     // TKW = 10 / 8: the workgroup's tile is 128 x 640 / 128 x 512 (all k columns of the operand), 2 waves along n x 4 along k.
     // TKW = 5: 128 x 320 - HALF the k columns, two k halves per n tile (KH = 2), 4 waves along n x 2 along k: the same five k tiles per
@@ -1394,11 +1402,11 @@ __device__ __forceinline__ void wgrad_big_body(unsigned char* __restrict__ smem,
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = n0 + wn0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (row < N) out[(size_t)row * K + col] = acc[i][j][r];
+                if (row < N) mg_store_sel(WT, &out[(size_t)row * K + col], acc[i][j][r]);
             }
         }
     }
-    if (bias_valu && tid < BNT && n0 + tid < N) bslab[(size_t)s * sstride + n0 + tid] = bsum;
+    if (bias_valu && tid < BNT && n0 + tid < N) mg_store_sel(WT, &bslab[(size_t)s * sstride + n0 + tid], bsum);
     if ((bias_free || bias_extra) && lr == 0) {            // every column of the ones-product holds the same sums
 #pragma unroll
         for (int i = 0; i < TNW; ++i) {
@@ -1406,7 +1414,7 @@ __device__ __forceinline__ void wgrad_big_body(unsigned char* __restrict__ smem,
             for (int r = 0; r < 16; ++r) {
                 const int row = n0 + wn0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 const float v = bias_free ? acc[i][TKT - 1][r] : accb[kExtraBias ? i : 0][r];
-                if (row < N) bslab[(size_t)s * sstride + row] = v;
+                if (row < N) mg_store_sel(WT, &bslab[(size_t)s * sstride + row], v);
             }
         }
     }
@@ -1459,16 +1467,18 @@ __global__ __launch_bounds__(512) void wgrad_dgrad_pair_kernel(unsigned wg_block
                                                                int xcd_group, const uint16_t* __restrict__ WT, int ldwt,
                                                                const uint16_t* __restrict__ H, int ldh, void* __restrict__ dX, int lddx,
                                                                int tiles_m, int tiles_n, unsigned nt_blocks, ExpandReduceArgs xr, int riders,
-                                                               float* __restrict__ colsum) {
+                                                               float* __restrict__ colsum, int wt) {
     constexpr int LDS = WG_BIG_LDS(TKW) > NT_BIG_LDS(BN) ? WG_BIG_LDS(TKW) : NT_BIG_LDS(BN);
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDS];
-    if (blockIdx.x < wg_blocks)
-        wgrad_big_body<TKW, false, 1, (X3 && WG_STAGES(TKW) == 4) ? 2 : X3>(smem, blockIdx.x, dY, lddy, A, lda, nullptr, M, N, K, m_chunk, slab, bslab, sstride,
-                                                                            xcd_group);       // (native pair planes where the ring has four slots)
+    if (blockIdx.x < wg_blocks) {
+        constexpr int WX3 = (X3 && WG_STAGES(TKW) == 4) ? 2 : X3;       // (native pair planes where the ring has four slots)
+        if (wt) wgrad_big_body<TKW, false, 1, WX3, true>(smem, blockIdx.x, dY, lddy, A, lda, nullptr, M, N, K, m_chunk, slab, bslab, sstride, xcd_group);
+        else wgrad_big_body<TKW, false, 1, WX3, false>(smem, blockIdx.x, dY, lddy, A, lda, nullptr, M, N, K, m_chunk, slab, bslab, sstride, xcd_group);
+    }
     else if (blockIdx.x < wg_blocks + nt_blocks)
         // C[M, K] = dY[M, N] WT[K, N]^T with the sigmoid-grad epilogue: contraction N, output width K (as mg_linear_dgrad_bf16)
         gemm_nt_big_body<BN, EPI_SIGMOID_GRAD, X3>(smem, blockIdx.x - wg_blocks, dY, lddy, nullptr, M, N, WT, ldwt, K, nullptr, H, ldh, nullptr, dX,
-                                                   lddx, tiles_m, tiles_n, 0, colsum);
+                                                   lddx, tiles_m, tiles_n, 0, colsum, wt);
     else
         mg_expand_reduce_rider<512>(xr, (int)(blockIdx.x - wg_blocks - nt_blocks), riders, smem);
 }
@@ -1710,13 +1720,15 @@ int mg_launch_phone_front_gemm(const PhoneFrontArgs& pf, const uint16_t* A, int 
     PhoneFrontArgs a = pf;
     a.lds_ints = LDS_INTS;
 #ifdef MG_EXPERIMENTS      // lab builds only: 67 = idle riders (the front's outputs are not written), 70 + mask = parts of the rider off
-    if (g_mg_tuning[MG_TUNE_AB] == 67) a.lds_ints = 0;
-    if (g_mg_tuning[MG_TUNE_AB] >= 70 && g_mg_tuning[MG_TUNE_AB] < 86) a.probe = g_mg_tuning[MG_TUNE_AB] - 70;
+    if (g_mg_tuning[MG_TUNE_AB] == 67) a.lds_ints = 0;         // (masks 0 .. 14 only: 85 = 70 + 15, every part off, is now the product's plain-stores switch)
+    if (g_mg_tuning[MG_TUNE_AB] >= 70 && g_mg_tuning[MG_TUNE_AB] < 85) a.probe = g_mg_tuning[MG_TUNE_AB] - 70;
 #endif
     dim3 grid((unsigned)(side + g)), block(512);
 #define LAUNCH_PFG(EPI_, BMV_, BK_)                                                                                                             \
     hipLaunchKernelGGL((phone_front_gemm_kernel<EPI_, BMV_, 0, BK_>), grid, block, 0, st, (unsigned)side, wave_ints, a, A, lda, M, K, Bm, ldb, N, bias, C, \
-                       ldc, (int)tiles_m, tiles_n)
+                       ldc, (int)tiles_m, tiles_n, wt)
+    // one tile per workgroup here (blocks <= 224): H1 leaves as write-through stores (MG_TUNE_AB 85: plain)
+    const int wt = (mg_wt_mask() & MG_WT_FWD) ? 1 : 0;
     // MG_TUNE_AB 88 (A/B, round 5): 64-deep stages in two 64 KB slots - a DMA row is then a whole 128-byte line, half the line requests
     // of two 32-deep stages for the same bytes.  MEASURED EQUAL (C2 step 0.1041 vs 0.1050 ms, box noise): the front's intake follows the
     // bytes, not the request count; the pair-plane form with 64-deep three-pass stages (87) was 4 % slower than the native 32-deep one.
@@ -1793,27 +1805,29 @@ int mg_launch_wgrad_dgrad_pair(const uint16_t* dY, int lddy, const uint16_t* A, 
         if (riders < 1) riders = 1;
         if (riders > 1024) riders = 1024;
     }
+    // every workgroup of this grid owns a CU and runs one tile or split: its outputs leave as write-through stores (MG_TUNE_AB 85: plain)
+    const int wt = (mg_wt_mask() & MG_WT_PAIR) ? 1 : 0;
     if (x3) {
         // pair planes: no bias slabs (the sums of the split values would count hi twice); riders as in the bf16 form
         if (ksplit)
             hipLaunchKernelGGL((wgrad_dgrad_pair_kernel<4, 256, 1>), dim3((unsigned)(2 * S) + nt_blocks + riders), dim3(512), 0, st, (unsigned)(2 * S),
                                dY, lddy, A, lda, M, N, K, m_chunk, slab, (float*)nullptr, sstride, 1, WT, ldwt, A, lda, (void*)dX, lddx, (int)tiles_m,
-                               tiles_n, nt_blocks, xr, riders, colsum);
+                               tiles_n, nt_blocks, xr, riders, colsum, wt);
         else
             hipLaunchKernelGGL((wgrad_dgrad_pair_kernel<8, 256, 1>), dim3((unsigned)S + nt_blocks + riders), dim3(512), 0, st, (unsigned)S, dY, lddy,
                                A, lda, M, N, K, m_chunk, slab, (float*)nullptr, sstride, 1, WT, ldwt, A, lda, (void*)dX, lddx, (int)tiles_m, tiles_n,
-                               nt_blocks, xr, riders, colsum);
+                               nt_blocks, xr, riders, colsum, wt);
         *S_out = S;
         return 1;
     }
     if (ksplit)
         hipLaunchKernelGGL((wgrad_dgrad_pair_kernel<4, 256>), dim3((unsigned)(2 * S) + nt_blocks + riders), dim3(512), 0, st, (unsigned)(2 * S), dY,
                            lddy, A, lda, M, N, K, m_chunk, slab, slab + (int64_t)N * K, sstride, 1, WT, ldwt, A, lda, (void*)dX, lddx, (int)tiles_m,
-                           tiles_n, nt_blocks, xr, riders, (float*)nullptr);
+                           tiles_n, nt_blocks, xr, riders, (float*)nullptr, wt);
     else
         hipLaunchKernelGGL((wgrad_dgrad_pair_kernel<8, 256>), dim3((unsigned)S + nt_blocks + riders), dim3(512), 0, st, (unsigned)S, dY, lddy, A, lda,
                            M, N, K, m_chunk, slab, slab + (int64_t)N * K, sstride, 1, WT, ldwt, A, lda, (void*)dX, lddx, (int)tiles_m, tiles_n,
-                           nt_blocks, xr, riders, (float*)nullptr);
+                           nt_blocks, xr, riders, (float*)nullptr, wt);
     *S_out = S;
     return 1;
 }
@@ -1870,7 +1884,10 @@ int mg_launch_nt_persist_x3(const PhoneFrontArgs* pf, const uint16_t* A, int lda
     dim3 grid((unsigned)(side + g)), block(512);
 #define LAUNCH_PFG3(EPI_, BMV_, X3_, BK_)                                                                                                        \
     hipLaunchKernelGGL((phone_front_gemm_kernel<EPI_, BMV_, X3_, BK_>), grid, block, 0, st, (unsigned)side, wave_ints, a, A, lda, M, K, Bm, ldb, N, bias, C, \
-                       ldc, (int)tiles_m, tiles_n)
+                       ldc, (int)tiles_m, tiles_n, wt)
+    // write-through epilogue stores in the phone-rate step's first launch (the front rides: one tile per workgroup), as
+    // mg_launch_phone_front_gemm; the GEMM alone keeps plain stores
+    const int wt = ((mg_wt_mask() & MG_WT_FWD) && side > 0) ? 1 : 0;
     // X3_ = 2: the native form (one ring slot holds the 32-deep k-tile of all four planes); MG_TUNE_AB 89 (A/B): three passes over the
     // plane, 32-deep; 87 (A/B): three passes with 64-deep stages (whole-line DMA rows, 1.5x the bytes of the native form)
     const int ab3 = g_mg_tuning[MG_TUNE_AB];

@@ -1352,7 +1352,7 @@ static int f0_l2tail_launch(const char* name, const uint16_t* H1, int ldh1, int 
     // lab builds only: MG_TUNE_AB 64 = the producer / consumer role split (same results, measured slower); 1 .. 32 = the product
     // kernel with parts switched off (timing probes, results garbage)
     static const int wide_env = getenv("MG_L2TAIL_WIDE") ? atoi(getenv("MG_L2TAIL_WIDE")) : 0;      // lab: the wide form with every other switch at its default
-    if (g_mg_tuning[MG_TUNE_AB] == 69 || g_mg_tuning[MG_TUNE_AB] > 100 || (wide_env && g_mg_tuning[MG_TUNE_AB] == 0)) {          // the wide form and its timing probes
+    if (g_mg_tuning[MG_TUNE_AB] == 69 || (g_mg_tuning[MG_TUNE_AB] > 100 && g_mg_tuning[MG_TUNE_AB] < 300) || (wide_env && g_mg_tuning[MG_TUNE_AB] == 0)) {          // the wide form and its timing probes
         // (up to 256 slabs: the lab build's workspace holds them - the role split's ring lies behind the slab area)
         blocks = mg_launch_f0_l2tail_wide(H1, ldh1, W2, ldw2, b2, W3, b3, W4, b4, target, seq_len, M, B, T, grad_scale, pred, dZ2, lddz, slab,
                                           row_weight, rev, 256, st);
