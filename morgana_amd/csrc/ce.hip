@@ -14,6 +14,7 @@
 //       rescales the running sum at every new maximum; the plain form keeps the sum a blocked sum of exp(x - max): tests/ce_ref64.py.)
 // Pad frames (t >= n_b) read nothing: their gradient row is written as zero, their argmax as 0, their targets are never looked at.
 #include "common.h"
+#include "seq_reduce.h"
 
 #define CE_REG_MAX 1024      // widest row of the register path (16 values per lane)
 #define CE_ROWS_REG 16       // frames per workgroup, register path (4 per wave)
@@ -21,29 +22,6 @@
 #define CE_IGNORE (-100)     // F.cross_entropy's default ignore_index
 
 static inline int ce_rows_per_wg(int C) { return C <= CE_REG_MAX ? CE_ROWS_REG : CE_ROWS_WIDE; }
-
-__device__ __forceinline__ float ce_wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-// (value, index) of the maximum, the LOWEST index among equal maxima (torch.argmax on NaN-free rows)
-__device__ __forceinline__ void ce_argmax_merge(float& m, int& i, float om, int oi) {
-    if (om > m || (om == m && oi < i)) {
-        m = om;
-        i = oi;
-    }
-}
-
-__device__ __forceinline__ void ce_wave_argmax(float& m, int& i) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float om = __shfl_xor(m, off, 64);
-        const int oi = __shfl_xor(i, off, 64);
-        ce_argmax_merge(m, i, om, oi);
-    }
-}
 
 struct ce_args {
     const float* pred;
@@ -56,13 +34,6 @@ struct ce_args {
     float grad_scale;
 };
 
-__device__ __forceinline__ int64_t ce_valid_frames(const ce_args& a, int b) {
-    int64_t n_b = a.seq_len ? a.seq_len[b] : (int64_t)a.T;
-    if (n_b > a.T) n_b = a.T;
-    if (n_b < 0) n_b = 0;
-    return n_b;
-}
-
 // The target of a valid frame: 0 = score it, 1 = ignore_index (loss and gradient 0), 2 = outside [0, C) (NaN loss, zero gradient)
 __device__ __forceinline__ int ce_target_class(int64_t y, int C) { return y == CE_IGNORE ? 1 : (y < 0 || y >= C) ? 2 : 0; }
 
@@ -72,7 +43,7 @@ __global__ __launch_bounds__(256) void masked_ce_reg_kernel(ce_args a) {
     __shared__ float red[4];
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int C = a.C;
-    const int64_t n_b = ce_valid_frames(a, b);
+    const int64_t n_b = mg_valid_frames(a.seq_len, b, a.T);
     const float coef = a.grad_scale / ((float)n_b * (float)a.B);
     const int t0 = blockIdx.x * CE_ROWS_REG;
     float acc = 0.f;
@@ -102,9 +73,9 @@ __global__ __launch_bounds__(256) void masked_ce_reg_kernel(ce_args a) {
                 m = v[j];
                 im = lane + 64 * j;
             }
-        float mx = ce_wave_max(m);
+        float mx = mg_wave_max(m);
         if (a.argmax) {
-            ce_wave_argmax(m, im);
+            mg_wave_argmax(m, im);
             if (lane == 0) a.argmax[row] = im < C ? im : C - 1;
         }
         float s = 0.f;
@@ -139,7 +110,7 @@ __global__ __launch_bounds__(256) void masked_ce_wide_kernel(ce_args a) {
     __shared__ float red_s[4];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int C = a.C;
-    const int64_t n_b = ce_valid_frames(a, b);
+    const int64_t n_b = mg_valid_frames(a.seq_len, b, a.T);
     const float coef = a.grad_scale / ((float)n_b * (float)a.B);
     const int t0 = blockIdx.x * CE_ROWS_WIDE;
     float acc = 0.f;
@@ -164,7 +135,7 @@ __global__ __launch_bounds__(256) void masked_ce_wide_kernel(ce_args a) {
                 im = c;
             }
         }
-        ce_wave_argmax(m, im);
+        mg_wave_argmax(m, im);
         __syncthreads();                                  // the previous row's readers of red_* are done
         if (lane == 0) {
             red_m[wave] = m;
@@ -174,7 +145,7 @@ __global__ __launch_bounds__(256) void masked_ce_wide_kernel(ce_args a) {
         m = red_m[0];
         im = red_i[0];
 #pragma unroll
-        for (int w = 1; w < 4; ++w) ce_argmax_merge(m, im, red_m[w], red_i[w]);
+        for (int w = 1; w < 4; ++w) mg_argmax_merge(m, im, red_m[w], red_i[w]);
         const float mx = m;
         if (a.argmax && tid == 0) a.argmax[row] = im < C ? im : C - 1;
         float s = 0.f;
@@ -201,23 +172,9 @@ __global__ __launch_bounds__(256) void masked_ce_finish_kernel(const float* __re
                                                                int T, int chunks, float loss_weight, float loss_keep,
                                                                float* __restrict__ loss) {
     __shared__ float red[256];
-    float acc = 0.f;
-    for (int b = threadIdx.x; b < B; b += 256) {
-        float s = 0.f;
-        for (int c = 0; c < chunks; ++c) s += partial[(size_t)b * chunks + c];
-        int64_t n_b = seq_len ? seq_len[b] : (int64_t)T;
-        if (n_b > T) n_b = T;
-        if (n_b < 0) n_b = 0;
-        acc += s / (float)n_b;                            // 0 / 0 = NaN for an utterance without a valid frame (reference behaviour)
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
+    const float sum = mg_utterance_mean_sum(partial, seq_len, B, T, chunks, red);
     if (threadIdx.x == 0) {
-        const float l = loss_weight * (red[0] / (float)B);
+        const float l = loss_weight * (sum / (float)B);
         loss[0] = loss_keep != 0.f ? l + loss_keep * loss[0] : l;
     }
 }

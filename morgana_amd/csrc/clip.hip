@@ -18,6 +18,7 @@
 // MG_CLIP_MAX_BLOCKS workgroups of 256 threads, chunks a multiple of 1024 floats, so that every chunk starts at the buffer's own
 // misalignment and one scalar head of at most 3 elements brings each to 16-byte loads.
 #include "common.h"
+#include "seq_reduce.h"
 
 #define CLIP_THREADS 256
 #define CLIP_MIN_CHUNK 4096       // floats: 4 x 16 bytes per thread
@@ -28,16 +29,6 @@ static inline int64_t clip_chunk(int64_t n) {
     return even > CLIP_MIN_CHUNK ? even : CLIP_MIN_CHUNK;
 }
 static inline int clip_blocks(int64_t n) { return (int)mg_ceil_div(n, clip_chunk(n)); }
-
-// Sum over the workgroup, the same value in every thread: xor butterfly inside each wave, then the four wave sums in a fixed order.
-__device__ __forceinline__ double clip_block_sum(double v, double* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // [begin, end) of this workgroup's chunk, split into a scalar head up to the first 16-byte boundary, float4s and a scalar tail.
 struct clip_span {
@@ -76,7 +67,7 @@ __global__ __launch_bounds__(CLIP_THREADS) void grad_sumsq_kernel(const float* _
         const double x = (double)g[s.tail_begin + tid];
         acc += x * x;
     }
-    const double total = clip_block_sum(acc, red);
+    const double total = mg_block_sum_f64(acc, red);
     if (tid == 0) partial[blockIdx.x] = total;
 }
 
@@ -87,7 +78,7 @@ __global__ __launch_bounds__(CLIP_THREADS) void grad_clip_scale_kernel(float* __
     const int tid = threadIdx.x;
     double acc = 0.0;
     for (int i = tid; i < n_partial; i += CLIP_THREADS) acc += partial[i];
-    const double norm = sqrt(clip_block_sum(acc, red)) * inv_world;
+    const double norm = sqrt(mg_block_sum_f64(acc, red)) * inv_world;
     const double ratio = max_norm / (norm + 1e-6);
     const double clamped = ratio > 1.0 ? 1.0 : ratio;              // a NaN ratio stays NaN (torch.clamp(max=1.0))
     const float coef = (float)clamped;

@@ -2,7 +2,7 @@
 // running float64 state on the device: what the normaliser parameter files ({name}_mvn.json, {name}_minmax.json) are made of.
 // The reference takes those files from the un-vendored tts_data_tools; nothing in it computes them.
 //
-// Numerics.  No sum of raw squares: an accumulator sums d = x - k and d^2 in float64 for at most COLSTATS_FLUSH values, k being
+// Numerics.  No sum of raw squares: an accumulator sums d = x - k and d^2 in float64 for at most MG_MOMENTS_FLUSH values, k being
 // the first value it saw (x - k is exact or rounded once in float64, and small: the column's spread, not its offset), turns the sums
 // into (n, mean = k + s1 / n, M2 = s2 - s1^2 / n) and folds that chunk into its running (n, mean, M2) by Chan's update
 //     delta = mean_b - mean_a,   mean = mean_a + delta n_b / n,   M2 = M2_a + M2_b + delta^2 n_a n_b / n.
@@ -23,10 +23,9 @@
 // [first, last) is read.  Wide odd features (lcm(D, 4) > 1024: D = 609 -> W = 2436) take several quads per thread, one after the
 // other.  Launch 2 reads the job records (8 + 24 D bytes each, at most COLSTATS_MAX_JOBS of them) and the state.
 #include "common.h"
-#include "moments.h"      // mg_chan_merge: Chan's update, b folded into a
+#include "moments.h"      // the accumulator, the streaming pass, the tree and Chan's update; no fp pragma in front of it, on purpose
 
 #define COLSTATS_THREADS 256
-#define COLSTATS_FLUSH 32          // values per shifted chunk (a multiple of 4)
 #define COLSTATS_MAX_JOBS 1024     // workgroups of launch 1 when B allows: four per CU
 #define COLSTATS_MIN_STEPS 16      // steps per workgroup before an item is cut into more chunks
 #define COLSTATS_LDS_BYTES 65536
@@ -36,7 +35,6 @@
 struct colstats_plan {
     int vec;       // 4: 16-byte loads over the flat item (ld == D); 1: one element per load, any ld
     int W;         // elements per step, a multiple of D (and of 4 when vec == 4)
-    int passes;    // quads (elements) a thread owns, taken one after the other
 };
 
 static inline int colstats_gcd(int a, int b) {
@@ -54,11 +52,9 @@ static inline colstats_plan colstats_plan_of(int D, bool contiguous) {
     if (contiguous && 20 * unit + 8 * (int64_t)D <= COLSTATS_LDS_BYTES) {
         p.vec = 4;
         p.W = (int)(unit <= 1024 ? unit * (1024 / unit) : unit);
-        p.passes = (int)mg_ceil_div(p.W / 4 + 1, COLSTATS_THREADS);      // + 1: the quad past the end when the item starts off a boundary
     } else {
         p.vec = 1;
         p.W = D <= COLSTATS_THREADS ? D * (COLSTATS_THREADS / D) : D;
-        p.passes = (int)mg_ceil_div(p.W, COLSTATS_THREADS);
     }
     return p;
 }
@@ -83,14 +79,6 @@ __device__ __forceinline__ unsigned colstats_key(float v) {
 }
 __device__ __forceinline__ float colstats_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
-struct colstats_acc {
-    double anchor;             // the batch's anchor of this column: means are held as mean - anchor
-    double k, s1, s2;          // the open chunk: shift, sum (x - k), sum (x - k)^2
-    int cnt;
-    double rn, rmean, rm2;     // the chunks folded so far
-    float mn, mx;
-};
-
 // Means travel as (mean - anchor), anchor = the column's value in the first frame of the batch (0 if that is not finite): a mean
 // held in full would be rounded to 2^-53 |mean| at every merge, and the delta^2 terms would inherit that - relative to the
 // column's offset, not to its spread.  The anchor comes back once, where the batch meets the state.
@@ -111,42 +99,11 @@ __device__ __forceinline__ double colstats_anchor(const float* row, int col) {
     return __builtin_isfinite(v) ? (double)v : 0.0;
 }
 
-__device__ __forceinline__ void colstats_init(colstats_acc& a, double anchor) {
-    a.anchor = anchor;
-    a.k = a.s1 = a.s2 = 0.0;
-    a.cnt = 0;
-    a.rn = a.rmean = a.rm2 = 0.0;
-    a.mn = __builtin_inff();
-    a.mx = -__builtin_inff();
-}
-
-__device__ __forceinline__ void colstats_add(colstats_acc& a, float x) {
-    const double v = (double)x;
-    if (a.cnt == 0) a.k = v;
-    const double d = v - a.k;
-    a.s1 += d;
-    a.s2 += d * d;
-    a.cnt += 1;
-    a.mn = fminf(a.mn, x);
-    a.mx = fmaxf(a.mx, x);
-}
-
-__device__ __forceinline__ void colstats_flush(colstats_acc& a) {
-    if (a.cnt == 0) return;
-    const double n = (double)a.cnt;
-    const double mean = (a.k - a.anchor) + a.s1 / n;
-    double m2 = a.s2 - a.s1 * a.s1 / n;
-    if (m2 < 0.0) m2 = 0.0;                                  // rounding only; a NaN stays
-    mg_chan_merge(a.rn, a.rmean, a.rm2, n, mean, m2);
-    a.s1 = a.s2 = 0.0;
-    a.cnt = 0;
-}
-
 // Launch 1.  Job (b, c) writes one record: n, (mean - anchor)[D], M2[D] (float64), min[D], max[D] (float32) of its share of item b.
 template <int VEC>
 __global__ __launch_bounds__(COLSTATS_THREADS) void colstats_partial_kernel(const float* __restrict__ x, int64_t ld, int D, int T,
                                                                             const int64_t* __restrict__ offsets,
-                                                                            const int64_t* __restrict__ seq_len, int W, int passes,
+                                                                            const int64_t* __restrict__ seq_len, int W,
                                                                             unsigned char* __restrict__ records, size_t job_stride) {
     extern __shared__ __attribute__((aligned(16))) double s_colstats[];
     double* s_mean = s_colstats;                             // [W]
@@ -180,8 +137,6 @@ __global__ __launch_bounds__(COLSTATS_THREADS) void colstats_partial_kernel(cons
         return;
     }
     const float* base = x + lo * ld;
-    const int64_t E = len * D;                               // elements of the item (VEC == 4: ld == D)
-    const int pre = VEC == 4 ? (int)(((uintptr_t)base >> 2) & 3u) : 0;      // elements between the 16-byte boundary below and base
     const float* anchor_row = colstats_anchor_row(x, ld, gridDim.y, T, offsets, seq_len);
 
     for (int d = tid; d < D; d += COLSTATS_THREADS) {
@@ -190,129 +145,15 @@ __global__ __launch_bounds__(COLSTATS_THREADS) void colstats_partial_kernel(cons
     }
     __syncthreads();
 
-    for (int p = 0; p < passes; ++p) {
-        const int q = tid + COLSTATS_THREADS * p;
-        colstats_acc acc[VEC];
-        int since = 0;
-        if constexpr (VEC == 4) {
-            // element j of quad q of step m is item element m W + ent0 + j, for 0 <= ent0 + j < W
-            const int ent0 = 4 * q - pre;
-            if (ent0 + 3 < 0 || ent0 >= W) continue;         // no entry of this quad is inside a step
-            const bool inner = ent0 >= 0 && ent0 + 3 < W;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {                     // (an entry outside [0, W) never gets an element: any column will do)
-                const int ent = ent0 + j;
-                colstats_init(acc[j], colstats_anchor(anchor_row, ent >= 0 && ent < W ? ent % D : 0));
-            }
-            const float* src = base + ent0;
-            int64_t m = c;
-            if (inner) {
-                const int64_t mfull = E >= (int64_t)ent0 + 4 ? (E - ent0 - 4) / W + 1 : 0;      // steps whose whole quad is valid
-                for (; m + 3 * (int64_t)CH < mfull; m += 4 * (int64_t)CH) {
-                    f32x4 v[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(src + (m + (int64_t)u * CH) * W);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) colstats_add(acc[j], v[u][j]);
-                    }
-                    since += 4;
-                    if (since >= COLSTATS_FLUSH) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) colstats_flush(acc[j]);
-                        since = 0;
-                    }
-                }
-                for (; m < mfull; m += CH) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(src + m * W);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) colstats_add(acc[j], v[j]);
-                    if (++since >= COLSTATS_FLUSH) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) colstats_flush(acc[j]);
-                        since = 0;
-                    }
-                }
-            }
-            for (; m < NS; m += CH) {                         // quads across an end of the step or of the item: element by element
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int ent = ent0 + j;
-                    const int64_t e = m * W + ent;
-                    if (ent >= 0 && ent < W && e < E) colstats_add(acc[j], base[e]);
-                }
-                if (++since >= COLSTATS_FLUSH) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) colstats_flush(acc[j]);
-                    since = 0;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int ent = ent0 + j;
-                if (ent < 0 || ent >= W) continue;
-                colstats_flush(acc[j]);
-                s_mean[ent] = acc[j].rmean;
-                s_m2[ent] = acc[j].rm2;
-                s_n[ent] = (int)acc[j].rn;
-                const int col = ent % D;
-                atomicMin(&s_min[col], colstats_key(acc[j].mn));
-                atomicMax(&s_max[col], colstats_key(acc[j].mx));
-            }
-        } else {
-            const int ent = q;
-            if (ent >= W) continue;
-            const int erow = ent / D, col = ent - erow * D;
-            colstats_init(acc[0], colstats_anchor(anchor_row, col));
-            const float* src = base + (int64_t)erow * ld + col;
-            const int64_t row_step = (int64_t)RS * ld;
-            const int64_t mfull = len > erow ? (len - erow - 1) / RS + 1 : 0;       // steps in which frame m RS + erow exists
-            int64_t m = c;
-            for (; m + 3 * (int64_t)CH < mfull; m += 4 * (int64_t)CH) {
-                float v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) v[u] = src[(m + (int64_t)u * CH) * row_step];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) colstats_add(acc[0], v[u]);
-                since += 4;
-                if (since >= COLSTATS_FLUSH) {
-                    colstats_flush(acc[0]);
-                    since = 0;
-                }
-            }
-            for (; m < mfull; m += CH) {
-                colstats_add(acc[0], src[m * row_step]);
-                if (++since >= COLSTATS_FLUSH) {
-                    colstats_flush(acc[0]);
-                    since = 0;
-                }
-            }
-            colstats_flush(acc[0]);
-            s_mean[ent] = acc[0].rmean;
-            s_m2[ent] = acc[0].rm2;
-            s_n[ent] = (int)acc[0].rn;
-            atomicMin(&s_min[col], colstats_key(acc[0].mn));
-            atomicMax(&s_max[col], colstats_key(acc[0].mx));
-        }
-    }
-    __syncthreads();
-
-    // entries e and e + k D hold the same column: fold the upper half of the frames of a step onto the lower, level by level
-    for (int R = RS; R > 1;) {
-        const int half = (R + 1) >> 1;
-        const int n_pairs = (R - half) * D;
-        for (int i = tid; i < n_pairs; i += COLSTATS_THREADS) {
-            const int o = i + half * D;
-            double na = (double)s_n[i], ma = s_mean[i], Ma = s_m2[i];
-            mg_chan_merge(na, ma, Ma, (double)s_n[o], s_mean[o], s_m2[o]);
-            s_n[i] = (int)na;
-            s_mean[i] = ma;
-            s_m2[i] = Ma;
-        }
-        __syncthreads();
-        R = half;
-    }
+    // the steps c, c + CH, ... of the item (VEC == 4: ld == D)
+    mg_stream_moments<VEC, true>(
+        base, ld, 1, len, D, RS, W, (int64_t)c, (int64_t)CH, [&](int col) { return colstats_anchor(anchor_row, col); },
+        [&](int col, float mn, float mx) {
+            atomicMin(&s_min[col], colstats_key(mn));
+            atomicMax(&s_max[col], colstats_key(mx));
+        },
+        s_mean, s_m2, s_n);
+    mg_fold_step_frames(RS, D, s_mean, s_m2, s_n);
     for (int d = tid; d < D; d += COLSTATS_THREADS) {
         rec_mean[d] = s_mean[d];
         rec_m2[d] = s_m2[d];
@@ -460,10 +301,10 @@ int mg_column_stats_f32(const float* x, int64_t ld, int D, int B, int T, const i
     const dim3 grid((unsigned)ch, (unsigned)B);
     hipStream_t st = (hipStream_t)stream;
     if (p.vec == 4)
-        hipLaunchKernelGGL((colstats_partial_kernel<4>), grid, dim3(COLSTATS_THREADS), lds, st, x, ld, D, T, offsets, seq_len, p.W, p.passes,
+        hipLaunchKernelGGL((colstats_partial_kernel<4>), grid, dim3(COLSTATS_THREADS), lds, st, x, ld, D, T, offsets, seq_len, p.W,
                            (unsigned char*)workspace, stride);
     else
-        hipLaunchKernelGGL((colstats_partial_kernel<1>), grid, dim3(COLSTATS_THREADS), lds, st, x, ld, D, T, offsets, seq_len, p.W, p.passes,
+        hipLaunchKernelGGL((colstats_partial_kernel<1>), grid, dim3(COLSTATS_THREADS), lds, st, x, ld, D, T, offsets, seq_len, p.W,
                            (unsigned char*)workspace, stride);
     MG_CHECK_LAUNCH("mg_column_stats_f32");
     hipLaunchKernelGGL(colstats_merge_kernel, dim3((unsigned)mg_ceil_div(D, COLSTATS_MERGE_COLS), (unsigned)S), dim3(COLSTATS_THREADS), 0, st,

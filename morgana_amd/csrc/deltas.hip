@@ -18,6 +18,7 @@
 // A padded input whose output is packed has no offsets to search: every workgroup scans the clamped lengths once in LDS
 // (B <= MG_DELTAS_MAX_SCAN_ITEMS), the only use of LDS here.
 #include "common.h"
+#include "seq_reduce.h"
 
 #define DELTAS_THREADS 256
 #define DELTAS_CHUNK_ELEMS 2048      // input elements (rows x D) of one chunk when D % 4 == 0: two 16-byte trips per thread
@@ -67,31 +68,7 @@ __global__ __launch_bounds__(DELTAS_THREADS) void deltas_kernel(const float* __r
     const int tid = threadIdx.x;
     const int64_t* s_cum = s_deltas;
     if (MODE == DELTAS_TO_PACKED_SCAN) {
-        // exclusive scan of len_b = min(max(seq_len[b], 0), T_in): thread t owns items [t per, (t + 1) per)   (as unpad_rows_kernel)
-        int64_t* s_part = s_deltas + B + 1;
-        const int per = (B + DELTAS_THREADS - 1) / DELTAS_THREADS;
-        const int lo = tid * per < B ? tid * per : B, hi = lo + per < B ? lo + per : B;
-        int64_t sum = 0;
-        for (int b = lo; b < hi; ++b) {
-            const int64_t len = seq_len[b];
-            sum += len < 0 ? 0 : len > T_in ? T_in : len;
-        }
-        s_part[tid] = sum;
-        __syncthreads();
-        for (int off = 1; off < DELTAS_THREADS; off <<= 1) {
-            const int64_t v = tid >= off ? s_part[tid - off] : 0;
-            __syncthreads();
-            s_part[tid] += v;
-            __syncthreads();
-        }
-        int64_t run = s_part[tid] - sum;
-        for (int b = lo; b < hi; ++b) {
-            const int64_t len = seq_len[b];
-            s_deltas[b] = run;
-            run += len < 0 ? 0 : len > T_in ? T_in : len;
-        }
-        if (tid == DELTAS_THREADS - 1) s_deltas[B] = s_part[tid];
-        __syncthreads();
+        mg_clamped_length_scan(seq_len, B, T_in, s_deltas, s_deltas + B + 1);
     }
 
     const int W = win.n;

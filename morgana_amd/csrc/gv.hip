@@ -9,9 +9,9 @@
 // operands plus a finish over the (b, d) pairs, the backward one streaming pass that reads the predictions and writes the dense gradient;
 // what is kept between the two is (m_pred, c): 16 B D bytes.
 //
-// Numerics (the house rules of colstats.hip).  No sum of raw squares: an accumulator sums d = x - k and d^2 in float64 for at most
-// GV_FLUSH values, k being the first value it saw, turns them into (n, mean, M2 = s2 - s1^2 / n) and folds that into its running
-// triple by Chan's update (moments.h).  Means travel as mean - anchor, anchor = x[b,0,d] (0 when that is not finite): held in full a
+// Numerics (moments.h: the accumulator, the streaming pass and the tree are shared with colstats.hip).  No sum of raw squares: an
+// accumulator sums d = x - k and d^2 in float64 for at most MG_MOMENTS_FLUSH values, k being the first value it saw, turns them into
+// (n, mean, M2 = s2 - s1^2 / n) and folds that into its running triple by Chan's update.  Means travel as mean - anchor, anchor = x[b,0,d] (0 when that is not finite): held in full a
 // mean would be rounded relative to the column's offset at every merge, and the delta^2 terms would inherit it.  The anchor comes
 // back once, in the finish.  A constant column gives s1 = s2 = 0 and delta = 0 at every merge: v == 0.0 exactly.
 //
@@ -35,12 +35,12 @@
 #include "common.h"
 
 #pragma clang fp contract(off)
-#include "moments.h"
+#include "moments.h"          // after the pragma, on purpose: the shared pass is compiled without contraction here
+#include "seq_reduce.h"
 
 #define GV_THREADS 256
 #define GV_CHUNK_FRAMES 256        // frames of one utterance per workgroup of launch 1
 #define GV_STEP 1024               // elements per step, at most (D <= GV_STEP)
-#define GV_FLUSH 32                // values per shifted chunk (a multiple of 4)
 #define GV_FINISH_THREADS 256       // one (b, d) item per thread of the finish
 #define GV_FINISH_BATCH 4          // chunks whose records it loads at once
 #define GV_BWD_CHUNK 8192          // gradient elements of one utterance per workgroup of the backward
@@ -79,50 +79,9 @@ static size_t gv_ws_bytes(int B, int T, int D) {
     return gv_records_bytes(B, T, D) + gv_weights_bytes(B, T) + gv_partials_bytes(B, D) + 256;
 }
 
-__device__ __forceinline__ int64_t gv_valid_frames(const int64_t* __restrict__ seq_len, int b, int T) {
-    int64_t n_b = seq_len ? seq_len[b] : (int64_t)T;
-    if (n_b > T) n_b = T;
-    if (n_b < 0) n_b = 0;
-    return n_b;
-}
-
 __device__ __forceinline__ double gv_anchor(const float* first, int64_t stride_d, int col) {
     const float v = first[(int64_t)col * stride_d];
     return __builtin_isfinite(v) ? (double)v : 0.0;
-}
-
-struct gv_acc {
-    double anchor;             // means are held as mean - anchor
-    double k, s1, s2;          // the open chunk: shift, sum (x - k), sum (x - k)^2
-    int cnt;
-    double rn, rmean, rm2;     // the chunks folded so far
-};
-
-__device__ __forceinline__ void gv_init(gv_acc& a, double anchor) {
-    a.anchor = anchor;
-    a.k = a.s1 = a.s2 = 0.0;
-    a.cnt = 0;
-    a.rn = a.rmean = a.rm2 = 0.0;
-}
-
-__device__ __forceinline__ void gv_add(gv_acc& a, float x) {
-    const double v = (double)x;
-    if (a.cnt == 0) a.k = v;
-    const double d = v - a.k;
-    a.s1 += d;
-    a.s2 += d * d;
-    a.cnt += 1;
-}
-
-__device__ __forceinline__ void gv_flush(gv_acc& a) {
-    if (a.cnt == 0) return;
-    const double n = (double)a.cnt;
-    const double mean = (a.k - a.anchor) + a.s1 / n;
-    double m2 = a.s2 - a.s1 * a.s1 / n;
-    if (m2 < 0.0) m2 = 0.0;                                  // rounding only; a NaN stays
-    mg_chan_merge(a.rn, a.rmean, a.rm2, n, mean, m2);
-    a.s1 = a.s2 = 0.0;
-    a.cnt = 0;
 }
 
 // Workgroup (c, b, operand): `len` >= 1 valid frames from `base` on -> rec[0 .. D) = mean - anchor, rec[D .. 2 D) = M2.
@@ -130,129 +89,11 @@ template <int VEC>
 __device__ __forceinline__ void gv_chunk_moments(const float* __restrict__ base, int64_t stride_t, int64_t stride_d,
                                                  const float* __restrict__ first, int len, int D, int R, int W, double* s_mean,
                                                  double* s_m2, int* s_n, double* __restrict__ rec) {
-    const int tid = threadIdx.x;
-    const int64_t E = (int64_t)len * D;                      // elements of the chunk
-    const int NS = (len + R - 1) / R;                        // steps of the chunk
-    if constexpr (VEC == 4) {
-        const int pre = (int)(((uintptr_t)base >> 2) & 3u);  // elements between the 16-byte boundary below and base
-        const int quads = W / 4 + (pre ? 1 : 0);
-        for (int q = tid; q < quads; q += GV_THREADS) {
-            // element j of quad q of step m is chunk element m W + ent0 + j, for 0 <= ent0 + j < W
-            const int ent0 = 4 * q - pre;
-            const bool inner = ent0 >= 0 && ent0 + 3 < W;
-            gv_acc acc[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {                     // (an entry outside [0, W) never gets an element: any column will do)
-                const int ent = ent0 + j;
-                gv_init(acc[j], gv_anchor(first, 1, ent >= 0 && ent < W ? ent % D : 0));
-            }
-            const float* src = base + ent0;
-            int since = 0;
-            int m = 0;
-            if (inner) {
-                const int mfull = E >= (int64_t)ent0 + 4 ? (int)((E - ent0 - 4) / W) + 1 : 0;      // steps whose whole quad is valid
-                for (; m + 3 < mfull; m += 4) {
-                    f32x4 v[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(src + (int64_t)(m + u) * W);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) gv_add(acc[j], v[u][j]);
-                    }
-                    since += 4;
-                    if (since >= GV_FLUSH) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) gv_flush(acc[j]);
-                        since = 0;
-                    }
-                }
-                for (; m < mfull; ++m) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(src + (int64_t)m * W);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) gv_add(acc[j], v[j]);
-                    if (++since >= GV_FLUSH) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) gv_flush(acc[j]);
-                        since = 0;
-                    }
-                }
-            }
-            for (; m < NS; ++m) {                             // quads across an end of the step or of the chunk: element by element
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int ent = ent0 + j;
-                    const int64_t e = (int64_t)m * W + ent;
-                    if (ent >= 0 && ent < W && e < E) gv_add(acc[j], base[e]);
-                }
-                if (++since >= GV_FLUSH) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) gv_flush(acc[j]);
-                    since = 0;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int ent = ent0 + j;
-                if (ent < 0 || ent >= W) continue;
-                gv_flush(acc[j]);
-                s_mean[ent] = acc[j].rmean;
-                s_m2[ent] = acc[j].rm2;
-                s_n[ent] = (int)acc[j].rn;
-            }
-        }
-    } else {
-        for (int ent = tid; ent < W; ent += GV_THREADS) {
-            const int erow = ent / D, col = ent - erow * D;
-            gv_acc acc;
-            gv_init(acc, gv_anchor(first, stride_d, col));
-            const float* src = base + (int64_t)erow * stride_t + (int64_t)col * stride_d;
-            const int64_t row_step = (int64_t)R * stride_t;
-            const int mfull = len > erow ? (len - erow - 1) / R + 1 : 0;       // steps in which frame m R + erow exists
-            int since = 0;
-            int m = 0;
-            for (; m + 3 < mfull; m += 4) {
-                float v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) v[u] = src[(int64_t)(m + u) * row_step];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) gv_add(acc, v[u]);
-                since += 4;
-                if (since >= GV_FLUSH) {
-                    gv_flush(acc);
-                    since = 0;
-                }
-            }
-            for (; m < mfull; ++m) {
-                gv_add(acc, src[(int64_t)m * row_step]);
-                if (++since >= GV_FLUSH) {
-                    gv_flush(acc);
-                    since = 0;
-                }
-            }
-            gv_flush(acc);
-            s_mean[ent] = acc.rmean;
-            s_m2[ent] = acc.rm2;
-            s_n[ent] = (int)acc.rn;
-        }
-    }
-    __syncthreads();
-    // entries e and e + k D hold the same column: fold the upper half of the frames of a step onto the lower, level by level
-    for (int rows = R; rows > 1;) {
-        const int half = (rows + 1) >> 1;
-        const int n_pairs = (rows - half) * D;
-        for (int i = tid; i < n_pairs; i += GV_THREADS) {
-            const int o = i + half * D;
-            double na = (double)s_n[i], ma = s_mean[i], Ma = s_m2[i];
-            mg_chan_merge(na, ma, Ma, (double)s_n[o], s_mean[o], s_m2[o]);
-            s_n[i] = (int)na;
-            s_mean[i] = ma;
-            s_m2[i] = Ma;
-        }
-        __syncthreads();
-        rows = half;
-    }
-    for (int d = tid; d < D; d += GV_THREADS) {
+    mg_stream_moments<VEC, false>(
+        base, stride_t, stride_d, len, D, R, W, 0, 1, [&](int col) { return gv_anchor(first, stride_d, col); }, [](int, float, float) {},
+        s_mean, s_m2, s_n);
+    mg_fold_step_frames(R, D, s_mean, s_m2, s_n);
+    for (int d = threadIdx.x; d < D; d += GV_THREADS) {
         rec[d] = s_mean[d];
         rec[D + d] = s_m2[d];
     }
@@ -272,7 +113,7 @@ __global__ __launch_bounds__(GV_THREADS) void gv_partial_kernel(const float* __r
     int* s_n = (int*)(s_gv + 2 * (size_t)W);                 // [W]
     const int b = blockIdx.y, c = blockIdx.x, B = gridDim.y, CH = gridDim.x;
     if (b == 0 && c == 0 && blockIdx.z == 0 && threadIdx.x == 0) arrivals[0] = 0u;      // the finish counts its workgroups from 0
-    const int64_t n_b = gv_valid_frames(seq_len, b, T);
+    const int64_t n_b = mg_valid_frames(seq_len, b, T);
     const int64_t t0 = (int64_t)c * GV_CHUNK_FRAMES;
     if (n_b <= t0) return;                                   // workgroup-uniform: only pad frames here
     const int len = (int)(n_b - t0 < GV_CHUNK_FRAMES ? n_b - t0 : GV_CHUNK_FRAMES);
@@ -287,19 +128,9 @@ __global__ __launch_bounds__(GV_THREADS) void gv_partial_kernel(const float* __r
     const float* first = x + (int64_t)b * sb;
     double* rec = records + (((size_t)op * B + b) * CH + c) * 2 * (size_t)D;
     if (op ? t_vec : p_vec)
-        gv_chunk_moments<4>(first + t0 * st, st, sd, first, len, D, R, W, s_mean, s_m2, s_n, rec);
+        gv_chunk_moments<4>(first + t0 * st, st, 1, first, len, D, R, W, s_mean, s_m2, s_n, rec);      // vec: sd == 1
     else
         gv_chunk_moments<1>(first + t0 * st, st, sd, first, len, D, R, W, s_mean, s_m2, s_n, rec);
-}
-
-// Sum over the workgroup of GV_FINISH_THREADS in a fixed tree, the same value in every thread.
-__device__ __forceinline__ double gv_finish_sum(double v, double* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // Launch 2, the finish, one thread per (b, d): chunks merged in ascending order with the weights of launch 1 (the update of
@@ -326,7 +157,7 @@ __global__ __launch_bounds__(GV_FINISH_THREADS) void gv_finish_kernel(const floa
     const int64_t i = (int64_t)blockIdx.x * GV_FINISH_THREADS + threadIdx.x;
     if (i < items) {
         const int b = (int)(i / D), d = (int)(i - (int64_t)b * D);
-        const int64_t n_b = gv_valid_frames(seq_len, b, T);
+        const int64_t n_b = mg_valid_frames(seq_len, b, T);
         const int nch = (int)((n_b + GV_CHUNK_FRAMES - 1) / GV_CHUNK_FRAMES);      // chunks that hold frames: the ones launch 1 wrote
         const double* w = weights + (size_t)b * CH * 2;
         const double* rec[2];
@@ -382,7 +213,7 @@ __global__ __launch_bounds__(GV_FINISH_THREADS) void gv_finish_kernel(const floa
         }
     }
     if (!tgt) return;
-    const double mine = gv_finish_sum(acc, red);
+    const double mine = mg_block_sum_f64(acc, red);
     if (threadIdx.x == 0) {
         __hip_atomic_store(&partials[blockIdx.x], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned ticket = __hip_atomic_fetch_add(arrivals, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
@@ -393,7 +224,7 @@ __global__ __launch_bounds__(GV_FINISH_THREADS) void gv_finish_kernel(const floa
     double sum = 0.0;
     for (unsigned j = threadIdx.x; j < gridDim.x; j += GV_FINISH_THREADS)
         sum += __hip_atomic_load(&partials[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const double total = gv_finish_sum(sum, red);
+    const double total = mg_block_sum_f64(sum, red);
     if (threadIdx.x == 0) loss[0] = (float)(total / ((double)B * (double)D));
 }
 
@@ -407,7 +238,7 @@ __global__ __launch_bounds__(GV_THREADS) void gv_bwd_kernel(const float* __restr
     const int64_t row_elems = (int64_t)T * D;
     const int64_t lo = (int64_t)blockIdx.x * GV_BWD_CHUNK;
     const int len = (int)(row_elems - lo < GV_BWD_CHUNK ? row_elems - lo : GV_BWD_CHUNK);
-    const int64_t n_b = gv_valid_frames(seq_len, b, T);
+    const int64_t n_b = mg_valid_frames(seq_len, b, T);
     const int64_t valid = n_b * D - lo;                      // local indices below it are valid frames
     const float off = n_b > 0 ? 0.f : __builtin_nanf("");
     const double g = (double)grad_loss[0];

@@ -7,6 +7,7 @@
 // writes the gradient, a second tiny pass finishes the per-utterance normalisation in a fixed order (deterministic).
 // Algorithmic bytes for K4: B*T*D*(4+4) read + B*T*D*4 written.
 #include "common.h"
+#include "seq_reduce.h"
 
 #define MSE_CHUNK 8192  // elements of one utterance handled by one workgroup (256 threads x 32)
 
@@ -50,9 +51,7 @@ __global__ __launch_bounds__(256) void masked_mse_stage1(const float* __restrict
     const int b = blockIdx.y;
     const int chunk = blockIdx.x;
     const int64_t row_elems = (int64_t)T * D;
-    int64_t n_b = seq_len ? seq_len[b] : (int64_t)T;
-    if (n_b > T) n_b = T;
-    if (n_b < 0) n_b = 0;
+    const int64_t n_b = mg_valid_frames(seq_len, b, T);
     const int64_t valid_elems = n_b * D;
     // grad_scale / (n_b * B * D); n_b == 0 gives inf so that 0 * inf = NaN on every element of that utterance.
     const float coef = grad_scale / ((float)n_b * (float)((int64_t)B * D));
@@ -94,22 +93,8 @@ __global__ __launch_bounds__(256) void masked_mse_stage1(const float* __restrict
 __global__ __launch_bounds__(256) void masked_mse_stage2(const float* __restrict__ partial, const int64_t* __restrict__ seq_len,
                                                          int B, int T, float final_div, int chunks, float* __restrict__ loss) {
     __shared__ float red[256];
-    float acc = 0.f;
-    for (int b = threadIdx.x; b < B; b += 256) {
-        float s = 0.f;
-        for (int c = 0; c < chunks; ++c) s += partial[(size_t)b * chunks + c];
-        int64_t n_b = seq_len ? seq_len[b] : (int64_t)T;
-        if (n_b > T) n_b = T;
-        if (n_b < 0) n_b = 0;
-        acc += s / (float)n_b;   // 0 / 0 = NaN when an utterance has no valid frame (reference behaviour)
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = red[0] / final_div;
+    const float sum = mg_utterance_mean_sum(partial, seq_len, B, T, chunks, red);
+    if (threadIdx.x == 0) loss[0] = sum / final_div;
 }
 
 __global__ __launch_bounds__(256) void normalise_kernel(const float* __restrict__ x, float* __restrict__ out,
@@ -167,9 +152,7 @@ __global__ __launch_bounds__(256) void stream_loss_stage1(const float* __restric
     __syncthreads();
     const int b = blockIdx.y;
     const int64_t row_elems = (int64_t)T * D;
-    int64_t n_b = seq_len ? seq_len[b] : (int64_t)T;
-    if (n_b > T) n_b = T;
-    if (n_b < 0) n_b = 0;
+    const int64_t n_b = mg_valid_frames(seq_len, b, T);
     const float inv_nb = grad_scale / (float)n_b;   // inf for an empty utterance: 0 * inf = NaN, as the reference's 0 / 0
     const size_t base = (size_t)b * row_elems;
     const int64_t lo = (int64_t)blockIdx.x * MSE_CHUNK;

@@ -27,6 +27,7 @@
 //       HBM still sees one.  MDN_ROWS_WIDE (4) frames per workgroup, one per wave.
 // Pad frames (t >= n_b) read nothing: their gradient row is written as zero, their target is never looked at.
 #include "common.h"
+#include "seq_reduce.h"
 
 #define MDN_REG_MAX 1024        // longest K*D of the register path (16 pairs per lane)
 #define MDN_SMALL_D 16          // widest D summed by one lane per component
@@ -36,12 +37,6 @@
 #define MDN_HALF_LOG_2PI 0.9189385332046727f
 
 static inline int mdn_rows_per_wg(int K, int D) { return K * D <= MDN_REG_MAX ? MDN_ROWS_REG : MDN_ROWS_WIDE; }
-
-__device__ __forceinline__ float mdn_wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
 
 // LDS traffic of ONE wave is in order: this keeps the compiler from moving it and waits for the reads to have landed
 __device__ __forceinline__ void mdn_wave_fence() {
@@ -62,13 +57,6 @@ struct mdn_args {
     float grad_scale;
 };
 
-__device__ __forceinline__ int64_t mdn_valid_frames(const int64_t* seq_len, int b, int T) {
-    int64_t n_b = seq_len ? seq_len[b] : (int64_t)T;
-    if (n_b > T) n_b = T;
-    if (n_b < 0) n_b = 0;
-    return n_b;
-}
-
 __device__ __forceinline__ int mdn_component(int i, int D, unsigned magic) { return D == 1 ? i : (int)__umulhi((unsigned)i, magic); }
 
 // max(s, floor) as torch.clamp has it (a NaN stays a NaN); `floored` = the gradient of s is cut
@@ -79,7 +67,7 @@ __device__ __forceinline__ float mdn_floor(float s, const mdn_args& a, bool& flo
 
 // q (one component per lane, -inf past K) -> responsibilities r = exp(q - logsumexp q) in the same lanes, returns -logsumexp q
 __device__ __forceinline__ float mdn_responsibilities(float q, float& r) {
-    const float qmax = mdn_wave_max(q);
+    const float qmax = mg_wave_max(q);
     const float e = expf(q - qmax);                       // exp(-inf) = 0: a removed component (and a lane past K) adds nothing
     const float s = mg_wave_sum(e);
     r = e / s;
@@ -94,7 +82,7 @@ __global__ __launch_bounds__(256) void masked_mdn_reg_kernel(mdn_args a) {
     __shared__ float red[4];
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int K = a.K, D = a.D, N = K * D;
-    const int64_t n_b = mdn_valid_frames(a.seq_len, b, a.T);
+    const int64_t n_b = mg_valid_frames(a.seq_len, b, a.T);
     const float coef = a.grad_scale / ((float)D * (float)n_b * (float)a.B);
     const float norm = (float)D * MDN_HALF_LOG_2PI;
     const int t0 = blockIdx.x * MDN_ROWS_REG;
@@ -145,7 +133,7 @@ __global__ __launch_bounds__(256) void masked_mdn_reg_kernel(mdn_args a) {
             }
         }
         const float av = lane < K ? x[lane] : -INFINITY;
-        const float amax = mdn_wave_max(av);
+        const float amax = mg_wave_max(av);
         const float ea = expf(av - amax);                 // all logits -inf: -inf - -inf = NaN, the frame's loss is NaN
         const float sa = mg_wave_sum(ea);
         const float q = lane < K ? (((av - amax) - logf(sa)) - sum) - norm : -INFINITY;
@@ -177,7 +165,7 @@ __global__ __launch_bounds__(256) void masked_mdn_reread_kernel(mdn_args a) {
     __shared__ float red[4];
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int K = a.K, D = a.D, N = K * D;
-    const int64_t n_b = mdn_valid_frames(a.seq_len, b, a.T);
+    const int64_t n_b = mg_valid_frames(a.seq_len, b, a.T);
     const float coef = a.grad_scale / ((float)D * (float)n_b * (float)a.B);
     const float norm = (float)D * MDN_HALF_LOG_2PI;
     const int t = blockIdx.x * MDN_ROWS_WIDE + wave;
@@ -206,7 +194,7 @@ __global__ __launch_bounds__(256) void masked_mdn_reread_kernel(mdn_args a) {
                 if (lane == k) sum = p;
             }
             const float av = lane < K ? x[lane] : -INFINITY;
-            const float amax = mdn_wave_max(av);
+            const float amax = mg_wave_max(av);
             const float ea = expf(av - amax);
             const float sa = mg_wave_sum(ea);
             const float q = lane < K ? (((av - amax) - logf(sa)) - sum) - norm : -INFINITY;
@@ -233,26 +221,14 @@ __global__ __launch_bounds__(256) void masked_mdn_reread_kernel(mdn_args a) {
     if (threadIdx.x == 0) a.partial[(size_t)b * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// One workgroup: loss = loss_weight * (1/B) sum_b ( sum_chunks partial[b,:] / n_b ) + loss_keep * loss, fixed summation order
-// (the form of ce.hip's finishing pass).
+// One workgroup: loss = loss_weight * (1/B) sum_b ( sum_chunks partial[b,:] / n_b ) + loss_keep * loss, fixed summation order.
 __global__ __launch_bounds__(256) void masked_mdn_finish_kernel(const float* __restrict__ partial, const int64_t* __restrict__ seq_len, int B,
                                                                 int T, int chunks, float loss_weight, float loss_keep,
                                                                 float* __restrict__ loss) {
     __shared__ float red[256];
-    float acc = 0.f;
-    for (int b = threadIdx.x; b < B; b += 256) {
-        float s = 0.f;
-        for (int c = 0; c < chunks; ++c) s += partial[(size_t)b * chunks + c];
-        acc += s / (float)mdn_valid_frames(seq_len, b, T);     // 0 / 0 = NaN for an utterance without a valid frame
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
+    const float sum = mg_utterance_mean_sum(partial, seq_len, B, T, chunks, red);
     if (threadIdx.x == 0) {
-        const float l = loss_weight * (red[0] / (float)B);
+        const float l = loss_weight * (sum / (float)B);
         loss[0] = loss_keep != 0.f ? l + loss_keep * loss[0] : l;
     }
 }
@@ -263,7 +239,7 @@ __global__ __launch_bounds__(256) void mdn_select_kernel(const float* __restrict
                                                          int K, int D, float floor, int has_floor, int64_t* __restrict__ component,
                                                          float* __restrict__ mean, float* __restrict__ variance) {
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t n_b = mdn_valid_frames(seq_len, b, T);
+    const int64_t n_b = mg_valid_frames(seq_len, b, T);
     const int t0 = blockIdx.x * MDN_ROWS_SELECT;
     for (int r = wave; r < MDN_ROWS_SELECT; r += 4) {
         const int t = t0 + r;
@@ -280,15 +256,7 @@ __global__ __launch_bounds__(256) void mdn_select_kernel(const float* __restrict
         const float* x = pred + row * ldp;
         float m = lane < K ? x[lane] : -INFINITY;
         int im = lane;                                    // lanes past K hold -inf and a larger index: they lose every merge
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float om = __shfl_xor(m, off, 64);
-            const int oi = __shfl_xor(im, off, 64);
-            if (om > m || (om == m && oi < im)) {
-                m = om;
-                im = oi;
-            }
-        }
+        mg_wave_argmax(m, im);
         im = __shfl(im, 0, 64);
         if (im >= K) im = K - 1;
         if (lane == 0) component[row] = im;

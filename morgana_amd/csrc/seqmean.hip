@@ -24,34 +24,18 @@
 // Every frame is read and multiplied by its mask value, as the reference does: a NaN or Inf in a pad frame makes the loss NaN, and
 // n_b == 0 gives 0 / 0 = NaN.
 #include "common.h"
+#include "seq_reduce.h"
 
 #define SEQ_THREADS 256
 #define SEQ_COLS 1024             // 4 per thread
 #define SEQ_CHUNK 8192            // elements of one utterance summed by one workgroup; a multiple of SEQ_COLS
-
-__device__ __forceinline__ int64_t seq_valid_frames(const int64_t* __restrict__ seq_len, int b, int T) {
-    int64_t n_b = seq_len ? seq_len[b] : (int64_t)T;
-    if (n_b > T) n_b = T;
-    if (n_b < 0) n_b = 0;
-    return n_b;
-}
-
-// Sum over the workgroup in a fixed tree, the same value in every thread.
-__device__ __forceinline__ double seq_block_sum(double v, double* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // The 1024 column sums (cols[c], written by whichever thread held column c) -> the chunk's sum, in an order fixed by c alone.
 __device__ __forceinline__ double seq_columns_sum(const double* cols, double* red) {
     __syncthreads();
     const int tid = threadIdx.x;
     const double v = (cols[tid] + cols[tid + 256]) + (cols[tid + 512] + cols[tid + 768]);
-    return seq_block_sum(v, red);
+    return mg_block_sum_f64(v, red);
 }
 
 __global__ __launch_bounds__(SEQ_THREADS) void seq_mean_vec_kernel(const float* __restrict__ x, int64_t stride_b,
@@ -63,7 +47,7 @@ __global__ __launch_bounds__(SEQ_THREADS) void seq_mean_vec_kernel(const float* 
     const int64_t row_elems = (int64_t)T * D;
     const int64_t lo = (int64_t)blockIdx.x * SEQ_CHUNK;
     const int len = (int)(row_elems - lo < SEQ_CHUNK ? row_elems - lo : SEQ_CHUNK);
-    const int64_t valid = seq_valid_frames(seq_len, b, T) * D - lo;      // local indices below it are valid frames
+    const int64_t valid = mg_valid_frames(seq_len, b, T) * D - lo;      // local indices below it are valid frames
     const float* p = x + (int64_t)b * stride_b + lo;
     const int a = (int)(((uintptr_t)p >> 2) & 3u);                       // floats between the last 16-byte boundary and p
     const int nvec = (len + a + 3) >> 2;
@@ -96,7 +80,7 @@ __global__ __launch_bounds__(SEQ_THREADS) void seq_mean_strided_kernel(const flo
     const int64_t row_elems = (int64_t)T * D;
     const int64_t lo = (int64_t)blockIdx.x * SEQ_CHUNK;
     const int len = (int)(row_elems - lo < SEQ_CHUNK ? row_elems - lo : SEQ_CHUNK);
-    const int64_t n_b = seq_valid_frames(seq_len, b, T);
+    const int64_t n_b = mg_valid_frames(seq_len, b, T);
     const float* p = x + (int64_t)b * stride_b;
     const int dt = SEQ_COLS / D, dd = SEQ_COLS % D;                      // (t, d) of a column moves by this from one element to the next
 #pragma unroll
@@ -126,9 +110,9 @@ __global__ __launch_bounds__(SEQ_THREADS) void seq_mean_finish_kernel(const doub
     for (int b = threadIdx.x; b < B; b += SEQ_THREADS) {
         double s = 0.0;
         for (int c = 0; c < chunks; ++c) s += partial[(size_t)b * chunks + c];
-        acc += s / (double)seq_valid_frames(seq_len, b, T);              // 0 / 0 = NaN for an utterance without a valid frame
+        acc += s / (double)mg_valid_frames(seq_len, b, T);              // 0 / 0 = NaN for an utterance without a valid frame
     }
-    const double total = seq_block_sum(acc, red);
+    const double total = mg_block_sum_f64(acc, red);
     if (threadIdx.x == 0) loss[0] = (float)(total / ((double)B * (double)D));
 }
 
@@ -140,7 +124,7 @@ __global__ __launch_bounds__(SEQ_THREADS) void seq_mean_bwd_kernel(const float* 
     const int64_t row_elems = (int64_t)T * D;
     const int64_t lo = (int64_t)blockIdx.x * SEQ_CHUNK;
     const int len = (int)(row_elems - lo < SEQ_CHUNK ? row_elems - lo : SEQ_CHUNK);
-    const int64_t n_b = seq_valid_frames(seq_len, b, T);
+    const int64_t n_b = mg_valid_frames(seq_len, b, T);
     const int64_t valid = n_b * D - lo;
     const float nan = __builtin_nanf("");
     const float on = n_b > 0 ? (float)((double)grad_loss[0] / ((double)n_b * (double)B * (double)D)) : nan;

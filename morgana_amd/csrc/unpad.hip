@@ -8,6 +8,7 @@
 // one piece are contiguous, so the piece is copied at the widest access their RELATIVE alignment allows (16, 4 or 1 bytes), with the
 // few bytes in front of and behind the aligned body moved one by one.
 #include "common.h"
+#include "seq_reduce.h"
 
 #define UNPAD_THREADS 256
 #define UNPAD_CHUNK (UNPAD_THREADS * 16 * 4)        // destination bytes per chunk: four 16-byte trips per thread
@@ -47,30 +48,7 @@ __global__ __launch_bounds__(UNPAD_THREADS) void unpad_rows_kernel(UnpadBatch ba
     if ((int64_t)blockIdx.x * UNPAD_CHUNK >= f.block_bytes) return;
     const int tid = threadIdx.x;
 
-    // exclusive scan of len_b = min(max(seq_len[b], 0), T): thread t owns items [t * per, (t + 1) * per)
-    const int per = (B + UNPAD_THREADS - 1) / UNPAD_THREADS;
-    const int lo = tid * per < B ? tid * per : B, hi = lo + per < B ? lo + per : B;
-    int64_t sum = 0;
-    for (int b = lo; b < hi; ++b) {
-        int64_t len = seq_len[b];
-        sum += len < 0 ? 0 : len > T ? T : len;
-    }
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int off = 1; off < UNPAD_THREADS; off <<= 1) {
-        const int64_t v = tid >= off ? s_part[tid - off] : 0;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    int64_t run = s_part[tid] - sum;
-    for (int b = lo; b < hi; ++b) {
-        int64_t len = seq_len[b];
-        s_off[b] = run;
-        run += len < 0 ? 0 : len > T ? T : len;
-    }
-    if (tid == UNPAD_THREADS - 1) s_off[B] = s_part[tid];
-    __syncthreads();
+    mg_clamped_length_scan(seq_len, B, T, s_off, s_part);
 
     // rows that do not fit the block are dropped: nothing is written at or beyond dst_offset + block_bytes
     int64_t rows = s_off[B];

@@ -28,7 +28,13 @@ def _stream():
     return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
 
 
-def _require(t, dtype, name):
+def _require(t, dtype, name, contiguous=True, rows=False):
+    """The tensor check of every wrapper: ``t`` is a device tensor of ``dtype``.  Returns it contiguous (a copy if need be);
+    ``contiguous=False`` returns it as it is, for the entry points that take strides.
+
+    ``rows=True``: a (B, T, C) tensor -> (tensor, row stride) such that frame (b, t) starts at data_ptr + (b T + t) * stride elements:
+    the tensor itself when its last dimension is contiguous and its frames are evenly spaced (a column slice of a contiguous
+    (B, T, D) tensor), else a contiguous copy."""
     if not isinstance(t, torch.Tensor):
         raise TypeError('%s must be a torch.Tensor, got %s' % (name, type(t)))
     if not t.is_cuda:
@@ -36,7 +42,51 @@ def _require(t, dtype, name):
                                    % (name, t.device))
     if t.dtype != dtype:
         raise TypeError('%s must be %s, got %s' % (name, dtype, t.dtype))
-    return t if t.is_contiguous() else t.contiguous()
+    if rows:
+        if t.dim() != 3:
+            raise ValueError('%s must be (B, T, C), got %s' % (name, tuple(t.shape)))
+        b, n, c = t.shape
+        ld = t.stride(1)
+        if (t.stride(2) == 1 or c == 1) and ld >= c and (b == 1 or t.stride(0) == n * ld) and ld < 2 ** 31:
+            return t, ld
+        return t.contiguous(), c
+    return t if not contiguous or t.is_contiguous() else t.contiguous()
+
+
+def _lengths(seq_len, b, what='', flat=True):
+    """``seq_len`` of a (B, ...) batch: None, or int64 on the device with one length per item - the kernels read B of them.
+    ``flat``: it must be (B,); otherwise any shape of B elements will do (the models pass (B, 1))."""
+    if seq_len is None:
+        return None
+    seq_len = _require(seq_len, torch.int64, 'seq_len')
+    if flat and tuple(seq_len.shape) != (b,):
+        raise ValueError('%sseq_len must be (B,) = (%d,), got %s' % (what, b, tuple(seq_len.shape)))
+    if seq_len.numel() != b:
+        raise ValueError('%sseq_len must hold B = %d lengths, got %s' % (what, b, tuple(seq_len.shape)))
+    return seq_len
+
+
+def _one_element(grad_loss):
+    """The upstream gradient of a scalar loss: a one-element float32 device tensor that the kernel reads (no host read)."""
+    grad_loss = _require(grad_loss, torch.float32, 'grad_loss')
+    if grad_loss.numel() != 1:
+        raise ValueError('grad_loss must hold one element, got %s' % (tuple(grad_loss.shape),))
+    return grad_loss
+
+
+def _loss_and_grad_out(what, pred, width, col0, want_grad, grad_out, loss_out):
+    """Where a column-slice loss (``masked_ce``, ``masked_mdn``) leaves its results -> (loss, grad returned, grad written, ldg, gcol0).
+    ``grad_out``: a buffer shaped like ``pred`` whose columns [col0, col0 + width) take the gradient; else a new (B, T, width)."""
+    loss = torch.empty((), dtype=torch.float32, device=pred.device) if loss_out is None else loss_out
+    if not want_grad:
+        return loss, None, None, 0, 0
+    if grad_out is None:
+        grad = torch.empty((pred.shape[0], pred.shape[1], width), dtype=torch.float32, device=pred.device)
+        return loss, grad, grad, width, 0
+    g, ldg = _require(grad_out, torch.float32, 'grad_out', rows=True)
+    if g is not grad_out or tuple(g.shape) != tuple(pred.shape):
+        raise ValueError('%s: grad_out must be a (B, T, D) tensor with evenly spaced rows, shaped like predictions' % what)
+    return loss, grad_out, g, ldg, col0
 
 
 def workspace(nbytes, device):
@@ -341,9 +391,8 @@ def masked_mse(pred, target, seq_len, want_grad, grad_scale=1.0, kind='mse'):
     if pred.shape != target.shape or pred.dim() != 3:
         raise ValueError('mse: predictions %s and targets %s must both be (B, T, D)' % (tuple(pred.shape),
                                                                                      tuple(target.shape)))
-    if seq_len is not None:
-        seq_len = _require(seq_len, torch.int64, 'seq_len')
     b, t, d = pred.shape
+    seq_len = _lengths(seq_len, b, '%s: ' % kind, flat=False)
     loss = torch.empty((), dtype=torch.float32, device=pred.device)
     grad = torch.empty_like(pred) if want_grad else None
     nbytes = lib.mg_masked_mse_workspace_bytes(b, t, d)
@@ -354,37 +403,16 @@ def masked_mse(pred, target, seq_len, want_grad, grad_scale=1.0, kind='mse'):
     return loss, grad
 
 
-def _require_in_place(t, dtype, name):
-    """``_require`` without the contiguous copy: for the entry points that take strides."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError('%s must be a torch.Tensor, got %s' % (name, type(t)))
-    if not t.is_cuda:
-        raise _lib.MorganaHipError('%s is on %s: the morgana_amd ops run only on an MI355X device (no CPU fallback)'
-                                   % (name, t.device))
-    if t.dtype != dtype:
-        raise TypeError('%s must be %s, got %s' % (name, dtype, t.dtype))
-    return t
-
-
-def _seq_mean_lengths(seq_len, b):
-    if seq_len is None:
-        return None
-    seq_len = _require(seq_len, torch.int64, 'seq_len')
-    if tuple(seq_len.shape) != (b,):
-        raise ValueError('seq_len must be (B,) = (%d,), got %s' % (b, tuple(seq_len.shape)))
-    return seq_len
-
-
 def masked_seq_mean(x, seq_len):
     """Masked sequence mean of a feature loss (mg_seq_mean_f32, csrc/seqmean.hip): x (B, T, D) float32, read in place through its
     strides (a column slice, a misaligned base, an expanded operand); seq_len (B,) int64 or None.  Returns the 0-d float32 loss
     ``mean_{b,d}( sum_{t} x[b,t,d] [t < n_b] / n_b )`` on the device, accumulated in float64 in a fixed order."""
     lib = _lib.load()
-    x = _require_in_place(x, torch.float32, 'feature loss')
+    x = _require(x, torch.float32, 'feature loss', contiguous=False)
     if x.dim() != 3 or 0 in x.shape:
         raise ValueError('feature loss must be a non-empty (B, T, D) tensor, got %s' % (tuple(x.shape),))
     b, t, d = x.shape
-    seq_len = _seq_mean_lengths(seq_len, b)
+    seq_len = _lengths(seq_len, b)
     loss = torch.empty((), dtype=torch.float32, device=x.device)
     ws = workspace(lib.mg_seq_mean_workspace_bytes(b, t, d), x.device)
     _lib.check(lib.mg_seq_mean_f32(_p(x), x.stride(0), x.stride(1), x.stride(2), _p(seq_len), b, t, d, _p(loss), _p(ws), ws.numel(),
@@ -397,20 +425,18 @@ def masked_seq_mean_bwd(grad_loss, seq_len, shape):
     B D) on valid frames, 0 on pad frames, NaN on an utterance without a valid frame.  ``grad_loss``: the upstream gradient, a
     one-element float32 device tensor that the kernel reads (no host read)."""
     lib = _lib.load()
-    grad_loss = _require(grad_loss, torch.float32, 'grad_loss')
-    if grad_loss.numel() != 1:
-        raise ValueError('grad_loss must hold one element, got %s' % (tuple(grad_loss.shape),))
+    grad_loss = _one_element(grad_loss)
     if len(shape) != 3 or min(shape) <= 0:
         raise ValueError('shape must be a non-empty (B, T, D), got %s' % (tuple(shape),))
     b, t, d = (int(v) for v in shape)
-    seq_len = _seq_mean_lengths(seq_len, b)
+    seq_len = _lengths(seq_len, b)
     grad = torch.empty((b, t, d), dtype=torch.float32, device=grad_loss.device)
     _lib.check(lib.mg_seq_mean_bwd_f32(_p(grad_loss), _p(seq_len), b, t, d, _p(grad), _stream()), 'mg_seq_mean_bwd_f32')
     return grad
 
 
 def _gv_operand(x, name):
-    x = _require_in_place(x, torch.float32, name)
+    x = _require(x, torch.float32, name, contiguous=False)
     if x.dim() != 3 or 0 in x.shape:
         raise ValueError('%s must be a non-empty (B, T, D) tensor, got %s' % (name, tuple(x.shape)))
     if min(x.stride()) < 0:
@@ -430,7 +456,7 @@ def gv(pred, target, seq_len=None, log=True, eps=1e-6, want_variances=False):
         target = _gv_operand(target, 'targets')
         if target.shape != pred.shape:
             raise ValueError('gv: predictions %s and targets %s must both be (B, T, D)' % (tuple(pred.shape), tuple(target.shape)))
-    seq_len = _seq_mean_lengths(seq_len, b)
+    seq_len = _lengths(seq_len, b)
     dev = pred.device
     loss = state = v_pred = v_tgt = None
     if target is not None:
@@ -452,15 +478,13 @@ def gv_backward(grad_loss, state, pred, seq_len=None):
     frames, NaN on an utterance without a valid frame.  ``grad_loss``: the upstream gradient, a one-element float32 device tensor
     that the kernel reads (no host read); ``state``: what ``gv`` returned; ``pred`` is read in place through its strides."""
     lib = _lib.load()
-    grad_loss = _require(grad_loss, torch.float32, 'grad_loss')
-    if grad_loss.numel() != 1:
-        raise ValueError('grad_loss must hold one element, got %s' % (tuple(grad_loss.shape),))
+    grad_loss = _one_element(grad_loss)
     pred = _gv_operand(pred, 'predictions')
     b, t, d = pred.shape
     state = _require(state, torch.float64, 'state')
     if tuple(state.shape) != (b, d, 2):
         raise ValueError('state must be (B, D, 2) = (%d, %d, 2), got %s' % (b, d, tuple(state.shape)))
-    seq_len = _seq_mean_lengths(seq_len, b)
+    seq_len = _lengths(seq_len, b)
     grad = torch.empty((b, t, d), dtype=torch.float32, device=pred.device)
     _lib.check(lib.mg_gv_bwd_f32(_p(grad_loss), _p(state), _p(pred), pred.stride(0), pred.stride(1), pred.stride(2), _p(seq_len), b, t, d,
                                  _p(grad), _stream()), 'mg_gv_bwd_f32')
@@ -477,8 +501,7 @@ def stream_loss(pred, targets, kinds, seq_len, want_grad, want_prob=False, grad_
     b, t, d = pred.shape
     if sum(int(y.shape[-1]) for y in targets) != d:
         raise ValueError('stream_loss: stream widths %s do not add up to D=%d' % ([int(y.shape[-1]) for y in targets], d))
-    if seq_len is not None:
-        seq_len = _require(seq_len, torch.int64, 'seq_len')
+    seq_len = _lengths(seq_len, b, 'stream_loss: ', flat=False)
     descs = (_lib.mg_stream_desc * len(targets))()
     keep, col0, prob = [], 0, None
     for k, (y, kind) in enumerate(zip(targets, kinds)):
@@ -501,27 +524,6 @@ def stream_loss(pred, targets, kinds, seq_len, want_grad, want_prob=False, grad_
     return loss, grad, prob
 
 
-def _rows_in_place(x, name):
-    """(B, T, C) f32 device tensor -> (tensor, row stride) such that frame (b, t) starts at data_ptr + (b T + t) * stride floats: the
-    tensor itself when its last dimension is contiguous and its frames are evenly spaced (a column slice of a contiguous (B, T, D)
-    tensor), else a contiguous copy."""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError('%s must be a torch.Tensor, got %s' % (name, type(x)))
-    if not x.is_cuda:
-        raise _lib.MorganaHipError('%s is on %s: the morgana_amd ops run only on an MI355X device (no CPU fallback)' % (name, x.device))
-    if x.dtype != torch.float32:
-        raise TypeError('%s must be %s, got %s' % (name, torch.float32, x.dtype))
-    if x.dim() != 3:
-        raise ValueError('%s must be (B, T, C), got %s' % (name, tuple(x.shape)))
-    b, t, c = x.shape
-    ld = x.stride(1)
-    in_place = (x.stride(2) == 1 or c == 1) and ld >= c and (b == 1 or x.stride(0) == t * ld) and ld < 2 ** 31
-    if not in_place:
-        x = x.contiguous()
-        ld = c
-    return x, ld
-
-
 def masked_ce(pred, target, seq_len, want_grad, grad_scale=1.0, want_argmax=False, col0=0, width=None, grad_out=None, loss_out=None,
               loss_weight=1.0, loss_keep=0.0):
     """Masked categorical cross entropy (mg_masked_ce_f32) of columns [col0, col0 + width) of ``pred`` (B, T, D) f32 - all of them by
@@ -532,7 +534,7 @@ def masked_ce(pred, target, seq_len, want_grad, grad_scale=1.0, want_argmax=Fals
     new (B, T, width) tensor.  ``loss_out`` / ``loss_weight`` / ``loss_keep``: loss_out = loss_weight * loss + loss_keep * loss_out
     on the device (``loss_keep == 0``: loss_out is only written)."""
     lib = _lib.load()
-    pred, ldp = _rows_in_place(pred, 'predictions')
+    pred, ldp = _require(pred, torch.float32, 'predictions', rows=True)
     b, t, d = pred.shape
     c = d - col0 if width is None else int(width)
     if col0 < 0 or c < 1 or col0 + c > d:
@@ -540,18 +542,8 @@ def masked_ce(pred, target, seq_len, want_grad, grad_scale=1.0, want_argmax=Fals
     target = _require(target, torch.int64, 'targets')
     if tuple(target.shape) != (b, t):
         raise ValueError('ce: targets %s do not match predictions %s: (B, T) class indices wanted' % (tuple(target.shape), tuple(pred.shape)))
-    if seq_len is not None:
-        seq_len = _require(seq_len, torch.int64, 'seq_len')
-    loss = torch.empty((), dtype=torch.float32, device=pred.device) if loss_out is None else loss_out
-    grad, g, ldg, gcol0 = None, None, 0, 0
-    if want_grad and grad_out is not None:
-        g, ldg = _rows_in_place(grad_out, 'grad_out')
-        if g is not grad_out or tuple(g.shape) != (b, t, d):
-            raise ValueError('ce: grad_out must be a (B, T, D) tensor with evenly spaced rows, shaped like predictions')
-        grad, gcol0 = grad_out, col0
-    elif want_grad:
-        grad = g = torch.empty((b, t, c), dtype=torch.float32, device=pred.device)
-        ldg = c
+    seq_len = _lengths(seq_len, b, 'ce: ', flat=False)
+    loss, grad, g, ldg, gcol0 = _loss_and_grad_out('ce', pred, c, col0, want_grad, grad_out, loss_out)
     argmax = torch.empty((b, t), dtype=torch.int64, device=pred.device) if want_argmax else None
     ws = workspace(lib.mg_masked_ce_workspace_bytes(b, t, c), pred.device)
     _lib.check(lib.mg_masked_ce_f32(_p(pred), ldp, col0, _p(target), _p(seq_len), b, t, c, float(grad_scale), float(loss_weight),
@@ -591,26 +583,14 @@ def masked_mdn(pred, target, seq_len, n_components, want_grad, min_log_std=None,
     (B, T, K (1 + 2 D)) tensor.  ``loss_out`` / ``loss_weight`` / ``loss_keep``: loss_out = loss_weight * loss + loss_keep *
     loss_out on the device (``loss_keep == 0``: loss_out is only written)."""
     lib = _lib.load()
-    pred, ldp = _rows_in_place(pred, 'predictions')
-    target, ldt = _rows_in_place(target, 'targets')
-    b, t, width = pred.shape
+    pred, ldp = _require(pred, torch.float32, 'predictions', rows=True)
+    target, ldt = _require(target, torch.float32, 'targets', rows=True)
+    b, t, _ = pred.shape
     if target.shape[0] != b or target.shape[1] != t:
         raise ValueError('mdn: targets %s do not match predictions %s: (B, T, D) wanted' % (tuple(target.shape), tuple(pred.shape)))
     k, d, w = _mdn_shape('mdn', pred, n_components, target.shape[2], col0)
-    if seq_len is not None:
-        seq_len = _require(seq_len, torch.int64, 'seq_len')
-        if tuple(seq_len.shape) != (b,):
-            raise ValueError('mdn: seq_len must be (B,) = (%d,), got %s' % (b, tuple(seq_len.shape)))
-    loss = torch.empty((), dtype=torch.float32, device=pred.device) if loss_out is None else loss_out
-    grad, g, ldg, gcol0 = None, None, 0, 0
-    if want_grad and grad_out is not None:
-        g, ldg = _rows_in_place(grad_out, 'grad_out')
-        if g is not grad_out or tuple(g.shape) != (b, t, width):
-            raise ValueError('mdn: grad_out must be a (B, T, D) tensor with evenly spaced rows, shaped like predictions')
-        grad, gcol0 = grad_out, col0
-    elif want_grad:
-        grad = g = torch.empty((b, t, w), dtype=torch.float32, device=pred.device)
-        ldg = w
+    seq_len = _lengths(seq_len, b, 'mdn: ')
+    loss, grad, g, ldg, gcol0 = _loss_and_grad_out('mdn', pred, w, col0, want_grad, grad_out, loss_out)
     ws = workspace(lib.mg_masked_mdn_workspace_bytes(b, t, k, d), pred.device)
     _lib.check(lib.mg_masked_mdn_f32(_p(pred), ldp, col0, _p(target), ldt, _p(seq_len), b, t, k, d,
                                      0.0 if min_log_std is None else float(min_log_std), int(min_log_std is not None), float(grad_scale),
@@ -624,13 +604,10 @@ def mdn_select(pred, seq_len, n_components, dim, min_log_std=None, col0=0):
     ``masked_mdn``, D = ``dim``): (component (B, T) int64 - the lowest index among the largest logits, mean (B, T, D) - that
     component's means, copied, variance (B, T, D) = exp(2 max(log std, min_log_std)) of that component).  Pad frames hold 0, 0 and 1."""
     lib = _lib.load()
-    pred, ldp = _rows_in_place(pred, 'predictions')
+    pred, ldp = _require(pred, torch.float32, 'predictions', rows=True)
     b, t, _ = pred.shape
     k, d, _ = _mdn_shape('mdn_select', pred, n_components, dim, col0)
-    if seq_len is not None:
-        seq_len = _require(seq_len, torch.int64, 'seq_len')
-        if tuple(seq_len.shape) != (b,):
-            raise ValueError('mdn_select: seq_len must be (B,) = (%d,), got %s' % (b, tuple(seq_len.shape)))
+    seq_len = _lengths(seq_len, b, 'mdn_select: ')
     component = torch.empty((b, t), dtype=torch.int64, device=pred.device)
     mean = torch.empty((b, t, d), dtype=torch.float32, device=pred.device)
     variance = torch.empty((b, t, d), dtype=torch.float32, device=pred.device)
@@ -650,8 +627,7 @@ def stream_loss_ce(pred, targets, kinds, widths, seq_len, want_grad, want_prob=F
     if pred.dim() != 3 or len(targets) != len(kinds) or not 1 <= len(targets) <= _lib.MG_STREAMS_MAX:
         raise ValueError('stream_loss: predictions must be (B, T, D) with 1..%d streams' % _lib.MG_STREAMS_MAX)
     b, t, d = pred.shape
-    if seq_len is not None:
-        seq_len = _require(seq_len, torch.int64, 'seq_len')
+    seq_len = _lengths(seq_len, b, 'stream_loss: ', flat=False)
     n = len(kinds)
     widths = [int(w) for w in widths]
     if len(widths) != n or min(widths) < 1 or sum(widths) != d:
