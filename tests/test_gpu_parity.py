@@ -444,7 +444,7 @@ def test_l2tail_kernel_vs_numpy_and_unfused_pair(bt, l2tail_variant):
     """mg_f0_l2tail_bf16 (the 512 -> 128 sigmoid layer inside the fused tail: README.rst:65-73 layers 2-4 + losses.py:29-51, forward
     and backward in one pass over H1) against a float64 restatement fed the same bf16 operands and the kernel's own bf16 rounding of
     H2, and against the unfused pair it replaces (mg_linear_fwd_bf16 + mg_f0_tail_bf16): those two differ only in the summation
-    order inside the 512-deep dot products."""
+    order inside the 512-deep dot products.  (Element by element against float64 bounds: tests/test_gpu_phone_step_ref64.py.)"""
     b, t = bt
     m = b * t
     rng = np.random.RandomState(b * t + 1)
@@ -502,7 +502,7 @@ def test_l2tail_kernel_vs_numpy_and_unfused_pair(bt, l2tail_variant):
 
 def test_l2tail_rows_kernel_vs_unfused_pair():
     """mg_f0_l2tail_rows_bf16 (phone-rate form: rows that stand for groups of frames, weights and mean targets from
-    mg_phone_target_stats) against mg_linear_fwd_bf16 + mg_f0_tail_rows_bf16."""
+    mg_phone_target_stats) against mg_linear_fwd_bf16 + mg_f0_tail_rows_bf16.  (Both against float64: tests/test_gpu_phone_step_ref64.py.)"""
     m = 21504
     rng = np.random.RandomState(11)
     h1_d = ops.cast_pad_bf16(dev(rng.uniform(0.05, 0.95, (m, 512)).astype(np.float32)))
