@@ -263,7 +263,19 @@ int mg_masked_ce_f32(const float* pred, int ldp, int col0, const int64_t* target
  * workspace: mg_masked_mdn_workspace_bytes(B,T,K,D) bytes.
  * mg_mdn_select_f32 (generation, forward only, one launch): component[b,t] = the lowest index among the largest logits,
  * mean[b,t,:] = mu of that component (exact copies), variance[b,t,:] = exp(2 max(s, floor)) of that component; pad frames are
- * written as 0, 0 and 1.  component [B,T] int64, mean / variance [B,T,D] f32, contiguous. */
+ * written as 0, 0 and 1.  component [B,T] int64, mean / variance [B,T,D] f32, contiguous.
+ * mg_mdn_sample_f32 (generation by sampling, forward only, one launch, no workspace, no atomics, no host read; layout, caps and pad
+ * rule of mg_mdn_select_f32): per valid frame, row index r = b T + t, in fp32, one wave per frame:
+ *   w_k = expf((a_k - max_j a_j) * inv_temperature)  (a -inf logit gives exactly 0),  c_k = w_0 + .. + w_k as a wave scan in one
+ *   fixed order,  S = c_{K-1};  u = u(word r % 4 of Philox block r / 4) under component_site - counter words, key and u(w) as
+ *   documented for mg_vae_sample_f32 below;  component[b,t] = the lowest k with u * S < c_k;  if there is none (the product rounded
+ *   up to S) the highest k with w_k > 0;  if S is NaN (every logit -inf) what mg_mdn_select_f32 returns.  A component whose logit is
+ *   -inf is never drawn otherwise.  variance[b,t,d] = exp(2 max(s_kd, floor)) of that component.  noise_scale == 0: mean[b,t,d] =
+ *   mu_kd, an exact copy, no noise word is drawn;  otherwise mean[b,t,d] = mu_kd + noise_scale exp(max(s_kd, floor)) g, g the
+ *   N(0, 1) value of flat element r * D + d under noise_site by the Box-Muller mapping of mg_vae_sample_f32, word for word (blocks
+ *   straddle rows when D % 4 != 0).  The counters of pad frames are not used: a frame's draw is a function of (seed, site, *counter,
+ *   b, t, d) alone, not of seq_len or ldp.  inv_temperature finite and > 0, noise_scale finite and >= 0, component_site !=
+ *   noise_site (MG_EINVAL otherwise, before any launch); seed, the sites and counter (DEVICE uint64, NULL = 0) as mg_vae_sample_f32. */
 #define MG_MDN_MAX_COMPONENTS 64
 #define MG_MDN_MAX_ROW 16384
 size_t mg_masked_mdn_workspace_bytes(int B, int T, int K, int D);
@@ -272,6 +284,9 @@ int mg_masked_mdn_f32(const float* pred, int ldp, int col0, const float* target,
                       float* grad, int ldg, int gcol0, void* workspace, size_t workspace_bytes, void* stream);
 int mg_mdn_select_f32(const float* pred, int ldp, int col0, const int64_t* seq_len, int B, int T, int K, int D, float min_log_std,
                       int has_floor, int64_t* component, float* mean, float* variance, void* stream);
+int mg_mdn_sample_f32(const float* pred, int ldp, int col0, const int64_t* seq_len, int B, int T, int K, int D, float min_log_std,
+                      int has_floor, float inv_temperature, float noise_scale, uint64_t seed, uint32_t component_site, uint32_t noise_site,
+                      const uint64_t* counter, int64_t* component, float* mean, float* variance, void* stream);
 
 /* Streaming metrics (reference: morgana/metrics.py:359-695; accumulated inside the shipped model's loss() every step,
  * models/RNN_SPSS.py:120-129): accum[0] += sum, accum[1] += count on the device - no host read-back (the reference calls .item()

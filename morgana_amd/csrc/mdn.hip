@@ -1,5 +1,5 @@
-// K19 - seq_len-masked mixture-density negative log likelihood, forward + backward, and the most-probable-component selection that
-// generation feeds to MLPG.  The reference ships no MDN layer (its author trained one with it; Zen & Senior, "Deep mixture density
+// K19 - seq_len-masked mixture-density negative log likelihood, forward + backward, and what generation feeds to MLPG: the most
+// probable component (mdn_select_kernel) or a component DRAWN from the mixture weights (mdn_sample_kernel).  The reference ships no MDN layer (its author trained one with it; Zen & Senior, "Deep mixture density
 // networks for acoustic modeling in statistical parametric speech synthesis", ICASSP 2014): the definition is include/morgana_hip.h's.
 //
 // A frame's row holds K logits a, K*D means mu and K*D log standard deviations s (component-major); the target y has D values.
@@ -26,14 +26,18 @@
 //       here) and the gradient phase reads the row again.  A row is at most 128 KB and was just read: the second read hits the L2,
 //       HBM still sees one.  MDN_ROWS_WIDE (4) frames per workgroup, one per wave.
 // Pad frames (t >= n_b) read nothing: their gradient row is written as zero, their target is never looked at.
+#include <float.h>
+
 #include "common.h"
+#include "philox_noise.h"
 #include "seq_reduce.h"
 
 #define MDN_REG_MAX 1024        // longest K*D of the register path (16 pairs per lane)
 #define MDN_SMALL_D 16          // widest D summed by one lane per component
 #define MDN_ROWS_REG 16         // frames per workgroup, register path (4 per wave)
 #define MDN_ROWS_WIDE 4         // frames per workgroup, re-read path (1 per wave)
-#define MDN_ROWS_SELECT 16      // frames per workgroup, selection
+#define MDN_ROWS_SELECT 16      // frames per workgroup, selection and sampling
+#define MDN_SAMPLE_ELEMENT_D 64 // widest D whose noise is drawn one element per lane; above, one Philox block (4 elements) per lane
 #define MDN_HALF_LOG_2PI 0.9189385332046727f
 
 static inline int mdn_rows_per_wg(int K, int D) { return K * D <= MDN_REG_MAX ? MDN_ROWS_REG : MDN_ROWS_WIDE; }
@@ -271,6 +275,113 @@ __global__ __launch_bounds__(256) void mdn_select_kernel(const float* __restrict
     }
 }
 
+// Generation by SAMPLING: component k with probability softmax(a / temperature)_k, then that component's mean (plus noise_scale
+// standard deviations of N(0, 1) noise when NOISE) and variance - mdn_select_kernel's frame mapping, grid and pad rule.  One wave
+// per frame, lane k owns logit k:
+//   w_k = expf((a_k - max a) inv_temperature)       0 exactly for a -inf logit and for the lanes past K
+//   c_k = inclusive prefix sum of w over the lanes  Hillis-Steele, offsets 1, 2, ..., 32: ONE association on every call
+//   S   = c_63                                      = c_{K-1}: the lanes past K add exact zeros
+//   u   = u(word r % 4 of Philox block r / 4), r = b T + t, under component_site: a frame's draw does not depend on seq_len,
+//         the grid or ldp (a pad frame's counter is simply not used)
+//   k*  = the lowest k with u S < c_k, by ballot.  A component with w_k = 0 has c_k = c_{k-1} (c_0 = 0 < u S): never the lowest.
+//         No such k (u S rounded up to S): the highest k with w_k > 0.  S is NaN (every logit -inf, an inf or a NaN among them):
+//         mdn_select_kernel's component, the lowest index among the largest logits.
+// Mean, NOISE: fmaf(noise_scale expf(s'), g, mu) with g = the N(0, 1) value of flat element r D + d under noise_site (philox_noise.h:
+// the noise mapping of mg_vae_sample_f32); without NOISE an exact copy, no noise word is drawn.
+// Where the arithmetic goes: a Philox block is 10 rounds of two 32 x 32 -> 64 multiplies, and every lane that needs one word of it
+// pays for all four.  So the wave's four frames draw their uniforms in ONE pass before the loop (lane l: frame l & 3), and with
+// NOISE and D > MDN_SAMPLE_ELEMENT_D a lane owns a whole BLOCK of the flat element array - four values, two Box-Muller pairs - and
+// writes those of them that lie in its row (blocks straddle rows when D % 4 != 0: the first and the last block of a row are shared
+// with its neighbours, which draw them again to the same bits).  Up to MDN_SAMPLE_ELEMENT_D values a row is one pass of one element
+// per lane either way, and the block form would only double each lane's dependent chain (measured at D = 3: 46 against 42 us).
+template <bool NOISE>
+__global__ __launch_bounds__(256) void mdn_sample_kernel(const float* __restrict__ pred, int ldp, const int64_t* __restrict__ seq_len, int T,
+                                                         int K, int D, float floor, int has_floor, float inv_temperature, float noise_scale,
+                                                         unsigned seed_lo, unsigned seed_hi, unsigned component_site, unsigned noise_site,
+                                                         const unsigned long long* __restrict__ counter, int64_t* __restrict__ component,
+                                                         float* __restrict__ mean, float* __restrict__ variance) {
+    const unsigned long long ctr = counter ? counter[0] : 0ull;
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t n_b = mg_valid_frames(seq_len, b, T);
+    const int t0 = blockIdx.x * MDN_ROWS_SELECT;
+    float u_mine;                                         // lane l: the uniform of the wave's frame t0 + wave + 4 (l & 3)
+    {
+        const size_t row_l = (size_t)b * T + (size_t)(t0 + wave + 4 * (lane & 3));
+        u_mine = smp_uniform(smp_word(smp_block((int64_t)(row_l >> 2), ctr, component_site, seed_lo, seed_hi), (int)(row_l & 3)));
+    }
+    for (int r = wave; r < MDN_ROWS_SELECT; r += 4) {
+        const int t = t0 + r;
+        if (t >= T) break;
+        const size_t row = (size_t)b * T + t;
+        if (t >= n_b) {
+            if (lane == 0) component[row] = 0;
+            for (int d = lane; d < D; d += 64) {
+                mean[row * D + d] = 0.f;
+                variance[row * D + d] = 1.f;
+            }
+            continue;
+        }
+        const float* x = pred + row * ldp;
+        const float a = lane < K ? x[lane] : -INFINITY;
+        const float amax = mg_wave_max(a);
+        const float w = lane < K ? expf((a - amax) * inv_temperature) : 0.f;
+        float c = w;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const float below = __shfl_up(c, off, 64);
+            if (lane >= off) c += below;
+        }
+        const float total = __shfl(c, 63, 64);
+        int im;
+        if (total != total) {                             // wave-uniform
+            float m = a;
+            im = lane;                                    // lanes past K hold -inf and a larger index: they lose every merge
+            mg_wave_argmax(m, im);
+            im = __shfl(im, 0, 64);
+            if (im >= K) im = K - 1;
+        } else {
+            const float us = __shfl(u_mine, r >> 2, 64) * total;
+            const unsigned long long above = __ballot(lane < K && us < c);
+            const unsigned long long live = __ballot(w > 0.f);            // never empty: the largest logit has w = 1
+            im = above ? __ffsll((long long)above) - 1 : 63 - __clzll((long long)live);
+            if (im < 0) im = 0;                           // cannot happen (above); the reads below stay inside the row whatever
+            if (im >= K) im = K - 1;
+        }
+        if (lane == 0) component[row] = im;
+        const float* mu = x + K + (size_t)im * D;
+        const float* sd = mu + (size_t)K * D;
+        if (NOISE && D > MDN_SAMPLE_ELEMENT_D) {
+            const int64_t e0 = (int64_t)row * D;          // the row's flat elements are [e0, e0 + D): blocks e0 / 4 .. (e0 + D - 1) / 4
+            for (int64_t q = (e0 >> 2) + lane; q <= ((e0 + D - 1) >> 2); q += 64) {
+                const u32q words = smp_block(q, ctr, noise_site, seed_lo, seed_hi);
+                float g[4];
+                smp_normal_pair(words.x, words.y, g[0], g[1]);
+                smp_normal_pair(words.z, words.w, g[2], g[3]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int64_t d = 4 * q + j - e0;
+                    if (d >= 0 && d < D) {
+                        float s = sd[d];
+                        if (has_floor && s < floor) s = floor;
+                        variance[e0 + d] = expf(2.f * s);
+                        mean[e0 + d] = fmaf(noise_scale * expf(s), g[j], mu[d]);
+                    }
+                }
+            }
+        } else {                                          // one element per lane: with NOISE a lane's chain is one block and ONE pair
+            for (int d = lane; d < D; d += 64) {
+                float s = sd[d];
+                if (has_floor && s < floor) s = floor;
+                variance[row * D + d] = expf(2.f * s);
+                if (NOISE)
+                    mean[row * D + d] = fmaf(noise_scale * expf(s), smp_normal((int64_t)(row * D + d), ctr, noise_site, seed_lo, seed_hi), mu[d]);
+                else
+                    mean[row * D + d] = mu[d];
+            }
+        }
+    }
+}
+
 static size_t mdn_ws_bytes(int B, int T, int K, int D) {
     if (B <= 0 || T <= 0 || K <= 0 || D <= 0 || K > MG_MDN_MAX_COMPONENTS || (int64_t)K * D > MG_MDN_MAX_ROW) return 256;
     const int64_t chunks = mg_ceil_div(T, mdn_rows_per_wg(K, D));
@@ -353,6 +464,37 @@ int mg_mdn_select_f32(const float* pred, int ldp, int col0, const int64_t* seq_l
     hipLaunchKernelGGL(mdn_select_kernel, dim3((unsigned)mg_ceil_div(T, MDN_ROWS_SELECT), B), dim3(256), 0, (hipStream_t)stream, pred + col0,
                        ldp, seq_len, T, K, D, min_log_std, has_floor != 0, component, mean, variance);
     MG_CHECK_LAUNCH("mg_mdn_select_f32");
+    return MG_OK;
+}
+
+int mg_mdn_sample_f32(const float* pred, int ldp, int col0, const int64_t* seq_len, int B, int T, int K, int D, float min_log_std,
+                      int has_floor, float inv_temperature, float noise_scale, uint64_t seed, uint32_t component_site, uint32_t noise_site,
+                      const uint64_t* counter, int64_t* component, float* mean, float* variance, void* stream) {
+    MG_CHECK_ARG(pred && component && mean && variance, "mg_mdn_sample_f32: pred, component, mean and variance must not be NULL");
+    MG_CHECK_ARG(B > 0 && T > 0 && K > 0 && D > 0, "mg_mdn_sample_f32: bad shape (B=%d T=%d K=%d D=%d)", B, T, K, D);
+    MG_CHECK_ARG(K <= MG_MDN_MAX_COMPONENTS, "mg_mdn_sample_f32: K=%d exceeds the cap of %d components", K, MG_MDN_MAX_COMPONENTS);
+    MG_CHECK_ARG((int64_t)K * D <= MG_MDN_MAX_ROW, "mg_mdn_sample_f32: K*D=%lld exceeds the cap of %d means per frame", (long long)K * D,
+                 MG_MDN_MAX_ROW);
+    MG_CHECK_ARG(B <= 65535, "mg_mdn_sample_f32: B=%d exceeds 65535", B);
+    const int W = K * (1 + 2 * D);
+    MG_CHECK_ARG(col0 >= 0 && (int64_t)ldp >= (int64_t)col0 + W, "mg_mdn_sample_f32: columns [%d, %d + %d) do not fit the row stride ldp=%d",
+                 col0, col0, W, ldp);
+    MG_CHECK_ARG(inv_temperature > 0.f && inv_temperature <= FLT_MAX, "mg_mdn_sample_f32: inv_temperature=%g must be finite and positive",
+                 (double)inv_temperature);
+    MG_CHECK_ARG(noise_scale >= 0.f && noise_scale <= FLT_MAX, "mg_mdn_sample_f32: noise_scale=%g must be finite and not negative",
+                 (double)noise_scale);
+    MG_CHECK_ARG(component_site != noise_site, "mg_mdn_sample_f32: the component and the noise site are both 0x%x: one stream for two draws",
+                 (unsigned)component_site);
+    const dim3 grid((unsigned)mg_ceil_div(T, MDN_ROWS_SELECT), B);
+    if (noise_scale != 0.f)
+        hipLaunchKernelGGL(mdn_sample_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, pred + col0, ldp, seq_len, T, K, D, min_log_std,
+                           has_floor != 0, inv_temperature, noise_scale, (unsigned)seed, (unsigned)(seed >> 32), component_site, noise_site,
+                           (const unsigned long long*)counter, component, mean, variance);
+    else
+        hipLaunchKernelGGL(mdn_sample_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, pred + col0, ldp, seq_len, T, K, D, min_log_std,
+                           has_floor != 0, inv_temperature, noise_scale, (unsigned)seed, (unsigned)(seed >> 32), component_site, noise_site,
+                           (const unsigned long long*)counter, component, mean, variance);
+    MG_CHECK_LAUNCH("mg_mdn_sample_f32");
     return MG_OK;
 }
 

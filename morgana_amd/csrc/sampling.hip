@@ -8,30 +8,7 @@
 // scan run in one fixed order (no atomics): the same bits on every call.  Every entry point checks its arguments on the host,
 // allocates nothing and never synchronises.  Only vector (global) stores.
 #include "common.h"
-#include "philox.h"
-
-// the u(w) of vae.hip: odd multiple of 2^-24 inside (0, 1), exact in fp32
-__device__ __forceinline__ float smp_uniform(unsigned x) { return (float)((x >> 8) | 1u) * 5.9604644775390625e-8f; }
-
-__device__ __forceinline__ u32q smp_block(int64_t q, unsigned long long ctr, unsigned site, unsigned seed_lo, unsigned seed_hi) {
-    return philox4x32_10(u32q{(unsigned)q, (unsigned)((unsigned long long)q >> 32), (unsigned)ctr, site ^ (unsigned)(ctr >> 32)}, seed_lo,
-                         seed_hi);
-}
-
-__device__ __forceinline__ unsigned smp_word(const u32q& w, int j) { return j == 0 ? w.x : j == 1 ? w.y : j == 2 ? w.z : w.w; }
-
-// N(0, 1) value of flat element i: words (x, y) of block i / 4 make elements 4q, 4q + 1 and (z, w) make 4q + 2, 4q + 3 as
-// sqrt(-2 ln u(a)) (cos, sin)(2 pi u(b)) - vae_box_muller's arithmetic, one element of the pair.  Never 0: u < 1 and 2 u(b) is an odd
-// multiple of 2^-23, never a multiple of 1/2.
-__device__ __forceinline__ float smp_normal(int64_t i, unsigned long long ctr, unsigned site, unsigned seed_lo, unsigned seed_hi) {
-    const u32q w = smp_block(i >> 2, ctr, site, seed_lo, seed_hi);
-    const int j = (int)(i & 3);
-    const unsigned a = j < 2 ? w.x : w.z, b = j < 2 ? w.y : w.w;
-    const float r = sqrtf(-2.f * logf(smp_uniform(a)));
-    float s, c;
-    sincospif(2.f * smp_uniform(b), &s, &c);
-    return r * ((j & 1) ? s : c);
-}
+#include "philox_noise.h"                                 // smp_uniform / smp_block / smp_word / smp_normal: shared with mdn.hip
 
 // Rows of up to SPH_REG * 64 values stay in registers between the norm and the scaling; longer rows loop over chunks of 64 with a
 // carried per-lane partial sum and draw their noise a second time (the same function of the same words: the same bits).

@@ -155,11 +155,33 @@ def mdn_select(predictions, n_components, dim, seq_len=None, min_log_std=None):
     """Generation from a mixture-density stream (the layout of ``mdn``, D = ``dim``): per frame the most probable component (the
     lowest index among the largest logits), its means and its variances ``exp(2 max(s, min_log_std))`` - what MLPG takes as per-frame
     means and variances.  Returns (component (B, T) int64, mean (B, T, D), variance (B, T, D)), detached; pad frames hold 0, 0 and 1.
-    One launch (csrc/mdn.hip).  Sampling a component instead of taking the largest is not provided."""
+    One launch (csrc/mdn.hip).  ``mdn_sample`` draws a component from the mixture weights instead of taking the largest."""
     _mdn_predictions('mdn_select', predictions, n_components, dim)
     if seq_len is not None and seq_len.dtype != torch.int64:
         seq_len = seq_len.long()
     return ops.mdn_select(predictions.detach(), seq_len, int(n_components), int(dim), min_log_std=min_log_std)
+
+
+def mdn_sample(predictions, n_components, dim, seq_len=None, min_log_std=None, temperature=1., noise_scale=0.):
+    """Sampled generation from a mixture-density stream (the layout of ``mdn``, D = ``dim``): per frame ONE component drawn with
+    probability ``softmax(logits / temperature)``, its means and its variances ``exp(2 max(s, min_log_std))`` - what MLPG takes as
+    per-frame means and variances, a different rendition on every call where ``mdn_select`` always gives the mode.  Returns
+    (component (B, T) int64, mean (B, T, D), variance (B, T, D)), detached; pad frames hold 0, 0 and 1.
+
+    ``temperature`` (a finite Python number > 0): below 1 the draw leans towards the most probable component, above 1 towards the
+    uniform one; 0 is refused - that limit is ``mdn_select``.  ``noise_scale`` (>= 0): 0 returns the drawn component's mean as it is;
+    otherwise the mean is ``mu + noise_scale * exp(max(s, min_log_std)) * g`` with g ~ N(0, 1) per element (1: a draw from the mixture
+    itself).  A -inf logit is never drawn.  One launch (csrc/mdn.hip); the draws are Philox words of (torch's seed, ops.MDN_COMPONENT_SITE
+    / ops.MDN_NOISE_SITE, ONE draw of the device's step counter, frame [, element]), so ``torch.manual_seed`` makes a run repeatable
+    and a captured graph draws anew on every replay.  No gradient flows through the draw."""
+    temperature, noise_scale = ops.mdn_sample_arguments('mdn_sample', temperature, noise_scale)
+    _mdn_predictions('mdn_sample', predictions, n_components, dim)
+    if seq_len is not None and seq_len.dtype != torch.int64:
+        seq_len = seq_len.long()
+    predictions = predictions.detach()
+    ops.mdn_sample_shape(predictions, n_components, dim)      # the caps, before the step counter moves
+    return ops.mdn_sample(predictions, seq_len, int(n_components), int(dim), ops.dropout_seed(), ops.dropout_draw(predictions.device),
+                          min_log_std=min_log_std, temperature=temperature, noise_scale=noise_scale)
 
 
 _HALF_LOG_2PI = 0.9189385332046727

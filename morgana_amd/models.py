@@ -181,7 +181,9 @@ class Stream(object):
     ``losses.mdn`` against ``normalised_<name>_deltas`` and is a delta stream for target, normaliser, trajectory and metrics.  Its raw
     parameters go out as ``<name>_mdn``, the most probable component's mean as ``normalised_<name>_deltas`` and its per-frame
     variance as ``normalised_<name>_deltas_variance`` (``losses.mdn_select``, both detached); MLPG then runs on the denormalised mean
-    under the PER-FRAME variances ``variance * std_dev^2``.  Such a stream takes no trajectory loss.
+    under the PER-FRAME variances ``variance * std_dev^2``.  Such a stream takes no trajectory loss.  In ``eval()`` mode after
+    ``StreamModel.sample_mixtures(temperature, noise_scale)`` the component is DRAWN per frame instead (``losses.mdn_sample``: the
+    same two keys, plus the component as ``<name>_component``); ``select_mixtures()`` restores the default.
     ``gv_weight`` > 0 (delta streams only) adds a global-variance term on the same differentiable trajectory, against over-smoothing:
     ``gv_weight * losses.gv(normalised trajectory, normalised_<name>, n_frames, log=gv_log)``; with ``trajectory_weight`` as well the
     trajectory is solved and normalised once.
@@ -338,6 +340,25 @@ class StreamModel(BaseSPSS):
                 sources[st.name] = data.MeanVarianceNormaliser(st.name, use_deltas=True)
         return sources
 
+    # -- generation from mixture-density streams -------------------------------------------------------------------------------------
+    _mixture_sampling = None      # (temperature, noise_scale) while sample_mixtures is in force
+
+    def sample_mixtures(self, temperature=1., noise_scale=0.):
+        """In ``eval()`` mode every 'mdn' stream from now on DRAWS its component per frame (``losses.mdn_sample`` with these two
+        arguments) instead of taking the most probable one: each ``predict`` is another rendition.  The drawn mean and variance go out
+        under the keys of the selected ones (MLPG, denormalisation and metrics read them unchanged), the component as
+        ``<name>_component``.  In ``train()`` mode nothing changes: the most probable component, as before.  Returns the model."""
+        if not any(st.is_mdn for st in self.streams):
+            raise ValueError("sample_mixtures: the model has no 'mdn' stream to draw from (streams: %s)"
+                             % ', '.join('%s: %s' % (st.name, st.loss if not callable(st.loss) else 'callable') for st in self.streams))
+        self._mixture_sampling = ops.mdn_sample_arguments('sample_mixtures', temperature, noise_scale)
+        return self
+
+    def select_mixtures(self):
+        """Back to the most probable component of every frame (``losses.mdn_select``), the default.  Returns the model."""
+        self._mixture_sampling = None
+        return self
+
     # -- pieces ----------------------------------------------------------------------------------------------------------------------
     def _run_layers(self, features):
         norm_counters = features['normalised_counters']
@@ -357,8 +378,14 @@ class StreamModel(BaseSPSS):
         for st, part in zip(self.streams, parts):
             if st.is_mdn:
                 outputs[st.name + '_mdn'] = part          # what the loss reads (the column slice, in place)
-                _, outputs[st.output_key], outputs[st.output_key + '_variance'] = losses.mdn_select(
-                    part, st.n_components, st.dim, seq_len=seq_len, min_log_std=st.min_log_std)
+                if self._mixture_sampling is not None and not self.training:
+                    temperature, noise_scale = self._mixture_sampling
+                    outputs[st.name + '_component'], outputs[st.output_key], outputs[st.output_key + '_variance'] = losses.mdn_sample(
+                        part, st.n_components, st.dim, seq_len=seq_len, min_log_std=st.min_log_std, temperature=temperature,
+                        noise_scale=noise_scale)
+                else:
+                    _, outputs[st.output_key], outputs[st.output_key + '_variance'] = losses.mdn_select(
+                        part, st.n_components, st.dim, seq_len=seq_len, min_log_std=st.min_log_std)
             elif st.is_gaussian:
                 outputs[st.name + '_gaussian'] = part     # what the loss reads (the column slice, in place)
                 mean, log_std = part[..., :st.dim], part[..., st.dim:]

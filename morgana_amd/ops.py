@@ -2,6 +2,8 @@
 HIP stream.  No arithmetic happens here and nothing falls back to torch ops: a missing library or a CPU tensor raises.
 """
 import ctypes
+import math
+import numbers
 
 import os
 
@@ -613,6 +615,56 @@ def mdn_select(pred, seq_len, n_components, dim, min_log_std=None, col0=0):
     variance = torch.empty((b, t, d), dtype=torch.float32, device=pred.device)
     _lib.check(lib.mg_mdn_select_f32(_p(pred), ldp, col0, _p(seq_len), b, t, k, d, 0.0 if min_log_std is None else float(min_log_std),
                                      int(min_log_std is not None), _p(component), _p(mean), _p(variance), _stream()), 'mg_mdn_select_f32')
+    return component, mean, variance
+
+
+def mdn_sample_arguments(what, temperature, noise_scale):
+    """(temperature, noise_scale) of a mixture draw as floats, or ValueError: ``temperature`` a finite Python number > 0,
+    ``noise_scale`` a finite Python number >= 0.  No device is needed."""
+    for name, value in (('temperature', temperature), ('noise_scale', noise_scale)):
+        if isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(value):
+            raise ValueError('%s: %s must be a finite Python number, got %r' % (what, name, value))
+    if temperature == 0:
+        raise ValueError('%s: temperature=0 is the most probable component of every frame: that is mdn_select, not a draw' % what)
+    if temperature < 0:
+        raise ValueError('%s: temperature must be > 0, got %r' % (what, temperature))
+    if noise_scale < 0:
+        raise ValueError('%s: noise_scale must be >= 0, got %r' % (what, noise_scale))
+    inv = 1.0 / float(temperature)
+    if not 0.0 < inv <= 3.4028234663852886e38:
+        raise ValueError('%s: 1 / temperature = %r is no positive finite float32' % (what, inv))
+    return float(temperature), float(noise_scale)
+
+
+def mdn_sample_shape(pred, n_components, dim, col0=0):
+    """The refusals of ``mdn_sample`` that depend on the tensor alone (device, dtype, the caps, the column range), for a caller
+    that wants them before it reserves a draw of the step counter."""
+    pred = _require(pred, torch.float32, 'predictions', contiguous=False)
+    if pred.dim() != 3:
+        raise ValueError('predictions must be (B, T, C), got %s' % (tuple(pred.shape),))
+    return _mdn_shape('mdn_sample', pred, n_components, dim, col0)
+
+
+def mdn_sample(pred, seq_len, n_components, dim, seed, used, min_log_std=None, temperature=1., noise_scale=0., col0=0):
+    """A DRAW from every frame of a mixture-density stream (mg_mdn_sample_f32; the column layout of ``masked_mdn``, D = ``dim``):
+    (component (B, T) int64 ~ softmax(logits / temperature), mean (B, T, D) - that component's means, plus ``noise_scale`` of its
+    standard deviations times N(0, 1) noise when ``noise_scale`` > 0, variance (B, T, D) = exp(2 max(log std, min_log_std)) of that
+    component).  The uniform of frame (b, t) and the noise of element (b, t, d) come from (seed, MDN_COMPONENT_SITE / MDN_NOISE_SITE,
+    used[0], b T + t [, d]): the same four numbers give the same bits.  ``used``: a 1-element int64 DEVICE tensor (``dropout_draw``).
+    Pad frames hold 0, 0 and 1."""
+    temperature, noise_scale = mdn_sample_arguments('mdn_sample', temperature, noise_scale)
+    lib = _lib.load()
+    pred, ldp = _require(pred, torch.float32, 'predictions', rows=True)
+    b, t, _ = pred.shape
+    k, d, _ = _mdn_shape('mdn_sample', pred, n_components, dim, col0)
+    seq_len = _lengths(seq_len, b, 'mdn_sample: ')
+    component = torch.empty((b, t), dtype=torch.int64, device=pred.device)
+    mean = torch.empty((b, t, d), dtype=torch.float32, device=pred.device)
+    variance = torch.empty((b, t, d), dtype=torch.float32, device=pred.device)
+    _lib.check(lib.mg_mdn_sample_f32(_p(pred), ldp, col0, _p(seq_len), b, t, k, d, 0.0 if min_log_std is None else float(min_log_std),
+                                     int(min_log_std is not None), 1.0 / temperature, noise_scale, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                     MDN_COMPONENT_SITE, MDN_NOISE_SITE, _p(used), _p(component), _p(mean), _p(variance), _stream()),
+               'mg_mdn_sample_f32')
     return component, mean, variance
 
 
@@ -1257,6 +1309,8 @@ def dropout(x, p, seed, site, used, out=None):
 SAMPLE_SITE = 0x56414500     # the Philox site of the VAE sampler's noise (dropout masks use the module index of their layer)
 SPHERE_SITE = 0x53504800     # the Philox sites of sampling.UniformSphereSurfaceSampler's noise ...
 ELLIPSOID_SITE = 0x454C4C00  # ... and of sampling.UniformEllipsoidSurfaceApproximateSampler's angles: three streams, never one
+MDN_COMPONENT_SITE = 0x4D444300   # mdn_sample: the uniform that picks a frame's mixture component ...
+MDN_NOISE_SITE = 0x4D444E00       # ... and the N(0, 1) noise around its mean: two more streams, independent of each other
 
 
 def _latent_rows(t, name):
