@@ -347,6 +347,24 @@ size_t mg_mlpg_grad_mv_workspace_bytes(int B, int T, int D, int padding, int n_w
 int mg_mlpg_grad_mv_f32(const float* grad_out, const float* means, const float* variances, const int64_t* seq_len, int B, int T, int D,
                         int n_windows, const int* win_l, const int* win_u, const double* win_coeff, int padding, void* grad_means,
                         void* grad_variances, int out_f64, void* workspace, size_t workspace_bytes, void* stream);
+/* Parameter generation under a global-variance prior (csrc/mlpg_gv.hip; Toda & Tokuda 2007 - the reference generates with plain MLPG
+ * only).  means, variances, var_per_frame, seq_len, windows and padding as in mg_mlpg_f32, with the same checks; gv_mean and
+ * gv_variance f32 [D], or [B,D] if gv_per_item (per-speaker statistics): mean and variance of the per-utterance variance of the static
+ * feature.  Per (b, d), with P, rhs and the output rows O of mg_mlpg_f32, n = len, omega = 1/(W n) and v(x) the biased variance over O:
+ *   minimise  omega (x^T P x / 2 - x^T rhs) + (gv_weight / 2) (v(x) - gv_mean)^2 / gv_variance
+ * through its stationarity system (P + gamma E - (gamma/n) e e^T) x = rhs, gamma = 2 W kappa, kappa = gv_weight (v(x) - gv_mean) /
+ * gv_variance: a bracketed scalar root search on kappa inside ONE launch, one thread per system, every evaluation an unpivoted banded
+ * LDL^T of the shifted band with two right-hand sides and a rank-one correction, feasibility by inertia; at most max_iter (>= 3)
+ * evaluations.  float32 1/var and mean/var as in mg_mlpg_f32, float64 after that.  out [B,T,D] f32, or f64 if out_f64, zero past
+ * seq_len (whose input frames are never read).  info: NULL or f64 [B,D,4] = (kappa, final |h|, evaluations used, flag); flag 1 =
+ * fallback, the output is the plain MLPG solution: len < 2, gv_weight = 0, gv_variance <= 0, or a search that ended with
+ * |h| > 1e-6 (1 + |kappa|).  gv_weight = 0 runs mg_mlpg_f32 itself: the same bits.  No atomics, no host read, deterministic,
+ * graph-capturable.  workspace: mg_mlpg_gv_workspace_bytes(...) bytes = twice mg_mlpg_workspace_bytes(...). */
+size_t mg_mlpg_gv_workspace_bytes(int B, int T, int D, int padding, int n_windows, const int* win_l, const int* win_u);
+int mg_mlpg_gv_f32(const float* means, const float* variances, int var_per_frame, const float* gv_mean, const float* gv_variance,
+                   int gv_per_item, const int64_t* seq_len, int B, int T, int D, int n_windows, const int* win_l, const int* win_u,
+                   const double* win_coeff, int padding, double gv_weight, int max_iter, void* out, int out_f64, double* info,
+                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * K5 mvn / minmax normalisers           reference: morgana/data.py:533-538, 579-590

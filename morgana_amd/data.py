@@ -1186,3 +1186,80 @@ def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out
         for normaliser in normalisers.values():
             normaliser.save_params(out_dir, data_root)
     return results
+
+
+GV_SUFFIX = '_gv'
+
+
+def fit_global_variance(utterances, names, device='cuda:0', batch_size=64, out_dir=None, data_root='.', speaker_id_list=None, ddof=0):
+    """Fit the statistics of the global-variance prior of ``ops.mlpg_gv`` / ``StreamModel.generate_with_gv`` to a corpus: for every
+    feature of ``names`` the mean and standard deviation, over the utterances, of the per-utterance variance of each column.
+
+    ``utterances``: a ``FilesDataset`` (read through ``raw``) or a sequence of raw utterance dicts holding the STATIC feature under its
+    name, (frames, D).  Batch by batch the feature is padded and uploaded, ``losses.global_variance`` gives the (utterances, D)
+    biased variances on ``device`` (an utterance of one frame counts with variance 0), and those rows - one item of one frame each -
+    go into a ``ColumnStats``; ``speaker_id_list`` (a file of names under ``data_root``) keeps one state row per speaker, every
+    utterance assigned by its ``speaker_id``.  One read per feature at the end.
+
+    Returns {name + '_gv': normaliser}: an ordinary ``MeanVarianceNormaliser(name + '_gv')`` (``mean`` = the GV mean, ``std_dev``^2 =
+    the GV variance), or its speaker-dependent twin, with the parameters set; with ``out_dir`` also saved by ``save_params`` as
+    ``{name}_gv_mvn.json`` (``{speaker}/{name}_gv_mvn.json``), which ``load_params`` reads back bit for bit.  Raises ValueError
+    before anything is written if a listed speaker has no utterance or a statistic is not finite."""
+    from ._lib import MorganaHipError
+    from . import losses
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise MorganaHipError('fit_global_variance runs on an MI355X device, got %s (there is no CPU fallback)' % device)
+    if batch_size <= 0:
+        raise ValueError('batch_size must be positive, got %r' % (batch_size,))
+    names = [names] if isinstance(names, str) else list(names)
+    if not names:
+        raise ValueError('fit_global_variance: no feature names')
+    order = None if speaker_id_list is None else _read_id_list(os.path.join(data_root, speaker_id_list))
+    fetch = utterances.raw if isinstance(utterances, FilesDataset) else utterances.__getitem__
+    stats = {}
+    for start in range(0, len(utterances), batch_size):
+        items = [fetch(i) for i in range(start, min(start + batch_size, len(utterances)))]
+        item_row = None
+        if order is not None:
+            if SPEAKER_ID_KEY not in items[0]:
+                raise KeyError("per-speaker statistics need a '%s' entry in every utterance" % SPEAKER_ID_KEY)
+            item_row = torch.from_numpy(speaker_index_of([item[SPEAKER_ID_KEY] for item in items], order)).to(device)
+        for name in names:
+            rows = [np.asarray(_fit_rows(item, name), dtype=np.float32) for item in items]
+            lens = np.array([len(r) for r in rows], dtype=np.int64)
+            if (lens <= 0).any():
+                raise ValueError('fit_global_variance: feature %r of an utterance has no frame' % name)
+            padded = np.zeros((len(rows), int(lens.max()), rows[0].shape[1]), dtype=np.float32)
+            for i, r in enumerate(rows):
+                padded[i, :len(r)] = r
+            variances = losses.global_variance(torch.from_numpy(padded).to(device), torch.from_numpy(lens).to(device))      # (B, D)
+            if name not in stats:
+                stats[name] = ColumnStats(variances.shape[1], groups=1 if order is None else len(order), device=device)
+            stats[name].update_padded(variances[:, None, :].contiguous(), torch.ones(len(rows), dtype=torch.int64, device=device), item_row)
+    if not stats:
+        raise ValueError('fit_global_variance: no utterances')
+    results = {name: stats[name].result(ddof) for name in names}
+    for name in names:                                    # refuse before anything is written
+        result = results[name]
+        if order is not None:
+            absent = [spk for row, spk in enumerate(order) if not result['count'][row].any()]
+            if absent:
+                raise ValueError('fit_global_variance: feature %r has no utterance of the listed speakers %s' % (name, absent))
+        for key in ('mean', 'std_dev'):
+            if not np.isfinite(result[key]).all():
+                raise ValueError('fit_global_variance: %s of the variances of feature %r is not finite' % (key, name))
+    fitted = {}
+    for name in names:
+        if order is None:
+            normaliser = MeanVarianceNormaliser(name + GV_SUFFIX)
+            normaliser.set_params(stats[name].params('mvn', result=results[name]), device=device)
+        else:
+            normaliser = SpeakerDependentMeanVarianceNormaliser(name + GV_SUFFIX, speaker_id_list)
+            normaliser.speaker_ids = list(order)
+            normaliser.set_params({spk: stats[name].params('mvn', row, result=results[name]) for row, spk in enumerate(order)},
+                                  device=device)
+        if out_dir is not None:
+            normaliser.save_params(out_dir, data_root)
+        fitted[name + GV_SUFFIX] = normaliser
+    return fitted

@@ -338,7 +338,55 @@ class StreamModel(BaseSPSS):
                 sources[st.name] = data.SpeakerDependentMeanVarianceNormaliser(st.name, self.speaker_id_list, use_deltas=True)
             elif st.is_delta:
                 sources[st.name] = data.MeanVarianceNormaliser(st.name, use_deltas=True)
+            if st.is_delta and self._gv_generation is not None:      # the prior's statistics (data.fit_global_variance writes them)
+                sources[st.name + data.GV_SUFFIX] = (
+                    data.SpeakerDependentMeanVarianceNormaliser(st.name + data.GV_SUFFIX, self.speaker_id_list)
+                    if self.speaker_id_list is not None else data.MeanVarianceNormaliser(st.name + data.GV_SUFFIX))
         return sources
+
+    # -- generation under a global-variance prior ------------------------------------------------------------------------------------
+    _gv_generation = None         # (gv_weight, max_iter) while generate_with_gv is in force
+
+    def generate_with_gv(self, gv_weight=1., max_iter=48):
+        """In ``eval()`` mode every delta stream's trajectory from now on is generated under the global-variance prior of its
+        ``{name}_gv`` normaliser (``ops.mlpg_gv``: mean and std_dev of the per-utterance variance of the static feature, fitted by
+        ``data.fit_global_variance``; per speaker with ``speaker_id_list``) instead of being the plain MLPG solution, and
+        ``normaliser_sources()`` lists those normalisers.  In ``train()`` mode nothing changes, and neither do the differentiable
+        trajectories of a trajectory or global-variance LOSS.  Returns the model."""
+        if not any(st.is_delta for st in self.streams):
+            raise ValueError('generate_with_gv: the model has no delta stream to generate a trajectory for (streams: %s)'
+                             % ', '.join(st.name for st in self.streams))
+        gv_weight, max_iter = float(gv_weight), int(max_iter)
+        if not 0. <= gv_weight < float('inf'):
+            raise ValueError('generate_with_gv: gv_weight must be finite and >= 0, got %r' % gv_weight)
+        if max_iter < 3:
+            raise ValueError('generate_with_gv: max_iter must be at least 3, got %r' % max_iter)
+        self._gv_generation = (gv_weight, max_iter)
+        return self
+
+    def generate_without_gv(self):
+        """Back to the plain MLPG solution, the default.  Returns the model."""
+        self._gv_generation = None
+        return self
+
+    def _gv_trajectory(self, name, pred_deltas, variances, seq_len, index=None):
+        """``ops.mlpg_gv`` under the ``{name}_gv`` normaliser: row ``index[b]`` of its tables for utterance b when it is per speaker."""
+        gv_weight, max_iter = self._gv_generation
+        prior = self.normalisers.get(name + data.GV_SUFFIX) if hasattr(self.normalisers, 'get') else None
+        if prior is None or not prior.params:
+            raise KeyError('generate_with_gv: the normalisers hold no parameters for %r (fit them with data.fit_global_variance and load '
+                           'them through normaliser_sources())' % (name + data.GV_SUFFIX))
+        if isinstance(prior, data._SpeakerDependentNormaliser):
+            if index is None:
+                raise KeyError("the normaliser of %r is speaker-dependent: the batch needs features['%s'] (the loaders write it)"
+                               % (name + data.GV_SUFFIX, data.SPEAKER_INDEX_KEY))
+            mean, std_dev = (ops.item_rows(table, index) for table in prior.tables(pred_deltas.device))
+        else:
+            mean, std_dev = (prior.params_torch[key].to(device=pred_deltas.device, dtype=torch.float32) for key in ('mean', 'std_dev'))
+        if seq_len is not None:
+            seq_len = seq_len.reshape(-1).to(device=pred_deltas.device, dtype=torch.int64)
+        return ops.mlpg_gv(pred_deltas, variances, mean, std_dev ** 2, viz.synthesis.DEFAULT_WINDOWS, padding_size=100, seq_len=seq_len,
+                           gv_weight=gv_weight, max_iter=max_iter)
 
     # -- generation from mixture-density streams -------------------------------------------------------------------------------------
     _mixture_sampling = None      # (temperature, noise_scale) while sample_mixtures is in force
@@ -429,6 +477,9 @@ class StreamModel(BaseSPSS):
             pred_deltas = normaliser.denormalise(pred_norm_deltas, speaker_index, deltas=True)
             index = normaliser.speaker_index(speaker_index, pred_deltas.device)
             std_dev = ops.item_rows(normaliser.tables(pred_deltas.device, deltas=True)[1], index)
+            if self._gv_generation is not None and not self.training:
+                variances = std_dev ** 2 if norm_variance is None else norm_variance.detach() * (std_dev ** 2)[:, None, :]
+                return self._gv_trajectory(name, pred_deltas.detach(), variances, seq_len, index)
             if differentiable and variance_grad:
                 return viz.synthesis.mlpg_trajectory(pred_deltas, norm_variance * (std_dev ** 2)[:, None, :], padding_size=100,
                                                      seq_len=seq_len, variance_grad=True)
@@ -437,6 +488,10 @@ class StreamModel(BaseSPSS):
             variances = std_dev ** 2 if norm_variance is None else norm_variance.detach() * (std_dev ** 2)[:, None, :]
             return ops.mlpg(pred_deltas, variances, viz.synthesis.DEFAULT_WINDOWS, padding_size=100, seq_len=seq_len)
         pred_deltas = normaliser.denormalise(pred_norm_deltas, deltas=True)
+        if self._gv_generation is not None and not self.training:
+            std_dev = normaliser.delta_params_torch['std_dev'].to(device=pred_deltas.device, dtype=torch.float32)
+            variances = std_dev ** 2 if norm_variance is None else norm_variance.detach() * std_dev ** 2
+            return self._gv_trajectory(name, pred_deltas.detach(), variances, seq_len)
         if differentiable and variance_grad:
             std_dev = normaliser.delta_params_torch['std_dev'].to(device=pred_deltas.device, dtype=torch.float32)
             return viz.synthesis.mlpg_trajectory(pred_deltas, norm_variance * std_dev ** 2, padding_size=100, seq_len=seq_len,

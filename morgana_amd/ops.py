@@ -2763,6 +2763,65 @@ def mlpg(means, variances, windows, padding_size=0, seq_len=None, out_dtype=torc
     return out
 
 
+def mlpg_gv(means, variances, gv_mean, gv_variance, windows, padding_size=0, seq_len=None, gv_weight=1., max_iter=48,
+            out_dtype=torch.float32, want_info=False):
+    """``mlpg`` under a global-variance prior (csrc/mlpg_gv.hip, mg_mlpg_gv_f32; Toda & Tokuda 2007): per (utterance, dimension) the
+    trajectory x that minimises  omega (x'Px/2 - x'rhs) + gv_weight/2 (v(x) - gv_mean)^2 / gv_variance  with P, rhs of ``mlpg``,
+    omega = 1 / (windows x frames) and v the biased variance of x over the utterance's frames - an exact root search on the one
+    multiplier of its stationarity system, inside one launch.  means, variances (all three layouts), windows, padding_size and seq_len
+    as given to ``mlpg``; gv_mean and gv_variance (D,) or (B, D) f32 (tensors, arrays or sequences): mean and variance of the
+    per-utterance variances (``data.fit_global_variance``).  Returns (B, T, D), zero past seq_len; with want_info also a float64
+    (B, D, 4) tensor of (kappa, final |h|, evaluations used, flag), flag 1 where the plain ``mlpg`` solution came back: fewer than two
+    frames, gv_weight 0, a non-positive gv_variance, or a search that did not converge.  gv_weight=0 is ``mlpg`` bit for bit."""
+    lib = _lib.load()
+    means = _require(means, torch.float32, 'means')
+    variances = _require(variances, torch.float32, 'variances')
+    if means.dim() != 3:
+        raise ValueError('means must have shape (batch, time, windows * features), got %s' % (tuple(means.shape),))
+    b, t, width = means.shape
+    n_win = len(windows)
+    if n_win == 0 or n_win > MLPG_MAX_WINDOWS or width % n_win != 0:
+        raise ValueError('%d windows for %d stream columns (1..%d windows, columns a multiple of it)' % (n_win, width, MLPG_MAX_WINDOWS))
+    d = width // n_win
+    if variances.dim() == 1 and variances.shape[0] == width:
+        per_frame = 0
+    elif variances.shape == means.shape:
+        per_frame = 1
+    elif variances.dim() == 2 and tuple(variances.shape) == (b, width):
+        per_frame = MLPG_VAR_ITEM
+    else:
+        raise ValueError('variances %s fit neither (%d,) nor %s nor (%d, %d)' % (tuple(variances.shape), width, tuple(means.shape), b, width))
+    if not isinstance(gv_variance, torch.Tensor) or gv_variance.device.type == 'cpu':      # a host value: checked here
+        if not bool((torch.as_tensor(gv_variance, dtype=torch.float64) > 0).all()):
+            raise ValueError('gv_variance must be positive everywhere')
+    stats = []
+    for name, value in (('gv_mean', gv_mean), ('gv_variance', gv_variance)):
+        value = torch.as_tensor(value).to(device=means.device, dtype=torch.float32).contiguous()
+        if tuple(value.shape) not in ((d,), (b, d)):
+            raise ValueError('%s %s fits neither (%d,) nor (%d, %d)' % (name, tuple(value.shape), d, b, d))
+        stats.append(value)
+    if stats[0].dim() != stats[1].dim():
+        raise ValueError('gv_mean %s and gv_variance %s differ in layout' % (tuple(stats[0].shape), tuple(stats[1].shape)))
+    gv_weight = float(gv_weight)
+    if not 0.0 <= gv_weight < float('inf'):
+        raise ValueError('gv_weight must be finite and >= 0, got %r' % gv_weight)
+    if int(max_iter) < 3:
+        raise ValueError('max_iter must be at least 3, got %r' % (max_iter,))
+    win_l, win_u, win_c = _window_arrays(windows)
+    if seq_len is not None:
+        seq_len = _require(seq_len, torch.int64, 'seq_len')
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError('out_dtype must be torch.float32 or torch.float64')
+    out = torch.empty((b, t, d), dtype=out_dtype, device=means.device)
+    info = torch.empty((b, d, 4), dtype=torch.float64, device=means.device) if want_info else None
+    nbytes = lib.mg_mlpg_gv_workspace_bytes(b, t, d, int(padding_size), n_win, win_l, win_u)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=means.device)
+    _lib.check(lib.mg_mlpg_gv_f32(_p(means), _p(variances), per_frame, _p(stats[0]), _p(stats[1]), int(stats[0].dim() == 2), _p(seq_len),
+                                  b, t, d, n_win, win_l, win_u, win_c, int(padding_size), gv_weight, int(max_iter), _p(out),
+                                  int(out_dtype == torch.float64), _p(info), _p(ws), ws.numel(), _stream()), 'mg_mlpg_gv_f32')
+    return (out, info) if want_info else out
+
+
 def mlpg_backward(grad_out, variances, windows, padding_size=0, seq_len=None, out_dtype=torch.float32):
     """The gradient of ``mlpg``'s trajectory with respect to its means (csrc/mlpg.hip, mg_mlpg_grad_f32): grad_out (B, T, D) f32 ->
     (B, T, W*D), zero past seq_len (whose frames of grad_out are never read).  One more solve with the forward's matrix and a window

@@ -68,6 +68,49 @@ def MLPG(means, variances, windows=None, padding_size=0, seq_len=None):
     return out if as_tensor else out.cpu().numpy()    # :176-178
 
 
+def MLPG_GV(means, variances, gv_mean, gv_variance, windows=None, padding_size=0, seq_len=None, gv_weight=1., max_iter=48):
+    r"""``MLPG`` under a global-variance prior (Toda & Tokuda 2007; ``csrc/mlpg_gv.hip`` - the reference generates with ``MLPG`` only).
+
+    means, variances, windows, padding_size, seq_len and the return conventions are ``MLPG``'s.  gv_mean, gv_variance :
+    (feat_dim // len(windows),) mean and variance of the per-utterance variance of the static feature
+    (``data.fit_global_variance``), or (batch_size, feat_dim // len(windows)) with one row per utterance (per-speaker statistics);
+    gv_weight : the weight of the prior against the per-frame likelihood of ``MLPG`` (0: ``MLPG`` itself); max_iter : the most
+    evaluations of the root search, a banded solve each.  An utterance of fewer than two frames, and any system whose search does
+    not converge, comes back as ``MLPG`` gives it (``ops.mlpg_gv(..., want_info=True)`` tells which).
+    """
+    device = _device_of(means, variances, seq_len, gv_mean, gv_variance)
+    as_tensor = device is not None
+    if device is None:
+        if not torch.cuda.is_available():
+            raise _lib.MorganaHipError('MLPG_GV runs only on an MI355X device (no CPU fallback)')
+        device = torch.device('cuda', torch.cuda.current_device())
+
+    def put(x, dtype):
+        if isinstance(x, torch.Tensor):
+            return x.detach().to(device=device, dtype=dtype)
+        return torch.from_numpy(np.array(x)).to(device=device, dtype=dtype)      # a copy: a read-only array is welcome
+
+    means = put(means, torch.float32)
+    variances = put(variances, torch.float32)
+    if windows is None:
+        windows = DEFAULT_WINDOWS
+    using_batches = means.dim() != 2
+    if not using_batches:
+        means = means[None]
+        if variances.dim() == 2:
+            variances = variances[None]
+    if seq_len is not None:
+        seq_len = put(seq_len, torch.int64).reshape(-1)
+    if not isinstance(gv_variance, torch.Tensor) and not (np.asarray(gv_variance, np.float64) > 0).all():
+        raise ValueError('gv_variance must be positive everywhere')
+    out = ops.mlpg_gv(means, variances, put(gv_mean, torch.float32), put(gv_variance, torch.float32), windows,
+                      padding_size=padding_size, seq_len=seq_len, gv_weight=gv_weight, max_iter=max_iter,
+                      out_dtype=torch.float32 if as_tensor else torch.float64)
+    if not using_batches:
+        out = out.squeeze(0)
+    return out if as_tensor else out.cpu().numpy()
+
+
 def mlpg_trajectory(means, variances, windows=None, padding_size=0, seq_len=None, variance_grad=False):
     r"""``MLPG`` as a differentiable layer (trajectory / minimum-generation-error training; the reference's host MLPG has no gradient).
 
