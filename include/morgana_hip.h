@@ -92,7 +92,8 @@ const char* mg_build_arch(void); /* "gfx950" */
 /* ------------------------------------------------------------------------------------------------------------------
  * K1  upsample_to_repetitions            reference: morgana/utils.py:175-228
  * ---------------------------------------------------------------------------------------------------------------- */
-/* n_frames[b] = sum_p dur[b,p]; *tmax = max_b n_frames[b]  (utils.py:198-199).  dur int64 [B,P]. */
+/* n_frames[b] = sum_p max(dur[b,p], 0); *tmax = max_b n_frames[b]  (utils.py:198-199).  dur int64 [B,P]; a negative duration
+ * counts as 0, as in the index maps below (the reference's np.repeat raises on one). */
 int mg_upsample_lengths(const int64_t* dur, int B, int P, int64_t* n_frames, int64_t* tmax, void* stream);
 
 /* Frame->phone map (utils.py:214-220, the per-utterance np.repeat loop).  Any of the outputs may be NULL.

@@ -44,7 +44,11 @@ __global__ __launch_bounds__(256) void upsample_lengths_kernel(const int64_t* __
     __shared__ long long red[4];
     const int b = blockIdx.x;
     long long s = 0;
-    for (int p = threadIdx.x; p < P; p += 256) s += dur[(size_t)b * P + p];
+    // a negative duration owns no frame, as in block_scan_durations: n_frames / tmax agree with the index map of the same tensor
+    for (int p = threadIdx.x; p < P; p += 256) {
+        const long long d = dur[(size_t)b * P + p];
+        s += d > 0 ? d : 0;
+    }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;

@@ -55,6 +55,12 @@ def _require(t, dtype, name, contiguous=True, rows=False):
     return t if not contiguous or t.is_contiguous() else t.contiguous()
 
 
+def _aligned16(t):
+    """``t`` (contiguous) with a 16-byte aligned base: itself, or a copy when it is a view that starts inside its storage - as
+    ``_require`` copies a non-contiguous one.  For the kernels that read 16 bytes per lane and refuse any other base."""
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 def _lengths(seq_len, b, what='', flat=True):
     """``seq_len`` of a (B, ...) batch: None, or int64 on the device with one length per item - the kernels read B of them.
     ``flat``: it must be (B,); otherwise any shape of B elements will do (the models pass (B, 1))."""
@@ -143,6 +149,15 @@ pad8 = pad_ld
 
 
 # ----------------------------------------------------------------------------------------------------------------- K1
+MAX_PHONES = 12288      # csrc/upsample.hip MG_MAX_PHONES: the scan of one utterance's durations lives in LDS (4 bytes a phone + 1 KB)
+
+
+def _phones(p, what):
+    """The library refuses more than MAX_PHONES phones (segments) per utterance; said here, before the call, with the same limit."""
+    if not 0 < p <= MAX_PHONES:
+        raise ValueError('%s: %d phones per utterance, the kernels take 1..%d' % (what, p, MAX_PHONES))
+
+
 def upsample_lengths(dur):
     """dur int64 (B, P) -> (n_frames int64 (B,), tmax int64 0-d), both on device (no sync)."""
     lib = _lib.load()
@@ -158,6 +173,7 @@ def upsample_index(dur, t_cap, want_idx64=False, want_rows=True):
     lib = _lib.load()
     dur = _require(dur, torch.int64, 'dur')
     b, p = dur.shape
+    _phones(p, 'upsample_index')
     idx64 = torch.empty((b, t_cap), dtype=torch.int64, device=dur.device) if want_idx64 else None
     rows = torch.empty((b, t_cap), dtype=torch.int32, device=dur.device) if want_rows else None
     _lib.check(lib.mg_upsample_index(_p(dur), b, p, int(t_cap), _p(idx64), _p(rows), _stream()), 'mg_upsample_index')
@@ -169,6 +185,7 @@ def upsample_index_maps(dur, t_cap):
     lib = _lib.load()
     dur = _require(dur, torch.int64, 'dur')
     b, p = dur.shape
+    _phones(p, 'upsample_index_maps')
     rows = torch.empty((2, b, t_cap), dtype=torch.int32, device=dur.device)
     seg = torch.empty((2, b * p), dtype=torch.int32, device=dur.device)
     _lib.check(lib.mg_upsample_index_maps(_p(dur), b, p, int(t_cap), _p(rows[0]), _p(rows[1]), b * p, _p(seg[0]), _p(seg[1]),
@@ -182,6 +199,7 @@ def gather_rows(src2d, rows, out_bf16=False, ld=None):
     rows = _require(rows, torch.int32, 'rows')
     m, f = rows.numel(), src2d.shape[1]
     if out_bf16:
+        src2d = _aligned16(src2d)
         ldo = pad8(f) if ld is None else int(ld)
         out = torch.empty((m, ldo), dtype=torch.bfloat16, device=src2d.device)
         _lib.check(lib.mg_gather_rows_bf16(_p(src2d), _p(rows), _p(out), m, f, ldo, _stream()), 'mg_gather_rows_bf16')
@@ -196,6 +214,7 @@ def segment_index(seg_lens2d, t, max_len=None, want_split=True, want_ends=True):
     lib = _lib.load()
     seg_lens2d = _require(seg_lens2d, torch.int64, 'segment_lens')
     b, s = seg_lens2d.shape
+    _phones(s, 'segment_index')
     length = int(max_len) if want_split else 0
     split = torch.empty((b, s, length), dtype=torch.int32, device=seg_lens2d.device) if want_split else None
     ends = torch.empty((b, s), dtype=torch.int32, device=seg_lens2d.device) if want_ends else None
@@ -231,7 +250,15 @@ def pad_rows_colsum(g, seq_len, out):
     """out (D,) = sum of g[b, t, :] over the padded frames t >= seq_len[b] (mg_pad_rows_colsum_f32); g (B, T, D) f32."""
     lib = _lib.load()
     g = _require(g, torch.float32, 'gradient')
+    if g.dim() != 3:
+        raise ValueError('pad_rows_colsum: the gradient must be (B, T, D), got %s' % (tuple(g.shape),))
     b, t, d = g.shape
+    seq_len = _lengths(seq_len, b, 'pad_rows_colsum: ', flat=False)
+    if seq_len is None:
+        raise ValueError('pad_rows_colsum: seq_len is required (without it no frame is padding)')
+    # the result is written in place (a row of the caller's tensor): a copy made here would be lost
+    if _require(out, torch.float32, 'out', contiguous=False).numel() != d or not out.is_contiguous() or out.device != g.device:
+        raise ValueError('pad_rows_colsum: out must be %d contiguous float32 elements on %s, got %s' % (d, g.device, tuple(out.shape)))
     ws = torch.empty(lib.mg_pad_rows_colsum_workspace_bytes(b, t, d), dtype=torch.uint8, device=g.device)
     _lib.check(lib.mg_pad_rows_colsum_f32(_p(g), _p(seq_len), b, t, d, _p(out), _p(ws), ws.numel(), _stream()), 'mg_pad_rows_colsum_f32')
     return out
@@ -247,6 +274,7 @@ def gather_concat(src2d, rows, extra2d, out_bf16=False):
     if extra2d.shape[0] != m:
         raise ValueError('gather_concat: %d frame rows but %d rows of frame-level features' % (m, extra2d.shape[0]))
     if out_bf16:
+        src2d = _aligned16(src2d)
         ldo = pad_ld(f + c)
         out = torch.empty((m, ldo), dtype=torch.bfloat16, device=src2d.device)
         _lib.check(lib.mg_gather_concat_bf16(_p(src2d), _p(rows), _p(extra2d), _p(out), m, f, c, ldo, _stream()),
@@ -263,6 +291,7 @@ def upsample_backward(grad_out, dur, n_phones):
     grad_out = _require(grad_out, torch.float32, 'grad_out')
     dur = _require(dur, torch.int64, 'dur')
     b, t, f = grad_out.shape
+    _phones(n_phones, 'upsample_backward')
     grad_src = torch.empty((b, n_phones, f), dtype=torch.float32, device=grad_out.device)
     _lib.check(lib.mg_upsample_backward_f32(_p(grad_out), _p(dur), _p(grad_src), b, n_phones, t, f, _stream()),
                'mg_upsample_backward_f32')
@@ -282,6 +311,8 @@ def sequence_mask(seq_len, max_len, dtype):
     elem, as_float = _MASK_TYPES[dtype]
     b = seq_len.shape[0]
     mask = torch.empty((b, max_len, 1), dtype=dtype, device=seq_len.device)
+    if mask.numel() == 0:      # max_len = 0: nothing to write, and an empty tensor has no address to hand the library
+        return mask
     _lib.check(lib.mg_sequence_mask(_p(seq_len), b, int(max_len), _p(mask), elem, as_float, _stream()),
                'mg_sequence_mask')
     return mask
@@ -736,9 +767,13 @@ def pad_normalise(packed, offsets, t, p0=None, p1=None, kind=None, want_raw=True
             raise ValueError('pad_normalise: the bf16 table is the NORMALISED feature: it needs normaliser parameters')
         ldb = pad_ld(d)
         table = torch.empty((b * int(t) + int(bf16_extra_rows), ldb), dtype=torch.bfloat16, device=packed.device)
+        if table.numel() == 0:      # t = 0 without extra rows: every output is empty (no address to hand the library)
+            return raw, norm, table
         _lib.check(lib.mg_pad_normalise_bf16_f32(_p(packed), _p(offsets), b, int(t), d, _p(p0), _p(p1), kind, _p(raw), _p(norm), _p(table), ldb,
                                                  int(bf16_extra_rows), _stream()), 'mg_pad_normalise_bf16_f32')
         return raw, norm, table
+    if int(t) == 0:                 # empty outputs: the library would see NULL for both and call it "no output requested"
+        return raw, norm
     _lib.check(lib.mg_pad_normalise_f32(_p(packed), _p(offsets), b, int(t), d, _p(p0), _p(p1), -1 if kind is None else kind,
                                         _p(raw), _p(norm), _stream()), 'mg_pad_normalise_f32')
     return raw, norm
@@ -2713,6 +2748,11 @@ def metric_accumulate(kind, accum, target, pred=None, voiced=None, seq_len=None,
         raise ValueError('metric inputs must have shape (batch, time, features), got %s' % (tuple(target.shape),))
     b, t, d = target.shape
     width = d - col0 if width is None else width
+    seq_len = _lengths(seq_len, b, 'metric_accumulate: ', flat=False)
+    # accum is added to in place: a copy made here would be lost
+    if (_require(accum, torch.float64, 'accum', contiguous=False).numel() != 2 or not accum.is_contiguous()
+            or accum.device != target.device):
+        raise ValueError('metric_accumulate: accum must be 2 contiguous float64 elements on %s, got %s' % (target.device, tuple(accum.shape)))
     if pred is not None:
         pred = _require(pred, torch.float32, 'pred')
         if pred.shape != target.shape:
