@@ -5,10 +5,11 @@
 //
 // Decomposition.  Batch items never interact inside the recurrence, so the batch is cut into 8 independent GROUPS of
 // R = ceil(B / 8) items; a group is served by H / 16 workgroups (SLOTS), slot s owning hidden units [16 s, 16 s + 16) of all
-// three gates: 48 rows of W_hh (bf16, 48 KB at H = 512) = 48 VGPRs per lane, loaded once.  Group = blockIdx % 8, so that the
-// workgroups of a group usually share an XCD (blocks are dealt round-robin); that is a speed affinity only - the protocol below is
-// placement independent.  Per step a workgroup reads the group's whole state h_{t-1} (R x H bf16), runs 3 H / 128 MFMAs per wave,
-// sums its 4 waves' partials through LDS, applies the cell and publishes its 16 columns of h_t.
+// three gates: 48 rows of W_hh (bf16, 48 KB at H = 512) = 48 VGPRs per lane, loaded once.  A workgroup joins the group of the XCD
+// it finds itself on (a ticket: gp_claim_slot, persist_common.h), so that the workgroups of a group share an XCD whatever the dealing
+// order was; that is a speed affinity only - the protocol below is placement independent.  Per step a workgroup reads the group's
+// whole state h_{t-1} (R x H bf16), runs 3 H / 128 MFMAs per wave, sums its 4 waves' partials through LDS, applies the cell and
+// publishes its 16 columns of h_t.
 //
 // Hand-off (cdna_hip_programming.md §6 Guideline 16, form R1 with sc1 loads in place of the acquire): every byte of the bf16
 // state that another workgroup reads in this launch is written by a 16-byte sc1 (write-through) store of wave 0, drained with
@@ -43,29 +44,13 @@ __global__ __launch_bounds__(384) void gru_fwd_persist_kernel(const float* __res
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, q = lane >> 4;
     const int n_slots = H / GT;
-    // which (group, slot) this workgroup serves: a ticket of the XCD it finds itself on (persist_common.h), not its block index
-    const int claim = gp_claim_slot((gu32*)sync + GP_TICKET_OFFSET, n_slots, tid, &s_xcd, force_sc1 & 2);
-    if (claim < 0) return;
-    const int group = claim / GP_SLOTS, slot = claim % GP_SLOTS;
-    const int row0 = group * R;
-    const int nrows = min(R, B - row0);
-    if (slot >= n_slots || nrows <= 0) return;
+    // which (group, slot) this workgroup serves, its rows of the batch and whether the group sits on one XCD (persist_common.h)
+    const gp_place p = gp_enter(sync, n_slots, B, R, force_sc1, tid, &s_abort, &s_xcd);
+    if (!p.ok) return;
+    const int group = p.group, slot = p.slot, row0 = p.row0, nrows = p.nrows, one_xcd = p.one_xcd;
+    gu32 *const flags = p.flags, *const status = p.status;
     const int j0 = slot * GT;
-    gu32* flags = (gu32*)sync + group * GP_SLOTS;
-    gu32* status = (gu32*)sync + GP_FLAG_WORDS;
-    if (tid == 0) s_abort = 0;
-    const int one_xcd = (force_sc1 & 1) ? 0 : gp_group_on_one_xcd((gu32*)sync + GP_GROUPS * GP_SLOTS + group * GP_SLOTS, slot, n_slots, tid, &s_xcd);
-    if (one_xcd < 0) {
-        if (tid == 0) __hip_atomic_store(status, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-
-    // longest sequence of the group
-    int gmax = 0;
-    for (int r = 0; r < nrows; ++r) {
-        const int64_t n = seq_len ? seq_len[row0 + r] : (int64_t)T;
-        gmax = max(gmax, (int)(n < T ? n : T));
-    }
+    const int gmax = gp_longest(seq_len, row0, nrows, T);
 
     // W_hh fragments of this slot, for the whole launch
     const int kbase = (wave & 3) * (H / 4) + 8 * q;   // (the storing waves 4, 5 run the prologue as waves 0, 1: same loads, same LDS values)
@@ -196,7 +181,7 @@ __global__ __launch_bounds__(384) void gru_fwd_persist_kernel(const float* __res
         if (wave == 0 && !gp_wait_flags(flags, n_slots, (unsigned)(t + 1), lane)) s_abort = 1;
         gp_lds_barrier();
         if (s_abort) {
-            if (tid == 0) __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) gp_report(status, GP_ST_GRU_FWD);
             return;
         }
         MG_STAMP(tb);
@@ -337,29 +322,14 @@ __global__ __launch_bounds__(256) void gru_bwd_persist_kernel(const float* __res
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, q = lane >> 4;
     const int n_slots = H / GT;
-    // which (group, slot) this workgroup serves: a ticket of the XCD it finds itself on (persist_common.h), not its block index
-    const int claim = gp_claim_slot((gu32*)sync + GP_TICKET_OFFSET, n_slots, tid, &s_xcd, force_sc1 & 2);
-    if (claim < 0) return;
-    const int group = claim / GP_SLOTS, slot = claim % GP_SLOTS;
-    const int row0 = group * R;
-    const int nrows = min(R, B - row0);
-    if (slot >= n_slots || nrows <= 0) return;
+    // which (group, slot) this workgroup serves, its rows of the batch and whether the group sits on one XCD (persist_common.h)
+    const gp_place p = gp_enter(sync, n_slots, B, R, force_sc1, tid, &s_abort, &s_xcd);
+    if (!p.ok) return;
+    const int group = p.group, slot = p.slot, row0 = p.row0, nrows = p.nrows, one_xcd = p.one_xcd;
+    gu32 *const flags = p.flags, *const status = p.status;
     const int j0 = slot * GT;
     const int G = 3 * H;
-    gu32* flags = (gu32*)sync + group * GP_SLOTS;
-    gu32* status = (gu32*)sync + GP_FLAG_WORDS;
-    if (tid == 0) s_abort = 0;
-    const int one_xcd = (force_sc1 & 1) ? 0 : gp_group_on_one_xcd((gu32*)sync + GP_GROUPS * GP_SLOTS + group * GP_SLOTS, slot, n_slots, tid, &s_xcd);
-    if (one_xcd < 0) {
-        if (tid == 0) __hip_atomic_store(status, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-
-    int gmax = 0;
-    for (int r = 0; r < nrows; ++r) {
-        const int64_t n = seq_len ? seq_len[row0 + r] : (int64_t)T;
-        gmax = max(gmax, (int)(n < T ? n : T));
-    }
+    const int gmax = gp_longest(seq_len, row0, nrows, T);
 
     // W_hh^T fragments: lane (li, q) holds row j0 + li, gate rows gbase + 32 i .. + 7
     const int gbase = wave * (G / 4) + 8 * q;
@@ -452,7 +422,7 @@ __global__ __launch_bounds__(256) void gru_bwd_persist_kernel(const float* __res
             if (wave == 0 && !gp_wait_flags(flags, n_slots, (unsigned)(gmax - t - 1), lane)) s_abort = 1;
             gp_lds_barrier();
             if (s_abort) {
-                if (tid == 0) __hip_atomic_store(status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (tid == 0) gp_report(status, GP_ST_GRU_BWD);
                 return;
             }
             MG_STAMP(tb);
@@ -626,7 +596,7 @@ __global__ __launch_bounds__(256) void gru_bwd_persist_wide_kernel(const float* 
     const int li = lane & 15, q = lane >> 4;
     const int n_slots = H / GT;                    // tickets per XCD group: as many workgroups as the narrow kernel's
     const int n_vslots = H / UW;
-    const int claim = gp_claim_slot((gu32*)sync + GP_TICKET_OFFSET, n_slots, tid, &s_xcd, force_sc1 & 2);
+    const int claim = gp_claim_slot((gu32*)sync + GP_TICKET_OFFSET, n_slots, tid, &s_xcd);
     if (claim < 0) return;
     const int xg = claim / GP_SLOTS, ticket = claim % GP_SLOTS;
     if (ticket >= n_slots) return;
@@ -640,19 +610,10 @@ __global__ __launch_bounds__(256) void gru_bwd_persist_wide_kernel(const float* 
     gu32* flags = (gu32*)sync + xg * GP_SLOTS + vsub * n_vslots;
     gu32* status = (gu32*)sync + GP_FLAG_WORDS;
     if (tid == 0) s_abort = 0;
-    const int one_xcd = (force_sc1 & 1) ? 0
-                                        : gp_group_on_one_xcd((gu32*)sync + GP_GROUPS * GP_SLOTS + xg * GP_SLOTS + vsub * n_vslots, slot,
-                                                              n_vslots, tid, &s_xcd);
-    if (one_xcd < 0) {
-        if (tid == 0) __hip_atomic_store(status, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-
-    int gmax = 0;
-    for (int r = 0; r < nrows; ++r) {
-        const int64_t n = seq_len ? seq_len[row0 + r] : (int64_t)T;
-        gmax = max(gmax, (int)(n < T ? n : T));
-    }
+    const int one_xcd = gp_one_xcd_or_report((gu32*)sync + GP_GROUPS * GP_SLOTS + xg * GP_SLOTS + vsub * n_vslots, slot, n_vslots, tid, &s_xcd,
+                                             force_sc1, status);
+    if (one_xcd < 0) return;
+    const int gmax = gp_longest(seq_len, row0, nrows, T);
 
     // W_hh^T fragments: lane (li, q) holds rows j0 + 16 u + li, gate columns gk + 32 i + 8 q .. + 7 (gk = the wave's quarter of 3 H)
     const int gk = wave * (G / 4);
@@ -727,7 +688,7 @@ __global__ __launch_bounds__(256) void gru_bwd_persist_wide_kernel(const float* 
             if (wave == 0 && !gp_wait_flags(flags, n_vslots, (unsigned)(gmax - t - 1), lane)) s_abort = 1;
             gp_lds_barrier();
             if (s_abort) {
-                if (tid == 0) __hip_atomic_store(status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (tid == 0) gp_report(status, GP_ST_GRU_BWD);
                 return;
             }
             const unsigned off = ((t + 1) & 1) * par_bytes + (unsigned)((li < nrows ? li : 0) * 64);
@@ -848,27 +809,13 @@ __global__ __launch_bounds__(256) void gru_fwd_persist_f32_kernel(const float* _
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, q = lane >> 4;
     const int n_slots = H / GT;
-    // which (group, slot) this workgroup serves: a ticket of the XCD it finds itself on (persist_common.h), not its block index
-    const int claim = gp_claim_slot((gu32*)sync + GP_TICKET_OFFSET, n_slots, tid, &s_xcd, force_sc1 & 2);
-    if (claim < 0) return;
-    const int group = claim / GP_SLOTS, slot = claim % GP_SLOTS;
-    const int row0 = group * R;
-    const int nrows = min(R, B - row0);
-    if (slot >= n_slots || nrows <= 0) return;
+    // which (group, slot) this workgroup serves, its rows of the batch and whether the group sits on one XCD (persist_common.h)
+    const gp_place p = gp_enter(sync, n_slots, B, R, force_sc1, tid, &s_abort, &s_xcd);
+    if (!p.ok) return;
+    const int group = p.group, slot = p.slot, row0 = p.row0, nrows = p.nrows, one_xcd = p.one_xcd;
+    gu32 *const flags = p.flags, *const status = p.status;
     const int j0 = slot * GT;
-    gu32* flags = (gu32*)sync + group * GP_SLOTS;
-    gu32* status = (gu32*)sync + GP_FLAG_WORDS;
-    if (tid == 0) s_abort = 0;
-    const int one_xcd = (force_sc1 & 1) ? 0 : gp_group_on_one_xcd((gu32*)sync + GP_GROUPS * GP_SLOTS + group * GP_SLOTS, slot, n_slots, tid, &s_xcd);
-    if (one_xcd < 0) {
-        if (tid == 0) __hip_atomic_store(status, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    int gmax = 0;
-    for (int r = 0; r < nrows; ++r) {
-        const int64_t n = seq_len ? seq_len[row0 + r] : (int64_t)T;
-        gmax = max(gmax, (int)(n < T ? n : T));
-    }
+    const int gmax = gp_longest(seq_len, row0, nrows, T);
     // W_hh fragments: block i of this wave = columns 16 (wave + 4 i) + 4 q .. + 3 of rows j0 + li of the three gates
     f32x4 fr[KS], fz[KS], fn[KS];
     {
@@ -923,7 +870,7 @@ __global__ __launch_bounds__(256) void gru_fwd_persist_f32_kernel(const float* _
         if (wave == 0 && !gp_wait_flags(flags, n_slots, (unsigned)(t + 1), lane)) s_abort = 1;
         gp_lds_barrier();
         if (s_abort) {
-            if (tid == 0) __hip_atomic_store(status, 7u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) gp_report(status, GP_ST_GRU_FWD_F32);
             return;
         }
         u32x4 raw[KS];
@@ -1022,24 +969,14 @@ __global__ __launch_bounds__(256) void gru_bwd_persist_f32_kernel(const float* _
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, q = lane >> 4;
     const int n_slots = H / GT;
-    // which (group, slot) this workgroup serves: a ticket of the XCD it finds itself on (persist_common.h), not its block index
-    const int claim = gp_claim_slot((gu32*)sync + GP_TICKET_OFFSET, n_slots, tid, &s_xcd, force_sc1 & 2);
-    if (claim < 0) return;
-    const int group = claim / GP_SLOTS, slot = claim % GP_SLOTS;
-    const int row0 = group * R;
-    const int nrows = min(R, B - row0);
-    if (slot >= n_slots || nrows <= 0) return;
+    // which (group, slot) this workgroup serves, its rows of the batch and whether the group sits on one XCD (persist_common.h)
+    const gp_place p = gp_enter(sync, n_slots, B, R, force_sc1, tid, &s_abort, &s_xcd);
+    if (!p.ok) return;
+    const int group = p.group, slot = p.slot, row0 = p.row0, nrows = p.nrows, one_xcd = p.one_xcd;
+    gu32 *const flags = p.flags, *const status = p.status;
     const int j0 = slot * GT;
     const int G = 3 * H;
-    gu32* flags = (gu32*)sync + group * GP_SLOTS;
-    gu32* status = (gu32*)sync + GP_FLAG_WORDS;
-    if (tid == 0) s_abort = 0;
-    const int one_xcd = (force_sc1 & 1) ? 0 : gp_group_on_one_xcd((gu32*)sync + GP_GROUPS * GP_SLOTS + group * GP_SLOTS, slot, n_slots, tid, &s_xcd);
-    if (one_xcd < 0) {
-        if (tid == 0) __hip_atomic_store(status, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    int gmax = 0;
+    int gmax = 0;                                  // longest sequence of the group (open-coded: through gp_longest this kernel takes 2 to 6 more registers)
     for (int r = 0; r < nrows; ++r) {
         const int64_t n = seq_len ? seq_len[row0 + r] : (int64_t)T;
         gmax = max(gmax, (int)(n < T ? n : T));
@@ -1090,7 +1027,7 @@ __global__ __launch_bounds__(256) void gru_bwd_persist_f32_kernel(const float* _
             if (wave == 0 && !gp_wait_flags(flags, n_slots, (unsigned)(gmax - t - 1), lane)) s_abort = 1;
             gp_lds_barrier();
             if (s_abort) {
-                if (tid == 0) __hip_atomic_store(status, 8u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (tid == 0) gp_report(status, GP_ST_GRU_BWD_F32);
                 return;
             }
             const unsigned off = ((t + 1) & 1) * par_bytes + (unsigned)((li < nrows ? li : 0) * 64);
@@ -1227,22 +1164,15 @@ int mg_gru_fwd_persist_out_bf16(const float* xproj, const int32_t* xrows, int64_
                  "mg_gru_fwd_persist_bf16: bad arguments (B=%d T=%d H=%d)", B, T, H);
     MG_CHECK_ARG(mg_gru_persist_supported(B, T, H) && ldw >= H && ldw % 8 == 0,
                  "mg_gru_fwd_persist_bf16: unsupported shape (B=%d T=%d H=%d ldw=%d): needs H %% 128 == 0, H <= 512, B <= 256", B, T, H, ldw);
-    MG_CHECK_ARG((((uintptr_t)w_hh_bf | (uintptr_t)hstate_bf | (uintptr_t)workspace) % 16) == 0,
-                 "mg_gru_fwd_persist_bf16: bf16 buffers and workspace must be 16-byte aligned");
-    if (!workspace || workspace_bytes < mg_gru_persist_workspace_bytes(B, H)) {
-        mg_set_error("mg_gru_fwd_persist_bf16: workspace of %zu bytes needed, got %zu", mg_gru_persist_workspace_bytes(B, H), workspace_bytes);
-        return MG_EWORKSPACE;
-    }
+    MG_CHECK_ARG((((uintptr_t)w_hh_bf | (uintptr_t)hstate_bf) % 16) == 0, "mg_gru_fwd_persist_bf16: bf16 buffers must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(workspace, 0, (size_t)GP_FLAG_WORDS * sizeof(unsigned), st) != hipSuccess) {
-        mg_set_error("mg_gru_fwd_persist_bf16: memset failed");
-        return MG_ELAUNCH;
-    }
-    const int R = (int)mg_ceil_div(B, GP_GROUPS);
-    const unsigned grid = (unsigned)(GP_GROUPS * (H / GT));
+    gp_launch l;
+    const int rc = gp_prepare_launch("mg_gru_fwd_persist_bf16", B, H, workspace, workspace_bytes, st, &l);
+    if (rc != MG_OK) return rc;
+    const int R = l.R;
 #define GP_FWD(MT, KS)                                                                                                                  \
-    hipLaunchKernelGGL((gru_fwd_persist_kernel<MT, KS>), dim3(grid), dim3(384), 0, st, xproj, w_hh_bf, ldw, b_hh, seq_len, B, T, H, R, hstate, \
-                       hstate_bf, out, saved, (unsigned*)workspace, (uint16_t*)((char*)workspace + GP_RING_OFFSET), g_mg_tuning[MG_TUNE_GRU_HANDOFF], xrows, out_bf)
+    hipLaunchKernelGGL((gru_fwd_persist_kernel<MT, KS>), dim3(l.grid), dim3(384), 0, st, xproj, w_hh_bf, ldw, b_hh, seq_len, B, T, H, R, hstate, \
+                       hstate_bf, out, saved, (unsigned*)workspace, (uint16_t*)l.ring, l.handoff, xrows, out_bf)
 #define GP_FWD_KS(MT)            \
     switch (H / 128) {           \
         case 1: GP_FWD(MT, 1); break; \
@@ -1267,23 +1197,16 @@ int mg_gru_bwd_persist_bf16(const float* grad_out, const float* grad_hn, const f
                  "mg_gru_bwd_persist_bf16: bad arguments (B=%d T=%d H=%d)", B, T, H);
     MG_CHECK_ARG(mg_gru_persist_supported(B, T, H) && ldt >= 3 * H && ldt % 8 == 0,
                  "mg_gru_bwd_persist_bf16: unsupported shape (B=%d T=%d H=%d ldt=%d): needs H %% 128 == 0, H <= 512, B <= 256", B, T, H, ldt);
-    MG_CHECK_ARG((((uintptr_t)w_hh_t_bf | (uintptr_t)dhproj_bf | (uintptr_t)dxproj_bf | (uintptr_t)workspace) % 16) == 0,
-                 "mg_gru_bwd_persist_bf16: bf16 buffers and workspace must be 16-byte aligned");
-    if (!workspace || workspace_bytes < mg_gru_persist_workspace_bytes(B, H)) {
-        mg_set_error("mg_gru_bwd_persist_bf16: workspace of %zu bytes needed, got %zu", mg_gru_persist_workspace_bytes(B, H), workspace_bytes);
-        return MG_EWORKSPACE;
-    }
+    MG_CHECK_ARG((((uintptr_t)w_hh_t_bf | (uintptr_t)dhproj_bf | (uintptr_t)dxproj_bf) % 16) == 0,
+                 "mg_gru_bwd_persist_bf16: bf16 buffers must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(workspace, 0, (size_t)GP_FLAG_WORDS * sizeof(unsigned), st) != hipSuccess) {
-        mg_set_error("mg_gru_bwd_persist_bf16: memset failed");
-        return MG_ELAUNCH;
-    }
-    const int R = (int)mg_ceil_div(B, GP_GROUPS);
-    const unsigned grid = (unsigned)(GP_GROUPS * (H / GT));
+    gp_launch l;
+    const int rc = gp_prepare_launch("mg_gru_bwd_persist_bf16", B, H, workspace, workspace_bytes, st, &l);
+    if (rc != MG_OK) return rc;
+    const int R = l.R;
 #define GP_BWD(MT, KS)                                                                                                                      \
-    hipLaunchKernelGGL((gru_bwd_persist_kernel<MT, KS>), dim3(grid), dim3(256), 0, st, grad_out, grad_hn, hstate, saved, w_hh_t_bf, ldt, seq_len, \
-                       B, T, H, R, dxproj, dhproj, dhproj_bf, dxproj_bf, dh0, (unsigned*)workspace, (uint16_t*)((char*)workspace + GP_RING_OFFSET),           \
-                       g_mg_tuning[MG_TUNE_GRU_HANDOFF])
+    hipLaunchKernelGGL((gru_bwd_persist_kernel<MT, KS>), dim3(l.grid), dim3(256), 0, st, grad_out, grad_hn, hstate, saved, w_hh_t_bf, ldt, seq_len, \
+                       B, T, H, R, dxproj, dhproj, dhproj_bf, dxproj_bf, dh0, (unsigned*)workspace, (uint16_t*)l.ring, l.handoff)
 #define GP_BWD_KS(MT)                  \
     switch (H / 128) {                 \
         case 1: GP_BWD(MT, 3); break;  \
@@ -1294,11 +1217,10 @@ int mg_gru_bwd_persist_bf16(const float* grad_out, const float* grad_hn, const f
     // Wide slots (gru_bwd_persist_wide_kernel): 16 groups of at most 8 items, two per XCD - half the hand-off lines per step and slot.
     // MG_TUNE_GRU_HANDOFF bit 2 (4): the narrow kernel for A/B.
     const int Rw = (int)mg_ceil_div(B, 2 * GP_GROUPS);
-    if (Rw <= 8 && !(g_mg_tuning[MG_TUNE_GRU_HANDOFF] & 4)) {
+    if (Rw <= 8 && !(l.handoff & 4)) {
 #define GP_BWDW(KS)                                                                                                                          \
-    hipLaunchKernelGGL((gru_bwd_persist_wide_kernel<KS>), dim3(grid), dim3(256), 0, st, grad_out, grad_hn, hstate, saved, w_hh_t_bf, ldt, seq_len, \
-                       B, T, H, Rw, dxproj, dhproj, dhproj_bf, dxproj_bf, dh0, (unsigned*)workspace, (uint16_t*)((char*)workspace + GP_RING_OFFSET),  \
-                       g_mg_tuning[MG_TUNE_GRU_HANDOFF] & 3)
+    hipLaunchKernelGGL((gru_bwd_persist_wide_kernel<KS>), dim3(l.grid), dim3(256), 0, st, grad_out, grad_hn, hstate, saved, w_hh_t_bf, ldt, seq_len, \
+                       B, T, H, Rw, dxproj, dhproj, dhproj_bf, dxproj_bf, dh0, (unsigned*)workspace, (uint16_t*)l.ring, l.handoff & 1)
         switch (H / 128) {
             case 1: GP_BWDW(3); break;
             case 2: GP_BWDW(6); break;
@@ -1326,21 +1248,12 @@ int mg_gru_fwd_persist_f32(const float* xproj, const float* w_hh, const float* b
                            float* hstate, float* out, float* saved, void* workspace, size_t workspace_bytes, void* stream) {
     MG_CHECK_ARG(xproj && w_hh && b_hh && hstate && out && saved, "mg_gru_fwd_persist_f32: null argument");
     MG_CHECK_ARG(mg_gru_persist_f32_supported(B, T, H), "mg_gru_fwd_persist_f32: unsupported shape (B=%d T=%d H=%d)", B, T, H);
-    MG_CHECK_ARG((((uintptr_t)w_hh | (uintptr_t)workspace) % 16) == 0, "mg_gru_fwd_persist_f32: w_hh and workspace must be 16-byte aligned");
-    if (!workspace || workspace_bytes < mg_gru_persist_workspace_bytes(B, H)) {
-        mg_set_error("mg_gru_fwd_persist_f32: workspace of %zu bytes needed, got %zu", mg_gru_persist_workspace_bytes(B, H), workspace_bytes);
-        return MG_EWORKSPACE;
-    }
+    MG_CHECK_ARG(((uintptr_t)w_hh % 16) == 0, "mg_gru_fwd_persist_f32: w_hh must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(workspace, 0, (size_t)GP_FLAG_WORDS * sizeof(unsigned), st) != hipSuccess) {
-        mg_set_error("mg_gru_fwd_persist_f32: memset failed");
-        return MG_ELAUNCH;
-    }
-    const int R = (int)mg_ceil_div(B, GP_GROUPS);
-    const unsigned grid = (unsigned)(GP_GROUPS * (H / GT));
-    float* ring = (float*)((char*)workspace + GP_RING_OFFSET);
-    const int force = g_mg_tuning[MG_TUNE_GRU_HANDOFF];
-#define GPF_FWD(KS) hipLaunchKernelGGL((gru_fwd_persist_f32_kernel<KS>), dim3(grid), dim3(256), 0, st, xproj, w_hh, b_hh, seq_len, B, T, H, R, hstate, out, saved, (unsigned*)workspace, ring, force)
+    gp_launch l;
+    const int rc = gp_prepare_launch("mg_gru_fwd_persist_f32", B, H, workspace, workspace_bytes, st, &l);
+    if (rc != MG_OK) return rc;
+#define GPF_FWD(KS) hipLaunchKernelGGL((gru_fwd_persist_f32_kernel<KS>), dim3(l.grid), dim3(256), 0, st, xproj, w_hh, b_hh, seq_len, B, T, H, l.R, hstate, out, saved, (unsigned*)workspace, (float*)l.ring, l.handoff)
     switch (H / 64) {
         case 4: GPF_FWD(4); break;
         case 5: GPF_FWD(5); break;
@@ -1357,21 +1270,11 @@ int mg_gru_bwd_persist_f32(const float* grad_out, const float* grad_hn, const fl
                            size_t workspace_bytes, void* stream) {
     MG_CHECK_ARG(grad_out && hstate && saved && w_hh && dxproj && dhproj && dh0, "mg_gru_bwd_persist_f32: null argument");
     MG_CHECK_ARG(mg_gru_persist_f32_supported(B, T, H), "mg_gru_bwd_persist_f32: unsupported shape (B=%d T=%d H=%d)", B, T, H);
-    MG_CHECK_ARG(((uintptr_t)workspace % 16) == 0, "mg_gru_bwd_persist_f32: workspace must be 16-byte aligned");
-    if (!workspace || workspace_bytes < mg_gru_persist_workspace_bytes(B, H)) {
-        mg_set_error("mg_gru_bwd_persist_f32: workspace of %zu bytes needed, got %zu", mg_gru_persist_workspace_bytes(B, H), workspace_bytes);
-        return MG_EWORKSPACE;
-    }
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(workspace, 0, (size_t)GP_FLAG_WORDS * sizeof(unsigned), st) != hipSuccess) {
-        mg_set_error("mg_gru_bwd_persist_f32: memset failed");
-        return MG_ELAUNCH;
-    }
-    const int R = (int)mg_ceil_div(B, GP_GROUPS);
-    const unsigned grid = (unsigned)(GP_GROUPS * (H / GT));
-    float* ring = (float*)((char*)workspace + GP_RING_OFFSET);
-    const int force = g_mg_tuning[MG_TUNE_GRU_HANDOFF];
-#define GPF_BWD(KS) hipLaunchKernelGGL((gru_bwd_persist_f32_kernel<KS>), dim3(grid), dim3(256), 0, st, grad_out, grad_hn, hstate, saved, w_hh, seq_len, B, T, H, R, dxproj, dhproj, dh0, (unsigned*)workspace, ring, force)
+    gp_launch l;
+    const int rc = gp_prepare_launch("mg_gru_bwd_persist_f32", B, H, workspace, workspace_bytes, st, &l);
+    if (rc != MG_OK) return rc;
+#define GPF_BWD(KS) hipLaunchKernelGGL((gru_bwd_persist_f32_kernel<KS>), dim3(l.grid), dim3(256), 0, st, grad_out, grad_hn, hstate, saved, w_hh, seq_len, B, T, H, l.R, dxproj, dhproj, dh0, (unsigned*)workspace, (float*)l.ring, l.handoff)
     switch (H / 64) {
         case 4: GPF_BWD(12); break;
         case 5: GPF_BWD(15); break;

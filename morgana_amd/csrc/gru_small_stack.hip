@@ -36,7 +36,7 @@ __device__ __forceinline__ float gss_load(const float* p) { return __hip_atomic_
 __device__ __forceinline__ void gss_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // the consumer's side of the hand-off: `v` was loaded a while ago; poll while it is still the sentinel
-__device__ __forceinline__ float gss_take(float v, const float* p, bool& dead, gu32* status, unsigned code) {
+__device__ __forceinline__ float gss_take(float v, const float* p, bool& dead, gu32* status, gp_status code) {
     if (__float_as_uint(v) != GSS_SENTINEL || dead) return v;
     for (unsigned spins = 0; spins < GP_SPIN_LIMIT; ++spins) {
         v = gss_load(p);
@@ -44,7 +44,7 @@ __device__ __forceinline__ float gss_take(float v, const float* p, bool& dead, g
         __builtin_amdgcn_s_sleep(1);
     }
     dead = true;
-    __hip_atomic_store(status, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    gp_report(status, code);
     return 0.f;
 }
 
@@ -153,11 +153,11 @@ __global__ __launch_bounds__(512) void gru_stack_fwd_small64_kernel(GssLayers a,
         xr = xp[0], xz = xp[H], xn = xp[2 * H];
     } else if (mine) {
         const int t_lag = T - 1 < GSS_LAG ? T - 1 : GSS_LAG;
-        (void)gss_take(gss_load(xin + (size_t)t_lag * H), xin + (size_t)t_lag * H, dead, status, 8u);     // the start lag (see GSS_LAG)
+        (void)gss_take(gss_load(xin + (size_t)t_lag * H), xin + (size_t)t_lag * H, dead, status, GP_ST_GRU_STACK_FWD);     // the start lag (see GSS_LAG)
         float x0 = gss_load(xin);
         xa = T > 1 ? gss_load(xin + H) : 0.f;
         xb = T > 2 ? gss_load(xin + 2 * H) : 0.f;
-        xs[0][er][ej] = gss_take(x0, xin, dead, status, 8u);
+        xs[0][er][ej] = gss_take(x0, xin, dead, status, GP_ST_GRU_STACK_FWD);
         xsb[0][er][ej] = mg_f2bf(xs[0][er][ej]);
     }
     __syncthreads();
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(512) void gru_stack_fwd_small64_kernel(GssLayers a,
             MG_STAMP(tb);
             MG_STAMP_ADD(sum_cell, tb, ta);
             if (upper && t + 1 < T) {
-                const float xv = gss_take(x_use, xin + (size_t)(t + 1) * H, dead, status, 8u);
+                const float xv = gss_take(x_use, xin + (size_t)(t + 1) * H, dead, status, GP_ST_GRU_STACK_FWD);
                 xs[(t + 1) & 1][er][ej] = xv;
                 if (FAST) xsb[(t + 1) & 1][er][ej] = mg_f2bf(xv);
                 if (t + 3 < T) x_use = gss_load(xin + (size_t)(t + 3) * H);
@@ -394,7 +394,7 @@ __global__ __launch_bounds__(512) void gru_stack_bwd_small64_kernel(GssLayers a,
     if (mine) {
         if (!top) {                                  // the start lag (see GSS_LAG): the layer above is GSS_LAG steps down its pass
             const int t_lag = T - 1 - GSS_LAG > 0 ? T - 1 - GSS_LAG : 0;
-            (void)gss_take(gss_load(p_g + (size_t)t_lag * H), p_g + (size_t)t_lag * H, dead, status, 9u);
+            (void)gss_take(gss_load(p_g + (size_t)t_lag * H), p_g + (size_t)t_lag * H, dead, status, GP_ST_GRU_STACK_BWD);
         }
         ga = top ? p_g[(size_t)(T - 1) * H] : gss_load(p_g + (size_t)(T - 1) * H);
         if (T > 1) gb = top ? p_g[(size_t)(T - 2) * H] : gss_load(p_g + (size_t)(T - 2) * H);
@@ -480,7 +480,7 @@ __global__ __launch_bounds__(512) void gru_stack_bwd_small64_kernel(GssLayers a,
             if (t < 0) {
                 P.dh0[(size_t)b * H + ej] = dstate;
             } else {
-                const float gout = top ? g_use : gss_take(g_use, p_g + (size_t)t * H, dead, status, 9u);
+                const float gout = top ? g_use : gss_take(g_use, p_g + (size_t)t * H, dead, status, GP_ST_GRU_STACK_BWD);
                 if (t >= 2) g_use = top ? p_g[(size_t)(t - 2) * H] : gss_load(p_g + (size_t)(t - 2) * H);
                 float dr = 0.f, dz = 0.f, dn = 0.f, dnr = 0.f, c = dstate;
                 if (t < len) {

@@ -25,27 +25,13 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_kernel(const float* __re
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, q = lane >> 4;
     const int n_slots = H / GT;
-    // which (group, slot) this workgroup serves: a ticket of the XCD it finds itself on (persist_common.h), not its block index
-    const int claim = gp_claim_slot((gu32*)sync + GP_TICKET_OFFSET, n_slots, tid, &s_xcd, force_sc1 & 2);
-    if (claim < 0) return;
-    const int group = claim / GP_SLOTS, slot = claim % GP_SLOTS;
-    const int row0 = group * R;
-    const int nrows = min(R, B - row0);
-    if (slot >= n_slots || nrows <= 0) return;
+    // which (group, slot) this workgroup serves, its rows of the batch and whether the group sits on one XCD (persist_common.h)
+    const gp_place p = gp_enter(sync, n_slots, B, R, force_sc1, tid, &s_abort, &s_xcd);
+    if (!p.ok) return;
+    const int group = p.group, slot = p.slot, row0 = p.row0, nrows = p.nrows, one_xcd = p.one_xcd;
+    gu32 *const flags = p.flags, *const status = p.status;
     const int j0 = slot * GT;
-    gu32* flags = (gu32*)sync + group * GP_SLOTS;
-    gu32* status = (gu32*)sync + GP_FLAG_WORDS;
-    if (tid == 0) s_abort = 0;
-    const int one_xcd = (force_sc1 & 1) ? 0 : gp_group_on_one_xcd((gu32*)sync + GP_GROUPS * GP_SLOTS + group * GP_SLOTS, slot, n_slots, tid, &s_xcd);
-    if (one_xcd < 0) {
-        if (tid == 0) __hip_atomic_store(status, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    int gmax = 0;
-    for (int r = 0; r < nrows; ++r) {
-        const int64_t n = seq_len ? seq_len[row0 + r] : (int64_t)T;
-        gmax = max(gmax, (int)(n < T ? n : T));
-    }
+    const int gmax = gp_longest(seq_len, row0, nrows, T);
     // W_hh fragments of this slot (4 gates x 16 units), for the whole launch
     const int kbase = wave * (H / 4) + 8 * q;
     gbf8 fw[4][KS];
@@ -113,7 +99,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_kernel(const float* __re
         if (wave == 0 && !gp_wait_flags(flags, n_slots, (unsigned)(t + 1), lane)) s_abort = 1;
         gp_lds_barrier();
         if (s_abort) {
-            if (tid == 0) __hip_atomic_store(status, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) gp_report(status, GP_ST_LSTM_FWD);
             return;
         }
         u32x4 raw[MT][KS];
@@ -241,8 +227,9 @@ __global__ __launch_bounds__(256) void lstm_bwd_persist_kernel(const float* __re
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, q = lane >> 4;
     const int n_slots = H / GT;
-    // which (group, slot) this workgroup serves: a ticket of the XCD it finds itself on (persist_common.h), not its block index
-    const int claim = gp_claim_slot((gu32*)sync + GP_TICKET_OFFSET, n_slots, tid, &s_xcd, force_sc1 & 2);
+    // which (group, slot) this workgroup serves, its rows of the batch and whether the group sits on one XCD (persist_common.h)
+    // gp_enter's lines, open-coded: through the helper the <2, 16> kernel (256 VGPRs, spilling to AGPRs) is allocated differently
+    const int claim = gp_claim_slot((gu32*)sync + GP_TICKET_OFFSET, n_slots, tid, &s_xcd);
     if (claim < 0) return;
     const int group = claim / GP_SLOTS, slot = claim % GP_SLOTS;
     const int row0 = group * R;
@@ -253,16 +240,9 @@ __global__ __launch_bounds__(256) void lstm_bwd_persist_kernel(const float* __re
     gu32* flags = (gu32*)sync + group * GP_SLOTS;
     gu32* status = (gu32*)sync + GP_FLAG_WORDS;
     if (tid == 0) s_abort = 0;
-    const int one_xcd = (force_sc1 & 1) ? 0 : gp_group_on_one_xcd((gu32*)sync + GP_GROUPS * GP_SLOTS + group * GP_SLOTS, slot, n_slots, tid, &s_xcd);
-    if (one_xcd < 0) {
-        if (tid == 0) __hip_atomic_store(status, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    int gmax = 0;
-    for (int r = 0; r < nrows; ++r) {
-        const int64_t n = seq_len ? seq_len[row0 + r] : (int64_t)T;
-        gmax = max(gmax, (int)(n < T ? n : T));
-    }
+    const int one_xcd = gp_one_xcd_or_report((gu32*)sync + GP_GROUPS * GP_SLOTS + group * GP_SLOTS, slot, n_slots, tid, &s_xcd, force_sc1, status);
+    if (one_xcd < 0) return;
+    const int gmax = gp_longest(seq_len, row0, nrows, T);
     const int gbase = wave * (G / 4) + 8 * q;           // = wave * H + 8 q: wave w contracts over gate w
     gbf8 fb[KS];
     unsigned rd_off[KS];
@@ -341,7 +321,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_persist_kernel(const float* __re
             if (wave == 0 && !gp_wait_flags(flags, n_slots, (unsigned)(gmax - t - 1), lane)) s_abort = 1;
             gp_lds_barrier();
             if (s_abort) {
-                if (tid == 0) __hip_atomic_store(status, 5u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (tid == 0) gp_report(status, GP_ST_LSTM_BWD);
                 return;
             }
 #pragma unroll
@@ -551,16 +531,9 @@ __global__ __launch_bounds__(256, UT == 1 ? 2 : 1) void lstm_stack_fwd_persist_k
     gu32* flags_up = layer + 1 < L ? flags_x + G * GP_SLOTS : (gu32*)nullptr;
     gu32* status = (gu32*)sync + GP_FLAG_WORDS;
     if (tid == 0) s_abort = 0;
-    const int one_xcd = (force_sc1 & 1) ? 0 : gp_group_on_one_xcd((gu32*)sync + LPS_XCC_WORD + id * GP_SLOTS, slot, n_slots, tid, &s_xcd);
-    if (one_xcd < 0) {
-        if (tid == 0) __hip_atomic_store(status, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    int gmax = 0;
-    for (int r = 0; r < nrows; ++r) {
-        const int64_t n = seq_len ? seq_len[row0 + r] : (int64_t)T;
-        gmax = max(gmax, (int)(n < T ? n : T));
-    }
+    const int one_xcd = gp_one_xcd_or_report((gu32*)sync + LPS_XCC_WORD + id * GP_SLOTS, slot, n_slots, tid, &s_xcd, force_sc1, status);
+    if (one_xcd < 0) return;
+    const int gmax = gp_longest(seq_len, row0, nrows, T);
     const int kbase = wave * (H / 4) + 8 * q;
     // fwi: the W_ih slice of a layer above the first.  Layer 0 has no such slice and keeps its xproj values of the current
     // step in the same registers (XG below) - the kernel sits at the 256-VGPR limit of two workgroups per CU.
@@ -680,7 +653,7 @@ __global__ __launch_bounds__(256, UT == 1 ? 2 : 1) void lstm_stack_fwd_persist_k
             s_abort = 1;
         gp_lds_barrier();
         if (s_abort) {
-            if (tid == 0) __hip_atomic_store(status, 6u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) gp_report(status, GP_ST_LSTM_STACK_FWD);
             return;
         }
         MG_STAMP(tb);
@@ -980,12 +953,9 @@ __global__ __launch_bounds__(256, UT == 1 ? 2 : 1) void lstm_stack_bwd_persist_k
     gu32* flags_lo = layer > 0 ? flags_x - G * GP_SLOTS : (gu32*)nullptr;
     gu32* status = (gu32*)sync + GP_FLAG_WORDS;
     if (tid == 0) s_abort = 0;
-    const int one_xcd = (force_sc1 & 1) ? 0 : gp_group_on_one_xcd((gu32*)sync + LPS_XCC_WORD + id * GP_SLOTS, slot, n_slots, tid, &s_xcd);
-    if (one_xcd < 0) {
-        if (tid == 0) __hip_atomic_store(status, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    int gmax = 0;
+    const int one_xcd = gp_one_xcd_or_report((gu32*)sync + LPS_XCC_WORD + id * GP_SLOTS, slot, n_slots, tid, &s_xcd, force_sc1, status);
+    if (one_xcd < 0) return;
+    int gmax = 0;                                  // longest sequence of the group (open-coded: through gp_longest the UT = 2 kernels of H = 128 get another register count)
     for (int r = 0; r < nrows; ++r) {
         const int64_t n = seq_len ? seq_len[row0 + r] : (int64_t)T;
         gmax = max(gmax, (int)(n < T ? n : T));
@@ -1131,7 +1101,7 @@ __global__ __launch_bounds__(256, UT == 1 ? 2 : 1) void lstm_stack_bwd_persist_k
             if (wave == 0 && !lps_wait(flags_a, 0u, flags_up, gmax - t, seen_up, (gu32*)nullptr, 0, seen_lo, n_slots, lane)) s_abort = 1;
             gp_lds_barrier();
             if (s_abort) {
-                if (tid == 0) __hip_atomic_store(status, 7u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (tid == 0) gp_report(status, GP_ST_LSTM_STACK_BWD);
                 return;
             }
             run_jobs(std::integral_constant<int, 1>{});
@@ -1155,7 +1125,7 @@ __global__ __launch_bounds__(256, UT == 1 ? 2 : 1) void lstm_stack_bwd_persist_k
             s_abort = 1;
         gp_lds_barrier();
         if (s_abort) {
-            if (tid == 0) __hip_atomic_store(status, 7u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) gp_report(status, GP_ST_LSTM_STACK_BWD);
             return;
         }
         MG_STAMP(tb);
@@ -1300,23 +1270,15 @@ int mg_lstm_fwd_persist_bf16(const float* xproj, const uint16_t* w_hh_bf, int ld
                  "mg_lstm_fwd_persist_bf16: bad arguments (B=%d T=%d H=%d)", B, T, H);
     MG_CHECK_ARG(mg_lstm_persist_supported(B, T, H) && ldw >= H && ldw % 8 == 0,
                  "mg_lstm_fwd_persist_bf16: unsupported shape (B=%d T=%d H=%d ldw=%d): needs H %% 128 == 0, H <= 512, B <= 256", B, T, H, ldw);
-    MG_CHECK_ARG((((uintptr_t)w_hh_bf | (uintptr_t)hstate_bf | (uintptr_t)workspace) % 16) == 0,
-                 "mg_lstm_fwd_persist_bf16: bf16 buffers and workspace must be 16-byte aligned");
-    if (!workspace || workspace_bytes < mg_gru_persist_workspace_bytes(B, H)) {
-        mg_set_error("mg_lstm_fwd_persist_bf16: workspace of %zu bytes needed, got %zu", mg_gru_persist_workspace_bytes(B, H), workspace_bytes);
-        return MG_EWORKSPACE;
-    }
+    MG_CHECK_ARG((((uintptr_t)w_hh_bf | (uintptr_t)hstate_bf) % 16) == 0, "mg_lstm_fwd_persist_bf16: bf16 buffers must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(workspace, 0, (size_t)GP_FLAG_WORDS * sizeof(unsigned), st) != hipSuccess) {
-        mg_set_error("mg_lstm_fwd_persist_bf16: memset failed");
-        return MG_ELAUNCH;
-    }
-    const int R = (int)mg_ceil_div(B, GP_GROUPS);
-    const unsigned grid = (unsigned)(GP_GROUPS * (H / GT));
+    gp_launch l;
+    const int rc = gp_prepare_launch("mg_lstm_fwd_persist_bf16", B, H, workspace, workspace_bytes, st, &l);
+    if (rc != MG_OK) return rc;
+    const int R = l.R;
 #define LP_FWD(MT, KS)                                                                                                                          \
-    hipLaunchKernelGGL((lstm_fwd_persist_kernel<MT, KS>), dim3(grid), dim3(256), 0, st, xproj, w_hh_bf, ldw, b_hh, seq_len, B, T, H, R, hstate, \
-                       cstate, hstate_bf, out, saved, (unsigned*)workspace, (uint16_t*)((char*)workspace + GP_RING_OFFSET),                   \
-                       g_mg_tuning[MG_TUNE_GRU_HANDOFF])
+    hipLaunchKernelGGL((lstm_fwd_persist_kernel<MT, KS>), dim3(l.grid), dim3(256), 0, st, xproj, w_hh_bf, ldw, b_hh, seq_len, B, T, H, R, hstate, \
+                       cstate, hstate_bf, out, saved, (unsigned*)workspace, (uint16_t*)l.ring, l.handoff)
 #define LP_FWD_KS(MT)                 \
     switch (H / 128) {                \
         case 1: LP_FWD(MT, 1); break; \
@@ -1340,23 +1302,16 @@ int mg_lstm_bwd_persist_bf16(const float* grad_out, const float* grad_hn, const 
                  "mg_lstm_bwd_persist_bf16: bad arguments (B=%d T=%d H=%d)", B, T, H);
     MG_CHECK_ARG(mg_lstm_persist_supported(B, T, H) && ldt >= 4 * H && ldt % 8 == 0,
                  "mg_lstm_bwd_persist_bf16: unsupported shape (B=%d T=%d H=%d ldt=%d): needs H %% 128 == 0, H <= 512, B <= 256", B, T, H, ldt);
-    MG_CHECK_ARG((((uintptr_t)w_hh_t_bf | (uintptr_t)dgates_bf | (uintptr_t)workspace) % 16) == 0,
-                 "mg_lstm_bwd_persist_bf16: bf16 buffers and workspace must be 16-byte aligned");
-    if (!workspace || workspace_bytes < mg_gru_persist_workspace_bytes(B, H)) {
-        mg_set_error("mg_lstm_bwd_persist_bf16: workspace of %zu bytes needed, got %zu", mg_gru_persist_workspace_bytes(B, H), workspace_bytes);
-        return MG_EWORKSPACE;
-    }
+    MG_CHECK_ARG((((uintptr_t)w_hh_t_bf | (uintptr_t)dgates_bf) % 16) == 0, "mg_lstm_bwd_persist_bf16: bf16 buffers must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(workspace, 0, (size_t)GP_FLAG_WORDS * sizeof(unsigned), st) != hipSuccess) {
-        mg_set_error("mg_lstm_bwd_persist_bf16: memset failed");
-        return MG_ELAUNCH;
-    }
-    const int R = (int)mg_ceil_div(B, GP_GROUPS);
-    const unsigned grid = (unsigned)(GP_GROUPS * (H / GT));
+    gp_launch l;
+    const int rc = gp_prepare_launch("mg_lstm_bwd_persist_bf16", B, H, workspace, workspace_bytes, st, &l);
+    if (rc != MG_OK) return rc;
+    const int R = l.R;
 #define LP_BWD(MT, KS)                                                                                                                        \
-    hipLaunchKernelGGL((lstm_bwd_persist_kernel<MT, KS>), dim3(grid), dim3(256), 0, st, grad_out, grad_hn, grad_cn, cstate, saved, w_hh_t_bf, ldt, \
+    hipLaunchKernelGGL((lstm_bwd_persist_kernel<MT, KS>), dim3(l.grid), dim3(256), 0, st, grad_out, grad_hn, grad_cn, cstate, saved, w_hh_t_bf, ldt, \
                        seq_len, B, T, H, R, dgates, dgates_bf, dh0, dc0, (unsigned*)workspace,                                              \
-                       (uint16_t*)((char*)workspace + GP_RING_OFFSET), g_mg_tuning[MG_TUNE_GRU_HANDOFF])
+                       (uint16_t*)l.ring, l.handoff)
 #define LP_BWD_KS(MT)                   \
     switch (H / 128) {                  \
         case 1: LP_BWD(MT, 4); break;   \

@@ -32,27 +32,13 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_f32_kernel(const float* 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, q = lane >> 4;
     const int n_slots = H / GT;
-    // which (group, slot) this workgroup serves: a ticket of the XCD it finds itself on (persist_common.h), not its block index
-    const int claim = gp_claim_slot((gu32*)sync + GP_TICKET_OFFSET, n_slots, tid, &s_xcd, force_sc1 & 2);
-    if (claim < 0) return;
-    const int group = claim / GP_SLOTS, slot = claim % GP_SLOTS;
-    const int row0 = group * R;
-    const int nrows = min(R, B - row0);
-    if (slot >= n_slots || nrows <= 0) return;
+    // which (group, slot) this workgroup serves, its rows of the batch and whether the group sits on one XCD (persist_common.h)
+    const gp_place p = gp_enter(sync, n_slots, B, R, force_sc1, tid, &s_abort, &s_xcd);
+    if (!p.ok) return;
+    const int group = p.group, slot = p.slot, row0 = p.row0, nrows = p.nrows, one_xcd = p.one_xcd;
+    gu32 *const flags = p.flags, *const status = p.status;
     const int j0 = slot * GT;
-    gu32* flags = (gu32*)sync + group * GP_SLOTS;
-    gu32* status = (gu32*)sync + GP_FLAG_WORDS;
-    if (tid == 0) s_abort = 0;
-    const int one_xcd = (force_sc1 & 1) ? 0 : gp_group_on_one_xcd((gu32*)sync + GP_GROUPS * GP_SLOTS + group * GP_SLOTS, slot, n_slots, tid, &s_xcd);
-    if (one_xcd < 0) {
-        if (tid == 0) __hip_atomic_store(status, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    int gmax = 0;
-    for (int r = 0; r < nrows; ++r) {
-        const int64_t n = seq_len ? seq_len[row0 + r] : (int64_t)T;
-        gmax = max(gmax, (int)(n < T ? n : T));
-    }
+    const int gmax = gp_longest(seq_len, row0, nrows, T);
     // W_hh fragments: block i of this wave = columns 16 (wave + 4 i) + 4 q .. + 3 of rows j0 + li of the four gates
     f32x4 fw[4][KS];
 #pragma unroll
@@ -106,7 +92,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_f32_kernel(const float* 
         if (wave == 0 && !gp_wait_flags(flags, n_slots, (unsigned)(t + 1), lane)) s_abort = 1;
         gp_lds_barrier();
         if (s_abort) {
-            if (tid == 0) __hip_atomic_store(status, 9u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) gp_report(status, GP_ST_LSTM_FWD_F32);
             return;
         }
         u32x4 raw[KS];
@@ -220,28 +206,14 @@ __global__ __launch_bounds__(256) void lstm_bwd_persist_f32_kernel(const float* 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, q = lane >> 4;
     const int n_slots = H / GT;
-    // which (group, slot) this workgroup serves: a ticket of the XCD it finds itself on (persist_common.h), not its block index
-    const int claim = gp_claim_slot((gu32*)sync + GP_TICKET_OFFSET, n_slots, tid, &s_xcd, force_sc1 & 2);
-    if (claim < 0) return;
-    const int group = claim / GP_SLOTS, slot = claim % GP_SLOTS;
-    const int row0 = group * R;
-    const int nrows = min(R, B - row0);
-    if (slot >= n_slots || nrows <= 0) return;
+    // which (group, slot) this workgroup serves, its rows of the batch and whether the group sits on one XCD (persist_common.h)
+    const gp_place p = gp_enter(sync, n_slots, B, R, force_sc1, tid, &s_abort, &s_xcd);
+    if (!p.ok) return;
+    const int group = p.group, slot = p.slot, row0 = p.row0, nrows = p.nrows, one_xcd = p.one_xcd;
+    gu32 *const flags = p.flags, *const status = p.status;
     const int j0 = slot * GT;
     const int G = 4 * H;
-    gu32* flags = (gu32*)sync + group * GP_SLOTS;
-    gu32* status = (gu32*)sync + GP_FLAG_WORDS;
-    if (tid == 0) s_abort = 0;
-    const int one_xcd = (force_sc1 & 1) ? 0 : gp_group_on_one_xcd((gu32*)sync + GP_GROUPS * GP_SLOTS + group * GP_SLOTS, slot, n_slots, tid, &s_xcd);
-    if (one_xcd < 0) {
-        if (tid == 0) __hip_atomic_store(status, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    int gmax = 0;
-    for (int r = 0; r < nrows; ++r) {
-        const int64_t n = seq_len ? seq_len[row0 + r] : (int64_t)T;
-        gmax = max(gmax, (int)(n < T ? n : T));
-    }
+    const int gmax = gp_longest(seq_len, row0, nrows, T);
     // block i of this wave = gate rows 16 (wave + 4 i) + 4 q + e of W_hh [4H, H]: W_hh[that row][j0 + li] as the B operand; its A
     // tile sits in the ring at (slot = block % n_slots, gate = block / n_slots) - wave-uniform, kept in scalar registers
     float fb[KS][4];
@@ -290,7 +262,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_persist_f32_kernel(const float* 
             if (wave == 0 && !gp_wait_flags(flags, n_slots, (unsigned)(gmax - t - 1), lane)) s_abort = 1;
             gp_lds_barrier();
             if (s_abort) {
-                if (tid == 0) __hip_atomic_store(status, 10u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (tid == 0) gp_report(status, GP_ST_LSTM_BWD_F32);
                 return;
             }
             const unsigned off = ((t + 1) & 1) * par_bytes + (unsigned)((li < nrows ? li : 0) * 64 + 16 * q);
@@ -391,33 +363,17 @@ int mg_lstm_persist_f32_supported(int B, int T, int H) {
     return gp_device_holds((long)GP_GROUPS * (H / GT));
 }
 
-static int lpf_prepare(const char* what, int B, int T, int H, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    MG_CHECK_ARG(mg_lstm_persist_f32_supported(B, T, H), "%s: unsupported shape (B=%d T=%d H=%d)", what, B, T, H);
-    MG_CHECK_ARG(workspace && ((uintptr_t)workspace % 16) == 0, "%s: workspace must be 16-byte aligned", what);
-    if (workspace_bytes < mg_gru_persist_workspace_bytes(B, H)) {
-        mg_set_error("%s: workspace of %zu bytes needed, got %zu", what, mg_gru_persist_workspace_bytes(B, H), workspace_bytes);
-        return MG_EWORKSPACE;
-    }
-    if (hipMemsetAsync(workspace, 0, (size_t)GP_FLAG_WORDS * sizeof(unsigned), st) != hipSuccess) {
-        mg_set_error("%s: memset failed", what);
-        return MG_ELAUNCH;
-    }
-    return MG_OK;
-}
-
 int mg_lstm_fwd_persist_f32(const float* xproj, const float* w_hh, const float* b_hh, const int64_t* seq_len, int B, int T, int H,
                             float* hstate, float* cstate, float* out, float* saved, void* workspace, size_t workspace_bytes,
                             void* stream) {
     MG_CHECK_ARG(xproj && w_hh && b_hh && hstate && cstate && out && saved, "mg_lstm_fwd_persist_f32: null argument");
     MG_CHECK_ARG(((uintptr_t)w_hh % 16) == 0, "mg_lstm_fwd_persist_f32: w_hh must be 16-byte aligned");
+    MG_CHECK_ARG(mg_lstm_persist_f32_supported(B, T, H), "mg_lstm_fwd_persist_f32: unsupported shape (B=%d T=%d H=%d)", B, T, H);
     hipStream_t st = (hipStream_t)stream;
-    const int rc = lpf_prepare("mg_lstm_fwd_persist_f32", B, T, H, workspace, workspace_bytes, st);
+    gp_launch l;
+    const int rc = gp_prepare_launch("mg_lstm_fwd_persist_f32", B, H, workspace, workspace_bytes, st, &l);
     if (rc != MG_OK) return rc;
-    const int R = (int)mg_ceil_div(B, GP_GROUPS);
-    const unsigned grid = (unsigned)(GP_GROUPS * (H / GT));
-    float* ring = (float*)((char*)workspace + GP_RING_OFFSET);
-    const int force = g_mg_tuning[MG_TUNE_GRU_HANDOFF];
-#define LPF_FWD(KS) hipLaunchKernelGGL((lstm_fwd_persist_f32_kernel<KS>), dim3(grid), dim3(256), 0, st, xproj, w_hh, b_hh, seq_len, B, T, H, R, hstate, cstate, out, saved, (unsigned*)workspace, ring, force)
+#define LPF_FWD(KS) hipLaunchKernelGGL((lstm_fwd_persist_f32_kernel<KS>), dim3(l.grid), dim3(256), 0, st, xproj, w_hh, b_hh, seq_len, B, T, H, l.R, hstate, cstate, out, saved, (unsigned*)workspace, (float*)l.ring, l.handoff)
     switch (H / 64) {
         case 4: LPF_FWD(4); break;
         case 5: LPF_FWD(5); break;
@@ -433,14 +389,12 @@ int mg_lstm_bwd_persist_f32(const float* grad_out, const float* grad_hn, const f
                             const float* w_hh, const int64_t* seq_len, int B, int T, int H, float* dgates, float* dh0, float* dc0,
                             void* workspace, size_t workspace_bytes, void* stream) {
     MG_CHECK_ARG(cstate && saved && w_hh && dgates && dh0 && dc0, "mg_lstm_bwd_persist_f32: null argument");
+    MG_CHECK_ARG(mg_lstm_persist_f32_supported(B, T, H), "mg_lstm_bwd_persist_f32: unsupported shape (B=%d T=%d H=%d)", B, T, H);
     hipStream_t st = (hipStream_t)stream;
-    const int rc = lpf_prepare("mg_lstm_bwd_persist_f32", B, T, H, workspace, workspace_bytes, st);
+    gp_launch l;
+    const int rc = gp_prepare_launch("mg_lstm_bwd_persist_f32", B, H, workspace, workspace_bytes, st, &l);
     if (rc != MG_OK) return rc;
-    const int R = (int)mg_ceil_div(B, GP_GROUPS);
-    const unsigned grid = (unsigned)(GP_GROUPS * (H / GT));
-    float* ring = (float*)((char*)workspace + GP_RING_OFFSET);
-    const int force = g_mg_tuning[MG_TUNE_GRU_HANDOFF];
-#define LPF_BWD(KS) hipLaunchKernelGGL((lstm_bwd_persist_f32_kernel<KS>), dim3(grid), dim3(256), 0, st, grad_out, grad_hn, grad_cn, cstate, saved, w_hh, seq_len, B, T, H, R, dgates, dh0, dc0, (unsigned*)workspace, ring, force)
+#define LPF_BWD(KS) hipLaunchKernelGGL((lstm_bwd_persist_f32_kernel<KS>), dim3(l.grid), dim3(256), 0, st, grad_out, grad_hn, grad_cn, cstate, saved, w_hh, seq_len, B, T, H, l.R, dgates, dh0, dc0, (unsigned*)workspace, (float*)l.ring, l.handoff)
     switch (H / 64) {
         case 4: LPF_BWD(16); break;
         case 5: LPF_BWD(20); break;

@@ -1,5 +1,6 @@
 // Shared pieces of the persistent (one launch for all time steps) recurrent kernels: group / slot geometry, the workspace layout,
-// the flag hand-off helpers and the XCD detection.  Protocol and measurements: gru_persist.hip (header comment), DESIGN.md section 4.
+// the flag hand-off helpers, the XCD detection, the kernels' common first lines, the time-out codes and the entry points' launch
+// set-up.  Protocol and measurements: gru_persist.hip (header comment), DESIGN.md section 4.
 #pragma once
 
 #include "common.h"
@@ -21,6 +22,28 @@ __device__ __forceinline__ gbf8 as_bf8(u32x4 v) {
     union { u32x4 u; gbf8 b; } c;
     c.u = v;
     return c.b;
+}
+
+// What a workgroup stores in the sticky status word (behind the flags; mg_gru_persist_status reports it) when one of its bounded waits
+// gives up.  The values are quoted by logs of earlier runs: they stay, also where two kernels share one.
+enum gp_status : unsigned {
+    GP_ST_GRU_FWD = 1,         // gru_fwd_persist_kernel: the group's state flags of a step
+    GP_ST_GRU_BWD = 2,         // gru_bwd_persist_kernel / gru_bwd_persist_wide_kernel: the group's gate-gradient flags of a step
+    GP_ST_XCD = 3,             // any kernel: the XCD ids of the group's other slots (gp_one_xcd_or_report, before the first step)
+    GP_ST_LSTM_FWD = 4,        // lstm_fwd_persist_kernel: the group's state flags of a step
+    GP_ST_LSTM_BWD = 5,        // lstm_bwd_persist_kernel: the group's gate-gradient flags of a step
+    GP_ST_LSTM_STACK_FWD = 6,  // lstm_stack_fwd_persist_kernel: own, lower or upper layer's flags of a step (lps_wait)
+    GP_ST_LSTM_STACK_BWD = 7,  // lstm_stack_bwd_persist_kernel: either of its two waits of a step (lps_wait)
+    GP_ST_GRU_FWD_F32 = 7,     // gru_fwd_persist_f32_kernel: the group's state flags of a step (the same number as the line above)
+    GP_ST_GRU_BWD_F32 = 8,     // gru_bwd_persist_f32_kernel: the group's gate-gradient flags of a step
+    GP_ST_GRU_STACK_FWD = 8,   // gru_stack_fwd_small64_kernel: the lower layer's output of a step (the same number as the line above)
+    GP_ST_LSTM_FWD_F32 = 9,    // lstm_fwd_persist_f32_kernel: the group's state flags of a step
+    GP_ST_GRU_STACK_BWD = 9,   // gru_stack_bwd_small64_kernel: the upper layer's input gradient of a step (the same number as the line above)
+    GP_ST_LSTM_BWD_F32 = 10,   // lstm_bwd_persist_f32_kernel: the group's gate-gradient flags of a step
+};
+
+__device__ __forceinline__ void gp_report(gu32* status, gp_status code) {
+    __hip_atomic_store(status, (unsigned)code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // the slot's flag: written through (sc1) in general; within one XCD a store that stays in the shared L2 (workgroup scope = no
@@ -56,14 +79,9 @@ __device__ __forceinline__ void gp_lds_barrier() { asm volatile("s_waitcnt lgkmc
 // workgroups, every ticket below n_slots is a distinct slot - so every workgroup finds one within 8 atomics and every slot gets
 // an owner (if all 8 groups were full, 8 n_slots OTHER workgroups would own slots: one more than exist).  A group that ends up
 // with members on several XCDs is found by gp_group_on_one_xcd below and keeps the placement-independent write-through form.
-// `legacy` != 0 (MG_TUNE_GRU_HANDOFF bit 1, for A/B): group = block % 8 as before.
 // Returns group * GP_SLOTS + slot, or -1 for a workgroup beyond the 8 n_slots the launch needs.  The tickets are zeroed with the
 // flags by the memset node ahead of the launch.
-__device__ __forceinline__ int gp_claim_slot(gu32* tickets, int n_slots, int tid, int* s_word, int legacy) {
-    if (legacy) {
-        const int slot = blockIdx.x / GP_GROUPS;
-        return slot < n_slots ? (int)(blockIdx.x % GP_GROUPS) * GP_SLOTS + slot : -1;
-    }
+__device__ __forceinline__ int gp_claim_slot(gu32* tickets, int n_slots, int tid, int* s_word) {
     if (tid == 0) {
         unsigned id;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(id));
@@ -107,6 +125,52 @@ __device__ __forceinline__ int gp_group_on_one_xcd(gu32* xcc_tab, int slot, int 
     return *s_word;
 }
 
+// The detection as the kernels use it: MG_TUNE_GRU_HANDOFF bit 0 skips it (0: the write-through form everywhere); a time-out is
+// reported here and comes back as -1, on which the kernel returns.
+__device__ __forceinline__ int gp_one_xcd_or_report(gu32* xcc_tab, int slot, int n_slots, int tid, int* s_word, int handoff, gu32* status) {
+    const int one_xcd = (handoff & 1) ? 0 : gp_group_on_one_xcd(xcc_tab, slot, n_slots, tid, s_word);
+    if (one_xcd < 0) {
+        if (tid == 0) gp_report(status, GP_ST_XCD);
+    }
+    return one_xcd;
+}
+
+// A single-layer kernel's first lines: which (group, slot) the workgroup serves (a ticket, gp_claim_slot), the group's rows
+// [row0, row0 + nrows) of the batch, its flag row, the status word, and whether the group sits on one XCD.  Clears *s_abort.
+// !ok: the workgroup has nothing to do, or the detection timed out (reported): the kernel returns.
+struct gp_place {
+    int group, slot, row0, nrows, one_xcd;
+    gu32 *flags, *status;
+    bool ok;
+};
+__device__ __forceinline__ gp_place gp_enter(unsigned* sync, int n_slots, int B, int R, int handoff, int tid, int* s_abort, int* s_word) {
+    gp_place p = {};
+    const int claim = gp_claim_slot((gu32*)sync + GP_TICKET_OFFSET, n_slots, tid, s_word);
+    if (claim < 0) return p;
+    p.group = claim / GP_SLOTS;
+    p.slot = claim % GP_SLOTS;
+    p.row0 = p.group * R;
+    p.nrows = min(R, B - p.row0);
+    if (p.slot >= n_slots || p.nrows <= 0) return p;
+    p.flags = (gu32*)sync + p.group * GP_SLOTS;
+    p.status = (gu32*)sync + GP_FLAG_WORDS;
+    if (tid == 0) *s_abort = 0;
+    p.one_xcd = gp_one_xcd_or_report((gu32*)sync + GP_GROUPS * GP_SLOTS + p.group * GP_SLOTS, p.slot, n_slots, tid, s_word, handoff, p.status);
+    p.ok = p.one_xcd >= 0;
+    return p;
+}
+
+// Longest sequence among the group's rows (at most T): steps at or beyond it need no matmul and no hand-off.  (Two kernels keep this
+// loop open-coded, and one gp_enter's lines: there the compiler allocates registers differently when they come from here.)
+__device__ __forceinline__ int gp_longest(const int64_t* seq_len, int row0, int nrows, int T) {
+    int gmax = 0;
+    for (int r = 0; r < nrows; ++r) {
+        const int64_t n = seq_len ? seq_len[row0 + r] : (int64_t)T;
+        gmax = max(gmax, (int)(n < T ? n : T));
+    }
+    return gmax;
+}
+
 // Residency: every workgroup of a persistent launch must be on the device at once.  The kernels need up to 256 VGPRs, i.e. as
 // few as two 256-thread workgroups per CU: a launch is offered only if the current device has room for `workgroups` at two
 // per CU (MI355X: 256 CUs; a partitioned or harvested device simply takes the per-step kernels instead of timing out).
@@ -122,3 +186,29 @@ static inline int gp_device_holds(long workgroups) {
 
 // workspace: [step flags 8 x 32 words | XCC ids 8 x 32 words | status word + 3 pad] [hand-off ring]
 #define GP_RING_OFFSET ((size_t)GP_SYNC_WORDS * sizeof(unsigned))
+
+// What every single-layer entry point does between its own argument checks and its launch: the workspace must be there, 16-byte
+// aligned and large enough (mg_gru_persist_workspace_bytes); the flags, XCC ids and tickets are zeroed on the stream; then the
+// launch geometry.  Returns MG_OK or the code the entry point returns (error text set).
+struct gp_launch {
+    int R;                 // items per group
+    unsigned grid;         // workgroups: 8 groups x H / 16 slots
+    void* ring;            // the hand-off ring behind the flags
+    int handoff;           // MG_TUNE_GRU_HANDOFF
+};
+static inline int gp_prepare_launch(const char* what, int B, int H, void* workspace, size_t workspace_bytes, hipStream_t st, gp_launch* l) {
+    MG_CHECK_ARG(((uintptr_t)workspace % 16) == 0, "%s: workspace must be 16-byte aligned", what);
+    if (!workspace || workspace_bytes < mg_gru_persist_workspace_bytes(B, H)) {
+        mg_set_error("%s: workspace of %zu bytes needed, got %zu", what, mg_gru_persist_workspace_bytes(B, H), workspace_bytes);
+        return MG_EWORKSPACE;
+    }
+    if (hipMemsetAsync(workspace, 0, (size_t)GP_FLAG_WORDS * sizeof(unsigned), st) != hipSuccess) {
+        mg_set_error("%s: memset failed", what);
+        return MG_ELAUNCH;
+    }
+    l->R = (int)mg_ceil_div(B, GP_GROUPS);
+    l->grid = (unsigned)(GP_GROUPS * (H / GT));
+    l->ring = (char*)workspace + GP_RING_OFFSET;
+    l->handoff = g_mg_tuning[MG_TUNE_GRU_HANDOFF];
+    return MG_OK;
+}

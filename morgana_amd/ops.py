@@ -2136,6 +2136,17 @@ def act_grad(dy, y, act):
 
 
 # ----------------------------------------------------------------------------------------------------------------- K3
+def _initial_state(init, b, t, h, dev, dtype=torch.float32):
+    """The (b, t + 1, h) state tensor of a recurrence: step 0 zeroed, or copied from ``init`` (anything of b * h elements); the
+    steps behind it are the kernel's to write."""
+    state = torch.empty((b, t + 1, h), dtype=dtype, device=dev)
+    if init is None:
+        state[:, 0].zero_()
+    else:
+        state[:, 0].copy_(init.reshape(b, h))
+    return state
+
+
 def gru_persist_f32_ok(b, t, h):
     return PERSISTENT_RECURRENCE and bool(_lib.load().mg_gru_persist_f32_supported(b, t, h))
 
@@ -2147,11 +2158,7 @@ def gru_fwd(xproj, w_hh, b_hh, seq_len, h0, b, t, h, persistent=None):
     dev = xproj.device
     if persistent is None:
         persistent = gru_persist_f32_ok(b, t, h)
-    hstate = torch.empty((b, t + 1, h), dtype=torch.float32, device=dev)
-    if h0 is None:
-        hstate[:, 0].zero_()
-    else:
-        hstate[:, 0].copy_(h0.reshape(b, h))
+    hstate = _initial_state(h0, b, t, h, dev)
     out = torch.empty((b, t, h), dtype=torch.float32, device=dev)
     saved = torch.empty((b, t, 4 * h), dtype=torch.float32, device=dev)
     if persistent:
@@ -2232,14 +2239,8 @@ def gru_fwd_bf16(xproj, w_hh, b_hh, seq_len, h0, b, t, h, persistent=None, xrows
     if out_bf is not None and (not persistent or out_bf.dtype != torch.bfloat16 or tuple(out_bf.shape) != (b, t, h) or not out_bf.is_contiguous()):
         raise ValueError('gru_fwd_bf16: out_bf must be a contiguous (b, t, h) bfloat16 tensor and needs the persistent launch')
     dev = xproj.device
-    hstate = torch.empty((b, t + 1, h), dtype=torch.float32, device=dev)
-    hstate_bf = torch.empty((b, t + 1, h), dtype=torch.bfloat16, device=dev)
-    if h0 is None:
-        hstate[:, 0].zero_()
-        hstate_bf[:, 0].zero_()
-    else:
-        hstate[:, 0].copy_(h0.reshape(b, h))
-        hstate_bf[:, 0].copy_(h0.reshape(b, h))
+    hstate = _initial_state(h0, b, t, h, dev)
+    hstate_bf = _initial_state(h0, b, t, h, dev, torch.bfloat16)
     if w_bf is None or w_bf.dtype != torch.bfloat16 or w_bf.shape[0] != 3 * h or w_bf.shape[1] < h or not w_bf.is_contiguous():
         w_bf = cast_pad_bf16(w_hh)
     out = torch.empty((b, t, h), dtype=torch.float32, device=dev)
@@ -2250,12 +2251,9 @@ def gru_fwd_bf16(xproj, w_hh, b_hh, seq_len, h0, b, t, h, persistent=None, xrows
             xrows = _require(xrows, torch.int32, 'xrows')
             if xrows.numel() != b * t or xproj.ndim != 2 or xproj.shape[1] != 3 * h:
                 raise ValueError('gru_fwd_bf16: row map of %d entries / table %s for b=%d t=%d h=%d' % (xrows.numel(), tuple(xproj.shape), b, t, h))
-            _lib.check(lib.mg_gru_fwd_persist_out_bf16(_p(xproj), _p(xrows), xproj.shape[0], _p(w_bf), w_bf.shape[1], _p(b_hh), _p(seq_len),
-                                                       b, t, h, _p(hstate), _p(hstate_bf), _p(out), _p(out_bf), _p(saved), _p(ws), ws.numel(),
-                                                       _stream()), 'mg_gru_fwd_persist_out_bf16')
-            return out, hstate, saved, hstate_bf
-        _lib.check(lib.mg_gru_fwd_persist_out_bf16(_p(xproj), None, 0, _p(w_bf), w_bf.shape[1], _p(b_hh), _p(seq_len), b, t, h, _p(hstate),
-                                                   _p(hstate_bf), _p(out), _p(out_bf), _p(saved), _p(ws), ws.numel(), _stream()),
+        n_rows = xproj.shape[0] if xrows is not None else 0
+        _lib.check(lib.mg_gru_fwd_persist_out_bf16(_p(xproj), _p(xrows), n_rows, _p(w_bf), w_bf.shape[1], _p(b_hh), _p(seq_len), b, t, h,
+                                                   _p(hstate), _p(hstate_bf), _p(out), _p(out_bf), _p(saved), _p(ws), ws.numel(), _stream()),
                    'mg_gru_fwd_persist_out_bf16')
     else:
         _lib.check(lib.mg_gru_fwd_bf16(_p(xproj), _p(w_bf), w_bf.shape[1], _p(b_hh), _p(seq_len), b, t, h, _p(hstate), _p(hstate_bf),
@@ -2273,19 +2271,13 @@ def gru_bwd_bf16(grad_out, grad_hn, hstate, saved, w_hh, seq_len, b, t, h, persi
     dev = grad_out.device
     if wt_bf is not None and (wt_bf.dtype != torch.bfloat16 or wt_bf.shape[0] != h or wt_bf.shape[1] < 3 * h or not wt_bf.is_contiguous()):
         wt_bf = None
-    if shadows_only and persistent:
+    shadows_only = shadows_only and persistent
+    dxproj = dhproj = dxproj_bf = None                             # fp32 gradients, or (shadows_only) the bf16 copy of dxproj
+    if shadows_only:
         dxproj_bf = torch.empty((b, t, 3 * h), dtype=torch.bfloat16, device=dev)
-        dhproj_bf = torch.empty((b, t, 3 * h), dtype=torch.bfloat16, device=dev)
-        dh0 = torch.empty((b, h), dtype=torch.float32, device=dev)
-        if wt_bf is None:
-            wt_bf = cast_transpose_bf16(w_hh)
-        ws = _persist_workspace(dev, b, h)
-        _lib.check(lib.mg_gru_bwd_persist_bf16(_p(grad_out), _p(grad_hn), _p(hstate), _p(saved), _p(wt_bf), wt_bf.shape[1], _p(seq_len),
-                                               b, t, h, None, None, _p(dhproj_bf), _p(dxproj_bf), _p(dh0), _p(ws), ws.numel(),
-                                               _stream()), 'mg_gru_bwd_persist_bf16')
-        return dxproj_bf, dhproj_bf, dh0
-    dxproj = torch.empty((b, t, 3 * h), dtype=torch.float32, device=dev)
-    dhproj = torch.empty((b, t, 3 * h), dtype=torch.float32, device=dev)
+    else:
+        dxproj = torch.empty((b, t, 3 * h), dtype=torch.float32, device=dev)
+        dhproj = torch.empty((b, t, 3 * h), dtype=torch.float32, device=dev)
     dhproj_bf = torch.empty((b, t, 3 * h), dtype=torch.bfloat16, device=dev)
     dh0 = torch.empty((b, h), dtype=torch.float32, device=dev)
     if wt_bf is None:
@@ -2293,9 +2285,9 @@ def gru_bwd_bf16(grad_out, grad_hn, hstate, saved, w_hh, seq_len, b, t, h, persi
     if persistent:
         ws = _persist_workspace(dev, b, h)
         _lib.check(lib.mg_gru_bwd_persist_bf16(_p(grad_out), _p(grad_hn), _p(hstate), _p(saved), _p(wt_bf), wt_bf.shape[1], _p(seq_len),
-                                               b, t, h, _p(dxproj), _p(dhproj), _p(dhproj_bf), None, _p(dh0), _p(ws), ws.numel(),
+                                               b, t, h, _p(dxproj), _p(dhproj), _p(dhproj_bf), _p(dxproj_bf), _p(dh0), _p(ws), ws.numel(),
                                                _stream()), 'mg_gru_bwd_persist_bf16')
-        return dxproj, dhproj, dh0, dhproj_bf
+        return (dxproj_bf, dhproj_bf, dh0) if shadows_only else (dxproj, dhproj, dh0, dhproj_bf)
     nbytes = lib.mg_gru_bwd_workspace_bytes(b, h)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     _lib.check(lib.mg_gru_bwd_bf16(_p(grad_out), _p(grad_hn), _p(hstate), _p(saved), _p(wt_bf), wt_bf.shape[1], _p(seq_len), b, t, h,
@@ -2316,13 +2308,8 @@ def lstm_fwd(xproj, w_hh, b_hh, seq_len, h0, c0, b, t, h, persistent=None):
     dev = xproj.device
     if persistent is None:
         persistent = lstm_persist_f32_ok(b, t, h)
-    hstate = torch.empty((b, t + 1, h), dtype=torch.float32, device=dev)
-    cstate = torch.empty((b, t + 1, h), dtype=torch.float32, device=dev)
-    for state, init in ((hstate, h0), (cstate, c0)):
-        if init is None:
-            state[:, 0].zero_()
-        else:
-            state[:, 0].copy_(init.reshape(b, h))
+    hstate = _initial_state(h0, b, t, h, dev)
+    cstate = _initial_state(c0, b, t, h, dev)
     out = torch.empty((b, t, h), dtype=torch.float32, device=dev)
     saved = torch.empty((b, t, 4 * h), dtype=torch.float32, device=dev)
     if persistent:
@@ -2364,14 +2351,9 @@ def lstm_fwd_bf16(xproj, w_hh, b_hh, seq_len, h0, c0, b, t, h):
     """lstm_fwd with bf16 matmul operands, one persistent launch.  Returns (out, hstate, cstate, saved, hstate_bf)."""
     lib = _lib.load()
     dev = xproj.device
-    hstate = torch.empty((b, t + 1, h), dtype=torch.float32, device=dev)
-    cstate = torch.empty((b, t + 1, h), dtype=torch.float32, device=dev)
-    hstate_bf = torch.empty((b, t + 1, h), dtype=torch.bfloat16, device=dev)
-    for state, init in ((hstate, h0), (cstate, c0), (hstate_bf, h0)):
-        if init is None:
-            state[:, 0].zero_()
-        else:
-            state[:, 0].copy_(init.reshape(b, h))
+    hstate = _initial_state(h0, b, t, h, dev)
+    cstate = _initial_state(c0, b, t, h, dev)
+    hstate_bf = _initial_state(h0, b, t, h, dev, torch.bfloat16)
     w_bf = cast_pad_bf16(w_hh)
     out = torch.empty((b, t, h), dtype=torch.float32, device=dev)
     saved = torch.empty((b, t, 4 * h), dtype=torch.float32, device=dev)
@@ -2424,15 +2406,10 @@ def lstm_pstack_fwd(xproj0, w_ih, w_hh, b_ih, b_hh, seq_len, h0s, c0s, b, t, h):
             else:
                 state[:, :, 0].copy_(init.reshape(n_layers, b, h))
     else:
-        hs_all = [torch.empty((b, t + 1, h), dtype=torch.float32, device=dev) for _ in range(n_layers)]
-        cs_all = [torch.empty((b, t + 1, h), dtype=torch.float32, device=dev) for _ in range(n_layers)]
-        hb_all = [torch.empty((b, t + 1, h), dtype=torch.bfloat16, device=dev) for _ in range(n_layers)]
-        for l in range(n_layers):
-            for state, init in ((hs_all[l], h0s), (cs_all[l], c0s), (hb_all[l], h0s)):
-                if init is None:
-                    state[:, 0].zero_()
-                else:
-                    state[:, 0].copy_(init[l].reshape(b, h))
+        layer_init = lambda inits, l: None if inits is None else inits[l]
+        hs_all = [_initial_state(layer_init(h0s, l), b, t, h, dev) for l in range(n_layers)]
+        cs_all = [_initial_state(layer_init(c0s, l), b, t, h, dev) for l in range(n_layers)]
+        hb_all = [_initial_state(layer_init(h0s, l), b, t, h, dev, torch.bfloat16) for l in range(n_layers)]
     # bf16 operands of W_hh (every layer) and W_ih (layers 1..): the parameters' shadows, stale ones re-cast by one batched launch
     wh_bf = weight_operands(w_hh)
     wi_bf = [None] + weight_operands(w_ih[1:])
@@ -2492,11 +2469,7 @@ def gru_stack_small_fwd(xproj0, w_ih, w_hh, b_ih, b_hh, seq_len, h0s, b, t, h, f
     descs = (_lib.mg_gru_stack_layer * n_layers)()
     outs, hstates, saveds = [], [], []
     for l in range(n_layers):
-        hs = torch.empty((b, t + 1, h), dtype=torch.float32, device=dev)
-        if h0s is None:
-            hs[:, 0].zero_()
-        else:
-            hs[:, 0].copy_(h0s[l].reshape(b, h))
+        hs = _initial_state(None if h0s is None else h0s[l], b, t, h, dev)
         o = torch.empty((b, t, h), dtype=torch.float32, device=dev)
         sv = torch.empty((b, t, 4 * h), dtype=torch.float32, device=dev)
         d = descs[l]

@@ -31,6 +31,19 @@ static void expect_code(const char* what, int rc) {
     }
 }
 
+/* A persistent entry point given a 16-byte (or no) workspace.  Its workspace check answers MG_EWORKSPACE, before the flag memset and
+ * before any launch - wherever the call gets that far: the shape check in front of it asks mg_*_supported, which holds every shape
+ * against the current device's CU count, so with every device hidden (this program) it refuses first, with MG_EINVAL.  `supported` is
+ * what that query says here; the MG_EWORKSPACE answers themselves are held on a device by tests/test_gpu_parity.py. */
+static void expect_workspace_refusal(const char* what, int supported, int rc) {
+    const int want = supported ? MG_EWORKSPACE : MG_EINVAL;
+    expect_code(what, rc);
+    if (rc != want) {
+        fprintf(stderr, "%s: return code %d, expected %d\n", what, rc, want);
+        ++n_bad;
+    }
+}
+
 /* Devices the HIP runtime (loaded with libmorgana_hip) reports; 0 when it reports an error, e.g. that there is none. */
 static int visible_devices(void) {
     int (*get_count)(int*) = (int (*)(int*))dlsym(RTLD_DEFAULT, "hipGetDeviceCount");
@@ -165,6 +178,26 @@ int main(void) {
     expect_code("segment_sum_feat(small slabs)", mg_segment_sum_feat_bf16(dh, 512, di, 64000, di, di, 5000, 1024, 512, dh, 512, df, 9, d, 16, NULL));
     expect_code("feat_wgrad_reduce(ok)", mg_feat_wgrad_reduce(d, 9, 512, 512, df, 609, 600, 1, NULL));
     expect_code("gru_fwd_persist_out(shape)", mg_gru_fwd_persist_out_bf16(df, NULL, 0, dh, 512, df, dl, 64, 1000, 512, df, dh, df, dh, df, d, 16, NULL));
+    /* the persistent single-layer entry points behind their shared launch set-up (csrc/persist_common.h): a supported shape, a
+     * workspace of 16 bytes; and the fp32 LSTM forward without a workspace, which answers as the others do */
+    {
+        const int B = 8, T = 4, H = 256;
+        const int gru32 = mg_gru_persist_f32_supported(B, T, H), lstm16 = mg_lstm_persist_supported(B, T, H),
+                  lstm32 = mg_lstm_persist_f32_supported(B, T, H);
+        expect_workspace_refusal("gru_fwd_persist_f32(small ws)", gru32, mg_gru_fwd_persist_f32(df, df, df, dl, B, T, H, df, df, df, d, 16, NULL));
+        expect_workspace_refusal("gru_bwd_persist_f32(small ws)", gru32,
+                                 mg_gru_bwd_persist_f32(df, df, df, df, df, dl, B, T, H, df, df, df, d, 16, NULL));
+        expect_workspace_refusal("lstm_fwd_persist_bf16(small ws)", lstm16,
+                                 mg_lstm_fwd_persist_bf16(df, dh, H, df, dl, B, T, H, df, df, dh, df, df, d, 16, NULL));
+        expect_workspace_refusal("lstm_bwd_persist_bf16(small ws)", lstm16,
+                                 mg_lstm_bwd_persist_bf16(df, df, df, df, df, dh, 4 * H, dl, B, T, H, df, dh, df, df, d, 16, NULL));
+        expect_workspace_refusal("lstm_fwd_persist_f32(small ws)", lstm32,
+                                 mg_lstm_fwd_persist_f32(df, df, df, dl, B, T, H, df, df, df, df, d, 16, NULL));
+        expect_workspace_refusal("lstm_bwd_persist_f32(small ws)", lstm32,
+                                 mg_lstm_bwd_persist_f32(df, df, df, df, df, df, dl, B, T, H, df, df, df, d, 16, NULL));
+        expect_workspace_refusal("lstm_fwd_persist_f32(no ws)", lstm32,
+                                 mg_lstm_fwd_persist_f32(df, df, df, dl, B, T, H, df, df, df, df, NULL, 0, NULL));
+    }
 
     /* plausible shapes: the host path runs its planning and set-up; without a device the launch itself fails (MG_ELAUNCH) */
     expect_code("upsample_index(C2)", mg_upsample_index(dl, 256, 80, 1000, NULL, di, NULL));

@@ -329,6 +329,19 @@ def test_product_library_holds_no_experiments():
         assert lib.mg_set_tuning(key, value) == 0, (key, value)
 
 
+def test_gru_handoff_tuning_takes_bits_0_and_2_only():
+    """MG_TUNE_GRU_HANDOFF (key 2): bit 0 = always write-through hand-off stores, bit 2 = the narrow bf16 GRU backward.  Bit 1 chose group
+    membership by block index; that path is gone, and a value that names it is refused like any other unknown value."""
+    lib = _lib.load()
+    try:
+        for value in (2, 3, 6, 7, 8, -1):
+            assert lib.mg_set_tuning(2, value) == -1 and 'does not take value %d' % value in _lib.last_error(), value
+        for value in (0, 1, 4, 5):
+            assert lib.mg_set_tuning(2, value) == 0, value
+    finally:
+        assert lib.mg_set_tuning(2, 0) == 0
+
+
 def test_host_pack_equals_concatenate():
     """mg_host_pack (the loader's host half: utterance arrays back to back into the pinned staging buffer, by host threads) against
     np.concatenate for ragged pieces, every thread count, a zero-length piece; a destination that is too small is refused."""

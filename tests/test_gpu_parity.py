@@ -1323,6 +1323,36 @@ def test_gru_persistent_equals_stepwise(b, t, hid, gru_handoff):
             assert torch.equal(dx_bf, want_b[0].to(torch.bfloat16)) and torch.equal(dh_bf, want_b[3]) and torch.equal(dh0, want_b[2])
 
 
+def test_persistent_entry_points_refuse_a_short_workspace():
+    """The eight single-layer persistent entry points share one launch set-up (csrc/persist_common.h): given a supported shape
+    and a workspace said to be 16 bytes long each answers MG_EWORKSPACE - before the flag memset and before any launch - and so
+    does the fp32 LSTM forward given no workspace at all (it used to answer MG_EINVAL).  On a device, because the shape check in
+    front of the set-up holds the shape against the device's CU count.  Every pointer is real memory of sufficient size."""
+    from morgana_amd import _lib
+    lib = _lib.load()
+    b, t, h = 8, 4, 256
+    assert ops.gru_persist_ok(b, t, h) and ops.gru_persist_f32_ok(b, t, h) and ops.lstm_persist_ok(b, t, h) and ops.lstm_persist_f32_ok(b, t, h)
+    buf = torch.zeros(max(b * (t + 1) * 4 * h, 4 * h * h), dtype=torch.float32, device='cuda:0')      # as large as the largest operand
+    ws = torch.zeros(lib.mg_gru_persist_workspace_bytes(b, h), dtype=torch.uint8, device='cuda:0')
+    p, w, ld3, ld4 = buf.data_ptr(), ws.data_ptr(), 3 * h, 4 * h
+    calls = {
+        'mg_gru_fwd_persist_out_bf16': lambda w, n: lib.mg_gru_fwd_persist_out_bf16(p, None, 0, p, h, p, None, b, t, h, p, p, p, None, p, w, n, None),
+        'mg_gru_bwd_persist_bf16': lambda w, n: lib.mg_gru_bwd_persist_bf16(p, p, p, p, p, ld3, None, b, t, h, p, p, p, None, p, w, n, None),
+        'mg_gru_fwd_persist_f32': lambda w, n: lib.mg_gru_fwd_persist_f32(p, p, p, None, b, t, h, p, p, p, w, n, None),
+        'mg_gru_bwd_persist_f32': lambda w, n: lib.mg_gru_bwd_persist_f32(p, p, p, p, p, None, b, t, h, p, p, p, w, n, None),
+        'mg_lstm_fwd_persist_bf16': lambda w, n: lib.mg_lstm_fwd_persist_bf16(p, p, h, p, None, b, t, h, p, p, p, p, p, w, n, None),
+        'mg_lstm_bwd_persist_bf16': lambda w, n: lib.mg_lstm_bwd_persist_bf16(p, p, p, p, p, p, ld4, None, b, t, h, p, p, p, p, w, n, None),
+        'mg_lstm_fwd_persist_f32': lambda w, n: lib.mg_lstm_fwd_persist_f32(p, p, p, None, b, t, h, p, p, p, p, w, n, None),
+        'mg_lstm_bwd_persist_f32': lambda w, n: lib.mg_lstm_bwd_persist_f32(p, p, p, p, p, p, None, b, t, h, p, p, p, w, n, None),
+    }
+    for name, call in calls.items():
+        assert call(w, 16) == _lib.MG_EWORKSPACE, (name, _lib.last_error())
+        assert 'workspace of %d bytes needed, got 16' % ws.numel() in _lib.last_error(), name
+    assert calls['mg_lstm_fwd_persist_f32'](None, 0) == _lib.MG_EWORKSPACE, _lib.last_error()
+    torch.cuda.synchronize()
+    ops.check_persistent_status()
+
+
 @pytest.mark.parametrize('b,t,hid', [(64, 40, 512), (5, 37, 128), (33, 20, 256), (200, 9, 128), (12, 15, 384), (3, 1, 128)])
 def test_lstm_persistent_vs_fp32_and_between_handoff_forms(b, t, hid):
     """The one-launch LSTM recurrence (csrc/lstm_persist.hip, bf16 matmul operands) against the exact-fp32 per-step kernels on
