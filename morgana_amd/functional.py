@@ -12,6 +12,7 @@ bf16 MFMA products per fp32 product, fp32 accumulate and fp32 activations: parit
 matrix rate; row-wise Linear / Sigmoid layers only, recurrent cells run their exact-fp32 form in this mode).
 """
 import os
+import typing
 
 import numpy as np
 import torch
@@ -342,37 +343,48 @@ class _RunDropout(object):
         return ops.dropout(x, self.drops[i], self.seed, self.site0 + i, self.used, out=x if inplace else None)
 
 
+class LinearStackSpec(typing.NamedTuple):
+    """What a ``LinearStackFn`` node runs, apart from its tensors: the opaque first argument of ``apply`` (autograd does not look inside:
+    the tensors of ``shadow`` and ``front`` need no gradient and get none).  acts: one ops.ACT_* per layer; precision: 'fp32', 'bf16' or 'bf16x3'.
+    extra      zero rows appended behind x2d (phone-rate tables: what padding frames gather).
+    rows_runs  ``rows`` is an upsample frame map (runs of equal indices): a hint for the layer-1 loader.
+    drop       active dropout behind layers of the run (utils._Run.drop_spec): masks drawn in forward, regenerated in backward; the activation
+               saved for the backward is the one BEFORE the mask (the sigmoid gradient needs it), the masked copy feeds the next layer.
+    shadow     a bf16 copy of x2d somebody already made (the GRU recurrence writes one of its output: GRUFn out_bf): layer 1's operand.
+    front      (rows, seg, frame features): the input is cat(x2d[rows], frame features) - the table of phone rows repeated by
+               upsample_to_repetitions with per-frame counters behind it (models/RNN_SPSS.py:76-81).  bf16 mode: the table's part of the first
+               layer runs once per phone, ops.phone_concat_layer adds the counters' part per frame; rows: -1 mapped to the first extra row.
+    latent     (col0, rows_per_item): the input's columns col0 : col0 + Z hold the latent z (B, Z) of row m's item m / rows_per_item
+               (ops.gather_concat_latent made the operand), and z follows the parameters as one more differentiable input: its
+               gradient is the per-item row sum of the first layer's pre-activation gradient times W[:, col0 : col0 + Z]."""
+    acts: tuple
+    precision: str
+    extra: int = 0
+    rows_runs: bool = False
+    drop: typing.Optional[tuple] = None
+    shadow: typing.Optional[torch.Tensor] = None
+    front: typing.Optional[tuple] = None
+    latent: typing.Optional[tuple] = None
+
+
 class LinearStackFn(torch.autograd.Function):
     """y = L_n(...sigma(L_1(x))...) over rows of a 2-D input (or of a gathered table).
 
-    forward(ctx, spec, x2d, rows, *params); spec = (acts, precision); params = w0, b0, w1, b1, ... (bias may be None).
+    forward(ctx, spec, x2d, rows, *params); spec = a ``LinearStackSpec``; params = w0, b0, w1, b1, ... (bias may be None).
     With ``rows`` the input row m is ``x2d[rows[m]]`` (zero row for -1): the frame-rate tensor is never materialised.
     When such a gathered input needs a gradient (packed frames, ``utils.FrameLayout``: the rows are distinct) the input gradient is
     scattered back to the rows of ``x2d``; rows no index points at get zeros.
-    Latent entry (spec[7] = (col0, rows_per_item)): the input's columns col0 : col0 + Z hold the latent z (B, Z) of row m's item
-    m / rows_per_item (ops.gather_concat_latent made the operand), and z follows the parameters as one more differentiable input:
-    its gradient is the per-item row sum of the first layer's pre-activation gradient times W[:, col0 : col0 + Z].
+    The layers themselves run in one of ``_stack_fwd_f32`` / ``_x3`` / ``_bf16`` and ``_stack_bwd_f32`` / ``_x3`` / ``_bf16`` below.
     """
 
     @staticmethod
     def forward(ctx, spec, x2d, rows, *params):
-        acts, precision = spec[:2]
-        extra = spec[2] if len(spec) > 2 else 0       # zero rows appended behind x2d (phone-rate tables: what padding frames gather)
-        rows_runs = bool(spec[3]) if len(spec) > 3 else False      # `rows` is an upsample frame map (runs of equal indices): a hint
-        # active dropout behind layers of the run (utils._Run.drop_spec): masks drawn here, regenerated in backward; the activation
-        # saved for the backward is the one BEFORE the mask (the sigmoid gradient needs it), the masked copy feeds the next layer
-        drop = _RunDropout(spec[4], x2d.device) if len(spec) > 4 and spec[4] is not None else None
-        ctx.drop = drop
-        # a bf16 copy of x2d somebody already made (the GRU recurrence writes one of its output: GRUFn out_bf): the first layer's operand
-        shadow = spec[5] if len(spec) > 5 else None
-        # `front` = (rows, seg, frame features): the input is cat(x2d[rows], frame features) - the table of phone rows repeated by
-        # upsample_to_repetitions with per-frame counters behind it (models/RNN_SPSS.py:76-81).  bf16 mode: the table's part of the first
-        # layer runs once per phone, ops.phone_concat_layer adds the counters' part per frame; rows: -1 mapped to the first extra row
-        front = spec[6] if len(spec) > 6 else None
+        acts, precision, extra, front, latent = spec.acts, spec.precision, spec.extra, spec.front, spec.latent
+        ctx.drop = _RunDropout(spec.drop, x2d.device) if spec.drop is not None else None
         n_layers = len(acts)
         weights = [params[2 * i] for i in range(n_layers)]
         biases = [params[2 * i + 1] for i in range(n_layers)]
-        latent = spec[7] if len(spec) > 7 else None
+        ctx.latent = None
         if latent is not None:
             z = params[2 * n_layers]
             if front is not None or ctx.needs_input_grad[1]:
@@ -382,8 +394,6 @@ class LinearStackFn(torch.autograd.Function):
                 raise ValueError('LinearStackFn: latent %s does not fit the first layer %s at column %d with %d rows per item'
                                  % (tuple(z.shape), tuple(weights[0].shape), latent[0], latent[1]))
             ctx.latent = (latent[0], latent[1], z.shape[0], z.shape[1])
-        else:
-            ctx.latent = None
         # a bf16 input is an already padded layer-1 operand (ops.gather_concat); anything else must be fp32
         pre_cast = precision == 'bf16' and x2d.dtype == torch.bfloat16
         x2d = ops._require(x2d, torch.bfloat16 if pre_cast else torch.float32, 'input')
@@ -396,123 +406,22 @@ class LinearStackFn(torch.autograd.Function):
             m = front[0].numel()
         ctx.spec, ctx.m = spec, m
         ctx.n_src = x2d.shape[0]
-        gathered_grad = rows is not None and ctx.needs_input_grad[1]
-        rows_k = rows                                  # the row map the kernels' loaders apply (None once the input is packed)
+        scatter_to = rows if (rows is not None and ctx.needs_input_grad[1]) else None     # gathered rows that want their gradient back
         ctx.has_bias = [b is not None for b in biases]
         ctx.dims = [(w.shape[0], w.shape[1]) for w in weights]
         k_in = weights[0].shape[1] - (front[2].shape[1] if front is not None else 0)
         if x2d.shape[1] != (ops.pad_ld(k_in) if pre_cast else k_in):
             raise ValueError('Linear expects %d input features, got %d' % (k_in, x2d.shape[1]))
-        hidden = []
-        if precision == 'fp32':
-            if extra:
-                x2d = torch.cat((x2d, x2d.new_zeros((extra, x2d.shape[1]))))
-            a, r = x2d, rows
-            for i in range(n_layers):
-                w = ops._require(weights[i], torch.float32, 'weight')
-                a = ops.linear_fwd_f32(a, r, m, w, biases[i], acts[i])
-                r = None
-                hidden.append(a)
-                if drop is not None:
-                    a = drop.apply(a, i)
-            out = a
-            ctx.save_for_backward(x2d, rows_k, rows if gathered_grad else None, *weights, *hidden)
-        elif precision == 'bf16x3':
-            # split-bf16: fp32 activations as in fp32 mode, every product as ONE bf16 GEMM over split operands (csrc/split3.hip)
-            split = [_x3_layer(w) for w in weights]
-            if extra and not split[0]:
-                x2d, extra = torch.cat((x2d, x2d.new_zeros((extra, x2d.shape[1])))), 0
-            a, r = x2d, rows
-            w3s = ops.x3_weight_operands([w for w, s in zip(weights, split) if s])[0]
-            kept = [None] * n_layers              # the activation splits: the backward's weight gradients multiply with them again
-            for i in range(n_layers):
-                if split[i]:
-                    # the zero rows behind a phone table (what padding frames gather) are rows of the split operand, never of an fp32 copy
-                    a3 = ops.split3([(a, 0, False, extra if i == 0 else 0)])[0]
-                    kept[i] = a3
-                    a = ops.linear_fwd_x3(a3, r, m, w3s.pop(0), biases[i], weights[i].shape[0], acts[i])
-                else:
-                    a = ops.linear_fwd_f32(a, r, m, ops._require(weights[i], torch.float32, 'weight'), biases[i], acts[i])
-                r = None
-                hidden.append(a)
-                if drop is not None:
-                    a = drop.apply(a, i)
-            out = a
-            ctx.save_for_backward(x2d, rows_k, rows if gathered_grad else None, *weights, *hidden)
-            ctx.param_refs = (list(weights), list(biases))
-            ctx.x3_extra = extra
-            ctx.x3_kept = kept
-        else:
-            if gathered_grad:
-                if pre_cast:
-                    raise ValueError('LinearStackFn: a gathered input that needs a gradient must be fp32')
-                # pack and cast in one pass: the bf16 operand holds exactly the gathered rows
-                a, rows_k = ops.gather_rows(x2d, rows, out_bf16=True, ld=ops.pad_ld(k_in)), None
-            elif (shadow is not None and not pre_cast and not extra and shadow.dtype == torch.bfloat16 and shadow.is_contiguous()
-                  and tuple(shadow.shape) == (x2d.shape[0], ops.pad_ld(k_in)) and k_in == ops.pad_ld(k_in)):
-                a = shadow
-            else:
-                # (a phone table in front of frame features is padded to the layer's full input width: its weight gradient then
-                # spans all of dW, with zeros in the features' columns - ops.feat_wgrad_reduce fills those)
-                a = x2d if pre_cast else ops.cast_pad_bf16(x2d, ld=ops.pad_ld(weights[0].shape[1]) if front is not None else None,
-                                                           extra_rows=extra)
-            a0, r = a, rows_k
-            # bf16 operands of the weights: copies that live on the parameters, refreshed by the optimiser's update kernel
-            # (ops.param_shadows) - no cast launch per layer and step
-            w_bfs = _w_plain(weights)
-            for i in range(n_layers):
-                n, k = weights[i].shape
-                last = i == n_layers - 1
-                if i == 0 and front is not None:
-                    a = ops.phone_concat_layer(a0, k_in, front[0], front[2], weights[0], w_bfs[0], biases[0], n, acts[0], out_f32=last)
-                else:
-                    a = ops.linear_fwd_bf16(a, r, m, k, w_bfs[i], biases[i], n, acts[i], out_f32=last, rows_runs=rows_runs)
-                r = None
-                hidden.append(a)
-                if drop is not None and not last:
-                    a = drop.apply(a, i)                 # over the padded bf16 buffer: zero padding stays zero
-            n_last = weights[-1].shape[0]
-            out = hidden[-1]
-            if out.shape[1] != n_last:
-                out = out[:, :n_last].contiguous()
-            unmasked = out                               # what a trailing sigmoid's gradient reads in backward
-            if drop is not None:
-                out = drop.apply(out, n_layers - 1)
-            ctx.save_for_backward(a0, rows_k, rows if gathered_grad else None, *weights, *hidden[:-1], unmasked)
-            ctx.param_refs = (list(weights), list(biases))        # the Parameter objects (their .grad views, their shadows)
-        return out
+        run = _stack_fwd_f32 if precision == 'fp32' else _stack_fwd_x3 if precision == 'bf16x3' else _stack_fwd_bf16
+        return run(ctx, spec, x2d, rows, scatter_to, m, weights, biases, pre_cast, k_in)
 
     @staticmethod
     def backward(ctx, grad_out):
-        acts, precision = ctx.spec[:2]
+        acts, precision = ctx.spec.acts, ctx.spec.precision
         n_layers = len(acts)
         saved = ctx.saved_tensors
-        x_in, rows, scatter_to = saved[0], saved[1], saved[2]
-        weights = saved[3:3 + n_layers]
-        hidden = saved[3 + n_layers:]
-        m = ctx.m
-        grads = [None] * (2 * n_layers)
-        need_x = ctx.needs_input_grad[1]
-        drop = getattr(ctx, 'drop', None)
-
-        def masked_input(i):
-            # the operand layer i multiplied in the forward pass: the saved activation of layer i - 1 under its dropout mask (regenerated)
-            return hidden[i - 1] if drop is None else drop.apply(hidden[i - 1], i - 1)
-
-        def unmask(g_, i):
-            # a gradient with respect to a MASKED activation -> with respect to the activation: the same mask (it commutes with the
-            # sigmoid gradient the dgrad kernels fuse, which reads the unmasked activation)
-            return g_ if drop is None else drop.apply(g_, i, inplace=True)
-
-        latent = ctx.latent
-        dz = None
-
-        def latent_grad(g0, bf16_cols=None, h=None):
-            # dz = (per-item row sums of the first layer's pre-activation gradient) . W_z
-            col0, per_item, n_items, zdim = latent
-            sums = ops.rows_sum_per_item(g0, n_items, per_item, n=ctx.dims[0][0], h=h)
-            return ops.linear_dgrad_f32(sums, weights[0][:, col0:col0 + zdim].contiguous(), None)
-
+        (x_in, rows, scatter_to), weights, hidden = saved[:3], saved[3:3 + n_layers], saved[3 + n_layers:]
+        drop = ctx.drop
         g = grad_out.contiguous()
         if drop is not None and drop.active(n_layers - 1):
             g = drop.apply(g, n_layers - 1)
@@ -520,131 +429,252 @@ class LinearStackFn(torch.autograd.Function):
             g = ops.sigmoid_grad(g, hidden[-1])
         elif acts[-1] != ops.ACT_NONE:
             g = ops.act_grad(g, hidden[-1], acts[-1])
-        grad_x = None
-
-        def fed_by(i):
-            # (output, activation) of the layer feeding layer i: what the dgrad epilogue multiplies f' from
-            return (hidden[i - 1], acts[i - 1]) if acts[i - 1] != ops.ACT_NONE else (None, ops.ACT_NONE)
-
-        if precision == 'fp32':
-            for i in range(n_layers - 1, -1, -1):
-                n, k = ctx.dims[i]
-                a_in, r = (x_in, rows) if i == 0 else (masked_input(i), None)
-                if i == 0 and latent is not None:
-                    dz = latent_grad(g)
-                dw, db = ops.linear_wgrad_f32(g, a_in, r, n, k, want_bias=ctx.has_bias[i])
-                grads[2 * i], grads[2 * i + 1] = dw, db
-                if i > 0:
-                    h, h_act = fed_by(i)
-                    g = unmask(ops.linear_dgrad_f32(g, weights[i], h, h_act), i - 1)
-                elif need_x:
-                    grad_x = ops.linear_dgrad_f32(g, weights[0], None)
-        elif precision == 'bf16x3':
-            w_params, b_params = ctx.param_refs
-            direct = all(ctx.has_bias) and _direct_params(*w_params, *b_params)
-            split = [_x3_layer(w) for w in w_params]
-            dgrad_of = [i for i in range(n_layers) if split[i] and (i > 0 or need_x)]
-            wt3_list = ops.x3_weight_operands([w_params[i] for i in dgrad_of], want_t=tuple(range(len(dgrad_of))))[1]
-            wt3s = dict(zip(dgrad_of, wt3_list))
-            sig = None        # sigmoid outputs whose gradient factor s (1 - s) g still lacks: fused into the next split of g (one pass less)
-            for i in range(n_layers - 1, -1, -1):
-                n, k = ctx.dims[i]
-                a_in, r = (x_in, rows) if i == 0 else (masked_input(i), None)
-                if i == 0 and latent is not None:
-                    dz = latent_grad(g, h=sig)         # a sigmoid factor still owed to g rides in the row sums
-                if not split[i]:                       # a narrow layer: exact fp32 products (see _x3_layer)
-                    grads[2 * i], grads[2 * i + 1] = ops.linear_wgrad_f32(g, a_in, r, n, k, want_bias=ctx.has_bias[i])
-                    if i > 0:
-                        g = unmask(ops.linear_dgrad_f32(g, weights[i], *fed_by(i)), i - 1)
-                    elif need_x:
-                        grad_x = ops.linear_dgrad_f32(g, weights[0], None)
-                    continue
-                need_g3 = i > 0 or need_x
-                kept = ctx.x3_kept[i]
-                if r is None and kept is not None and ops.split3_colsum_ok(n):
-                    # no row map: the gradient is split ONCE, [hi | lo | hi] - the layout its dgrad takes against W^T [hi | hi | lo] - and
-                    # the weight gradient is one launch of that buffer against the FORWARD's split of the layer's input, both read as
-                    # row-interleaved (3 m, ldp) stacks (ops.linear_wgrad_x3_rows); the bias gradient = the exact column sums of the
-                    # fp32 gradient, taken by the split pass.  (Was: gradient and input split again into row-stacked planes.)
-                    g1, colsum = ops.split3([(g, 1, False, 0, sig, True)])[0]
-                    sig = None
-                    g3 = g1
-                    if direct:
-                        ops.linear_wgrad_x3_rows(g1, colsum, kept, n, k, out_w=w_params[i].grad, out_b=b_params[i].grad, accumulate=True)
-                    else:
-                        dw, db = ops.linear_wgrad_x3_rows(g1, colsum if ctx.has_bias[i] else None, kept, n, k)
-                        grads[2 * i], grads[2 * i + 1] = dw, db
-                else:
-                    parts = ops.split3([(g, 2, False, 0, sig), (a_in, 2, False, ctx.x3_extra if i == 0 else 0)] +
-                                       ([(g, 1, False, 0, sig)] if need_g3 else []))
-                    sig = None
-                    g2, a2, g3 = parts[0], parts[1], (parts[2] if need_g3 else None)
-                    if direct:
-                        ops.linear_wgrad_x3(g2, a2, r, m, n, k, out_w=w_params[i].grad, out_b=b_params[i].grad, accumulate=True)
-                    else:
-                        dw, db = ops.linear_wgrad_x3(g2, a2, r, m, n, k)
-                        grads[2 * i], grads[2 * i + 1] = dw, (db if ctx.has_bias[i] else None)
-                if i > 0:
-                    g = unmask(ops.linear_dgrad_x3(g3, m, wt3s[i], k), i - 1)
-                    if acts[i - 1] == ops.ACT_SIGMOID:
-                        if split[i - 1]:
-                            sig = hidden[i - 1]             # layer i - 1 splits g next: the sigmoid gradient rides in that pass
-                        else:
-                            g = ops.sigmoid_grad(g, hidden[i - 1])
-                    elif acts[i - 1] != ops.ACT_NONE:
-                        g = ops.act_grad(g, hidden[i - 1], acts[i - 1])     # Tanh / ReLU: a launch of its own (the split pass knows s (1 - s))
-                elif need_x:
-                    grad_x = ops.linear_dgrad_x3(g3, m, wt3s[0], k)
-        else:
-            g = ops.cast_pad_bf16(g)
-            w_params, b_params = ctx.param_refs
-            direct = all(ctx.has_bias) and _direct_params(*w_params, *b_params)
-            beside = direct and _side_ok(g.device, level=2)
-            front = ctx.spec[6] if len(ctx.spec) > 6 else None
-            extra0 = ctx.spec[2] if len(ctx.spec) > 2 else 0
-            for i in range(n_layers - 1, -1, -1):
-                n, k = ctx.dims[i]
-                a_in, r = (x_in, rows) if i == 0 else (masked_input(i), None)
-                if i == 0 and front is not None:
-                    # dW = [dW_lab | dW_cnt]: the table's part from the per-phone sums of g (every frame of a phone multiplied the same
-                    # table row; the table's columns behind the labels are zero), the counters' part from the same pass over g
-                    # (slabs, reduced into their columns of dW afterwards); db = the column sums of the sums
-                    rows_f, seg_f, feat = front
-                    k_lab, n_tab = k - feat.shape[1], x_in.shape[0]
-                    sums, slabs = ops.segment_sum_feat(g, rows_f, seg_f, n_tab - extra0, g.shape[1], feat, extra=extra0)
-                    if direct:
-                        ops.linear_wgrad_bf16(sums, x_in, None, n_tab, n, k, out_w=w_params[0].grad, out_b=b_params[0].grad, accumulate=True)
-                        ops.feat_wgrad_reduce(slabs, feat.shape[1], sums.shape[1], n, w_params[0].grad, k_lab)
-                    else:
-                        dw, db = ops.linear_wgrad_bf16(sums, x_in, None, n_tab, n, k, want_bias=ctx.has_bias[0])
-                        ops.feat_wgrad_reduce(slabs, feat.shape[1], sums.shape[1], n, dw, k_lab)
-                        grads[0], grads[1] = dw, db
-                    continue
-                if i == 0 and latent is not None:
-                    dz = latent_grad(g)                # g: the padded bf16 gradient, its sigmoid factor applied by the dgrad before
-                if beside and (i > 0 or need_x):
-                    # the weight gradient feeds only the update: beside the dgrad chain (the last layer of the pass has no chain left
-                    # on this node, its weight gradient stays in line)
-                    with _Beside(g.device, g, a_in, r):
-                        _linear_grads_direct(w_params[i], b_params[i], g, a_in, r, m, n, k)
-                elif direct:
-                    _linear_grads_direct(w_params[i], b_params[i], g, a_in, r, m, n, k)
-                else:
-                    dw, db = ops.linear_wgrad_bf16(g, a_in, r, m, n, k, want_bias=ctx.has_bias[i])
-                    grads[2 * i], grads[2 * i + 1] = dw, db
-                if i > 0:
-                    wt = _w_t(w_params[i])
-                    h, h_act = fed_by(i)
-                    g = unmask(ops.linear_dgrad_bf16(g, m, n, wt, k, h, act=h_act), i - 1)
-                elif need_x:
-                    wt = _w_t(w_params[0])
-                    grad_x = ops.linear_dgrad_bf16(g, m, n, wt, k, None, out_f32=True)
-                    if grad_x.shape[1] != k:
-                        grad_x = grad_x[:, :k].contiguous()
-        if need_x and scatter_to is not None:
+        run = _stack_bwd_f32 if precision == 'fp32' else _stack_bwd_x3 if precision == 'bf16x3' else _stack_bwd_bf16
+        grads = [None] * (2 * n_layers)
+        grad_x, dz = run(ctx, g, x_in, rows, weights, hidden, grads)
+        if ctx.needs_input_grad[1] and scatter_to is not None:
             # the input rows were gathered (distinct rows): their gradients go back where they came from, all other rows get zeros
             grad_x = ops.scatter_rows(grad_x, scatter_to, ctx.n_src)
-        return (None, grad_x, None) + tuple(grads) + ((dz,) if latent is not None else ())
+        return (None, grad_x, None) + tuple(grads) + ((dz,) if ctx.latent is not None else ())
+
+
+def _stack_fwd_f32(ctx, spec, x2d, rows, scatter_to, m, weights, biases, pre_cast, k_in):
+    """LinearStackFn.forward, precision 'fp32': exact-fp32 tile programs, fp32 activations."""
+    drop, hidden = ctx.drop, []
+    if spec.extra:
+        x2d = torch.cat((x2d, x2d.new_zeros((spec.extra, x2d.shape[1]))))
+    a, r = x2d, rows
+    for i, act in enumerate(spec.acts):
+        w = ops._require(weights[i], torch.float32, 'weight')
+        a = ops.linear_fwd_f32(a, r, m, w, biases[i], act)
+        r = None
+        hidden.append(a)
+        if drop is not None:
+            a = drop.apply(a, i)
+    ctx.save_for_backward(x2d, rows, scatter_to, *weights, *hidden)
+    return a
+
+
+def _stack_fwd_x3(ctx, spec, x2d, rows, scatter_to, m, weights, biases, pre_cast, k_in):
+    """LinearStackFn.forward, precision 'bf16x3': split-bf16 - fp32 activations as in fp32 mode, every product as ONE bf16 GEMM over
+    split operands (csrc/split3.hip); the narrow layers (_x3_layer) on the exact-fp32 tile programs."""
+    acts, extra, drop, hidden, n_layers = spec.acts, spec.extra, ctx.drop, [], len(spec.acts)
+    split = [_x3_layer(w) for w in weights]
+    if extra and not split[0]:
+        x2d, extra = torch.cat((x2d, x2d.new_zeros((extra, x2d.shape[1])))), 0
+    a, r = x2d, rows
+    w3s = ops.x3_weight_operands([w for w, s in zip(weights, split) if s])[0]
+    kept = [None] * n_layers              # the activation splits: the backward's weight gradients multiply with them again
+    for i in range(n_layers):
+        if split[i]:
+            # the zero rows behind a phone table (what padding frames gather) are rows of the split operand, never of an fp32 copy
+            a3 = ops.split3([(a, 0, False, extra if i == 0 else 0)])[0]
+            kept[i] = a3
+            a = ops.linear_fwd_x3(a3, r, m, w3s.pop(0), biases[i], weights[i].shape[0], acts[i])
+        else:
+            a = ops.linear_fwd_f32(a, r, m, ops._require(weights[i], torch.float32, 'weight'), biases[i], acts[i])
+        r = None
+        hidden.append(a)
+        if drop is not None:
+            a = drop.apply(a, i)
+    ctx.save_for_backward(x2d, rows, scatter_to, *weights, *hidden)
+    ctx.param_refs, ctx.x3_extra, ctx.x3_kept = (list(weights), list(biases)), extra, kept
+    return a
+
+
+def _stack_fwd_bf16(ctx, spec, x2d, rows, scatter_to, m, weights, biases, pre_cast, k_in):
+    """LinearStackFn.forward, precision 'bf16': bf16 operands and activations (padded buffers), fp32 accumulate, fp32 output."""
+    acts, extra, shadow, front, drop, hidden = spec.acts, spec.extra, spec.shadow, spec.front, ctx.drop, []
+    rows_k = rows                                  # the row map the kernels' loaders apply (None once the input is packed)
+    if scatter_to is not None:
+        if pre_cast:
+            raise ValueError('LinearStackFn: a gathered input that needs a gradient must be fp32')
+        # pack and cast in one pass: the bf16 operand holds exactly the gathered rows
+        a, rows_k = ops.gather_rows(x2d, rows, out_bf16=True, ld=ops.pad_ld(k_in)), None
+    elif (shadow is not None and not pre_cast and not extra and shadow.dtype == torch.bfloat16 and shadow.is_contiguous()
+          and tuple(shadow.shape) == (x2d.shape[0], ops.pad_ld(k_in)) and k_in == ops.pad_ld(k_in)):
+        a = shadow
+    else:
+        # (a phone table in front of frame features is padded to the layer's full input width: its weight gradient then
+        # spans all of dW, with zeros in the features' columns - ops.feat_wgrad_reduce fills those)
+        a = x2d if pre_cast else ops.cast_pad_bf16(x2d, ld=ops.pad_ld(weights[0].shape[1]) if front is not None else None,
+                                                   extra_rows=extra)
+    a0, r = a, rows_k
+    # bf16 operands of the weights: copies that live on the parameters, refreshed by the optimiser's update kernel
+    # (ops.param_shadows) - no cast launch per layer and step
+    w_bfs = _w_plain(weights)
+    for i in range(len(acts)):
+        n, k = weights[i].shape
+        last = i == len(acts) - 1
+        if i == 0 and front is not None:
+            a = ops.phone_concat_layer(a0, k_in, front[0], front[2], weights[0], w_bfs[0], biases[0], n, acts[0], out_f32=last)
+        else:
+            a = ops.linear_fwd_bf16(a, r, m, k, w_bfs[i], biases[i], n, acts[i], out_f32=last, rows_runs=spec.rows_runs)
+        r = None
+        hidden.append(a)
+        if drop is not None and not last:
+            a = drop.apply(a, i)                 # over the padded bf16 buffer: zero padding stays zero
+    n_last = weights[-1].shape[0]
+    out = hidden[-1]
+    if out.shape[1] != n_last:
+        out = out[:, :n_last].contiguous()
+    unmasked = out                               # what a trailing sigmoid's gradient reads in backward
+    if drop is not None:
+        out = drop.apply(out, len(acts) - 1)
+    ctx.save_for_backward(a0, rows_k, scatter_to, *weights, *hidden[:-1], unmasked)
+    ctx.param_refs = (list(weights), list(biases))        # the Parameter objects (their .grad views, their shadows)
+    return out
+
+
+def _masked_input(hidden, drop, i):
+    """The operand layer i multiplied in the forward pass: the saved activation of layer i - 1 under its dropout mask (regenerated)."""
+    return hidden[i - 1] if drop is None else drop.apply(hidden[i - 1], i - 1)
+
+
+def _unmask(g, drop, i):
+    """A gradient with respect to a MASKED activation -> with respect to the activation: the same mask (it commutes with the
+    sigmoid gradient the dgrad kernels fuse, which reads the unmasked activation)."""
+    return g if drop is None else drop.apply(g, i, inplace=True)
+
+
+def _fed_by(hidden, acts, i):
+    """(output, activation) of the layer feeding layer i: what the dgrad epilogue multiplies f' from."""
+    return (hidden[i - 1], acts[i - 1]) if acts[i - 1] != ops.ACT_NONE else (None, ops.ACT_NONE)
+
+
+def _latent_grad(ctx, weights, g0, h=None):
+    """dz = (per-item row sums of the first layer's pre-activation gradient) . W_z"""
+    col0, per_item, n_items, zdim = ctx.latent
+    sums = ops.rows_sum_per_item(g0, n_items, per_item, n=ctx.dims[0][0], h=h)
+    return ops.linear_dgrad_f32(sums, weights[0][:, col0:col0 + zdim].contiguous(), None)
+
+
+def _layer_bwd_f32(ctx, i, g, a_in, r, weights, hidden, grads):
+    """Layer i's backward on exact-fp32 products (fp32 mode, and the narrow layers of 'bf16x3': see _x3_layer): the weight gradient
+    into ``grads``, then the gradient handed down - through the feeding layer's activation and dropout mask - or, at layer 0, the
+    input's.  Returns (g for layer i - 1, grad_x)."""
+    n, k = ctx.dims[i]
+    grads[2 * i], grads[2 * i + 1] = ops.linear_wgrad_f32(g, a_in, r, n, k, want_bias=ctx.has_bias[i])
+    if i > 0:
+        return _unmask(ops.linear_dgrad_f32(g, weights[i], *_fed_by(hidden, ctx.spec.acts, i)), ctx.drop, i - 1), None
+    return g, (ops.linear_dgrad_f32(g, weights[0], None) if ctx.needs_input_grad[1] else None)
+
+
+def _stack_bwd_f32(ctx, g, x_in, rows, weights, hidden, grads):
+    """LinearStackFn.backward, precision 'fp32'; ``g`` = the gradient of the last layer's pre-activation.  Fills ``grads`` (the
+    parameters') and returns (grad_x, dz), as its 'bf16x3' and 'bf16' counterparts below do."""
+    grad_x = dz = None
+    for i in range(len(ctx.spec.acts) - 1, -1, -1):
+        a_in, r = (x_in, rows) if i == 0 else (_masked_input(hidden, ctx.drop, i), None)
+        if i == 0 and ctx.latent is not None:
+            dz = _latent_grad(ctx, weights, g)
+        g, grad_x = _layer_bwd_f32(ctx, i, g, a_in, r, weights, hidden, grads)
+    return grad_x, dz
+
+
+def _stack_bwd_x3(ctx, g, x_in, rows, weights, hidden, grads):
+    """LinearStackFn.backward, precision 'bf16x3'."""
+    acts, drop, m, need_x = ctx.spec.acts, ctx.drop, ctx.m, ctx.needs_input_grad[1]
+    n_layers, grad_x, dz = len(acts), None, None
+    w_params, b_params = ctx.param_refs
+    direct = all(ctx.has_bias) and _direct_params(*w_params, *b_params)
+    split = [_x3_layer(w) for w in w_params]
+    dgrad_of = [i for i in range(n_layers) if split[i] and (i > 0 or need_x)]
+    wt3_list = ops.x3_weight_operands([w_params[i] for i in dgrad_of], want_t=tuple(range(len(dgrad_of))))[1]
+    wt3s = dict(zip(dgrad_of, wt3_list))
+    sig = None        # sigmoid outputs whose gradient factor s (1 - s) g still lacks: fused into the next split of g (one pass less)
+    for i in range(n_layers - 1, -1, -1):
+        n, k = ctx.dims[i]
+        a_in, r = (x_in, rows) if i == 0 else (_masked_input(hidden, drop, i), None)
+        if i == 0 and ctx.latent is not None:
+            dz = _latent_grad(ctx, weights, g, h=sig)         # a sigmoid factor still owed to g rides in the row sums
+        if not split[i]:                       # a narrow layer: exact fp32 products (see _x3_layer)
+            g, grad_x = _layer_bwd_f32(ctx, i, g, a_in, r, weights, hidden, grads)
+            continue
+        need_g3 = i > 0 or need_x
+        kept = ctx.x3_kept[i]
+        if r is None and kept is not None and ops.split3_colsum_ok(n):
+            # no row map: the gradient is split ONCE, [hi | lo | hi] - the layout its dgrad takes against W^T [hi | hi | lo] - and
+            # the weight gradient is one launch of that buffer against the FORWARD's split of the layer's input, both read as
+            # row-interleaved (3 m, ldp) stacks (ops.linear_wgrad_x3_rows); the bias gradient = the exact column sums of the
+            # fp32 gradient, taken by the split pass.  (Was: gradient and input split again into row-stacked planes.)
+            g1, colsum = ops.split3([(g, 1, False, 0, sig, True)])[0]
+            sig = None
+            g3 = g1
+            if direct:
+                ops.linear_wgrad_x3_rows(g1, colsum, kept, n, k, out_w=w_params[i].grad, out_b=b_params[i].grad, accumulate=True)
+            else:
+                grads[2 * i], grads[2 * i + 1] = ops.linear_wgrad_x3_rows(g1, colsum if ctx.has_bias[i] else None, kept, n, k)
+        else:
+            parts = ops.split3([(g, 2, False, 0, sig), (a_in, 2, False, ctx.x3_extra if i == 0 else 0)] +
+                               ([(g, 1, False, 0, sig)] if need_g3 else []))
+            sig = None
+            g2, a2, g3 = parts[0], parts[1], (parts[2] if need_g3 else None)
+            if direct:
+                ops.linear_wgrad_x3(g2, a2, r, m, n, k, out_w=w_params[i].grad, out_b=b_params[i].grad, accumulate=True)
+            else:
+                dw, db = ops.linear_wgrad_x3(g2, a2, r, m, n, k)
+                grads[2 * i], grads[2 * i + 1] = dw, (db if ctx.has_bias[i] else None)
+        if i > 0:
+            g = _unmask(ops.linear_dgrad_x3(g3, m, wt3s[i], k), drop, i - 1)
+            if acts[i - 1] == ops.ACT_SIGMOID:
+                if split[i - 1]:
+                    sig = hidden[i - 1]             # layer i - 1 splits g next: the sigmoid gradient rides in that pass
+                else:
+                    g = ops.sigmoid_grad(g, hidden[i - 1])
+            elif acts[i - 1] != ops.ACT_NONE:
+                g = ops.act_grad(g, hidden[i - 1], acts[i - 1])     # Tanh / ReLU: a launch of its own (the split pass knows s (1 - s))
+        elif need_x:
+            grad_x = ops.linear_dgrad_x3(g3, m, wt3s[0], k)
+    return grad_x, dz
+
+
+def _stack_bwd_bf16(ctx, g, x_in, rows, weights, hidden, grads):
+    """LinearStackFn.backward, precision 'bf16'."""
+    acts, drop, m, need_x = ctx.spec.acts, ctx.drop, ctx.m, ctx.needs_input_grad[1]
+    n_layers, grad_x, dz = len(acts), None, None
+    g = ops.cast_pad_bf16(g)
+    w_params, b_params = ctx.param_refs
+    direct = all(ctx.has_bias) and _direct_params(*w_params, *b_params)
+    beside = direct and _side_ok(g.device, level=2)
+    front, extra0 = ctx.spec.front, ctx.spec.extra
+    for i in range(n_layers - 1, -1, -1):
+        n, k = ctx.dims[i]
+        a_in, r = (x_in, rows) if i == 0 else (_masked_input(hidden, drop, i), None)
+        if i == 0 and front is not None:
+            # dW = [dW_lab | dW_cnt]: the table's part from the per-phone sums of g (every frame of a phone multiplied the same
+            # table row; the table's columns behind the labels are zero), the counters' part from the same pass over g
+            # (slabs, reduced into their columns of dW afterwards); db = the column sums of the sums
+            rows_f, seg_f, feat = front
+            k_lab, n_tab = k - feat.shape[1], x_in.shape[0]
+            sums, slabs = ops.segment_sum_feat(g, rows_f, seg_f, n_tab - extra0, g.shape[1], feat, extra=extra0)
+            if direct:
+                ops.linear_wgrad_bf16(sums, x_in, None, n_tab, n, k, out_w=w_params[0].grad, out_b=b_params[0].grad, accumulate=True)
+                ops.feat_wgrad_reduce(slabs, feat.shape[1], sums.shape[1], n, w_params[0].grad, k_lab)
+            else:
+                dw, db = ops.linear_wgrad_bf16(sums, x_in, None, n_tab, n, k, want_bias=ctx.has_bias[0])
+                ops.feat_wgrad_reduce(slabs, feat.shape[1], sums.shape[1], n, dw, k_lab)
+                grads[0], grads[1] = dw, db
+            continue
+        if i == 0 and ctx.latent is not None:
+            dz = _latent_grad(ctx, weights, g)     # g: the padded bf16 gradient, its sigmoid factor applied by the dgrad before
+        if beside and (i > 0 or need_x):
+            # the weight gradient feeds only the update: beside the dgrad chain (the last layer of the pass has no chain left
+            # on this node, its weight gradient stays in line)
+            with _Beside(g.device, g, a_in, r):
+                _linear_grads_direct(w_params[i], b_params[i], g, a_in, r, m, n, k)
+        elif direct:
+            _linear_grads_direct(w_params[i], b_params[i], g, a_in, r, m, n, k)
+        else:
+            grads[2 * i], grads[2 * i + 1] = ops.linear_wgrad_bf16(g, a_in, r, m, n, k, want_bias=ctx.has_bias[i])
+        if i > 0:
+            h, h_act = _fed_by(hidden, acts, i)
+            g = _unmask(ops.linear_dgrad_bf16(g, m, n, _w_t(w_params[i]), k, h, act=h_act), drop, i - 1)
+        elif need_x:
+            grad_x = ops.linear_dgrad_bf16(g, m, n, _w_t(w_params[0]), k, None, out_f32=True)
+            if grad_x.shape[1] != k:
+                grad_x = grad_x[:, :k].contiguous()
+    return grad_x, dz
 
 
 class RepeatTableRowsFn(torch.autograd.Function):
@@ -887,10 +917,24 @@ def _wgrad_into(mode, opt, w_param, b_param, g, a_in, rows, m, n, k):
         ops.linear_wgrad_bf16(g, a_in, rows, m, n, k, out_w=w_param.grad, out_b=b_param.grad, accumulate=True)
 
 
+class LinearStackMSESpec(typing.NamedTuple):
+    """What a ``LinearStackMSEFn`` node runs, apart from its tensors: the opaque first argument of ``apply``.  acts: one ops.ACT_* per layer.
+    maps        (seg, rows with -1 -> the first extra row): the phone-rate maps that came with the frame map (None: ops.segment_bounds).
+    table_bf16  the loader's bf16 copy of the phone table (data.add_bf16_table).
+    phone_rate  the caller's order of operations (utils.upsample_to_repetitions(phone_rate=); None = the process default).
+    pending     the utils.UpsampledSequence whose frame map no kernel has built yet (``rows`` is None then): the phone-rate step
+                builds it in the launch of its own front (ops.phone_front); every other path asks the sequence for it."""
+    acts: tuple
+    maps: typing.Optional[tuple] = None
+    table_bf16: typing.Optional[torch.Tensor] = None
+    phone_rate: typing.Optional[bool] = None
+    pending: typing.Optional[object] = None
+
+
 class LinearStackMSEFn(torch.autograd.Function):
     """bf16 Linear/Sigmoid stack ending in ... -> 128 -> 32 -> 1 TOGETHER with the masked MSE (losses.py:29-51).
 
-    forward(ctx, acts, x2d, rows, target (B,T,1), seq_len, *params) -> (loss, pred (B,T,1)).
+    forward(ctx, spec, x2d, rows, target (B,T,1), seq_len, *params) -> (loss, pred (B,T,1)); spec = a ``LinearStackMSESpec``.
     Layers up to the 128-wide one run as in LinearStackFn; the last two layers, the loss and their whole backward are ONE
     kernel (mg_f0_tail_bf16) that leaves dL/d(pre-activation of the 128-wide layer) for the remaining backward; when the 128-wide
     layer is 512 -> 128 + sigmoid it runs inside that kernel too (mg_f0_l2tail_bf16) and its output is never written.
@@ -898,17 +942,8 @@ class LinearStackMSEFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, acts, x2d, rows, target, seq_len, *params):
-        acts_in = acts
-        maps = table_bf16 = pending = order = None
-        if len(acts) in (2, 3, 4) and not isinstance(acts[0], int):  # (acts, maps[, table[, phone_rate]]): phone-rate maps that came with
-            acts, maps = acts[0], acts[1]                            # the frame map, the loader's bf16 copy of the phone table
-            table_bf16 = acts_in[2] if len(acts_in) >= 3 else None   # (data.add_bf16_table), and the caller's order of operations
-            order = acts_in[3] if len(acts_in) == 4 else None        # (utils.upsample_to_repetitions(phone_rate=); None = default)
-            if maps is not None and not isinstance(maps, tuple):
-                # an utils.UpsampledSequence whose frame map no kernel has built yet (rows is None): the phone-rate step builds it
-                # in the launch of its own front (ops.phone_front); every other path asks the sequence for it now
-                pending, maps = maps, None
+    def forward(ctx, spec, x2d, rows, target, seq_len, *params):
+        acts, maps, table_bf16, order, pending = spec
         n_layers = len(acts)
         weights = [params[2 * i] for i in range(n_layers)]
         biases = [params[2 * i + 1] for i in range(n_layers)]
@@ -916,8 +951,8 @@ class LinearStackMSEFn(torch.autograd.Function):
         target = ops._require(target, torch.float32, 'targets')
         b, t = target.shape[0], target.shape[1]
         m = b * t
-        n_layers_lead = n_layers - 2
-        front = (pending is not None and pending.t_cap == t and pending.dur.shape[0] == b and n_layers_lead == 2 and
+        lead = n_layers - 2
+        front = (pending is not None and pending.t_cap == t and pending.dur.shape[0] == b and lead == 2 and
                  ops.phone_rate_table_ok(x2d.shape[0], m, weights[0].shape[0], weights[1].shape[0], acts[0], order) and
                  ops.phone_front_ok(b, pending.dur.shape[1], t, ops.PHONE_RATE_EXTRA))
         if pending is not None and not front:
@@ -925,7 +960,9 @@ class LinearStackMSEFn(torch.autograd.Function):
         if (m if front else rows.numel() if rows is not None else x2d.shape[0]) != m:
             raise ValueError('prediction rows (%d) and target rows (%d) differ' % (
                 rows.numel() if rows is not None else x2d.shape[0], m))
-        lead = n_layers - 2
+        ctx.acts, ctx.m, ctx.lead = acts, m, lead
+        ctx.dims = [(w.shape[0], w.shape[1]) for w in weights]
+        ctx.params = list(params)
         # bf16 operands of the leading layers: copies that live on the parameters and are kept current by the optimiser's update
         # kernel (ops.param_shadows) - a training step launches no weight cast
         w_bf, w_t = ops.param_shadows(weights[:lead], want_t=tuple(range(1, lead)))
@@ -963,11 +1000,7 @@ class LinearStackMSEFn(torch.autograd.Function):
                 else:
                     a = ops.linear_fwd_bf16(a, None, n_rows, k, w_bf[i], biases[i], n, acts[i])
                 hidden.append(a)
-            sizes = [p.numel() for p in params]
-            offsets = [0]
-            for sz in sizes[:-1]:
-                offsets.append(offsets[-1] + sz)
-            flat = torch.empty(sum(sizes) + 1, dtype=torch.float32, device=x2d.device)
+            offsets, flat = _flat_grads_and_loss(params, x2d.device)
             if not front:
                 ybar, weight, partials = ops.phone_target_stats(target.reshape(-1), rows, seg, seq_len, b, t, n_table, extra)
             ctx.deferred_tail = None
@@ -982,7 +1015,6 @@ class LinearStackMSEFn(torch.autograd.Function):
                                                 rows, (partials, n_table, extra), defer=defer)
                 pred, loss, dz2 = res[:3]
                 ctx.deferred_tail = res[3] if defer else None
-                pred = pred.view(b, t, 1)
             else:
                 if l2tail:
                     pred_rows, loss, dz2 = ops.f0_l2tail_rows(hidden[-1], w_bf[lead - 1], biases[lead - 1], weights[lead], biases[lead],
@@ -990,15 +1022,8 @@ class LinearStackMSEFn(torch.autograd.Function):
                 else:
                     pred_rows, loss, dz2 = ops.f0_tail_rows(hidden[-1], weights[lead], biases[lead], weights[lead + 1], biases[lead + 1],
                                                             ybar, weight, flat[offsets[2 * lead]:])
-                pred = ops.expand_column(pred_rows, rows, loss_const=(partials, n_table, extra, loss)).view(b, t, 1)
-            ctx.acts, ctx.m, ctx.lead = acts, m, lead
-            ctx.dims = [(w.shape[0], w.shape[1]) for w in weights]
-            ctx.offsets = offsets
-            ctx.params = list(params)
-            ctx.save_for_backward(a0, rows, dz2, flat, *hidden[:lead - 1], *[wt for wt in w_t if wt is not None])
-            ctx.mark_non_differentiable(pred)
-            ctx.set_materialize_grads(False)
-            return loss, pred
+                pred = ops.expand_column(pred_rows, rows, loss_const=(partials, n_table, extra, loss))
+            return _mse_node_done(ctx, offsets, a0, rows, dz2, flat, hidden, w_t, loss, pred.view(b, t, 1))
         if table_bf16 is not None and table_bf16.shape[0] >= x2d.shape[0] and table_bf16.shape[1] == ops.pad_ld(x2d.shape[1]):
             a = table_bf16                                        # rows beyond the phone rows are never indexed by the gather
         else:
@@ -1010,11 +1035,7 @@ class LinearStackMSEFn(torch.autograd.Function):
             a = ops.linear_fwd_bf16(a, r, m, k, w_bf[i], biases[i], n, acts[i], rows_runs=True)      # rows: the upsample frame map
             r = None
             hidden.append(a)
-        sizes = [p.numel() for p in params]
-        offsets = [0]
-        for sz in sizes[:-1]:
-            offsets.append(offsets[-1] + sz)
-        flat = torch.empty(sum(sizes) + 1, dtype=torch.float32, device=x2d.device)    # + 1: the loss (see ops.f0_tail)
+        offsets, flat = _flat_grads_and_loss(params, x2d.device)
         tail_off = offsets[2 * lead]
         ctx.deferred_tail = None
         if l2tail:
@@ -1028,15 +1049,7 @@ class LinearStackMSEFn(torch.autograd.Function):
         else:
             pred, loss, dz2 = ops.f0_tail(hidden[-1], weights[lead], biases[lead], weights[lead + 1], biases[lead + 1],
                                           target.reshape(-1), seq_len, b, t, flat[tail_off:])
-        ctx.acts, ctx.m, ctx.lead = acts, m, lead
-        ctx.dims = [(w.shape[0], w.shape[1]) for w in weights]
-        ctx.offsets = offsets
-        ctx.params = list(params)
-        ctx.save_for_backward(a0, rows, dz2, flat, *hidden[:lead - 1], *[wt for wt in w_t if wt is not None])
-        pred = pred.view(b, t, 1)
-        ctx.mark_non_differentiable(pred)
-        ctx.set_materialize_grads(False)
-        return loss, pred
+        return _mse_node_done(ctx, offsets, a0, rows, dz2, flat, hidden, w_t, loss, pred.view(b, t, 1))
 
     @staticmethod
     def backward(ctx, grad_loss, grad_pred):
@@ -1050,6 +1063,7 @@ class LinearStackMSEFn(torch.autograd.Function):
             return (flat[ctx.offsets[2 * i]:ctx.offsets[2 * i] + n_ * k_].view(n_, k_),
                     flat[ctx.offsets[2 * i + 1]:ctx.offsets[2 * i + 1] + n_])
 
+        no_grads = (None,) * (5 + len(ctx.params))            # spec, x2d, rows, target, seq_len | the parameters (delivered directly)
         mode, opt = _grad_mode(ctx.params, grad_loss)
         tail = getattr(ctx, 'deferred_tail', None)            # forward left the repeated prediction and the tail's slab sum to us
         ctx.deferred_tail = None
@@ -1105,7 +1119,7 @@ class LinearStackMSEFn(torch.autograd.Function):
                     else:
                         ops.slab_reduce(floats[off:], n_slabs, st, cnt, first.grad.reshape(-1).as_strided((cnt,), (1,)), accumulate=True)
                 hand_over_tail_grads()
-                return (None, None, None, None, None) + (None,) * len(params)
+                return no_grads
             if pair and tail is not None and mode == 'defer':
                 # the update kernel sums the tail's slabs itself (one more source of its plan), and its launch's first blocks repeat
                 # the prediction and form the loss (optim.Adam.defer_tail: mg_adam_tail) - measured against riders at the end of the
@@ -1153,7 +1167,7 @@ class LinearStackMSEFn(torch.autograd.Function):
                 n_, k_ = ctx.dims[i - 1]
                 _wgrad_into(mode, opt, params[2 * (i - 1)], params[2 * (i - 1) + 1], g, hidden[i - 2] if i > 1 else a0,
                             None if i > 1 else r0, m_rows, n_, k_)
-            return (None, None, None, None, None) + (None,) * len(params)
+            return no_grads
 
         if tail is not None:                                          # gradients as tensors for autograd: nothing to ride in
             ops.finish_deferred_tail(tail)
@@ -1170,7 +1184,7 @@ class LinearStackMSEFn(torch.autograd.Function):
             ow, ob = grad_slots(0)
             ops.linear_wgrad_bf16(dz0, a0, None, table.shape[0], n0, k0, out_w=ow, out_b=ob)
             grads = _deliver_rest(ctx.params, flat[:flat.numel() - 1], ctx.offsets, grad_loss, early)
-            return (None, None, None, None, None) + tuple(grads)
+            return no_grads[:5] + tuple(grads)
         early = False
         if (lead == 2 and rows is not None and ctx.acts[0] == ops.ACT_SIGMOID and _EARLY_GRADS_HOOK is None and
                 os.environ.get('MORGANA_FUSE_WGRAD2', '1') != '0' and ops.can_fuse_bwd(m, ctx.dims[1][0], ctx.dims[1][1], ctx.dims[0][1], a0.shape[1])):
@@ -1182,7 +1196,7 @@ class LinearStackMSEFn(torch.autograd.Function):
             ops.slab_reduce(floats[off1:], n_slabs, st1, cnt1, flat[ctx.offsets[0]:ctx.offsets[0] + cnt1])
             ops.slab_reduce(floats[off2:], n_slabs, st2, cnt2, flat[ctx.offsets[2]:ctx.offsets[2] + cnt2])
             grads = _deliver_rest(ctx.params, flat[:flat.numel() - 1], ctx.offsets, grad_loss, False)
-            return (None, None, None, None, None) + tuple(grads)
+            return no_grads[:5] + tuple(grads)
         for i in range(lead - 1, -1, -1):
             n, k = ctx.dims[i]
             a_in, r = (a0, rows) if i == 0 else (hidden[i - 1], None)
@@ -1201,7 +1215,25 @@ class LinearStackMSEFn(torch.autograd.Function):
                 h = hidden[i - 1] if ctx.acts[i - 1] != ops.ACT_NONE else None
                 g = ops.linear_dgrad_bf16(g, m, n, w_t[i], k, h, act=ctx.acts[i - 1])
         grads = _deliver_rest(ctx.params, flat[:flat.numel() - 1], ctx.offsets, grad_loss, early)
-        return (None, None, None, None, None) + tuple(grads)
+        return no_grads[:5] + tuple(grads)
+
+
+def _flat_grads_and_loss(params, device):
+    """(offsets, flat): one fp32 buffer for every parameter's gradient in parameter order - ``offsets[j]`` = where parameter j's
+    starts - and one more float behind them: the loss (see ops.f0_tail)."""
+    offsets = [0]
+    for p in params[:-1]:
+        offsets.append(offsets[-1] + p.numel())
+    return offsets, torch.empty(offsets[-1] + params[-1].numel() + 1, dtype=torch.float32, device=device)
+
+
+def _mse_node_done(ctx, offsets, a0, rows, dz2, flat, hidden, w_t, loss, pred):
+    """The end of LinearStackMSEFn.forward at either rate: what its backward reads, and (loss, prediction for reporting)."""
+    ctx.offsets = offsets
+    ctx.save_for_backward(a0, rows, dz2, flat, *hidden[:ctx.lead - 1], *[wt for wt in w_t if wt is not None])
+    ctx.mark_non_differentiable(pred)
+    ctx.set_materialize_grads(False)
+    return loss, pred
 
 
 class F0StackX3Fn(torch.autograd.Function):

@@ -786,7 +786,7 @@ class SequentialWithRecurrent(nn.Sequential):
         if end != len(modules) or len(run) < 3 or precision != 'bf16' or targets.shape[-1] != 1 or any(run.drops):
             return None
         dims = [lin.weight.shape for lin, _ in run]
-        acts = tuple(act for _, act in run)
+        acts = run.acts
         ok = (tuple(dims[-1]) == (1, 32) and tuple(dims[-2]) == (32, 128) and acts[-1] == ops.ACT_NONE and
               all(a == ops.ACT_SIGMOID for a in acts[:-1]) and all(lin.bias is not None for lin, _ in run) and
               all(d[0] % 128 == 0 for d in dims[:-2]))
@@ -827,22 +827,16 @@ class SequentialWithRecurrent(nn.Sequential):
             out, _ = self.forward(input, seq_len=seq_len)
             return losses.mse(out, targets, seq_len), out
         run, acts = fused
-        maps = table = phone_rate = None
         if isinstance(input, UpsampledSequence):
-            phone_rate = input.phone_rate
-            x2d, table = input.source.reshape(-1, input.source.shape[-1]), input.table_bf16
-            if input.pending():
-                rows, maps = None, input               # the stack builds the maps with its own front, or asks ``input.rows`` for them
-            else:
-                rows, maps = input.rows.reshape(-1), input.maps
+            pending = input.pending()          # then the stack builds the maps with its own front, or asks ``input.rows`` for them
+            x2d, rows = input.source.reshape(-1, input.source.shape[-1]), None if pending else input.rows.reshape(-1)
+            spec = F_hip.LinearStackMSESpec(acts, maps=None if pending else input.maps, table_bf16=input.table_bf16,
+                                            phone_rate=input.phone_rate, pending=input if pending else None)
         else:
-            x2d, rows = input.reshape(-1, input.shape[-1]), None
+            x2d, rows, spec = input.reshape(-1, input.shape[-1]), None, F_hip.LinearStackMSESpec(acts)
         if seq_len is not None and seq_len.dtype != torch.int64:
             seq_len = seq_len.long()
-        params = []
-        for lin, _ in run:
-            params += [lin.weight, lin.bias]
-        return F_hip.LinearStackMSEFn.apply((acts, maps, table, phone_rate), x2d, rows, targets, seq_len, *params)
+        return F_hip.LinearStackMSEFn.apply(spec, x2d, rows, targets, seq_len, *run.params())
 
     def _fused_x3_params(self, input, targets, seq_len, precision):
         """The eight parameters of the stack when it is the README F0Model's (... -> 512 -> 128 -> 32 -> 1, sigmoids between, README.rst:65-73)
@@ -862,29 +856,30 @@ class SequentialWithRecurrent(nn.Sequential):
                 or not ops.phone_rate_choice(input.phone_rate)
                 or not ops.x3_step_ok(n_src, m, lin1.weight.shape[1], lin1.weight.shape[0], lin2.weight.shape[0])):
             return None
-        params = []
-        for lin, _ in run:
-            params += [lin.weight, lin.bias]
-        return params
+        return run.params()
+
+    @staticmethod
+    def _phone_rate_rows(input, targets, seq_len):
+        """(n_src, m): the phone rows and the frame rows of an ``UpsampledSequence`` input whose loss may be taken at phone rate - the
+        caller gave ``seq_len``, the targets are (B, T, 1) with the input's B and T, and there are several frames per phone
+        (ops.phone_rate_gru_ok, for the order of operations the input carries); else None."""
+        if (not isinstance(input, UpsampledSequence) or seq_len is None or targets.ndim != 3 or targets.shape[2] != 1
+                or tuple(targets.shape[:2]) != tuple(input.shape[:2])):
+            return None
+        n_src, m = input.source.shape[0] * input.source.shape[1], input.shape[0] * input.shape[1]
+        return (n_src, m) if ops.phone_rate_gru_ok(n_src, m, 8, input.phone_rate) else None
 
     def _phone_rate_f32_tail(self, input, targets, seq_len, precision):
         """(pre-activations of the 128-wide layer on the phone rows (B * P + extra, 128), Linear(128, 32), Linear(32, 1)) when the whole
         container is Linear / Sigmoid layers ending in ``-> 128 -> Sigmoid -> 32 -> Sigmoid -> 1`` on an ``UpsampledSequence`` at
         phone rate, exact-fp32 modes, (B, T, 1) targets; else None."""
         found = self._readme_tail(targets, precision)
-        if (found is None or not isinstance(input, UpsampledSequence) or seq_len is None
-                or tuple(targets.shape[:2]) != tuple(input.shape[:2])):
+        if found is None or self._phone_rate_rows(input, targets, seq_len) is None:
             return None
         run, lin3, lin4 = found
-        n_src = input.source.shape[0] * input.source.shape[1]
-        if not ops.phone_rate_gru_ok(n_src, input.shape[0] * input.shape[1], 8, input.phone_rate):
-            return None
-        params = []
-        for lin, _ in run[:-2]:
-            params += [lin.weight, lin.bias]
-        acts = tuple(act for _, act in run[:-3]) + (ops.ACT_NONE,)          # the 128-wide layer's sigmoid is taken by the tail kernel
-        spec = (acts, precision, ops.PHONE_RATE_EXTRA)
-        z2 = F_hip.LinearStackFn.apply(spec, input.source.reshape(-1, input.source.shape[-1]), None, *params)
+        acts = run.acts[:-3] + (ops.ACT_NONE,)          # the 128-wide layer's sigmoid is taken by the tail kernel
+        spec = F_hip.LinearStackSpec(acts, precision, extra=ops.PHONE_RATE_EXTRA)
+        z2 = F_hip.LinearStackFn.apply(spec, input.source.reshape(-1, input.source.shape[-1]), None, *run.params(-2))
         return z2, lin3, lin4
 
     def _readme_tail(self, targets, precision):
@@ -911,40 +906,81 @@ class SequentialWithRecurrent(nn.Sequential):
             return None
         run, lin3, lin4 = found
         if isinstance(input, UpsampledSequence):
-            n_src = input.source.shape[0] * input.source.shape[1]
-            if seq_len is not None and ops.phone_rate_gru_ok(n_src, input.shape[0] * input.shape[1], 8, input.phone_rate):
+            if self._phone_rate_rows(input, targets, seq_len) is not None:
                 return None                                # the phone-rate form takes it
             x2d, rows = input.source.reshape(-1, input.source.shape[-1]), input.rows.reshape(-1)
         elif torch.is_tensor(input) and input.ndim == 3:
             x2d, rows = input.reshape(-1, input.shape[-1]), None
         else:
             return None
-        params = []
-        for lin, _ in run[:-2]:
-            params += [lin.weight, lin.bias]
-        acts = tuple(act for _, act in run[:-3]) + (ops.ACT_NONE,)
-        spec = (acts, precision, 0, rows is not None, None)
-        z2 = F_hip.LinearStackFn.apply(spec, x2d, rows, *params)
+        spec = F_hip.LinearStackSpec(run.acts[:-3] + (ops.ACT_NONE,), precision, rows_runs=rows is not None)
+        z2 = F_hip.LinearStackFn.apply(spec, x2d, rows, *run.params(-2))
         return z2, lin3, lin4
 
     def _phone_rate_table(self, input, targets, seq_len, precision):
         """The (B * P + extra, 1) table of per-phone predictions when the whole container is one Linear / Sigmoid run on an
         ``UpsampledSequence`` at phone rate with a one-column output and (B, T, 1) targets; else None."""
         modules = list(self._modules.values())
-        if (not isinstance(input, UpsampledSequence) or seq_len is None or not modules or type(modules[0]) is not nn.Linear
-                or precision not in ('fp32', 'bf16x3') or targets.ndim != 3 or targets.shape[2] != 1
-                or tuple(targets.shape[:2]) != tuple(input.shape[:2])):
+        if (self._phone_rate_rows(input, targets, seq_len) is None or not modules or type(modules[0]) is not nn.Linear
+                or precision not in ('fp32', 'bf16x3')):
             return None
         end, run = self._linear_run(modules, 0)
-        n_src = input.source.shape[0] * input.source.shape[1]
-        if (end != len(modules) or any(run.drops) or run[-1][0].weight.shape[0] != 1
-                or not ops.phone_rate_gru_ok(n_src, input.shape[0] * input.shape[1], 8, input.phone_rate)):
+        if end != len(modules) or any(run.drops) or run[-1][0].weight.shape[0] != 1:
             return None
-        params = []
-        for lin, _ in run:
-            params += [lin.weight, lin.bias]
-        spec = (tuple(act for _, act in run), precision, ops.PHONE_RATE_EXTRA)
-        return F_hip.LinearStackFn.apply(spec, input.source.reshape(-1, input.source.shape[-1]), None, *params)
+        spec = F_hip.LinearStackSpec(run.acts, precision, extra=ops.PHONE_RATE_EXTRA)
+        return F_hip.LinearStackFn.apply(spec, input.source.reshape(-1, input.source.shape[-1]), None, *run.params())
+
+    def _forward_linear_run(self, input, run, end, modules, precision, seq_len, layout, zero_padded):
+        """One Linear run (``modules[end]`` follows it) as one ``functional.LinearStackFn`` node on whatever ``input`` is; returns the
+        new input.  Every arm builds the node's operand and the fields of its spec, applies it and shapes the 2-D result; the order
+        in which the arms are tested decides which one an input takes."""
+        params, drop = run.params(), run.drop_spec()
+
+        def node(x2d, rows=None, *more, **fields):
+            return F_hip.LinearStackFn.apply(F_hip.LinearStackSpec(run.acts, precision, **fields), x2d, rows, *params, *more)
+
+        def frames(out, lead=input.shape[:2]):
+            return out.view(*lead, out.shape[-1])
+
+        if (zero_padded and layout is not None and torch.is_tensor(input) and input.ndim == 3 and
+                tuple(input.shape[:2]) == (layout.b, layout.t) and layout.worthwhile_for_rows()):
+            # packed frames: the run's GEMMs take sum_b T_b + 1 rows instead of B * T; the first layer's loader (fp32) or one
+            # gather + cast pass (bf16) packs, ``layout.unpack`` restores (B, T, .) with the representative row on the padding
+            return layout.unpack(node(input.reshape(-1, input.shape[-1]), layout.rows, drop=drop))
+        if isinstance(input, UpsampledSequence):
+            nxt = modules[end] if end < len(modules) else None
+            n_src, source2d = input.source.shape[0] * input.source.shape[1], input.source.reshape(-1, input.source.shape[-1])
+            if (isinstance(nxt, RecurrentCuDNNWrapper) and nxt._hip_gru()
+                    and seq_len is not None and drop is None               # a frame's dropout mask is its own: no phone-rate form
+                    and ops.phone_rate_gru_ok(n_src, input.rows.numel(), run[-1][0].weight.shape[0], input.phone_rate)):
+                # Linear / Sigmoid commute with the row repetition of the upsample: run them on the phone rows (+ zero rows for
+                # the padding frames) and hand the GRU wrapper a table + row map; it repeats the rows of its own input projection
+                return PhoneTable(node(source2d, extra=ops.PHONE_RATE_EXTRA), input.rows, n_src, maps=input.phone_maps())
+            if end == len(modules) and drop is None and ops.phone_rate_gru_ok(n_src, input.rows.numel(), 8, input.phone_rate):
+                # the stack ends in this run and sees nothing but the repeated phone rows: every layer commutes with the
+                # repetition, so the run works on the phone rows (+ zero rows for padding frames) and its OUTPUT is repeated
+                table = node(source2d, extra=ops.PHONE_RATE_EXTRA)
+                seg, rows_mapped = input.phone_maps()
+                return frames(F_hip.RepeatTableRowsFn.apply(table, rows_mapped, seg, n_src))
+            # rows here is the frame map of upsample_to_repetitions: runs of equal indices (a hint for the layer-1 loader)
+            return frames(node(source2d, input.rows.reshape(-1), rows_runs=True, drop=drop))
+        if isinstance(input, UpsampledConcat):
+            up = input.upsampled
+            if (precision == 'bf16' and CONCAT_PHONE_RATE and input.latent is None and input.frame_feature.shape[-1] <= 16
+                    and ops.phone_rate_gru_ok(up.source.shape[0] * up.source.shape[1], up.rows.numel(), 8, up.phone_rate)):
+                # cat(repeated phone rows, frame counters) (models/RNN_SPSS.py:76-81): W = [W_lab | W_cnt], the lab part of the
+                # first layer commutes with the repetition and runs once per phone, the counters' part per frame
+                seg, rows_mapped = up.phone_maps()
+                feat = input.frame_feature.reshape(-1, input.frame_feature.shape[-1])
+                return frames(node(up.source.reshape(-1, up.source.shape[-1]), extra=ops.PHONE_RATE_EXTRA, drop=drop,
+                                   front=(rows_mapped.reshape(-1), seg, feat.contiguous())))
+            if input.latent is not None:
+                # [labels | counters | z of the item] in one gather pass; z's gradient comes from the run's latent entry
+                return frames(node(input.operand(precision == 'bf16'), None, input.latent, drop=drop, latent=input.latent_entry()))
+            return frames(node(input.operand(precision == 'bf16'), drop=drop))
+        shadow = bf16_copy_of(input) if (torch.is_tensor(input) and precision == 'bf16') else None
+        shadow = shadow.view(-1, shadow.shape[-1]) if shadow is not None else None
+        return frames(node(input.reshape(-1, input.shape[-1]), drop=drop, shadow=shadow), input.shape[:-1])
 
     def forward(self, input, hiddens=None, seq_len=None, max_len=None, layout=None):
         """``max_len`` (not in the reference) is handed to the recurrent wrappers: see ``RecurrentCuDNNWrapper.forward``.
@@ -962,93 +998,8 @@ class SequentialWithRecurrent(nn.Sequential):
             module = modules[i]
             if type(module) is nn.Linear:
                 end, run = self._linear_run(modules, i)
-                if (zero_padded and layout is not None and torch.is_tensor(input) and input.ndim == 3 and
-                        tuple(input.shape[:2]) == (layout.b, layout.t) and layout.worthwhile_for_rows()):
-                    # packed frames: the run's GEMMs take sum_b T_b + 1 rows instead of B * T; the first layer's loader (fp32) or one
-                    # gather + cast pass (bf16) packs, ``layout.unpack`` restores (B, T, .) with the representative row on the padding
-                    params = []
-                    for lin, _ in run:
-                        params += [lin.weight, lin.bias]
-                    spec = (tuple(act for _, act in run), precision, 0, False, run.drop_spec())
-                    packed = F_hip.LinearStackFn.apply(spec, input.reshape(-1, input.shape[-1]), layout.rows, *params)
-                    input = layout.unpack(packed)
-                    zero_padded = False
-                    i = end
-                    continue
+                input = self._forward_linear_run(input, run, end, modules, precision, seq_len, layout, zero_padded)
                 zero_padded = False
-                nxt = modules[end] if end < len(modules) else None
-                n_src = input.source.shape[0] * input.source.shape[1] if isinstance(input, UpsampledSequence) else 0
-                if (isinstance(input, UpsampledSequence) and isinstance(nxt, RecurrentCuDNNWrapper) and nxt._hip_gru()
-                        and seq_len is not None and not any(run.drops)         # a frame's dropout mask is its own: no phone-rate form
-                        and ops.phone_rate_gru_ok(n_src, input.rows.numel(), run[-1][0].weight.shape[0], input.phone_rate)):
-                    # Linear / Sigmoid commute with the row repetition of the upsample: run them on the phone rows (+ zero rows for
-                    # the padding frames) and hand the GRU wrapper a table + row map; it repeats the rows of its own input projection
-                    params = []
-                    for lin, _ in run:
-                        params += [lin.weight, lin.bias]
-                    spec = (tuple(act for _, act in run), precision, ops.PHONE_RATE_EXTRA)
-                    table = F_hip.LinearStackFn.apply(spec, input.source.reshape(-1, input.source.shape[-1]), None, *params)
-                    input = PhoneTable(table, input.rows, n_src, maps=input.phone_maps())
-                    i = end
-                    continue
-                if (isinstance(input, UpsampledSequence) and end == len(modules) and not any(run.drops)
-                        and ops.phone_rate_gru_ok(n_src, input.rows.numel(), 8, input.phone_rate)):
-                    # the stack ends in this run and sees nothing but the repeated phone rows: every layer commutes with the
-                    # repetition, so the run works on the phone rows (+ zero rows for padding frames) and its OUTPUT is repeated
-                    params = []
-                    for lin, _ in run:
-                        params += [lin.weight, lin.bias]
-                    spec = (tuple(act for _, act in run), precision, ops.PHONE_RATE_EXTRA)
-                    table = F_hip.LinearStackFn.apply(spec, input.source.reshape(-1, input.source.shape[-1]), None, *params)
-                    seg, rows_mapped = input.phone_maps()
-                    out = F_hip.RepeatTableRowsFn.apply(table, rows_mapped, seg, n_src)
-                    input = out.view(input.shape[0], input.shape[1], out.shape[-1])
-                    i = end
-                    continue
-                if isinstance(input, UpsampledSequence):
-                    lead, x2d, rows = input.shape[:2], input.source.reshape(-1, input.source.shape[-1]), \
-                        input.rows.reshape(-1)
-                elif (isinstance(input, UpsampledConcat) and precision == 'bf16' and CONCAT_PHONE_RATE and input.latent is None
-                      and input.frame_feature.shape[-1] <= 16
-                      and ops.phone_rate_gru_ok(input.upsampled.source.shape[0] * input.upsampled.source.shape[1],
-                                                input.upsampled.rows.numel(), 8, input.upsampled.phone_rate)):
-                    # cat(repeated phone rows, frame counters) (models/RNN_SPSS.py:76-81): W = [W_lab | W_cnt], the lab part of the
-                    # first layer commutes with the repetition and runs once per phone, the counters' part per frame
-                    up = input.upsampled
-                    seg, rows_mapped = up.phone_maps()
-                    feat = input.frame_feature.reshape(-1, input.frame_feature.shape[-1])
-                    params = []
-                    for lin, _ in run:
-                        params += [lin.weight, lin.bias]
-                    spec = (tuple(act for _, act in run), precision, ops.PHONE_RATE_EXTRA, False, run.drop_spec(), None,
-                            (rows_mapped.reshape(-1), seg, feat.contiguous()))
-                    out = F_hip.LinearStackFn.apply(spec, up.source.reshape(-1, up.source.shape[-1]), None, *params)
-                    input = out.view(*input.shape[:2], out.shape[-1])
-                    i = end
-                    continue
-                elif isinstance(input, UpsampledConcat) and input.latent is not None:
-                    # [labels | counters | z of the item] in one gather pass; z's gradient comes from the run's latent entry
-                    params = []
-                    for lin, _ in run:
-                        params += [lin.weight, lin.bias]
-                    spec = (tuple(act for _, act in run), precision, 0, False, run.drop_spec(), None, None, input.latent_entry())
-                    out = F_hip.LinearStackFn.apply(spec, input.operand(precision == 'bf16'), None, *params, input.latent)
-                    input = out.view(*input.shape[:2], out.shape[-1])
-                    i = end
-                    continue
-                elif isinstance(input, UpsampledConcat):
-                    lead, x2d, rows = input.shape[:2], input.operand(precision == 'bf16'), None
-                else:
-                    lead, x2d, rows = input.shape[:-1], input.reshape(-1, input.shape[-1]), None
-                params = []
-                for lin, _ in run:
-                    params += [lin.weight, lin.bias]
-                # rows here is the frame map of upsample_to_repetitions: runs of equal indices (a hint for the layer-1 loader)
-                shadow = bf16_copy_of(input) if (torch.is_tensor(input) and precision == 'bf16') else None
-                spec = (tuple(act for _, act in run), precision, 0, rows is not None, run.drop_spec(),
-                        shadow.view(-1, shadow.shape[-1]) if shadow is not None else None)
-                out = F_hip.LinearStackFn.apply(spec, x2d, rows, *params)
-                input = out.view(*lead, out.shape[-1])
                 i = end
                 continue
 
@@ -1148,6 +1099,17 @@ class _Run(list):
     """[(linear, act), ...] of ``SequentialWithRecurrent._linear_run`` plus ``drops`` (dropout probability behind each layer) and
     ``site0`` (index of the run's first module: numbers the dropout masks)."""
     drops, site0 = (), 0
+
+    @property
+    def acts(self):
+        return tuple(act for _, act in self)
+
+    def params(self, upto=None):
+        """[weight, bias, weight, bias, ...] of the run's layers (bias None where a layer has none); ``upto``: of ``run[:upto]`` only."""
+        params = []
+        for lin, _ in self[:upto]:
+            params += [lin.weight, lin.bias]
+        return params
 
     def drop_spec(self):
         return (self.drops, self.site0) if any(self.drops) else None

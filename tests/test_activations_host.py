@@ -30,6 +30,50 @@ def test_linear_run_collects_tanh_and_relu_like_sigmoid():
     assert end == 1 and tuple(act for _, act in run) == (ops.ACT_NONE,)
 
 
+def test_node_specs_and_run_accessors():
+    """The records the Linear-run nodes take as their first argument, and what a run hands them: defaults, keywords, and a
+    two-activation ``acts`` that stays ``acts`` (a bare tuple of two could once be read as (acts, maps))."""
+    from morgana_amd import functional as F_hip
+    spec = F_hip.LinearStackSpec((ops.ACT_SIGMOID, ops.ACT_NONE), 'fp32')
+    assert (spec.acts, spec.precision, spec.extra, spec.rows_runs) == ((ops.ACT_SIGMOID, ops.ACT_NONE), 'fp32', 0, False)
+    assert spec.drop is None and spec.shadow is None and spec.front is None and spec.latent is None
+    shadow = torch.zeros(2, 8, dtype=torch.bfloat16)
+    spec = F_hip.LinearStackSpec(acts=(ops.ACT_TANH,), precision='bf16', latent=(6, 3), shadow=shadow, rows_runs=True)
+    assert spec.latent == (6, 3) and spec.shadow is shadow and spec.rows_runs is True and spec.extra == 0 and spec.front is None
+    assert spec._fields == ('acts', 'precision', 'extra', 'rows_runs', 'drop', 'shadow', 'front', 'latent')
+    try:
+        spec.extra = 1
+        raise AssertionError('LinearStackSpec must be immutable')
+    except AttributeError:
+        pass
+
+    mods = [nn.Linear(6, 5), nn.Tanh(), nn.Dropout(0.25), nn.Linear(5, 4, bias=False), nn.ReLU(), nn.Linear(4, 3)]
+    net = utils.SequentialWithRecurrent(*mods)
+    net.train()
+    end, run = net._linear_run(list(net._modules.values()), 0)
+    assert end == len(mods) and run.acts == (ops.ACT_TANH, ops.ACT_RELU, ops.ACT_NONE)
+    want = [mods[0].weight, mods[0].bias, mods[3].weight, None, mods[5].weight, mods[5].bias]
+    got = run.params()
+    assert len(got) == len(want) and all(g is w for g, w in zip(got, want))
+    got = run.params(-2)
+    assert len(got) == 2 and got[0] is mods[0].weight and got[1] is mods[0].bias
+    assert len(run.params(2)) == 4 and run.params(2)[3] is None
+    assert run.drop_spec() == ((0.25, 0., 0.), 0)
+
+    two = (ops.ACT_SIGMOID, ops.ACT_NONE)
+    mse = F_hip.LinearStackMSESpec(two)
+    assert mse.acts == two and mse.maps is None and mse.table_bf16 is None and mse.phone_rate is None and mse.pending is None
+    assert mse._fields == ('acts', 'maps', 'table_bf16', 'phone_rate', 'pending')
+    maps, holder = (torch.zeros(2, 3), torch.zeros(4)), object()
+    mse = F_hip.LinearStackMSESpec(acts=two, maps=maps, phone_rate=True)
+    assert mse.acts == two and mse.maps is maps and mse.phone_rate is True and mse.pending is None
+    mse = F_hip.LinearStackMSESpec(two, pending=holder, table_bf16=shadow)
+    assert mse.acts == two and mse.maps is None and mse.pending is holder and mse.table_bf16 is shadow
+    # what forward unpacks: five fields in this order, whatever the length of acts
+    acts, maps_, table, order, pending = mse
+    assert (acts, maps_, order) == (two, None, None) and table is shadow and pending is holder
+
+
 def test_activation_constants_follow_the_header():
     import os
     import re
