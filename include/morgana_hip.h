@@ -1360,6 +1360,51 @@ int mg_gv_f32(const float* pred, int64_t pred_stride_b, int64_t pred_stride_t, i
 int mg_gv_bwd_f32(const float* grad_loss, const double* state, const float* pred, int64_t pred_stride_b, int64_t pred_stride_t,
                   int64_t pred_stride_d, const int64_t* seq_len, int B, int T, int D, float* grad, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * K28 (csrc/vq.hip)  vector quantisation for VQ-VAE latents, functional.VQFn (van den Oord et al. 2017); the reference has no discrete
+ *                    latent.
+ * z: N rows of D float32, row n at z + n ldz (ldz >= D, in elements): a column slice of a wider tensor and a base that is only
+ * 4-byte aligned are read in place.  codebook [K, D] float32, contiguous.  seq_len NULL: every row counts.  seq_len [B] int64 with
+ * N = B S: row b S + s counts when s < min(max(seq_len[b], 0), S); the other rows are NEVER READ, get index -1 and a zero
+ * quantised row and stay out of every mean and count.  With
+ *     d[n,k] = sum_d ( (double)z[n,d] - (double)E[k,d] )^2       (ascending d, float64, the direct difference, no contraction),
+ * index[n] [N] int64 is the smallest k that attains min_k d[n,k] (a NaN distance never wins; a row whose distances are all NaN
+ * gets code 0 and makes vq NaN), quantised [N, D] float32 is codebook[index[n]] bit for bit, vq[0] = sum_n d[n,index[n]] /
+ * (N_valid D) summed in float64 in an order fixed by n alone and rounded once, counts [K] int32 the number of rows per code,
+ * perplexity[0] = exp(-sum_k p_k ln p_k) with p_k = counts[k] / N_valid in float64, n_valid[0] (int64) = N_valid, which
+ * mg_vq_bwd_f32 reads.  N_valid == 0: vq and perplexity are NaN.  Three launches (one wave per row over codebook tiles of
+ * mg_vq_tile_codes(D) codes in LDS; a counting pass, one thread per code; a one-workgroup finish), no atomics, no host read:
+ * the same bits on every call, capturable.  K <= MG_VQ_MAX_CODES, D <= MG_VQ_MAX_DIM, N <= MG_VQ_MAX_ROWS (MG_EINVAL otherwise,
+ * nothing launched).  workspace: mg_vq_workspace_bytes(N, K) bytes (0 for a shape that is refused), 8-byte aligned; MG_EWORKSPACE
+ * when it is NULL or too small.
+ *
+ * mg_vq_bwd_f32, with g = g_loss[0] (one float32 ON THE DEVICE) and z, quantised, index, n_valid as the assignment left them:
+ *     dz[n,d] = (float)( g_lat[n,d] + g commitment_weight 2 (z[n,d] - q[n,d]) / (N_valid D) )      0 on rows with index -1,
+ *     dE[k,d] = (float)( g codebook_weight 2 sum_{n: index[n] = k} (q[n,d] - z[n,d]) / (N_valid D) )
+ * (q[n] is the code as the assignment read it: the codebook itself is not an argument and may have changed since), the members
+ * summed in ascending n in float64 and rounded once; a code without members gets exactly 0.  g_lat [N, D] may be NULL (zeros);
+ * dz [N, D] or dE [K, D] may be NULL: that part is skipped (not both).  One launch each, no atomics.
+ *
+ * mg_vq_ema_f32, the EMA codebook of the paper's appendix, in place (counts as the assignment left them):
+ *     cluster_size[k] <- (float)( decay n_k + (1 - decay) counts[k] ),     total = sum_k of the new sizes (float64, fixed order),
+ *     ema_sum[k,d]    <- (float)( m = decay m_kd + (1 - decay) sum_{n: index[n] = k} z[n,d] )      (ascending n, float64),
+ *     codebook[k,d]   <- (float)( m / ( (cluster_size[k] + eps) / (total + K eps) total ) )        (left as it is when total == 0).
+ * cluster_size [K], ema_sum [K, D], codebook [K, D] float32.  Two launches; workspace: 8 bytes (one float64), 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define MG_VQ_MAX_CODES 65536
+#define MG_VQ_MAX_DIM 256
+#define MG_VQ_MAX_ROWS 16777216
+int mg_vq_tile_codes(int D);
+size_t mg_vq_workspace_bytes(int64_t N, int K);
+int mg_vq_assign_f32(const float* z, int64_t ldz, int64_t N, int D, const int64_t* seq_len, int S, const float* codebook, int K,
+                     int64_t* index, float* quantised, float* vq, int32_t* counts, float* perplexity, int64_t* n_valid, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int mg_vq_bwd_f32(const float* g_lat, const float* g_loss, const float* z, int64_t ldz, const float* quantised, const int64_t* index,
+                  const int64_t* n_valid, int64_t N, int D, int K, double codebook_weight, double commitment_weight, float* dz, float* dE,
+                  void* stream);
+int mg_vq_ema_f32(const float* z, int64_t ldz, const int64_t* index, const int32_t* counts, int64_t N, int D, int K, double decay, double eps,
+                  float* cluster_size, float* ema_sum, float* codebook, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

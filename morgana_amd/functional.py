@@ -305,6 +305,44 @@ class KLDFn(torch.autograd.Function):
         return ops.kld_standard_normal_backward(grad, mean, log_variance)
 
 
+class VQFn(torch.autograd.Function):
+    """The quantiser of a VQ-VAE (van den Oord et al. 2017; ops.vq_assign / ops.vq_backward, csrc/vq.hip).
+    ``VQFn.apply(z_e, codebook, seq_len, codebook_weight, commitment_weight[, counts])`` -> (latent, index, loss, vq, perplexity):
+
+    * ``latent``: the quantised rows, with the straight-through estimator - its gradient reaches ``z_e`` unchanged;
+    * ``loss`` = (codebook_weight + commitment_weight) * vq in value, codebook_weight * mse(sg(z_e), e) + commitment_weight *
+      mse(z_e, sg(e)) in its gradients: the codebook's carries codebook_weight only, ``z_e``'s commitment_weight only;
+    * ``index`` (-1 on pad rows), ``vq`` (the mean squared distance) and ``perplexity``: not differentiable.
+
+    Saved for the backward: ``z_e``, the quantised rows and ``index`` - not the codebook, so an in-place (EMA) update of it between
+    forward and backward changes nothing.  ``counts`` (optional): a contiguous (K,) int32 device tensor that the assignment kernel fills
+    with the per-code usage, what ``ops.vq_ema_update`` reads next.  Double backward is NOT supported."""
+
+    @staticmethod
+    def forward(ctx, z_e, codebook, seq_len, codebook_weight, commitment_weight, counts=None):
+        index, quantised, vq, _, perplexity, n_valid = ops.vq_assign(z_e, codebook, seq_len, counts=counts)
+        ctx.weights = (float(codebook_weight), float(commitment_weight))
+        ctx.n_codes, ctx.rest = codebook.shape[0], (None,) * (3 if counts is None else 4)      # one gradient slot per further argument
+        ctx.save_for_backward(z_e, quantised, index, n_valid)
+        ctx.mark_non_differentiable(index, vq, perplexity)
+        return quantised, index, vq * (ctx.weights[0] + ctx.weights[1]), vq, perplexity
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_latent, _index, grad_loss, _vq, _perplexity):
+        z_e, quantised, index, n_valid = ctx.saved_tensors
+        codebook_weight, commitment_weight = ctx.weights
+        if grad_loss is None:
+            grad_loss = torch.zeros((), dtype=torch.float32, device=z_e.device)
+        elif grad_loss.dtype != torch.float32:
+            grad_loss = grad_loss.float()
+        if grad_latent is not None:
+            grad_latent = grad_latent.contiguous()
+        dz, de = ops.vq_backward(grad_latent, grad_loss, z_e, quantised, index, n_valid, ctx.n_codes, codebook_weight, commitment_weight,
+                                 want_dz=ctx.needs_input_grad[0], want_de=ctx.needs_input_grad[1] and codebook_weight != 0.)
+        return (dz, de) + ctx.rest
+
+
 class LatentConcatFn(torch.autograd.Function):
     """Dense fp32 ``cat(x, frame features, z broadcast over the rows of its item)``: the materialised form of a latent-conditioned
     ``utils.UpsampledConcat`` (one mg_gather_concat_latent_f32 pass).  Only z is differentiable; its gradient is the per-item sum of

@@ -1406,6 +1406,116 @@ def kld_standard_normal_backward(grad, mean, logvar):
     return dmean, dlogvar
 
 
+# --------------------------------------------------------------------------------------------- vector quantisation (csrc/vq.hip)
+VQ_EMA_EPS = 1e-5
+
+
+def _vq_rows(z, name, seq_len=None):
+    """``z`` (N, D) or (B, S, D) float32 -> (the tensor the kernel reads in place, row stride, N, D, S, seq_len): unit column
+    stride and evenly spaced rows (a column slice of a wider tensor) stay views, anything else becomes a contiguous copy."""
+    _require(z[..., :0], torch.float32, name)                  # type and device only: the view itself may be strided
+    if z.dim() not in (2, 3) or 0 in z.shape:
+        raise ValueError('%s must be a non-empty (N, D) or (B, S, D) tensor, got %s' % (name, tuple(z.shape)))
+    if seq_len is not None and z.dim() != 3:
+        raise ValueError('%s must be (B, S, D) when seq_len is given, got %s' % (name, tuple(z.shape)))
+    d = z.shape[-1]
+    if z.dim() == 3:
+        b, s, _ = z.shape
+        ld = z.stride(1) if s > 1 else (z.stride(0) if b > 1 else d)
+        even = (z.stride(2) == 1 or d == 1) and ld >= d and (b == 1 or s == 1 or z.stride(0) == s * ld)
+        n = b * s
+    else:
+        b, s, n = 1, z.shape[0], z.shape[0]
+        ld = z.stride(0) if n > 1 else d
+        even = (z.stride(1) == 1 or d == 1) and ld >= d
+    if not even:
+        z, ld = z.contiguous(), d
+    return z, ld, n, d, s, _lengths(seq_len, b)
+
+
+def _vq_codebook(codebook, d):
+    codebook = _require(codebook, torch.float32, 'codebook')
+    if codebook.dim() != 2 or codebook.shape[0] == 0 or codebook.shape[1] != d:
+        raise ValueError('codebook must be (K, D) with D = %d, got %s' % (d, tuple(codebook.shape)))
+    return codebook
+
+
+def vq_assign(z, codebook, seq_len=None, counts=None):
+    """Nearest code of every row (mg_vq_assign_f32, csrc/vq.hip): z (N, D) or (B, S, D) float32, read in place through its row stride;
+    codebook (K, D) float32; seq_len (B,) int64 or None - the rows at or past seq_len[b] are never read.  Returns (index int64,
+    shaped like z without its last dimension, -1 on pad rows; quantised, contiguous, shaped like z, ``codebook[index]`` bit for bit
+    and zero on pad rows; vq 0-d float32, the mean squared distance to the chosen code; counts (K,) int32; perplexity 0-d float32;
+    n_valid 0-d int64 for ``vq_backward``).  Distances are float64 sums of direct differences; ties go to the lowest index.
+    ``counts``: a contiguous (K,) int32 device tensor of the caller's to fill in place of a new one."""
+    lib = _lib.load()
+    z2, ld, n, d, s, seq_len = _vq_rows(z, 'z', seq_len)
+    codebook = _vq_codebook(codebook, d)
+    k, dev = codebook.shape[0], z2.device
+    index = torch.empty(tuple(z.shape[:-1]), dtype=torch.int64, device=dev)
+    quantised = torch.empty(tuple(z.shape), dtype=torch.float32, device=dev)
+    vq = torch.empty((), dtype=torch.float32, device=dev)
+    perplexity = torch.empty((), dtype=torch.float32, device=dev)
+    if counts is None:
+        counts = torch.empty((k,), dtype=torch.int32, device=dev)
+    elif _require(counts, torch.int32, 'counts', contiguous=False).shape != (k,) or not counts.is_contiguous():
+        raise ValueError('vq_assign: counts must be a contiguous (K,) = (%d,) int32 tensor, got %s' % (k, tuple(counts.shape)))
+    n_valid = torch.empty((), dtype=torch.int64, device=dev)
+    ws = workspace(lib.mg_vq_workspace_bytes(n, k), dev)
+    _lib.check(lib.mg_vq_assign_f32(_p(z2), ld, n, d, _p(seq_len), s, _p(codebook), k, _p(index), _p(quantised), _p(vq), _p(counts),
+                                    _p(perplexity), _p(n_valid), _p(ws), ws.numel(), _stream()), 'mg_vq_assign_f32')
+    return index, quantised, vq, counts, perplexity, n_valid
+
+
+def vq_backward(grad_latent, grad_loss, z, quantised, index, n_valid, n_codes, codebook_weight, commitment_weight, want_dz=True,
+                want_de=True):
+    """The gradients of ``vq_assign``'s loss and straight-through latent (mg_vq_bwd_f32) -> (dz shaped like z, dE (n_codes, D)), either
+    None when not wanted.  dz = grad_latent + grad_loss * commitment_weight * 2 (z - q) / (N_valid D), zero on pad rows; dE[k] =
+    grad_loss * codebook_weight * 2 sum_{index == k} (q - z) / (N_valid D), members in ascending order, exactly 0 for an unused
+    code.  ``grad_latent`` may be None; ``grad_loss`` is a one-element float32 device tensor that the kernel reads (no host read);
+    z, quantised, index, n_valid as ``vq_assign`` took and left them (the codebook is not needed: quantised holds its rows)."""
+    lib = _lib.load()
+    grad_loss = _one_element(grad_loss)
+    z2, ld, n, d, _, _ = _vq_rows(z, 'z')
+    quantised = _require(quantised, torch.float32, 'quantised')
+    index = _require(index, torch.int64, 'index')
+    n_valid = _require(n_valid, torch.int64, 'n_valid')
+    if tuple(quantised.shape) != tuple(z.shape) or tuple(index.shape) != tuple(z.shape[:-1]) or n_valid.numel() != 1:
+        raise ValueError('vq_backward: quantised %s and index %s do not go with z %s' % (tuple(quantised.shape), tuple(index.shape),
+                                                                                        tuple(z.shape)))
+    if grad_latent is not None:
+        grad_latent = _require(grad_latent, torch.float32, 'grad_latent')
+        if tuple(grad_latent.shape) != tuple(z.shape):
+            raise ValueError('vq_backward: grad_latent %s must be shaped like z %s' % (tuple(grad_latent.shape), tuple(z.shape)))
+    if not (want_dz or want_de):
+        return None, None
+    dev = z2.device
+    dz = torch.empty(tuple(z.shape), dtype=torch.float32, device=dev) if want_dz else None
+    de = torch.empty((int(n_codes), d), dtype=torch.float32, device=dev) if want_de else None
+    _lib.check(lib.mg_vq_bwd_f32(_p(grad_latent), _p(grad_loss), _p(z2), ld, _p(quantised), _p(index), _p(n_valid), n, d, int(n_codes),
+                                 float(codebook_weight), float(commitment_weight), _p(dz), _p(de), _stream()), 'mg_vq_bwd_f32')
+    return dz, de
+
+
+def vq_ema_update(z, index, counts, cluster_size, ema_sum, codebook, decay, eps=VQ_EMA_EPS):
+    """The EMA codebook update (mg_vq_ema_f32), IN PLACE on cluster_size (K,), ema_sum (K, D) and codebook (K, D), all float32 and
+    contiguous: cluster_size <- decay cluster_size + (1 - decay) counts, ema_sum <- decay ema_sum + (1 - decay) (sum of the rows
+    assigned to each code, ascending, float64), codebook <- ema_sum / the Laplace-smoothed cluster size.  z, index and counts as
+    ``vq_assign`` took and left them."""
+    lib = _lib.load()
+    z2, ld, n, d, _, _ = _vq_rows(z, 'z')
+    index = _require(index, torch.int64, 'index')
+    counts = _require(counts, torch.int32, 'counts')
+    k = counts.numel()
+    for name, t, shape in (('cluster_size', cluster_size, (k,)), ('ema_sum', ema_sum, (k, d)), ('codebook', codebook, (k, d))):
+        if _require(t, torch.float32, name, contiguous=False).shape != shape or not t.is_contiguous():
+            raise ValueError('vq_ema_update: %s must be a contiguous %s tensor (updated in place), got %s' % (name, shape, tuple(t.shape)))
+    if tuple(index.shape) != tuple(z.shape[:-1]) or k == 0:
+        raise ValueError('vq_ema_update: index %s does not go with z %s' % (tuple(index.shape), tuple(z.shape)))
+    ws = workspace(8, z2.device)                               # one float64: the sum of the new cluster sizes
+    _lib.check(lib.mg_vq_ema_f32(_p(z2), ld, _p(index), _p(counts), n, d, k, float(decay), float(eps), _p(cluster_size), _p(ema_sum),
+                                 _p(codebook), _p(ws), ws.numel(), _stream()), 'mg_vq_ema_f32')
+
+
 # ------------------------------------------------------------------------------------------- latent surface samplers (sampling)
 def _site_args(seed, site, used):
     return int(seed), int(site) & 0xFFFFFFFF, _p(used)
