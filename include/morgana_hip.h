@@ -1405,6 +1405,46 @@ int mg_vq_bwd_f32(const float* g_lat, const float* g_loss, const float* z, int64
 int mg_vq_ema_f32(const float* z, int64_t ldz, const int64_t* index, const int32_t* counts, int64_t N, int D, int K, double decay, double eps,
                   float* cluster_size, float* ema_sum, float* codebook, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * K29 (csrc/f0.hip)  continuous log-F0 and voicing from a raw F0 track: the `lf0` and `vuv` features every F0 model of the reference
+ *                    reads (models/f0_test_model.py, models/RNN_SPSS.py), which it gets as files from the un-vendored tts_data_tools;
+ *                    here computed on the device inside the loader, in front of mg_deltas_f32 and mg_column_stats_f32.
+ * Per item of n frames and per column d (columns are independent):
+ *     voiced[t] = x[t,d] > voiced_above                     (a NaN is unvoiced)
+ *     l[t]      = log((double)x[t,d]), or (double)x[t,d] when log_input != 0 (the track is a log-F0 track already)
+ *     lf0[t,d]  = (float)l[t] on a voiced frame; on an unvoiced frame between the nearest voiced frames a < t < b
+ *                 (float)( l[a] + (l[b] - l[a]) * w ), w = (double)(t - a) / (double)(b - a), in float64 in this order without
+ *                 contraction, rounded once; (float)l[b] with no voiced frame before t, (float)l[a] with none after (np.interp's
+ *                 convention); `fill` on every frame of an item without a voiced frame
+ *     vuv[t,d]  = 1.0f on a voiced frame, else 0.0f.
+ * A voiced value that is not finite, or whose logarithm is not, propagates by the formula.
+ * Input x, exactly one of
+ *   offsets (B + 1, int64): packed [N, D] - the rows of item b are [offsets[b], offsets[b + 1]); T_in is unused,
+ *   seq_len (B, int64):     padded [B, T_in, D] - item b is rows [b T_in, b T_in + min(max(seq_len[b], 0), T_in)); later frames are
+ *                           never read.
+ * Outputs, each may be NULL (not all):
+ *   packed_out [packed_rows, D]: lf0, row offsets[b] + t (packed input) or (the clamped lengths of the items before b) + t (padded
+ *                                input); rows that belong to no item, and rows from packed_rows on, are not written - what
+ *                                mg_deltas_f32 and mg_column_stats_f32 read next,
+ *   padded_out [B, out_rows, D]: lf0; frames from out_rows on are not written (the interpolation still sees the whole item), frames
+ *                                past the length are written as exact zeros by the same launch,
+ *   norm_out   [B, out_rows, D]: kind (MG_NORM_MVN or MG_NORM_MINMAX) with p0 / p1 [D] applied to the rounded float32 lf0, the
+ *                                arithmetic of mg_normalise_f32, zeros past the length; with item_row (B, int32) non-NULL p0 / p1 are
+ *                                tables [S, D] and item b takes row item_row[b]: an index outside [0, S) is never used as one and
+ *                                gives NaN in that item's valid frames,
+ *   vuv_out: vuv_form MG_F0_VUV_PADDED - [B, out_rows, D] as padded_out; MG_F0_VUV_PACKED - [packed_rows, D] as packed_out.
+ * Lengths 0, 1 and 2 are legal.  B == 0: MG_OK, nothing launched.  One launch (one workgroup per item, a wave per 64-frame segment,
+ * neighbours by ballot), no workspace, no atomics, no host read: the same bits on every call, capturable.
+ * mg_continuous_lf0_chunk_rows(): frames of one column a workgroup takes per trip, what a test needs to cross a chunk.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define MG_F0_VUV_PADDED 0
+#define MG_F0_VUV_PACKED 1
+int mg_continuous_lf0_chunk_rows(void);
+int mg_continuous_lf0_f32(const float* x, int D, int B, const int64_t* offsets, const int64_t* seq_len, int T_in, int log_input,
+                          float voiced_above, float fill, const float* p0, const float* p1, const int32_t* item_row, int S, int kind,
+                          int64_t out_rows, int64_t packed_rows, float* packed_out, float* padded_out, float* norm_out, float* vuv_out,
+                          int vuv_form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -623,6 +623,127 @@ def _delta_specs_of(utterances, delta_specs):
     return dict(delta_specs)
 
 
+VUV_KEY = 'vuv'
+
+
+class F0Spec(object):
+    """How the continuous log-F0 of one named feature is computed (``continuous_lf0``): ``source`` - the key of the raw F0 track in the
+    utterances, ``vuv`` - the key the voicing flag is written under, and the operator's ``log_input`` / ``voiced_above`` / ``fill``."""
+
+    def __init__(self, source='f0', vuv=VUV_KEY, log_input=False, voiced_above=None, fill=0.):
+        if not source or not vuv:
+            raise ValueError('F0Spec: source=%r and vuv=%r must be feature names' % (source, vuv))
+        self.source, self.vuv, self.log_input = source, vuv, bool(log_input)
+        self.voiced_above = ops.f0_voiced_above(voiced_above, self.log_input)
+        self.fill = float(np.float32(fill))
+
+    def __repr__(self):
+        return 'F0Spec(source=%r, vuv=%r, log_input=%r, voiced_above=%r, fill=%r)' % (
+            self.source, self.vuv, self.log_input, self.voiced_above, self.fill)
+
+
+def _host_continuous_lf0(f0, spec):
+    """The arithmetic of mg_continuous_lf0_f32 in NumPy for one (len, D) item: the comparison in float32, the logarithm and the three
+    operations of the interpolation in float64, in the kernel's order, one rounding to float32."""
+    x = np.asarray(f0)
+    if x.ndim != 2:
+        raise ValueError('continuous_lf0: a host track must be one (frames, features) array, got shape %s' % (x.shape,))
+    x = x.astype(np.float32)
+    n, d = x.shape
+    with np.errstate(all='ignore'):
+        voiced = x > np.float32(spec.voiced_above)            # False for a NaN
+        wide = x.astype(np.float64)
+        logs = wide if spec.log_input else np.log(np.where(voiced, wide, 1.0))
+    lf0 = np.full((n, d), np.float32(spec.fill), dtype=np.float32)
+    frames = np.arange(n)
+    for c in range(d):
+        at = np.flatnonzero(voiced[:, c])
+        if at.size == 0:
+            continue
+        pos = np.searchsorted(at, frames)                     # voiced frames before t: at[pos - 1] < t <= at[pos]
+        a, b = at[np.clip(pos - 1, 0, at.size - 1)], at[np.clip(pos, 0, at.size - 1)]
+        la, lb = logs[a, c], logs[b, c]
+        with np.errstate(all='ignore'):
+            w = (frames - a).astype(np.float64) / np.where(b > a, b - a, 1).astype(np.float64)
+            between = la + (lb - la) * w
+        value = np.where(pos == 0, lb, np.where(pos == at.size, la, between))
+        value = np.where(voiced[:, c], logs[:, c], value)
+        with np.errstate(all='ignore'):
+            lf0[:, c] = value.astype(np.float32)
+    return lf0, voiced.astype(np.float32)
+
+
+def continuous_lf0(f0, seq_len=None, log_input=False, voiced_above=None, fill=0.):
+    """``(lf0, vuv)`` of a raw F0 track: the two features every F0 model of the reference reads and gets as files from
+    ``tts_data_tools`` (models/f0_test_model.py, models/RNN_SPSS.py).  Per item and per column:
+
+    * ``vuv[t] = 1.0`` where ``f0[t] > voiced_above`` (a NaN is unvoiced), else 0.0.  ``voiced_above`` defaults to 0.0 - extractors
+      write 0 where unvoiced - and, with ``log_input``, to -1e9, so that the HTS / Merlin marker -1e10 reads as unvoiced.
+    * ``lf0[t] = log(f0[t])`` on a voiced frame (``f0[t]`` itself with ``log_input``: the track is a log-F0 track already); on an
+      unvoiced frame between the nearest voiced frames a < t < b it is ``l[a] + (l[b] - l[a]) * ((t - a) / (b - a))``; before the first
+      voiced frame it holds that frame's value, behind the last one that one's; an item without a voiced frame is ``fill``.
+
+    A NumPy ``(len, D)`` array is computed on the host; a device tensor ``(B, T, D)`` - with ``seq_len`` (B,), frames past it are not
+    read and come back as zeros - or ``(T, D)`` goes through the HIP kernel (csrc/f0.hip).  Both take the logarithm and the
+    interpolation in float64, in this order without contraction, and round once to float32; with ``log_input`` there is no
+    transcendental and the two give the same bits, otherwise they differ by what the two ``log`` implementations differ.  A voiced
+    value that is not finite (or whose logarithm is not) propagates by the formula.  There is no backward: a tensor that requires grad
+    is refused.
+
+    Holding the edge values is ``np.interp``'s convention.  Whether the ``lf0`` files of ``tts_data_tools`` were written that way could
+    not be verified - the package is not vendored with the reference - so this is a stated choice, not a matched one."""
+    spec = F0Spec(log_input=log_input, voiced_above=voiced_above, fill=fill)
+    if isinstance(f0, np.ndarray):
+        if seq_len is not None:
+            raise ValueError('continuous_lf0: seq_len goes with a batched device tensor; a host array is one whole item')
+        return _host_continuous_lf0(f0, spec)
+    if not isinstance(f0, torch.Tensor):
+        raise TypeError('continuous_lf0 takes a NumPy array or a device tensor, got %s' % type(f0))
+    if f0.requires_grad:
+        raise RuntimeError('continuous_lf0 has no backward: detach the track first')
+    if f0.dim() not in (2, 3):
+        raise ValueError('continuous_lf0: a tensor must be (frames, features) or (batch, frames, features), got %s' % (tuple(f0.shape),))
+    single = f0.dim() == 2
+    if single and seq_len is not None:
+        raise ValueError('continuous_lf0: seq_len goes with a batched (batch, frames, features) tensor')
+    batched = f0[None] if single else f0
+    if not batched.is_cuda:
+        from ._lib import MorganaHipError
+        raise MorganaHipError('continuous_lf0 takes NumPy arrays (host) or device tensors; got a tensor on %s (no CPU fallback for the '
+                              'device path)' % f0.device)
+    if seq_len is None:
+        seq_len = torch.full((batched.shape[0],), batched.shape[1], dtype=torch.int64, device=batched.device)
+    else:
+        seq_len = seq_len.to(device=batched.device, dtype=torch.int64).reshape(-1)
+    lf0, _, vuv, _ = ops.continuous_lf0(batched, seq_len=seq_len, t=batched.shape[1], log_input=spec.log_input,
+                                        voiced_above=spec.voiced_above, fill=spec.fill)
+    return (lf0[0], vuv[0]) if single else (lf0, vuv)
+
+
+def _f0_specs_of(utterances, f0_specs):
+    """The {feature name: F0Spec} a loader applies: the argument, or what the data sources of a ``FilesDataset`` ask for."""
+    if f0_specs is None:
+        return utterances.f0_specs() if isinstance(utterances, FilesDataset) else {}
+    return dict(f0_specs)
+
+
+def _check_f0_specs(f0_specs, first):
+    """Refuse a first utterance that carries what ``f0_specs`` computes, or lacks what they read."""
+    taken = set()
+    for name, spec in f0_specs.items():
+        for key in (name, spec.vuv):
+            if key in first:
+                raise ValueError('%r is in the utterances and in f0_specs: it is read from files or computed, not both' % key)
+            if key in taken:
+                raise ValueError('f0_specs write %r twice' % key)
+            taken.add(key)
+        if spec.source not in first:
+            raise KeyError('f0_specs read %r for %r, which the utterances do not have' % (spec.source, name))
+        track = first[spec.source]
+        if not (isinstance(track, np.ndarray) and track.ndim == 2 and track.dtype == np.float32):
+            raise TypeError('f0_specs read %r, which is not a float32 (frames, features) array' % spec.source)
+
+
 class _Staging(object):
     """Pinned host staging for the loader's packed features: per (device, feature) TWO buffers used in turn - the copy of the batch
     before last has certainly been issued when a buffer comes round again, and its event says when it has finished - grown
@@ -718,26 +839,50 @@ def _small_to_device(plain, device):
     return out
 
 
+def _normaliser_operands(out, key, normaliser, device, deltas=False):
+    """(kind, p0, p1, item_row) of the device passes that write a normalised twin: vectors for a plain normaliser, the (S, D) tables and
+    the batch's ``speaker_index`` for a speaker-dependent one; four Nones without a normaliser."""
+    if not isinstance(normaliser, FeatureNormaliser):
+        return None, None, None, None
+    spec = _KINDS[normaliser.kind]
+    if isinstance(normaliser, _SpeakerDependentNormaliser):
+        p0, p1 = normaliser.tables(device, deltas=deltas)
+        return spec['forward'], p0, p1, out[SPEAKER_INDEX_KEY]
+    prm = normaliser.fetch_params(torch.Tensor, deltas=deltas)
+    if prm is None:
+        raise RuntimeError('normaliser %r has no %sparameters: call load_params, set_params or fit_normalisers first' % (
+            key, 'delta ' if deltas else ''))
+    p0, p1 = (prm[n].to(device) for n in spec['params'])
+    return spec['forward'], p0, p1, None
+
+
 def _device_deltas(out, key, packed, offsets, t, spec, normaliser, device):
     """``out[key + '_deltas']`` (and its ``normalised_`` twin when ``normaliser`` normalises deltas) from the packed statics of ``key``
     that are on the device already: one mg_deltas_f32 launch, nothing more crosses PCIe."""
     kind = p0 = p1 = item_row = None
     if normaliser is not None and normaliser.use_deltas:
-        kind = _KINDS[normaliser.kind]['forward']
-        if isinstance(normaliser, _SpeakerDependentNormaliser):
-            (p0, p1), item_row = normaliser.tables(device, deltas=True), out[SPEAKER_INDEX_KEY]
-        else:
-            prm = normaliser.fetch_params(torch.Tensor, deltas=True)
-            if prm is None:
-                raise RuntimeError('normaliser %r has no delta parameters: call load_params, set_params or fit_normalisers first' % key)
-            p0, p1 = (prm[n].to(device) for n in _KINDS[normaliser.kind]['params'])
+        kind, p0, p1, item_row = _normaliser_operands(out, key, normaliser, device, deltas=True)
     raw, norm = ops.deltas(packed, spec.windows, offsets=offsets, edge=spec.edge, t=t, p0=p0, p1=p1, kind=kind, item_row=item_row)
     out[key + DELTAS_SUFFIX] = raw
     if norm is not None:
         out['normalised_' + key + DELTAS_SUFFIX] = norm
 
 
-def collate_to_device(batch, normalisers, device, bf16_tables=(), delta_specs=None):
+def _device_f0(out, name, spec, packed, offsets, t, normaliser, delta_spec, device):
+    """``out[name]``, ``out['normalised_' + name]`` (where ``normaliser`` is one) and ``out[spec.vuv]`` from the packed raw F0 track that
+    is on the device: one mg_continuous_lf0_f32 launch, which also leaves the packed continuous track when deltas follow
+    (``_device_deltas`` on that track: one more launch).  The raw track itself is not emitted."""
+    kind, p0, p1, item_row = _normaliser_operands(out, name, normaliser, device)
+    lf0, norm, vuv, track = ops.continuous_lf0(packed, offsets=offsets, t=t, want_packed=delta_spec is not None, log_input=spec.log_input,
+                                               voiced_above=spec.voiced_above, fill=spec.fill, p0=p0, p1=p1, kind=kind, item_row=item_row)
+    out[name], out[spec.vuv] = lf0, vuv
+    if norm is not None:
+        out['normalised_' + name] = norm
+    if delta_spec is not None:
+        _device_deltas(out, name, track, offsets, t, delta_spec, normaliser, device)
+
+
+def collate_to_device(batch, normalisers, device, bf16_tables=(), delta_specs=None, f0_specs=None):
     """``load_utterance`` + ``collate_fn`` + ``to_device`` for a list of RAW per-utterance feature dicts, with the float
     sequence features normalised and zero padded on the device (reference: data.py:119-127, 159-224, 648-663).
 
@@ -754,15 +899,25 @@ def collate_to_device(batch, normalisers, device, bf16_tables=(), delta_specs=No
     ``delta_specs``: {feature name: ``DeltaSpec``}.  The packed statics uploaded for such a feature also give ``name_deltas`` and -
     where its normaliser has ``use_deltas`` - ``normalised_name_deltas``, computed on the device by one more launch
     (mg_deltas_f32, csrc/deltas.hip): no ``{name}_deltas`` file is read and nothing is uploaded twice.  A batch that already
-    carries ``name_deltas`` is refused (ValueError): it is one or the other."""
+    carries ``name_deltas`` is refused (ValueError): it is one or the other.
+
+    ``f0_specs``: {feature name: ``F0Spec``}.  The raw F0 track ``spec.source`` is uploaded once and one launch (mg_continuous_lf0_f32,
+    csrc/f0.hip) writes ``name`` - the continuous log-F0 - ``normalised_name`` where ``name`` has a normaliser, and ``spec.vuv``; when
+    ``delta_specs`` names the feature too, the same launch leaves the packed continuous track and the delta launch reads that.  The raw
+    track is not emitted.  A batch that already carries ``name`` or ``spec.vuv`` is refused (ValueError): each is read or computed."""
     device = torch.device(device)
     bf16_tables = tuple(bf16_tables or ())
     delta_specs = dict(delta_specs or {})
+    f0_specs = dict(f0_specs or {})
+    _check_f0_specs(f0_specs, batch[0])
+    f0_sources = {}                                       # raw track -> the features computed from it
+    for name, spec in f0_specs.items():
+        f0_sources.setdefault(spec.source, []).append(name)
     for name in delta_specs:
         if name + DELTAS_SUFFIX in batch[0]:
             raise ValueError('%r is in the utterances and in delta_specs: deltas are read from files or computed, not both' % (
                 name + DELTAS_SUFFIX))
-        if name not in batch[0]:
+        if name not in batch[0] and name not in f0_specs:
             raise KeyError('delta_specs names %r, which the utterances do not have' % name)
     out, rest = {}, []
     order = _speaker_order(normalisers)
@@ -785,6 +940,11 @@ def collate_to_device(batch, normalisers, device, bf16_tables=(), delta_specs=No
             lens = np.array([x.shape[0] for x in items], dtype=np.int64)
             offsets = torch.from_numpy(np.concatenate(([0], np.cumsum(lens))).astype(np.int64))
             packed = torch.from_numpy(np.ascontiguousarray(np.concatenate(items, axis=0)))
+        if key in f0_sources:
+            for name in f0_sources[key]:
+                _device_f0(out, name, f0_specs[name], packed, offsets, int(lens.max()),
+                           normalisers.get(name) if normalisers is not None else None, delta_specs.get(name), device)
+            continue
         kind = p0 = p1 = None
         normaliser = normalisers.get(key) if normalisers is not None else None
         if isinstance(normaliser, _SpeakerDependentNormaliser):
@@ -866,6 +1026,32 @@ class NumpyBinarySource(object):
         return features
 
 
+class ContinuousLF0Source(object):
+    """``{data_dir}/{f0_name}/{base_name}.npy`` -> ``{f0_name: array}``: the data source of a continuous log-F0 feature ``name`` (and its
+    voicing flag ``vuv_name``) for a corpus that holds an extractor's raw F0 track - 0 where unvoiced - and not the ``lf0`` / ``vuv``
+    files of ``tts_data_tools``.  Only the raw track is loaded.  The source carries ``f0_spec`` (an ``F0Spec``: ``log_input``,
+    ``voiced_above``, ``fill`` - see ``continuous_lf0``): ``FilesDataset.__getitem__`` computes ``name`` and ``vuv_name`` on the host, the
+    device loaders (``DeviceBatches``, ``collate_to_device``, ``fit_normalisers``) on the device from the one column they upload.
+
+    ``use_deltas``: the feature has a delta stream ``{name}_deltas``.  Deltas of a computed feature are always computed: the source
+    then carries ``delta_spec = DeltaSpec(windows, edge)`` as ``NumpyBinarySource(..., deltas='compute')`` does."""
+
+    def __init__(self, name='lf0', f0_name='f0', vuv_name=VUV_KEY, use_deltas=False, windows=None, edge='replicate', ext='npy',
+                 log_input=False, voiced_above=None, fill=0.):
+        if len({name, f0_name, vuv_name}) != 3:
+            raise ValueError('ContinuousLF0Source: name=%r, f0_name=%r and vuv_name=%r must differ' % (name, f0_name, vuv_name))
+        self.name, self.f0_name, self.vuv_name, self.use_deltas, self.ext = name, f0_name, vuv_name, use_deltas, ext
+        self.f0_spec = F0Spec(source=f0_name, vuv=vuv_name, log_input=log_input, voiced_above=voiced_above, fill=fill)
+        self.delta_spec = DeltaSpec(windows, edge) if use_deltas else None
+
+    def file_path(self, base_name, data_dir):
+        return os.path.join(data_dir, self.f0_name, '{}.{}'.format(base_name, self.ext))
+
+    def __call__(self, base_name, data_dir):
+        track = np.load(self.file_path(base_name, data_dir)).astype(np.float32, copy=False)      # (WORLD writes float64 tracks)
+        return {self.f0_name: track.reshape(-1, 1) if track.ndim == 1 else track}
+
+
 class TextSource(object):
     """``{data_dir}/{name}/{base_name}.txt`` holding one number -> ``{name: int}`` (or float): the sentence-level counts
     (``n_frames``, ``n_phones``) of the reference's data layout (README.rst:139-150)."""
@@ -910,7 +1096,10 @@ class FilesDataset(object):
 
     A data source that computes its deltas (``NumpyBinarySource(..., deltas='compute')``) yields statics only: ``raw`` has no
     ``name_deltas``, ``__getitem__`` adds it (and its normalised twin) with the host form of ``compute_deltas``, and the device
-    loaders take ``delta_specs()`` and compute it on the device."""
+    loaders take ``delta_specs()`` and compute it on the device.
+
+    A ``ContinuousLF0Source`` yields the raw F0 track only: ``raw`` has ``f0``, ``__getitem__`` adds ``lf0`` and ``vuv`` with the host
+    form of ``continuous_lf0``, then the deltas and the normalised twins, in that order, and the device loaders take ``f0_specs()``."""
 
     def __init__(self, data_sources, data_dir, id_list, normalisers, data_root='.'):
         for name, normaliser in normalisers.items():
@@ -933,6 +1122,10 @@ class FilesDataset(object):
         """{feature name: DeltaSpec} of the data sources that compute their deltas."""
         return {name: source.delta_spec for name, source in self.data_sources.items() if getattr(source, 'delta_spec', None) is not None}
 
+    def f0_specs(self):
+        """{feature name: F0Spec} of the data sources that compute a continuous log-F0 from a raw F0 track."""
+        return {name: source.f0_spec for name, source in self.data_sources.items() if getattr(source, 'f0_spec', None) is not None}
+
     def raw(self, index):
         base_name = self.file_ids[index]
         features = {'name': base_name}
@@ -945,6 +1138,10 @@ class FilesDataset(object):
 
     def __getitem__(self, index):
         features = self.raw(index)
+        f0_specs = self.f0_specs()
+        _check_f0_specs(f0_specs, features)
+        for name, spec in f0_specs.items():
+            features[name], features[spec.vuv] = _host_continuous_lf0(features[spec.source], spec)
         for name, spec in self.delta_specs().items():
             features[name + DELTAS_SUFFIX] = compute_deltas(features[name], spec.windows, spec.edge)
         for name in self.data_sources:
@@ -961,13 +1158,14 @@ class FilesDataset(object):
     collate_fn = staticmethod(collate_fn)
 
 
-def batch(data_generator, batch_size=32, shuffle=True, num_data_threads=0, device='cuda:0', bf16_tables=(), delta_specs=None):
+def batch(data_generator, batch_size=32, shuffle=True, num_data_threads=0, device='cuda:0', bf16_tables=(), delta_specs=None,
+          f0_specs=None):
     """The reference's ``data.batch`` (data.py:29-57) for a ``FilesDataset``: a loader of device-resident batches.  Files are read
     on the calling thread as each batch is formed (``num_data_threads`` is accepted for signature compatibility; worker
     subprocesses are the reference's answer to a host-bound collate, which here runs on the device)."""
     rng = np.random.RandomState(torch.initial_seed() % (2 ** 32)) if shuffle else None
     return DeviceBatches(data_generator, batch_size, data_generator.normalisers, device, shuffle=rng, bf16_tables=bf16_tables,
-                         delta_specs=delta_specs)
+                         delta_specs=delta_specs, f0_specs=f0_specs)
 
 
 class DeviceBatches(object):
@@ -975,14 +1173,14 @@ class DeviceBatches(object):
     each batch padded and normalised there by ``collate_to_device``.  ``utterances`` is a ``FilesDataset`` (read lazily, batch by
     batch, through ``raw``) or a sequence of utterances that are already in host memory.
 
-    ``bf16_tables``, ``delta_specs``: see ``collate_to_device``; ``delta_specs=None`` takes what the data sources of a ``FilesDataset``
-    ask for (``FilesDataset.delta_specs``).  ``utterances`` is a sequence of RAW per-utterance feature dicts (what a ``_DataSource`` returns: float32 ``(len, D)``
+    ``bf16_tables``, ``delta_specs``, ``f0_specs``: see ``collate_to_device``; ``delta_specs=None`` / ``f0_specs=None`` take what the data
+    sources of a ``FilesDataset`` ask for (``FilesDataset.delta_specs`` / ``f0_specs``).  ``utterances`` is a sequence of RAW per-utterance feature dicts (what a ``_DataSource`` returns: float32 ``(len, D)``
     arrays, integer ``dur``, python ints, the name); ``normalisers`` maps feature names to normalisers (``Normalisers`` or a
     dict).  Batches are contiguous slices in the given order, or a fresh permutation per epoch from ``shuffle`` = a
     ``numpy.random.RandomState`` (the reference shuffles with torch's global generator, data.py:50); the last, smaller batch
     is kept, as ``DataLoader`` does by default.  ``ExperimentBuilder.train_epoch`` takes it like any other loader."""
 
-    def __init__(self, utterances, batch_size, normalisers, device, shuffle=None, bf16_tables=(), delta_specs=None):
+    def __init__(self, utterances, batch_size, normalisers, device, shuffle=None, bf16_tables=(), delta_specs=None, f0_specs=None):
         if batch_size <= 0:
             raise ValueError('batch_size must be positive, got %r' % (batch_size,))
         self.utterances = utterances if isinstance(utterances, FilesDataset) else list(utterances)
@@ -992,6 +1190,7 @@ class DeviceBatches(object):
         self.shuffle = shuffle
         self.bf16_tables = tuple(bf16_tables or ())
         self.delta_specs = _delta_specs_of(self.utterances, delta_specs)
+        self.f0_specs = _f0_specs_of(self.utterances, f0_specs)
 
     def use_bf16_tables(self, names):
         """The loader half of bf16 mode: every batch from now on carries the bf16 operand tables of these (normalised, phone-level)
@@ -1017,7 +1216,8 @@ class DeviceBatches(object):
         for start in range(0, len(order), self.batch_size):
             fetch = self.utterances.raw if isinstance(self.utterances, FilesDataset) else self.utterances.__getitem__
             batch = [fetch(int(i)) for i in order[start:start + self.batch_size]]
-            yield collate_to_device(batch, self.normalisers, self.device, bf16_tables=self.bf16_tables, delta_specs=self.delta_specs)
+            yield collate_to_device(batch, self.normalisers, self.device, bf16_tables=self.bf16_tables, delta_specs=self.delta_specs,
+                                    f0_specs=self.f0_specs)
 
 
 class ColumnStats(object):
@@ -1095,7 +1295,8 @@ def _fit_rows(utterance, key):
     return value
 
 
-def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out_dir=None, data_root='.', ddof=0, delta_specs=None):
+def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out_dir=None, data_root='.', ddof=0, delta_specs=None,
+                    f0_specs=None):
     """Fit the parameters of ``normalisers`` (a ``Normalisers`` or a dict name -> normaliser of any of the four classes) to a corpus:
     the step that produces the ``{name}_mvn.json`` / ``{name}_minmax.json`` files (the reference gets them from ``tts_data_tools``).
 
@@ -1108,6 +1309,11 @@ def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out
     ``delta_specs``: {feature name: ``DeltaSpec``}, default what the data sources of a ``FilesDataset`` ask for.  ``name + '_deltas'`` of
     such a feature is not read from the utterances: mg_deltas_f32 (csrc/deltas.hip) writes it, packed as the statics are, from the
     statics uploaded for ``name``, and ``ColumnStats.update_packed`` reads that.  An utterance that carries it anyway is refused.
+
+    ``f0_specs``: {feature name: ``F0Spec``}, default what the data sources of a ``FilesDataset`` ask for.  ``name`` is not read from the
+    utterances: the raw F0 track ``spec.source`` is uploaded and mg_continuous_lf0_f32 (csrc/f0.hip) writes the packed continuous
+    log-F0, over which the statistics of ``name`` - and, through mg_deltas_f32, of ``name + '_deltas'``, which must then be in
+    ``delta_specs`` - are taken: ALL frames, the interpolated ones included, the Merlin convention.
 
     Raises ValueError before anything is set or written if a listed speaker has no frame or a fitted parameter is not finite.
     ``ddof``: see ``ColumnStats.result``.  Returns {feature: ColumnStats.result()} (the ``_deltas`` features under their own names)."""
@@ -1132,6 +1338,10 @@ def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out
     for name in delta_specs:
         if name not in normalisers or not normalisers[name].use_deltas:
             raise ValueError('delta_specs names %r, which has no normaliser with use_deltas' % name)
+    f0_specs = {name: spec for name, spec in _f0_specs_of(utterances, f0_specs).items() if name in normalisers}
+    for name in f0_specs:
+        if normalisers[name].use_deltas and name not in delta_specs:
+            raise ValueError('%r is computed from %r: its deltas are computed too, name it in delta_specs' % (name, f0_specs[name].source))
     stats = {}
     for start in range(0, len(utterances), batch_size):
         items = [fetch(i) for i in range(start, min(start + batch_size, len(utterances)))]
@@ -1142,6 +1352,8 @@ def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out
             index = torch.from_numpy(speaker_index_of([item[SPEAKER_ID_KEY] for item in items], order))
             item_row = _small_to_device({SPEAKER_INDEX_KEY: index}, device)[SPEAKER_INDEX_KEY]
         uploaded = {}                                     # the packed statics of this batch, for the features whose deltas are computed
+        if start == 0:
+            _check_f0_specs(f0_specs, items[0])
         for key, normaliser, is_deltas in features:
             by_speaker = isinstance(normaliser, _SpeakerDependentNormaliser)
             base = key[:-len(DELTAS_SUFFIX)] if is_deltas else key
@@ -1151,8 +1363,12 @@ def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out
                 spec, (statics, offsets, lens) = delta_specs[base], uploaded[base]
                 packed, _ = ops.deltas(statics, spec.windows, offsets=offsets, edge=spec.edge, packed_rows=statics.shape[0])
             else:
-                rows = [_fit_rows(item, key) for item in items]
+                rows = [_fit_rows(item, f0_specs[key].source if key in f0_specs else key) for item in items]
                 packed, offsets, lens = _pack_pinned(rows, device, 'fit:' + key)
+                if key in f0_specs:                       # the raw track -> the packed continuous log-F0, in place of a file's rows
+                    spec = f0_specs[key]
+                    packed = ops.continuous_lf0(packed, offsets=offsets, log_input=spec.log_input, voiced_above=spec.voiced_above,
+                                                fill=spec.fill)[3]
                 if key in delta_specs:
                     uploaded[key] = (packed, offsets, lens)
             if key not in stats:

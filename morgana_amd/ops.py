@@ -3111,6 +3111,93 @@ def deltas(x, windows, *, offsets=None, seq_len=None, edge='replicate', t=None, 
     return raw, norm
 
 
+F0_VOICED_ABOVE = 0.0            # a raw F0 track is 0 where unvoiced
+F0_VOICED_ABOVE_LOG = -1e9       # a log-F0 track carries the HTS / Merlin marker -1e10 there
+
+
+def f0_voiced_above(voiced_above, log_input):
+    """The voicing threshold as the float32 the kernel and the host form compare with: the argument, or the default of the input kind."""
+    if voiced_above is None:
+        voiced_above = F0_VOICED_ABOVE_LOG if log_input else F0_VOICED_ABOVE
+    value = ctypes.c_float(float(voiced_above)).value
+    if value != value:
+        raise ValueError('continuous_lf0: voiced_above is NaN: no frame would be voiced')
+    return value
+
+
+def continuous_lf0(x, *, offsets=None, seq_len=None, t=None, packed_rows=None, want_packed=False, log_input=False, voiced_above=None,
+                   fill=0., p0=None, p1=None, kind=None, item_row=None):
+    """Continuous log-F0 and voicing of a float32 F0 track (csrc/f0.hip, mg_continuous_lf0_f32), one launch: per item and column
+    ``vuv = x > voiced_above`` and ``lf0 = log(x)`` (``x`` itself with ``log_input``) on voiced frames, interpolated linearly in float64
+    through the unvoiced ones, the first / last voiced value held at the edges, ``fill`` for an item without a voiced frame.
+
+    Input, exactly one of: ``offsets`` (B + 1,) int64 with x the packed rows (N, D), or ``seq_len`` (B,) int64 with x padded (B, T, D)
+    (frames past the length are never read).  Outputs: ``t`` - padded (B, t, D) lf0 and vuv, zeros past each length, and with ``kind``
+    (NORM_MVN / NORM_MINMAX) and p0 / p1 (D,) the normalised twin of lf0 (``item_row`` (B,) int32: tables (S, D), NaN for an index
+    outside [0, S)); ``want_packed`` adds the packed lf0 (packed_rows, D) the delta and statistics kernels read next (``packed_rows``
+    defaults to the rows of a packed input).  Without ``t``: ``packed_rows`` alone gives lf0 and vuv packed.
+    Returns (lf0 padded or None, normalised or None, vuv, lf0 packed or None)."""
+    lib = _lib.load()
+    x = _require(x, torch.float32, 'f0')
+    if (offsets is None) == (seq_len is None):
+        raise ValueError('continuous_lf0: give exactly one of offsets (packed rows) and seq_len (padded batch)')
+    if offsets is not None:
+        offsets = _require(offsets, torch.int64, 'offsets')
+        if x.dim() != 2 or offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError('continuous_lf0: packed rows %s must be (rows, features) and offsets %s (items + 1,)' % (
+                tuple(x.shape), tuple(offsets.shape)))
+        b, t_in, d = offsets.numel() - 1, 0, x.shape[1]
+        if packed_rows is None and (t is None or want_packed):
+            packed_rows = x.shape[0]
+    else:
+        seq_len = _require(seq_len, torch.int64, 'seq_len')
+        if x.dim() != 3 or seq_len.dim() != 1 or seq_len.numel() != x.shape[0]:
+            raise ValueError('continuous_lf0: padded batch %s must be (items, frames, features) and seq_len %s (items,)' % (
+                tuple(x.shape), tuple(seq_len.shape)))
+        b, t_in, d = x.shape
+    if d == 0:
+        raise ValueError('continuous_lf0: the feature has no columns')
+    if t is None and packed_rows is None:
+        raise ValueError('continuous_lf0: give t (padded outputs), packed_rows (packed outputs) or both')
+    if want_packed and packed_rows is None:
+        raise ValueError('continuous_lf0: want_packed of a padded input needs packed_rows')
+    if t is not None and packed_rows is not None and not want_packed:
+        raise ValueError('continuous_lf0: packed_rows next to t goes with want_packed=True')
+    if (t is not None and int(t) < 0) or (packed_rows is not None and int(packed_rows) < 0):
+        raise ValueError('continuous_lf0: a negative output size (t=%r, packed_rows=%r)' % (t, packed_rows))
+    if kind is None and (p0 is not None or p1 is not None or item_row is not None):
+        raise ValueError('continuous_lf0: normaliser parameters and item_row go with a kind (NORM_MVN or NORM_MINMAX)')
+    s = 0
+    if kind is not None:
+        if kind not in (NORM_MVN, NORM_MINMAX):
+            raise ValueError('continuous_lf0: kind %r is not NORM_MVN or NORM_MINMAX' % (kind,))
+        if t is None:
+            raise ValueError('continuous_lf0: the normalised twin is a padded output: give t')
+        if item_row is not None:
+            p0, p1, item_row = _item_tables(p0, p1, item_row, b, d, 'continuous_lf0')
+            s = p0.shape[0]
+        else:
+            p0 = _require(p0, torch.float32, 'param0')
+            p1 = _require(p1, torch.float32, 'param1')
+            if p0.numel() != d or p1.numel() != d:
+                raise ValueError('normaliser parameters have %d / %d entries, the feature has %d columns' % (p0.numel(), p1.numel(), d))
+    threshold = f0_voiced_above(voiced_above, log_input)
+    padded = norm = packed = None
+    if t is not None:
+        padded = torch.empty((b, int(t), d), dtype=torch.float32, device=x.device)
+        vuv, vuv_form = torch.empty_like(padded), _lib.MG_F0_VUV_PADDED
+        norm = torch.empty_like(padded) if kind is not None else None
+    else:
+        vuv, vuv_form = torch.empty((int(packed_rows), d), dtype=torch.float32, device=x.device), _lib.MG_F0_VUV_PACKED
+    if t is None or want_packed:
+        packed = torch.empty((int(packed_rows), d), dtype=torch.float32, device=x.device)
+    _lib.check(lib.mg_continuous_lf0_f32(_p(x), d, b, _p(offsets), _p(seq_len), int(t_in), 1 if log_input else 0, threshold, float(fill),
+                                         _p(p0), _p(p1), _p(item_row), s, -1 if kind is None else kind, 0 if t is None else int(t),
+                                         0 if packed_rows is None else int(packed_rows), _p(packed), _p(padded), _p(norm), _p(vuv),
+                                         vuv_form, _stream()), 'mg_continuous_lf0_f32')
+    return padded, norm, vuv, packed
+
+
 # ---------------------------------------------------------------------------------------------- phone-rate first layer
 # MORGANA_PHONE_RATE=0: every product at frame rate (the reference's order of operations).  This is only the DEFAULT of a per-call
 # choice: utils.upsample_to_repetitions(..., phone_rate=) records the choice on the lazy sequence it returns, the layers that consume

@@ -2,12 +2,14 @@
 """Fit normaliser parameter files to a corpus of ``.npy`` features (``data.fit_normalisers``: per-column statistics on the device,
 csrc/colstats.hip) - the files ``data.Normalisers`` and ``load_params`` read, which the reference takes from ``tts_data_tools``.
 
-    python scripts/fit_normalisers.py DATA_ROOT DATA_DIR ID_LIST NAME:KIND[:deltas[=compute]] [NAME:KIND[:deltas[=compute]] ...]
+    python scripts/fit_normalisers.py DATA_ROOT DATA_DIR ID_LIST NAME:KIND[:deltas[=compute]][:from=F0] [NAME:KIND... ...]
                                       [--speaker-id-list FILE] [--out-dir DIR] [--batch-size 64] [--ddof 0] [--device cuda:0]
 
 ``KIND`` is ``mvn`` or ``minmax``; ``:deltas`` also fits ``{NAME}_deltas`` from the files of ``DATA_ROOT/DATA_DIR/NAME_deltas``;
 ``:deltas=compute`` fits it without such files: the deltas are computed on the device from the statics (csrc/deltas.hip; default
-windows, replicated edges - ``data.compute_deltas``).  Features are read from ``DATA_ROOT/DATA_DIR/NAME/*.npy``
+windows, replicated edges - ``data.compute_deltas``).  ``:from=F0`` (``lf0:mvn:deltas=compute:from=f0``) fits a continuous log-F0 feature
+without ``NAME`` files: the raw F0 track ``DATA_ROOT/DATA_DIR/F0/*.npy`` is read and interpolated on the device (csrc/f0.hip -
+``data.continuous_lf0``), the statistics cover every frame, and its deltas are always computed.  Features are read from ``DATA_ROOT/DATA_DIR/NAME/*.npy``
 for the ids of ``DATA_ROOT/ID_LIST``.  With ``--speaker-id-list`` (relative to DATA_ROOT) every normaliser is speaker dependent: the
 speaker of an utterance is read from ``DATA_ROOT/DATA_DIR/speaker_id/*.txt`` and the files go to ``{speaker}/``.  The files are
 written under ``DATA_ROOT/OUT_DIR`` (default: DATA_DIR, where the reference's ``--normalisation_dir train`` looks for them).
@@ -26,13 +28,21 @@ CLASSES = {('mvn', False): data.MeanVarianceNormaliser, ('minmax', False): data.
 
 
 def parse_spec(spec, speaker_id_list):
+    """``NAME:KIND[:deltas[=compute]][:from=F0]`` -> (name, normaliser, 'file' or 'compute', the raw F0 track's name or None)."""
     name, _, rest = spec.partition(':')
-    kind, _, deltas = rest.partition(':')
-    if not name or kind not in ('mvn', 'minmax') or deltas not in ('', 'deltas', 'deltas=compute'):
-        raise SystemExit('cannot read %r: expected NAME:KIND, NAME:KIND:deltas or NAME:KIND:deltas=compute, KIND mvn or minmax' % spec)
+    kind, _, options = rest.partition(':')
+    options = options.split(':') if options else []
+    source = [option[len('from='):] for option in options if option.startswith('from=')]
+    deltas = [option for option in options if not option.startswith('from=')]
+    if (not name or kind not in ('mvn', 'minmax') or len(deltas) > 1 or len(source) > 1 or (deltas and deltas[0] not in ('deltas', 'deltas=compute'))
+            or (source and (not source[0] or source[0] == name))):
+        raise SystemExit('cannot read %r: expected NAME:KIND, NAME:KIND:deltas or NAME:KIND:deltas=compute, each optionally followed by '
+                         ':from=F0 (another feature name), KIND mvn or minmax' % spec)
+    if source and deltas == ['deltas']:
+        raise SystemExit('cannot read %r: the deltas of a feature computed from %r are computed too: write deltas=compute' % (spec, source[0]))
     cls = CLASSES[kind, speaker_id_list is not None]
     extra = (speaker_id_list,) if speaker_id_list is not None else ()
-    return name, cls(name, *extra, use_deltas=bool(deltas)), 'compute' if deltas == 'deltas=compute' else 'file'
+    return name, cls(name, *extra, use_deltas=bool(deltas)), 'compute' if deltas == ['deltas=compute'] else 'file', source[0] if source else None
 
 
 def main():
@@ -40,7 +50,7 @@ def main():
     parser.add_argument('data_root')
     parser.add_argument('data_dir')
     parser.add_argument('id_list')
-    parser.add_argument('features', nargs='+', metavar='NAME:KIND[:deltas[=compute]]')
+    parser.add_argument('features', nargs='+', metavar='NAME:KIND[:deltas[=compute]][:from=F0]')
     parser.add_argument('--speaker-id-list', default=None)
     parser.add_argument('--out-dir', default=None)
     parser.add_argument('--batch-size', type=int, default=64)
@@ -48,8 +58,10 @@ def main():
     parser.add_argument('--device', default='cuda:0')
     args = parser.parse_args()
     specs = [parse_spec(spec, args.speaker_id_list) for spec in args.features]
-    normalisers = {name: normaliser for name, normaliser, _ in specs}
-    sources = {name: data.NumpyBinarySource(name, use_deltas=normaliser.use_deltas, deltas=deltas) for name, normaliser, deltas in specs}
+    normalisers = {name: normaliser for name, normaliser, _, _ in specs}
+    sources = {name: (data.NumpyBinarySource(name, use_deltas=normaliser.use_deltas, deltas=deltas) if f0_name is None else
+                      data.ContinuousLF0Source(name, f0_name=f0_name, vuv_name=name + '_vuv', use_deltas=normaliser.use_deltas))
+               for name, normaliser, deltas, f0_name in specs}
     if args.speaker_id_list is not None:
         sources[data.SPEAKER_ID_KEY] = data.StringSource(data.SPEAKER_ID_KEY)
     dataset = data.FilesDataset(sources, args.data_dir, args.id_list, normalisers, data_root=args.data_root)
