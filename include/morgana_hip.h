@@ -1445,6 +1445,36 @@ int mg_continuous_lf0_f32(const float* x, int D, int B, const int64_t* offsets, 
                           int64_t out_rows, int64_t packed_rows, float* packed_out, float* padded_out, float* norm_out, float* vuv_out,
                           int vuv_form, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * K27  ragged segment pooling (csrc/segpool.hip): utils.pool_segments, frames -> phone / syllable / word / utterance rate.
+ *
+ *   out[b, s, f] = pool over t in [start_s, min(start_s + max(len_s, 0), n_b)) of x[b, t, f],   start_s = sum_{j < s} max(len_j, 0),
+ *   n_b = min(max(seq_len[b], 0), T) (seq_len NULL: T).  x f32 [B, T, F] read in place through its strides (elements; none negative):
+ *   16-byte loads when stride_f == 1, F % 4 == 0, x is 16-byte aligned and stride_t, stride_b are multiples of 4, else 4-byte loads,
+ *   the same bits either way.  seg_lens int64 [B, S] (a negative length counts as 0), out f32 [B, S, F] contiguous.
+ *   mode: MG_POOL_SUM / MG_POOL_MEAN - a float64 sum (MEAN: divided by the frame count m in float64) rounded to float32 once;
+ *         MG_POOL_MAX / MG_POOL_MIN - the value x[b, t*, f] bit for bit, t* the lowest frame that holds the extremum, or the lowest
+ *         NaN frame if there is one; arg int32 [B, S, F] (required for these two modes, unused otherwise) takes t*.
+ *   An empty range (m == 0) gives +0 and arg -1.  A frame outside every range is never read.  Segments are reduced in chunks of
+ *   mg_segment_pool_chunk() frames counted from the segment's own first frame, merged in ascending order: the order of operations
+ *   depends on m and the position inside the segment alone.  One launch, no workspace, no atomics, no host read: the same bits on
+ *   every call, capturable.
+ * mg_segment_pool_bwd_f32: the dense gradient grad f32 [B, T, F] (contiguous) from grad_out f32 [B, S, F] (contiguous), every element
+ *   written exactly once by one launch: SUM g, MEAN (float)((double)g / m), MAX / MIN g where arg[b, s, f] == t and +0 elsewhere,
+ *   +0 on every frame outside all ranges.  arg: what the forward wrote (MAX / MIN only).
+ * Refused (MG_EINVAL, nothing launched): an unknown mode, F < 1, a negative size or stride, B > 65535, S > 12288, a NULL or misaligned
+ *   pointer where one is read or written.  Zero work (forward: B == 0 or S == 0; backward: B == 0 or T == 0): MG_OK, no launch.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define MG_POOL_SUM 0
+#define MG_POOL_MEAN 1
+#define MG_POOL_MAX 2
+#define MG_POOL_MIN 3
+int mg_segment_pool_chunk(void);
+int mg_segment_pool_f32(const float* x, int64_t stride_b, int64_t stride_t, int64_t stride_f, const int64_t* seg_lens, const int64_t* seq_len,
+                        int B, int S, int T, int F, int mode, float* out, int32_t* arg, void* stream);
+int mg_segment_pool_bwd_f32(const float* grad_out, const int64_t* seg_lens, const int64_t* seq_len, const int32_t* arg, int B, int S, int T,
+                            int F, int mode, float* grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2079,6 +2079,32 @@ class SeqMeanFn(torch.autograd.Function):
         return ops.masked_seq_mean_bwd(grad_loss, seq_len, ctx.shape), None
 
 
+class SegmentPoolFn(torch.autograd.Function):
+    """``utils.pool_segments`` (ops.segment_pool, csrc/segpool.hip): sequence_feature (B, T, F) float32 -> (B, S, F), the sum / mean /
+    max / min over each segment's valid frames, one launch forward and one backward (ops.segment_pool_backward).  Kept between them:
+    the integer inputs and, for 'max' / 'min', the (B, S, F) int32 frame index of each extremum - never the feature itself.  The
+    integer inputs get no gradient.  Double backward is NOT supported."""
+
+    @staticmethod
+    def forward(ctx, sequence_feature, seg_lens2d, seq_len, mode):
+        out, arg = ops.segment_pool(sequence_feature, seg_lens2d, seq_len, mode)
+        ctx.mode, ctx.t = mode, sequence_feature.shape[1]
+        ctx.has_seq_len, ctx.has_arg = seq_len is not None, arg is not None
+        ctx.save_for_backward(*[v for v in (seg_lens2d, seq_len, arg) if v is not None])
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        saved = list(ctx.saved_tensors)
+        seg_lens2d = saved.pop(0)
+        seq_len = saved.pop(0) if ctx.has_seq_len else None
+        arg = saved.pop(0) if ctx.has_arg else None
+        if grad_out.dtype != torch.float32:
+            grad_out = grad_out.float()
+        return ops.segment_pool_backward(grad_out.contiguous(), seg_lens2d, seq_len, arg, ctx.mode, ctx.t), None, None, None
+
+
 class GVFn(torch.autograd.Function):
     """The global-variance loss of ``losses.gv`` (ops.gv): two launches forward, one backward (ops.gv_backward).  Kept between them:
     the (B, D, 2) float64 state (the predictions' means and the gradient coefficients), the predictions themselves, which the

@@ -753,11 +753,17 @@ class VAEF0Model(StreamModel, BaseVAE):
     appended to every frame of the decoder's input (``utils.concat_frame_features(..., latent)``: one gather pass, its gradient summed
     per utterance by the first layer's run).  Loss = the lf0 stream's masked MSE + ``kld_weight`` * KLD; ``kld`` is a metric of every
     collection.  State_dict keys: the decoder's ``layers.*`` as ``GRUF0Model`` (input ``input_dim + z_dim`` wide),
-    ``encoder.0.layer.*`` and ``encoder_projection.0.*``."""
+    ``encoder.0.layer.*`` and ``encoder_projection.0.*``.  ``encoder_pooling``: what of the encoder's output sequence goes into the
+    projection - 'last' (the GRU's last state, the default), or the 'mean' / 'max' over each utterance's valid frames
+    (``utils.pool_segments``); the parameters and their keys are the same in every case."""
+
+    ENCODER_POOLINGS = ('last', 'mean', 'max')
 
     def __init__(self, z_dim=16, kld_weight=1., encoder_hidden=64, dropout_prob=0., input_dim=600 + 9, output_dim=1 * 3, precision=None,
-                 fused_upsample=True, generate=True, speaker_id_list=None, trajectory_weight=0., gv_weight=0.):
-        self.input_dim, self.output_dim = input_dim, output_dim
+                 fused_upsample=True, generate=True, speaker_id_list=None, trajectory_weight=0., gv_weight=0., encoder_pooling='last'):
+        if encoder_pooling not in self.ENCODER_POOLINGS:
+            raise ValueError('VAEF0Model: encoder_pooling must be one of %s, got %r' % (self.ENCODER_POOLINGS, encoder_pooling))
+        self.input_dim, self.output_dim, self.encoder_pooling = input_dim, output_dim, encoder_pooling
         layers = _gru_f0_stack(input_dim + z_dim, output_dim, dropout_prob, precision)
         streams = [Stream('lf0', output_dim, 'mse', ('LF0_RMSE_Hz', metrics.LF0Distortion, 'voiced_trajectory'),
                           trajectory_weight=trajectory_weight, gv_weight=gv_weight)]
@@ -775,8 +781,13 @@ class VAEF0Model(StreamModel, BaseVAE):
 
     def encode(self, features):
         deltas = features['normalised_lf0_deltas']
-        _, hiddens = self.encoder(deltas, seq_len=features['n_frames'], max_len=deltas.shape[1])
-        statistics, _ = self.encoder_projection(hiddens[0][0])
+        output, hiddens = self.encoder(deltas, seq_len=features['n_frames'], max_len=deltas.shape[1])
+        if self.encoder_pooling == 'last':
+            summary = hiddens[0][0]
+        else:
+            n_frames = features['n_frames'].reshape(-1)
+            summary = utils.pool_segments(output, n_frames.reshape(-1, 1), self.encoder_pooling, seq_len=n_frames)[:, 0]
+        statistics, _ = self.encoder_projection(summary)
         return statistics[:, :self.z_dim], statistics[:, self.z_dim:]
 
     def decode(self, latent, features):

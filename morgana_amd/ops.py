@@ -524,6 +524,74 @@ def gv_backward(grad_loss, state, pred, seq_len=None):
     return grad
 
 
+POOL_MODES = {'sum': _lib.MG_POOL_SUM, 'mean': _lib.MG_POOL_MEAN, 'max': _lib.MG_POOL_MAX, 'min': _lib.MG_POOL_MIN}
+
+
+def _pool_mode(mode):
+    if mode not in POOL_MODES:
+        raise ValueError("pool_segments: mode must be one of 'sum', 'mean', 'max', 'min', got %r" % (mode,))
+    return POOL_MODES[mode]
+
+
+def _pool_lens(seg_lens2d, b, what):
+    seg_lens2d = _require(seg_lens2d, torch.int64, 'segment_lens')
+    if seg_lens2d.dim() != 2 or seg_lens2d.shape[0] != b:
+        raise ValueError('%s: segment_lens must be (B, S) with B = %d, got %s' % (what, b, tuple(seg_lens2d.shape)))
+    _phones(seg_lens2d.shape[1], what)
+    return seg_lens2d
+
+
+def segment_pool(x, seg_lens2d, seq_len, mode):
+    """Ragged segment pooling (mg_segment_pool_f32, csrc/segpool.hip): x (B, T, F) float32, read in place through its strides (a
+    column slice, a misaligned base, a transposed view, an expanded operand); seg_lens2d (B, S) int64; seq_len (B,) int64 or None;
+    mode 'sum' | 'mean' | 'max' | 'min'.  Returns (out (B, S, F) float32, arg): the (B, S, F) int32 frame index of each extremum for
+    'max' / 'min' (-1 for an empty segment), else None.  No host read: S is the shape of ``seg_lens2d``.  An empty dimension of
+    ``x`` and S = 0 are refused here (ValueError), as the other wrappers refuse them, although the C entry point takes them as
+    zero work."""
+    lib = _lib.load()
+    code = _pool_mode(mode)
+    x = _require(x, torch.float32, 'sequence_feature', contiguous=False)
+    if x.dim() != 3 or 0 in x.shape:
+        raise ValueError('sequence_feature must be a non-empty (B, T, F) tensor, got %s' % (tuple(x.shape),))
+    if min(x.stride()) < 0:
+        x = x.contiguous()
+    b, t, f = x.shape
+    seg_lens2d = _pool_lens(seg_lens2d, b, 'segment_pool')
+    s = seg_lens2d.shape[1]
+    seq_len = _lengths(seq_len, b, 'segment_pool: ')
+    out = torch.empty((b, s, f), dtype=torch.float32, device=x.device)
+    arg = torch.empty((b, s, f), dtype=torch.int32, device=x.device) if mode in ('max', 'min') else None
+    _lib.check(lib.mg_segment_pool_f32(_p(x), x.stride(0), x.stride(1), x.stride(2), _p(seg_lens2d), _p(seq_len), b, s, t, f, code, _p(out),
+                                       _p(arg), _stream()), 'mg_segment_pool_f32')
+    return out, arg
+
+
+def segment_pool_backward(grad_out, seg_lens2d, seq_len, arg, mode, t):
+    """d segment_pool / d x (mg_segment_pool_bwd_f32): the dense (B, t, F) float32 gradient from grad_out (B, S, F), written once by
+    one launch - grad_out at the segment of each frame ('sum'), divided by the segment's frame count in float64 ('mean'), at the
+    frame ``arg`` names and +0 elsewhere ('max' / 'min'), +0 on every frame outside all segments."""
+    lib = _lib.load()
+    code = _pool_mode(mode)
+    grad_out = _require(grad_out, torch.float32, 'grad_out')
+    if grad_out.dim() != 3 or 0 in grad_out.shape or int(t) <= 0:
+        raise ValueError('grad_out must be a non-empty (B, S, F) tensor and t positive, got %s, t=%r' % (tuple(grad_out.shape), t))
+    b, s, f = grad_out.shape
+    seg_lens2d = _pool_lens(seg_lens2d, b, 'segment_pool_backward')
+    if seg_lens2d.shape[1] != s:
+        raise ValueError('segment_pool_backward: grad_out has %d segments, segment_lens %d' % (s, seg_lens2d.shape[1]))
+    seq_len = _lengths(seq_len, b, 'segment_pool_backward: ')
+    if mode in ('max', 'min'):
+        arg = _require(arg, torch.int32, 'arg')
+        if tuple(arg.shape) != (b, s, f):
+            raise ValueError('arg must be (B, S, F) = %s, got %s' % ((b, s, f), tuple(arg.shape)))
+    else:
+        arg = None
+    grad = torch.empty((b, int(t), f), dtype=torch.float32, device=grad_out.device)
+    _lib.check(lib.mg_segment_pool_bwd_f32(_p(grad_out), _p(seg_lens2d), _p(seq_len), _p(arg), b, s, int(t), f, code, _p(grad), _stream()),
+               'mg_segment_pool_bwd_f32')
+    return grad
+
+
 def stream_loss(pred, targets, kinds, seq_len, want_grad, want_prob=False, grad_scale=1.0):
     """Multi-stream loss (mg_stream_loss_f32): pred (B, T, sum of widths), targets[k] (B, T, width_k) scored side by side
     in column order, kinds[k] in {'mse', 'sigmoid_bce'}.  Returns (loss 0-d, grad or None, prob or None)."""

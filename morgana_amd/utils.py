@@ -475,6 +475,24 @@ def get_segment_ends(sequence_feature, segment_lens):
     return out.view(b, lens2d.shape[1], f)
 
 
+def pool_segments(sequence_feature, segment_lens, mode='mean', seq_len=None):
+    """Pools the frames of each segment: the way back from frame rate to phone, syllable, word or utterance rate (not in the
+    reference, which ships ``split_to_segments`` and leaves the reduction over its zero-padded block to the user).
+
+    sequence_feature (B, T, F) float32, read in place through its strides; segment_lens (B, S, 1) or (B, S) integer (a negative
+    length counts as 0); ``seq_len`` (B,) int64 or None -> (B, S, F) float32, differentiable in ``sequence_feature``.  Segment ``s``
+    of item ``b`` covers the frames ``[start_s, min(start_s + len_s, n_b))``, ``start_s`` the sum of the lengths before it and
+    ``n_b = min(max(seq_len[b], 0), T)``; frames outside every range are never read.  ``mode``: 'sum' and 'mean' are float64 sums
+    rounded to float32 once, 'max' and 'min' return the extremum bit for bit (the lowest frame among equals takes the gradient; a
+    NaN in the segment gives NaN).  A segment without a frame gives zeros and no gradient, as ``get_segment_ends`` does.  One pass
+    over the valid frames, no host read (S is the shape of ``segment_lens``): the call can be captured into a graph.  A tensor
+    with an empty dimension and S = 0 raise ValueError (S is limited to 1..``ops.MAX_PHONES``)."""
+    if mode not in ops.POOL_MODES:
+        raise ValueError("pool_segments: mode must be one of 'sum', 'mean', 'max', 'min', got %r" % (mode,))
+    lens2d = _segment_lens_2d(sequence_feature, segment_lens)
+    return F_hip.SegmentPoolFn.apply(sequence_feature, lens2d, seq_len, mode)
+
+
 class RecurrentCuDNNWrapper(nn.Module):
     """Wraps a torch recurrent layer with the sort / pack / unpack semantics of morgana/utils.py:333-393.
 
