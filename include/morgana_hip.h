@@ -1475,6 +1475,40 @@ int mg_segment_pool_f32(const float* x, int64_t stride_b, int64_t stride_t, int6
 int mg_segment_pool_bwd_f32(const float* grad_out, const int64_t* seg_lens, const int64_t* seq_len, const int32_t* arg, int B, int S, int T,
                             int F, int mode, float* grad, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * K30 (csrc/counters.hip)  frame-level positional features from durations: the `counters` feature the acoustic models of the reference
+ *                          read (models/RNN_SPSS.py:65), which it gets as files from the un-vendored tts_data_tools; here computed on
+ *                          the device inside the loader from the durations it uploads anyway.
+ * dur int64, logical [B, P, S], read in place through its element strides (none negative): P phones of S sub-phone states (S = 1: a
+ * phone-level alignment).  A negative duration owns no frame.  n_phones (B, int64) or NULL: the phones from n_phones[b] on count as
+ * absent (NULL: all P count).  With start[p,s] = the sum of the durations before (p, s) in (p, s) order, n_s = dur[p,s],
+ * n_p = sum_s dur[p,s], and for frame t of the one segment with start <= t < start + n_s:  i = t - start[p,s],  j = t - start[p,0]:
+ *   MG_COUNTERS_FULL   C = 9:  (i+1)/n_s, (n_s-i)/n_s, n_s, s+1, S-s, n_p, n_s/n_p, (n_p-j)/n_p, (j+1)/n_p      (Merlin's 'full')
+ *   MG_COUNTERS_PHONE  C = 3:  (j+1)/n_p, (n_p-j)/n_p, n_p                                             (Merlin's 'minimal_phoneme')
+ * every quotient one float64 division of the two integers rounded once to float32 (below 2^24 frames per phone: the correctly rounded
+ * float32 of the exact rational), integer columns converted directly.  An item whose durations add up to 2^31 or more is outside the
+ * contract: the scan saturates (nothing is read or written out of bounds).
+ * Outputs, either may be NULL (not both):
+ *   raw_out  [B, T, C]: frames t < min(T, total_b, seq_len[b] if seq_len != NULL) hold the counters (total_b: the sum of the item's
+ *                       durations that count), every other frame exact zeros, written by the same launch,
+ *   norm_out [B, T, C]: norm_kind (MG_NORM_MVN or MG_NORM_MINMAX) with p0 / p1 [C] applied to the rounded float32 value, the
+ *                       arithmetic of mg_normalise_f32, zeros on the other frames; with item_row (B, int32) non-NULL p0 / p1 are tables
+ *                       [n_rows, C] and item b takes row item_row[b]: an index outside [0, n_rows) is never used as one and gives NaN
+ *                       in that item's valid frames.
+ * blocks_per_item: workgroups that share the T * C output elements of an item, each repeating the item's scan; 0: the library's
+ * choice (one per 768 elements).  The bits do not depend on it.
+ * Refused (MG_EINVAL, nothing launched): an unknown kind, P < 1, S < 1, P * S > 12288 (the scan lives in LDS), a negative size or
+ * stride, no output, a normalised output without parameters or kind.  B == 0 or T == 0: MG_OK, nothing launched.  One launch, no
+ * workspace, no atomics, no host read: the same bits on every call, capturable.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define MG_COUNTERS_FULL 0
+#define MG_COUNTERS_PHONE 1
+#define MG_COUNTERS_FULL_COLS 9
+#define MG_COUNTERS_PHONE_COLS 3
+int mg_frame_counters_f32(const int64_t* dur, int B, int P, int S, int64_t stride_b, int64_t stride_p, int64_t stride_s, const int64_t* n_phones,
+                          const int64_t* seq_len, int T, int counters_kind, const float* p0, const float* p1, const int32_t* item_row, int n_rows,
+                          int norm_kind, float* raw_out, float* norm_out, int blocks_per_item, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

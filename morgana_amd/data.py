@@ -744,6 +744,151 @@ def _check_f0_specs(f0_specs, first):
             raise TypeError('f0_specs read %r, which is not a float32 (frames, features) array' % spec.source)
 
 
+class CountersSpec(object):
+    """How the frame-level positional features of one named feature are computed (``frame_counters``): ``source`` - the key of the integer
+    durations in the utterances, ``(P,)`` / ``(P, 1)`` phone durations or ``(P, S)`` state durations - and ``kind``, 'full' (9 columns) or
+    'phone' (3 columns)."""
+
+    def __init__(self, source='dur', kind='full'):
+        if not source:
+            raise ValueError('CountersSpec: source=%r must be a feature name' % (source,))
+        if kind not in ops.COUNTERS_KINDS:
+            raise ValueError("CountersSpec: kind must be 'full' or 'phone', got %r" % (kind,))
+        self.source, self.kind = source, kind
+
+    @property
+    def columns(self):
+        return ops.COUNTERS_KINDS[self.kind][1]
+
+    def __repr__(self):
+        return 'CountersSpec(source=%r, kind=%r)' % (self.source, self.kind)
+
+
+def _host_durations(dur, what='frame_counters'):
+    """Integer durations ``(P,)``, ``(P, 1)`` or ``(P, S)`` as a non-negative int64 ``(P, S)`` array."""
+    d = np.asarray(dur)
+    if not np.issubdtype(d.dtype, np.integer):
+        raise TypeError('%s: durations must be integers, got %s' % (what, d.dtype))
+    if d.ndim == 1:
+        d = d.reshape(-1, 1)
+    if d.ndim != 2 or d.shape[1] == 0:
+        raise ValueError('%s: host durations must be (phones,), (phones, 1) or (phones, states), got shape %s' % (what, np.shape(dur)))
+    if (d < 0).any():
+        raise ValueError('%s: negative durations' % what)
+    return d.astype(np.int64)
+
+
+_HOST_COUNTERS_CHUNK = 1 << 18
+
+
+def _host_frame_counters(dur, kind):
+    """The arithmetic of mg_frame_counters_f32 in NumPy for one item: integers in int64, every quotient one float64 division rounded
+    once to float32, integer columns converted directly."""
+    if kind not in ops.COUNTERS_KINDS:
+        raise ValueError("frame_counters: kind must be 'full' or 'phone', got %r" % (kind,))
+    d = _host_durations(dur)
+    n_phones, n_states = d.shape
+    flat = d.ravel()
+    ends = np.cumsum(flat)                                # of every segment, in (phone, state) order
+    starts = ends - flat
+    phone_starts, phone_lens = starts[::n_states], d.sum(axis=1)
+    total = int(flat.sum())
+    out = np.empty((total, ops.COUNTERS_KINDS[kind][1]), dtype=np.float32)
+
+    def ratio(num, den):
+        return (num.astype(np.float64) / den.astype(np.float64)).astype(np.float32)
+
+    for lo in range(0, total, _HOST_COUNTERS_CHUNK):      # (in chunks of frames: the temporaries of a very long item stay small)
+        frame = np.arange(lo, min(lo + _HOST_COUNTERS_CHUNK, total))
+        segment = np.searchsorted(ends, frame, side='right')        # the first segment that ends behind the frame: empty ones are stepped over
+        phone = segment // n_states
+        n_p, j = phone_lens[phone], frame - phone_starts[phone]
+        rows = out[frame[0]:frame[-1] + 1]
+        if kind == 'phone':
+            rows[:, 0], rows[:, 1], rows[:, 2] = ratio(j + 1, n_p), ratio(n_p - j, n_p), n_p
+            continue
+        n_s, i, state = flat[segment], frame - starts[segment], segment - phone * n_states
+        rows[:, 0], rows[:, 1], rows[:, 2] = ratio(i + 1, n_s), ratio(n_s - i, n_s), n_s
+        rows[:, 3], rows[:, 4], rows[:, 5] = state + 1, n_states - state, n_p
+        rows[:, 6], rows[:, 7], rows[:, 8] = ratio(n_s, n_p), ratio(n_p - j, n_p), ratio(j + 1, n_p)
+    return out
+
+
+def frame_counters(dur, kind='full', seq_len=None, n_phones=None, max_len=None):
+    """Frame-level positional features from durations: the ``counters`` feature the acoustic models of the reference read
+    (models/RNN_SPSS.py:65) and get as files from ``tts_data_tools``.  ``dur[p, s]`` are integer durations in frames of P phones with S
+    sub-phone states each (S = 1: a phone-level alignment, 5: HTS state alignments).  Segment (p, s) starts at ``start[p, s]``, the sum
+    of all durations before it in (p, s) order; a zero-length segment or phone owns no frame.  For frame t of segment (p, s), with
+    ``i = t - start[p, s]``, ``n_s = dur[p, s]``, ``j = t - start[p, 0]`` and ``n_p = sum_s dur[p, s]``:
+
+    ``kind='full'``, 9 columns: ``(i+1)/n_s``, ``(n_s-i)/n_s``, ``n_s``, ``s+1``, ``S-s``, ``n_p``, ``n_s/n_p``, ``(n_p-j)/n_p``, ``(j+1)/n_p`` -
+    fraction through the state forwards and backwards, state length, state index forwards and backwards, phone length, the state's
+    share of the phone, fraction through the phone backwards and forwards.  This is Merlin's ``subphone_feats='full'``.
+    ``kind='phone'``, 3 columns: ``(j+1)/n_p``, ``(n_p-j)/n_p``, ``n_p`` - Merlin's ``minimal_phoneme``; state boundaries play no part.
+
+    Every quotient is taken in float64 from the two integers and rounded once to float32; integer columns are converted directly.  For
+    phone lengths below 2^24 that is the correctly rounded float32 of the exact rational (double rounding through 53 bits is innocuous
+    for a quotient of two 24-bit operands); above that no exactness claim is made.
+
+    A NumPy integer array ``(P,)``, ``(P, 1)`` or ``(P, S)`` is computed on the host and gives ``(sum of durations, C)``; negative
+    durations are refused there.  A device int64 tensor ``(B, P)`` or ``(B, P, S)`` goes through the HIP kernel (csrc/counters.hip), read
+    in place through its strides, and gives ``(B, T, C)``: the same bits.  On the device a negative duration owns no frame (as in
+    ``upsample_to_repetitions``), ``n_phones`` (B,) drops the phones from ``n_phones[b]`` on, and the frames of item b below
+    ``min(T, its sum of durations, seq_len[b])`` hold counters, all others zeros.  ``max_len`` supplies T when the caller knows it (the
+    padded target length); without it T is the largest sum of durations, at the cost of one device -> host read.  There is no backward.
+
+    That 'full' is what the ``counters`` files of ``tts_data_tools`` hold - nine columns, in Merlin's order - could not be verified: the
+    package is not vendored with the reference.  It is a stated choice, not a matched one."""
+    if isinstance(dur, np.ndarray):
+        if seq_len is not None or n_phones is not None or max_len is not None:
+            raise ValueError('frame_counters: seq_len, n_phones and max_len go with a batched device tensor; a host array is one whole item')
+        return _host_frame_counters(dur, kind)
+    if not isinstance(dur, torch.Tensor):
+        raise TypeError('frame_counters takes a NumPy array or a device tensor, got %s' % type(dur))
+    if dur.is_floating_point() or dur.dtype == torch.bool:
+        raise TypeError('frame_counters: durations must be an integer tensor, got %s' % dur.dtype)
+    if dur.dim() not in (2, 3):
+        raise ValueError('frame_counters: a tensor must be (batch, phones) or (batch, phones, states), got %s' % (tuple(dur.shape),))
+    if not dur.is_cuda:
+        from ._lib import MorganaHipError
+        raise MorganaHipError('frame_counters takes NumPy arrays (host) or device tensors; got a tensor on %s (no CPU fallback for the '
+                              'device path)' % dur.device)
+    dur = dur if dur.dtype == torch.int64 else dur.long()
+    batch_size = dur.shape[0]
+    if seq_len is not None:
+        seq_len = seq_len.to(device=dur.device, dtype=torch.int64).reshape(-1)
+    if n_phones is not None:
+        n_phones = n_phones.to(device=dur.device, dtype=torch.int64).reshape(-1)
+    if max_len is None:
+        _, tmax = ops.upsample_lengths(dur.reshape(batch_size, -1))
+        max_len = int(tmax.item())
+    return ops.frame_counters(dur, t=int(max_len), kind=kind, seq_len=seq_len, n_phones=n_phones)[0]
+
+
+def _counter_specs_of(utterances, counter_specs):
+    """The {feature name: CountersSpec} a loader applies: the argument, or what the data sources of a ``FilesDataset`` ask for."""
+    if counter_specs is None:
+        return utterances.counter_specs() if isinstance(utterances, FilesDataset) else {}
+    return dict(counter_specs)
+
+
+def _check_counter_specs(counter_specs, first):
+    """Refuse a first utterance that carries what ``counter_specs`` computes, or lacks the durations they read."""
+    for name, spec in counter_specs.items():
+        if name in first:
+            raise ValueError('%r is in the utterances and in counter_specs: it is read from files or computed, not both' % name)
+        if spec.source not in first:
+            raise KeyError('counter_specs read %r for %r, which the utterances do not have' % (spec.source, name))
+        dur = first[spec.source]
+        if not (isinstance(dur, np.ndarray) and dur.ndim in (1, 2) and np.issubdtype(dur.dtype, np.integer)):
+            raise TypeError('counter_specs read %r, which is not an integer (phones,), (phones, 1) or (phones, states) array' % spec.source)
+
+
+def _host_frame_total(dur):
+    """Frames the durations of one utterance add up to, a negative duration owning none (what the kernel counts)."""
+    return int(np.clip(np.asarray(dur), 0, None).sum())
+
+
 class _Staging(object):
     """Pinned host staging for the loader's packed features: per (device, feature) TWO buffers used in turn - the copy of the batch
     before last has certainly been issued when a buffer comes round again, and its event says when it has finished - grown
@@ -882,7 +1027,26 @@ def _device_f0(out, name, spec, packed, offsets, t, normaliser, delta_spec, devi
         _device_deltas(out, name, track, offsets, t, delta_spec, normaliser, device)
 
 
-def collate_to_device(batch, normalisers, device, bf16_tables=(), delta_specs=None, f0_specs=None):
+def _device_counters(out, name, spec, batch, normaliser, device):
+    """``out[name]`` and - where ``normaliser`` is one - ``out['normalised_' + name]`` from the durations ``out[spec.source]`` that are on
+    the device already: one mg_frame_counters_f32 launch, nothing more crosses PCIe.  With ``n_frames`` in the utterances the output is
+    as long as every other frame-level feature of the batch and cut to each utterance's ``n_frames``; otherwise it is as long as the
+    largest sum of durations (taken on the host)."""
+    dur = out[spec.source]
+    dur = dur if dur.dtype == torch.int64 else dur.long()
+    if FRAME_COUNT_KEY in batch[0]:
+        t, seq_len = max(int(item[FRAME_COUNT_KEY]) for item in batch), out[FRAME_COUNT_KEY].reshape(-1)
+        seq_len = seq_len if seq_len.dtype == torch.int64 else seq_len.long()
+    else:
+        t, seq_len = max(_host_frame_total(item[spec.source]) for item in batch), None
+    kind, p0, p1, item_row = _normaliser_operands(out, name, normaliser, device)
+    raw, norm = ops.frame_counters(dur, t=t, kind=spec.kind, seq_len=seq_len, p0=p0, p1=p1, norm_kind=kind, item_row=item_row)
+    out[name] = raw
+    if norm is not None:
+        out['normalised_' + name] = norm
+
+
+def collate_to_device(batch, normalisers, device, bf16_tables=(), delta_specs=None, f0_specs=None, counter_specs=None):
     """``load_utterance`` + ``collate_fn`` + ``to_device`` for a list of RAW per-utterance feature dicts, with the float
     sequence features normalised and zero padded on the device (reference: data.py:119-127, 159-224, 648-663).
 
@@ -904,12 +1068,21 @@ def collate_to_device(batch, normalisers, device, bf16_tables=(), delta_specs=No
     ``f0_specs``: {feature name: ``F0Spec``}.  The raw F0 track ``spec.source`` is uploaded once and one launch (mg_continuous_lf0_f32,
     csrc/f0.hip) writes ``name`` - the continuous log-F0 - ``normalised_name`` where ``name`` has a normaliser, and ``spec.vuv``; when
     ``delta_specs`` names the feature too, the same launch leaves the packed continuous track and the delta launch reads that.  The raw
-    track is not emitted.  A batch that already carries ``name`` or ``spec.vuv`` is refused (ValueError): each is read or computed."""
+    track is not emitted.  A batch that already carries ``name`` or ``spec.vuv`` is refused (ValueError): each is read or computed.
+
+    ``counter_specs``: {feature name: ``CountersSpec``}.  Once the integer features are on the device one launch (mg_frame_counters_f32,
+    csrc/counters.hip) writes ``name`` - the frame-level positional features of the durations ``spec.source`` - and ``normalised_name``
+    where ``name`` has a normaliser (plain or speaker dependent): no ``{name}`` file is read and nothing more is uploaded.  The output is
+    as long as the batch's largest ``n_frames`` and cut to each utterance's ``n_frames`` when the utterances carry it, so that it agrees
+    with every other frame-level feature; otherwise as long as the largest sum of durations.  A batch that already carries ``name`` is
+    refused (ValueError): a feature is read or computed, not both; durations that are missing are a KeyError."""
     device = torch.device(device)
     bf16_tables = tuple(bf16_tables or ())
     delta_specs = dict(delta_specs or {})
     f0_specs = dict(f0_specs or {})
+    counter_specs = dict(counter_specs or {})
     _check_f0_specs(f0_specs, batch[0])
+    _check_counter_specs(counter_specs, batch[0])
     f0_sources = {}                                       # raw track -> the features computed from it
     for name, spec in f0_specs.items():
         f0_sources.setdefault(spec.source, []).append(name)
@@ -985,6 +1158,8 @@ def collate_to_device(batch, normalisers, device, bf16_tables=(), delta_specs=No
                 plain['normalised_' + key] = collate_fn([{key: normaliser.normalise(
                     item[key], *((item[SPEAKER_ID_KEY],) if sd else ())).astype(np.float32)} for item in batch])[key]
         out.update(_small_to_device(plain, device))
+    for name, spec in counter_specs.items():
+        _device_counters(out, name, spec, batch, normalisers.get(name) if normalisers is not None else None, device)
     for key in bf16_tables:                               # features that did not take the fused pass (no normaliser, host path; pair planes)
         name, _, kind = key.partition(':')
         suffix = X3_TABLE_SUFFIX if kind == 'x3' else BF16_TABLE_SUFFIX
@@ -1052,6 +1227,25 @@ class ContinuousLF0Source(object):
         return {self.f0_name: track.reshape(-1, 1) if track.ndim == 1 else track}
 
 
+class FrameCountersSource(object):
+    """The data source of a frame-level positional feature ``name`` (``counters``) for a corpus that holds durations and not the
+    ``counters`` files of ``tts_data_tools``: it loads NO file.  ``dur_name`` is a feature another data source provides - ``'dur'``, or a
+    ``'state_dur'`` ``(P, S)`` array loaded by ``NumpyBinarySource('state_dur')``.  The source carries ``counter_spec`` (a ``CountersSpec``:
+    ``kind`` - see ``frame_counters``): ``FilesDataset.__getitem__`` computes the feature on the host, the device loaders (``DeviceBatches``,
+    ``collate_to_device``, ``fit_normalisers``) on the device from the durations they upload anyway."""
+
+    use_deltas = False
+
+    def __init__(self, name='counters', dur_name='dur', kind='full'):
+        if name == dur_name:
+            raise ValueError('FrameCountersSource: name=%r and dur_name=%r must differ' % (name, dur_name))
+        self.name, self.dur_name = name, dur_name
+        self.counter_spec = CountersSpec(source=dur_name, kind=kind)
+
+    def __call__(self, base_name, data_dir):
+        return {}
+
+
 class TextSource(object):
     """``{data_dir}/{name}/{base_name}.txt`` holding one number -> ``{name: int}`` (or float): the sentence-level counts
     (``n_frames``, ``n_phones``) of the reference's data layout (README.rst:139-150)."""
@@ -1099,7 +1293,11 @@ class FilesDataset(object):
     loaders take ``delta_specs()`` and compute it on the device.
 
     A ``ContinuousLF0Source`` yields the raw F0 track only: ``raw`` has ``f0``, ``__getitem__`` adds ``lf0`` and ``vuv`` with the host
-    form of ``continuous_lf0``, then the deltas and the normalised twins, in that order, and the device loaders take ``f0_specs()``."""
+    form of ``continuous_lf0``, then the deltas and the normalised twins, in that order, and the device loaders take ``f0_specs()``.
+
+    A ``FrameCountersSource`` loads nothing: ``raw`` does not have ``counters``, ``__getitem__`` adds it with the host form of
+    ``frame_counters`` from the durations another source loaded, before the normalised twins, and the device loaders take
+    ``counter_specs()``."""
 
     def __init__(self, data_sources, data_dir, id_list, normalisers, data_root='.'):
         for name, normaliser in normalisers.items():
@@ -1126,6 +1324,10 @@ class FilesDataset(object):
         """{feature name: F0Spec} of the data sources that compute a continuous log-F0 from a raw F0 track."""
         return {name: source.f0_spec for name, source in self.data_sources.items() if getattr(source, 'f0_spec', None) is not None}
 
+    def counter_specs(self):
+        """{feature name: CountersSpec} of the data sources that compute frame-level positional features from durations."""
+        return {name: source.counter_spec for name, source in self.data_sources.items() if getattr(source, 'counter_spec', None) is not None}
+
     def raw(self, index):
         base_name = self.file_ids[index]
         features = {'name': base_name}
@@ -1144,6 +1346,10 @@ class FilesDataset(object):
             features[name], features[spec.vuv] = _host_continuous_lf0(features[spec.source], spec)
         for name, spec in self.delta_specs().items():
             features[name + DELTAS_SUFFIX] = compute_deltas(features[name], spec.windows, spec.edge)
+        counter_specs = self.counter_specs()
+        _check_counter_specs(counter_specs, features)
+        for name, spec in counter_specs.items():
+            features[name] = _host_frame_counters(features[spec.source], spec.kind)
         for name in self.data_sources:
             normaliser = self.normalisers.get(name)
             if normaliser is None or name == SPEAKER_ID_KEY:
@@ -1159,13 +1365,13 @@ class FilesDataset(object):
 
 
 def batch(data_generator, batch_size=32, shuffle=True, num_data_threads=0, device='cuda:0', bf16_tables=(), delta_specs=None,
-          f0_specs=None):
+          f0_specs=None, counter_specs=None):
     """The reference's ``data.batch`` (data.py:29-57) for a ``FilesDataset``: a loader of device-resident batches.  Files are read
     on the calling thread as each batch is formed (``num_data_threads`` is accepted for signature compatibility; worker
     subprocesses are the reference's answer to a host-bound collate, which here runs on the device)."""
     rng = np.random.RandomState(torch.initial_seed() % (2 ** 32)) if shuffle else None
     return DeviceBatches(data_generator, batch_size, data_generator.normalisers, device, shuffle=rng, bf16_tables=bf16_tables,
-                         delta_specs=delta_specs, f0_specs=f0_specs)
+                         delta_specs=delta_specs, f0_specs=f0_specs, counter_specs=counter_specs)
 
 
 class DeviceBatches(object):
@@ -1173,14 +1379,16 @@ class DeviceBatches(object):
     each batch padded and normalised there by ``collate_to_device``.  ``utterances`` is a ``FilesDataset`` (read lazily, batch by
     batch, through ``raw``) or a sequence of utterances that are already in host memory.
 
-    ``bf16_tables``, ``delta_specs``, ``f0_specs``: see ``collate_to_device``; ``delta_specs=None`` / ``f0_specs=None`` take what the data
-    sources of a ``FilesDataset`` ask for (``FilesDataset.delta_specs`` / ``f0_specs``).  ``utterances`` is a sequence of RAW per-utterance feature dicts (what a ``_DataSource`` returns: float32 ``(len, D)``
+    ``bf16_tables``, ``delta_specs``, ``f0_specs``, ``counter_specs``: see ``collate_to_device``; ``delta_specs=None`` / ``f0_specs=None`` /
+    ``counter_specs=None`` take what the data sources of a ``FilesDataset`` ask for (``FilesDataset.delta_specs`` / ``f0_specs`` /
+    ``counter_specs``).  ``utterances`` is a sequence of RAW per-utterance feature dicts (what a ``_DataSource`` returns: float32 ``(len, D)``
     arrays, integer ``dur``, python ints, the name); ``normalisers`` maps feature names to normalisers (``Normalisers`` or a
     dict).  Batches are contiguous slices in the given order, or a fresh permutation per epoch from ``shuffle`` = a
     ``numpy.random.RandomState`` (the reference shuffles with torch's global generator, data.py:50); the last, smaller batch
     is kept, as ``DataLoader`` does by default.  ``ExperimentBuilder.train_epoch`` takes it like any other loader."""
 
-    def __init__(self, utterances, batch_size, normalisers, device, shuffle=None, bf16_tables=(), delta_specs=None, f0_specs=None):
+    def __init__(self, utterances, batch_size, normalisers, device, shuffle=None, bf16_tables=(), delta_specs=None, f0_specs=None,
+                 counter_specs=None):
         if batch_size <= 0:
             raise ValueError('batch_size must be positive, got %r' % (batch_size,))
         self.utterances = utterances if isinstance(utterances, FilesDataset) else list(utterances)
@@ -1191,6 +1399,7 @@ class DeviceBatches(object):
         self.bf16_tables = tuple(bf16_tables or ())
         self.delta_specs = _delta_specs_of(self.utterances, delta_specs)
         self.f0_specs = _f0_specs_of(self.utterances, f0_specs)
+        self.counter_specs = _counter_specs_of(self.utterances, counter_specs)
 
     def use_bf16_tables(self, names):
         """The loader half of bf16 mode: every batch from now on carries the bf16 operand tables of these (normalised, phone-level)
@@ -1217,7 +1426,7 @@ class DeviceBatches(object):
             fetch = self.utterances.raw if isinstance(self.utterances, FilesDataset) else self.utterances.__getitem__
             batch = [fetch(int(i)) for i in order[start:start + self.batch_size]]
             yield collate_to_device(batch, self.normalisers, self.device, bf16_tables=self.bf16_tables, delta_specs=self.delta_specs,
-                                    f0_specs=self.f0_specs)
+                                    f0_specs=self.f0_specs, counter_specs=self.counter_specs)
 
 
 class ColumnStats(object):
@@ -1296,7 +1505,7 @@ def _fit_rows(utterance, key):
 
 
 def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out_dir=None, data_root='.', ddof=0, delta_specs=None,
-                    f0_specs=None):
+                    f0_specs=None, counter_specs=None):
     """Fit the parameters of ``normalisers`` (a ``Normalisers`` or a dict name -> normaliser of any of the four classes) to a corpus:
     the step that produces the ``{name}_mvn.json`` / ``{name}_minmax.json`` files (the reference gets them from ``tts_data_tools``).
 
@@ -1314,6 +1523,11 @@ def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out
     utterances: the raw F0 track ``spec.source`` is uploaded and mg_continuous_lf0_f32 (csrc/f0.hip) writes the packed continuous
     log-F0, over which the statistics of ``name`` - and, through mg_deltas_f32, of ``name + '_deltas'``, which must then be in
     ``delta_specs`` - are taken: ALL frames, the interpolated ones included, the Merlin convention.
+
+    ``counter_specs``: {feature name: ``CountersSpec``}, default what the data sources of a ``FilesDataset`` ask for.  ``name`` is not read
+    from the utterances: the durations ``spec.source`` are uploaded, mg_frame_counters_f32 (csrc/counters.hip) writes the padded
+    counters and ``ColumnStats.update_padded`` reads the frames below each utterance's sum of durations - what a ``counters`` file of the
+    utterance would hold.  Such a feature has no deltas.
 
     Raises ValueError before anything is set or written if a listed speaker has no frame or a fitted parameter is not finite.
     ``ddof``: see ``ColumnStats.result``.  Returns {feature: ColumnStats.result()} (the ``_deltas`` features under their own names)."""
@@ -1342,6 +1556,10 @@ def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out
     for name in f0_specs:
         if normalisers[name].use_deltas and name not in delta_specs:
             raise ValueError('%r is computed from %r: its deltas are computed too, name it in delta_specs' % (name, f0_specs[name].source))
+    counter_specs = {name: spec for name, spec in _counter_specs_of(utterances, counter_specs).items() if name in normalisers}
+    for name in counter_specs:
+        if normalisers[name].use_deltas:
+            raise ValueError('%r is computed from the durations %r: it has no deltas' % (name, counter_specs[name].source))
     stats = {}
     for start in range(0, len(utterances), batch_size):
         items = [fetch(i) for i in range(start, min(start + batch_size, len(utterances)))]
@@ -1354,9 +1572,22 @@ def fit_normalisers(utterances, normalisers, device='cuda:0', batch_size=64, out
         uploaded = {}                                     # the packed statics of this batch, for the features whose deltas are computed
         if start == 0:
             _check_f0_specs(f0_specs, items[0])
+            _check_counter_specs(counter_specs, items[0])
         for key, normaliser, is_deltas in features:
             by_speaker = isinstance(normaliser, _SpeakerDependentNormaliser)
             base = key[:-len(DELTAS_SUFFIX)] if is_deltas else key
+            if key in counter_specs:                      # the durations -> padded counters on the device, in place of a file's rows
+                spec = counter_specs[key]
+                durs = [_host_durations(item[spec.source], 'fit_normalisers') for item in items]
+                lens = np.array([int(d.sum()) for d in durs], dtype=np.int64)
+                small = collate_fn([{'dur': d} for d in durs])
+                small['lens'] = torch.from_numpy(lens)
+                small = _small_to_device(small, device)
+                padded, _ = ops.frame_counters(small['dur'], t=int(lens.max()), kind=spec.kind)
+                if key not in stats:
+                    stats[key] = ColumnStats(padded.shape[2], groups=len(order) if by_speaker else 1, device=device)
+                stats[key].update_padded(padded, small['lens'], item_row if by_speaker else None)
+                continue
             if is_deltas and base in delta_specs:
                 if key in items[0]:
                     raise ValueError('%r is in the utterances and in delta_specs: deltas are read from files or computed, not both' % key)

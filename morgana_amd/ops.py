@@ -3266,6 +3266,71 @@ def continuous_lf0(x, *, offsets=None, seq_len=None, t=None, packed_rows=None, w
     return padded, norm, vuv, packed
 
 
+COUNTERS_KINDS = {'full': (_lib.MG_COUNTERS_FULL, _lib.MG_COUNTERS_FULL_COLS), 'phone': (_lib.MG_COUNTERS_PHONE, _lib.MG_COUNTERS_PHONE_COLS)}
+
+
+def frame_counters(dur, *, t, kind='full', seq_len=None, n_phones=None, p0=None, p1=None, norm_kind=None, item_row=None, want_raw=True,
+                   blocks_per_item=None):
+    """Frame-level positional features of integer durations (csrc/counters.hip, mg_frame_counters_f32), one launch.  ``dur`` int64
+    (B, P) or (B, P, S) - P phones of S sub-phone states - is read in place through its strides (a ``[..., 0]`` view, a transposed view
+    and a slice are not copied); a negative duration owns no frame.  For frame ``t`` of segment (p, s), i frames into the state and j
+    frames into the phone, with n_s / n_p the state's / phone's length:
+
+    ``kind='full'`` (9 columns): (i+1)/n_s, (n_s-i)/n_s, n_s, s+1, S-s, n_p, n_s/n_p, (n_p-j)/n_p, (j+1)/n_p;
+    ``kind='phone'`` (3 columns): (j+1)/n_p, (n_p-j)/n_p, n_p - every quotient a float64 division rounded once to float32.
+
+    Output (B, t, C): frames below min(t, the item's sum of durations, ``seq_len[b]`` if given) hold the counters, every other frame
+    zeros; ``n_phones`` (B,) int64 drops the phones from n_phones[b] on.  ``norm_kind`` (NORM_MVN / NORM_MINMAX) with p0 / p1 (C,) adds
+    the normalised twin; with ``item_row`` (B,) int32 they are tables (S, C) and item b takes row item_row[b] (NaN for an index outside
+    [0, S)).  ``blocks_per_item``: workgroups per item (None: the library's choice; the bits do not depend on it).
+    Returns (raw or None, normalised or None)."""
+    lib = _lib.load()
+    dur = _require(dur, torch.int64, 'dur', contiguous=False)
+    if kind not in COUNTERS_KINDS:
+        raise ValueError("frame_counters: kind must be 'full' or 'phone', got %r" % (kind,))
+    code, c = COUNTERS_KINDS[kind]
+    if dur.dim() not in (2, 3):
+        raise ValueError('frame_counters: dur must be (B, P) or (B, P, S), got %s' % (tuple(dur.shape),))
+    b, p = dur.shape[0], dur.shape[1]
+    s = dur.shape[2] if dur.dim() == 3 else 1
+    strides = (dur.stride(0), dur.stride(1), dur.stride(2) if dur.dim() == 3 else 0)
+    if p == 0 or s == 0 or p * s > MAX_PHONES:
+        raise ValueError('frame_counters: %d phones of %d states per utterance, the kernel takes 1..%d segments' % (p, s, MAX_PHONES))
+    if min(strides) < 0:
+        raise ValueError('frame_counters: dur has a negative stride %s' % (strides,))
+    if int(t) < 0:
+        raise ValueError('frame_counters: a negative output size t=%r' % (t,))
+    seq_len = _lengths(seq_len, b, 'frame_counters: ')
+    if n_phones is not None:
+        n_phones = _require(n_phones, torch.int64, 'n_phones')
+        if tuple(n_phones.shape) != (b,):
+            raise ValueError('frame_counters: n_phones must be (B,) = (%d,), got %s' % (b, tuple(n_phones.shape)))
+    if norm_kind is None and (want_raw is False or p0 is not None or p1 is not None or item_row is not None):
+        raise ValueError('frame_counters: normaliser parameters, item_row and want_raw=False go with a norm_kind (NORM_MVN or NORM_MINMAX)')
+    rows = 0
+    if norm_kind is not None:
+        if norm_kind not in (NORM_MVN, NORM_MINMAX):
+            raise ValueError('frame_counters: norm_kind %r is not NORM_MVN or NORM_MINMAX' % (norm_kind,))
+        if item_row is not None:
+            p0, p1, item_row = _item_tables(p0, p1, item_row, b, c, 'frame_counters')
+            rows = p0.shape[0]
+        else:
+            p0 = _require(p0, torch.float32, 'param0')
+            p1 = _require(p1, torch.float32, 'param1')
+            if p0.numel() != c or p1.numel() != c:
+                raise ValueError('normaliser parameters have %d / %d entries, %r counters have %d columns' % (p0.numel(), p1.numel(), kind, c))
+    if blocks_per_item is not None and int(blocks_per_item) < 1:
+        raise ValueError('frame_counters: blocks_per_item=%r must be positive' % (blocks_per_item,))
+    raw = torch.empty((b, int(t), c), dtype=torch.float32, device=dur.device) if want_raw else None
+    norm = torch.empty((b, int(t), c), dtype=torch.float32, device=dur.device) if norm_kind is not None else None
+    if b == 0 or int(t) == 0:           # empty outputs: no address to hand the library
+        return raw, norm
+    _lib.check(lib.mg_frame_counters_f32(_p(dur), b, p, s, strides[0], strides[1], strides[2], _p(n_phones), _p(seq_len), int(t), code,
+                                         _p(p0), _p(p1), _p(item_row), rows, -1 if norm_kind is None else norm_kind, _p(raw), _p(norm),
+                                         0 if blocks_per_item is None else int(blocks_per_item), _stream()), 'mg_frame_counters_f32')
+    return raw, norm
+
+
 # ---------------------------------------------------------------------------------------------- phone-rate first layer
 # MORGANA_PHONE_RATE=0: every product at frame rate (the reference's order of operations).  This is only the DEFAULT of a per-call
 # choice: utils.upsample_to_repetitions(..., phone_rate=) records the choice on the lazy sequence it returns, the layers that consume
