@@ -23,6 +23,7 @@
 // [first, last) is read.  Wide odd features (lcm(D, 4) > 1024: D = 609 -> W = 2436) take several quads per thread, one after the
 // other.  Launch 2 reads the job records (8 + 24 D bytes each, at most COLSTATS_MAX_JOBS of them) and the state.
 #include "common.h"
+#include "item_norm.h"
 #include "moments.h"      // the accumulator, the streaming pass, the tree and Chan's update; no fp pragma in front of it, on purpose
 
 #define COLSTATS_THREADS 256
@@ -121,15 +122,7 @@ __global__ __launch_bounds__(COLSTATS_THREADS) void colstats_partial_kernel(cons
     float* rec_max = rec_min + D;
 
     int64_t lo, len;
-    if (offsets) {
-        lo = offsets[b];
-        len = offsets[b + 1] - lo;
-    } else {
-        lo = (int64_t)b * T;
-        len = seq_len[b];
-        if (len > T) len = T;
-    }
-    if (len < 0) len = 0;
+    mg_item_rows(offsets, seq_len, T, b, lo, len);
     const int RS = W / D;                                    // frames per step
     const int64_t NS = (len + RS - 1) / RS;                  // steps of the item
     if (c >= NS) {                                           // workgroup-uniform: nothing of this item is ours
@@ -267,8 +260,7 @@ size_t mg_column_stats_workspace_bytes(int B, int64_t max_rows, int D) {
 
 int mg_column_stats_f32(const float* x, int64_t ld, int D, int B, int T, const int64_t* offsets, const int64_t* seq_len,
                         const int32_t* item_row, int S, double* state, void* workspace, size_t workspace_bytes, void* stream) {
-    MG_CHECK_ARG((offsets != NULL) != (seq_len != NULL),
-                 "mg_column_stats_f32: exactly one of offsets (packed rows) and seq_len (padded (B, T, D)) must be given");
+    MG_CHECK_ONE_LAYOUT("mg_column_stats_f32", offsets, seq_len, "(B, T, D)");
     MG_CHECK_ARG(D > 0 && D <= MG_COLSTATS_MAX_D, "mg_column_stats_f32: D=%d not in 1..%d", D, MG_COLSTATS_MAX_D);
     MG_CHECK_ARG(S > 0 && S <= 65535, "mg_column_stats_f32: S=%d groups not in 1..65535", S);
     MG_CHECK_ARG(S == 1 || item_row, "mg_column_stats_f32: S=%d groups need item_row", S);

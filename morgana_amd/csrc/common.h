@@ -19,6 +19,18 @@ void mg_set_error(const char* fmt, ...);
         }                                \
     } while (0)
 
+// The checks the data-path entry points share (`name`, `label` and `padded` are string literals: the message names its entry point).
+// A ragged input comes in exactly one layout: packed rows with offsets, or a padded batch `padded` with seq_len.
+#define MG_CHECK_ONE_LAYOUT(name, offsets, seq_len, padded)          \
+    MG_CHECK_ARG(((offsets) != NULL) != ((seq_len) != NULL),         \
+                 name ": exactly one of offsets (packed rows) and seq_len (padded " padded ") must be given")
+// A normalised twin needs both parameter operands and a forward kind.
+#define MG_CHECK_NORM_TWIN(name, norm_out, p0, p1, kind)                                                          \
+    MG_CHECK_ARG(!(norm_out) || ((p0) && (p1) && ((kind) == MG_NORM_MVN || (kind) == MG_NORM_MINMAX)),            \
+                 name ": a normalised output needs parameters and kind MG_NORM_MVN or MG_NORM_MINMAX (kind=%d)", kind)
+// item_row indexes tables of `rows` rows (the argument the entry point calls `label`).
+#define MG_CHECK_PARAM_ROWS(name, label, item_row, rows) MG_CHECK_ARG(!(item_row) || (rows) > 0, name ": " label "=%d parameter rows", rows)
+
 // Call right after a kernel launch: turns a launch-time error into MG_ELAUNCH.
 #define MG_CHECK_LAUNCH(name)                                                          \
     do {                                                                               \

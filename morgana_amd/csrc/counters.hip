@@ -29,13 +29,7 @@
 #define CNT_MAX_ITEM_BLOCKS 65535
 #define CNT_CHUNK_ELEMS 768       // output elements of one workgroup by default, three per thread: measured, DESIGN.md 4.27
 
-// the normaliser arithmetic of normalise_kernel (csrc/loss_norm.hip), kind MG_NORM_MVN or MG_NORM_MINMAX
-__device__ __forceinline__ float cnt_norm(float v, float a, float b, int kind) {
-    if (kind == MG_NORM_MVN) return (v - a) / (b + 1e-8f);
-    float scale = b - a;
-    if (fabsf(scale) <= 1e-8f) scale = 1.f;
-    return (v - a) / scale;
-}
+#include "item_norm.h"      // after the pragma: the normalised twin is mg_normalise_f32's float arithmetic on the rounded counter
 
 __device__ __forceinline__ float cnt_ratio(int num, int den) { return (float)((double)num / (double)den); }
 
@@ -101,14 +95,7 @@ __global__ __launch_bounds__(CNT_THREADS) void frame_counters_kernel(const int64
             if (len < valid) valid = len < 0 ? 0 : len;
         }
         const float *q0 = p0, *q1 = p1;
-        bool row_ok = true;
-        if (norm_out && item_row) {                                           // a bad row index never becomes an index: NaN in the valid frames
-            const int row = item_row[b];
-            row_ok = row >= 0 && row < n_rows;
-            const int64_t at = row_ok ? (int64_t)row * C : 0;
-            q0 += at;
-            q1 += at;
-        }
+        const bool row_ok = !norm_out || mg_item_param_rows(item_row, b, n_rows, C, q0, q1);      // false: NaN in the valid frames
         const int64_t base = (int64_t)b * elems;
         for (int64_t e = e_lo + tid; e < e_hi; e += CNT_THREADS) {
             const int t = (int)(e / C), c = (int)(e - (int64_t)t * C);
@@ -139,7 +126,7 @@ __global__ __launch_bounds__(CNT_THREADS) void frame_counters_kernel(const int64
                 } else {
                     v = c == 0 ? cnt_ratio(j + 1, n_p) : (c == 1 ? cnt_ratio(n_p - j, n_p) : (float)n_p);
                 }
-                if (norm_out) w = row_ok ? cnt_norm(v, q0[c], q1[c], norm_kind) : __builtin_nanf("");
+                if (norm_out) w = row_ok ? mg_norm_forward(v, q0[c], q1[c], norm_kind) : __builtin_nanf("");
             }
             if (raw_out) raw_out[base + e] = v;
             if (norm_out) norm_out[base + e] = w;
@@ -158,9 +145,8 @@ int mg_frame_counters_f32(const int64_t* dur, int B, int P, int S, int64_t strid
     MG_CHECK_ARG(stride_b >= 0 && stride_p >= 0 && stride_s >= 0, "mg_frame_counters_f32: negative strides (%lld, %lld, %lld)",
                  (long long)stride_b, (long long)stride_p, (long long)stride_s);
     MG_CHECK_ARG(raw_out || norm_out, "mg_frame_counters_f32: no output requested");
-    MG_CHECK_ARG(!norm_out || (p0 && p1 && (norm_kind == MG_NORM_MVN || norm_kind == MG_NORM_MINMAX)),
-                 "mg_frame_counters_f32: a normalised output needs parameters and kind MG_NORM_MVN or MG_NORM_MINMAX (kind=%d)", norm_kind);
-    MG_CHECK_ARG(!item_row || n_rows > 0, "mg_frame_counters_f32: n_rows=%d parameter rows", n_rows);
+    MG_CHECK_NORM_TWIN("mg_frame_counters_f32", norm_out, p0, p1, norm_kind);
+    MG_CHECK_PARAM_ROWS("mg_frame_counters_f32", "n_rows", item_row, n_rows);
     MG_CHECK_ARG(blocks_per_item >= 0, "mg_frame_counters_f32: blocks_per_item=%d must not be negative (0: the library's choice)", blocks_per_item);
     const int C = counters_kind == MG_COUNTERS_FULL ? MG_COUNTERS_FULL_COLS : MG_COUNTERS_PHONE_COLS;
     MG_CHECK_ARG(B == 0 || T == 0 || (int64_t)T <= INT64_MAX / 4 / C / B, "mg_frame_counters_f32: B=%d x T=%d x C=%d overflow 64 bits", B, T, C);

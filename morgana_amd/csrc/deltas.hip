@@ -6,18 +6,19 @@
 //
 // Numerics.  Every output element: the products coeff * x in float64, taps in ascending k, the first product starting the sum and
 // every later one added with one rounding each (no contraction into an fma: the NumPy restatement of data.compute_deltas has none),
-// the sum rounded once to float32.  The normalised twin is mg_normalise_f32's float arithmetic on that rounded value.  A tap outside
+// the sum rounded once to float32.  The normalised twin is mg_normalise_f32's float arithmetic (csrc/item_norm.h) on that rounded value.  A tap outside
 // [0, len) reads the item's first / last frame (MG_DELTAS_EDGE_REPLICATE) or is left out (MG_DELTAS_EDGE_ZERO: exactly W_w).
 //
 // Memory.  One streaming pass: every input frame is read from memory once (its neighbours t +- 1, t +- 2 come from L1 / L2: nothing
 // is staged in LDS), every output element written once, no atomics, no workspace.  The DESTINATION rows are cut into flat chunks of
 // mg_deltas_chunk_rows(D) rows (DELTAS_CHUNK_ELEMS input elements, DELTAS_CHUNK_ELEMS_NARROW when D % 4 != 0); a chunk finds its first item by a binary search in the items'
-// first destination rows (packed output; padded output: a division) and walks the item pieces inside it, as csrc/unpad.hip does.
+// first destination rows (packed output; padded output: a division) - mg_item_at of csrc/item_norm.h, as csrc/unpad.hip - and walks the item pieces inside it.
 // Inside a piece the item - its length, its source rows, its parameter row - is uniform for the workgroup.  16-byte loads and
 // stores when D % 4 == 0 and every base is 16-byte aligned, one element per access otherwise.  64-bit element indices throughout.
 // A padded input whose output is packed has no offsets to search: every workgroup scans the clamped lengths once in LDS
 // (B <= MG_DELTAS_MAX_SCAN_ITEMS), the only use of LDS here.
 #include "common.h"
+#include "item_norm.h"
 #include "seq_reduce.h"
 
 #define DELTAS_THREADS 256
@@ -42,7 +43,9 @@ static inline int deltas_chunk_rows(int D) {
     return D >= elems ? 1 : elems / D;
 }
 
-// the normaliser arithmetic of normalise_kernel (csrc/loss_norm.hip), kind MG_NORM_MVN or MG_NORM_MINMAX
+// mg_norm_forward (csrc/item_norm.h) written out: the same float operations in the same order.  Left here because with the shared
+// function, in any form tried, hipcc allocates deltas_kernel<4, *> other registers than it had (45 / 44 / 44 or 60 / 59 / 57, not
+// 46 / 45 / 45); tests/test_gpu_deltas.py holds the two to the same bits.
 __device__ __forceinline__ float deltas_norm(float v, float a, float b, int kind) {
     if (kind == MG_NORM_MVN) return (v - a) / (b + 1e-8f);
     float scale = b - a;
@@ -79,46 +82,21 @@ __global__ __launch_bounds__(DELTAS_THREADS) void deltas_kernel(const float* __r
     for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const int64_t c_lo = c * chunk_rows;
         const int64_t c_hi = c_lo + chunk_rows < out_rows ? c_lo + chunk_rows : out_rows;
-        // the item that holds destination row c_lo: the smallest b whose rows end behind it
-        int b;
-        if (MODE == DELTAS_TO_PADDED) {
-            b = (int)(c_lo / T_out);
-        } else {
-            int top = B;
-            b = 0;
-            while (b < top) {
-                const int mid = (b + top) >> 1;
-                if (deltas_first_row<MODE>(mid + 1, T_out, offsets, s_cum) <= c_lo) b = mid + 1; else top = mid;
-            }
-        }
+        const auto first_of = [&](int b) { return deltas_first_row<MODE>(b, T_out, offsets, s_cum); };
+        // the item that holds destination row c_lo, then the item pieces inside the chunk
+        int b = MODE == DELTAS_TO_PADDED ? (int)(c_lo / T_out) : mg_item_at(B, c_lo, first_of);
         for (; b < B; ++b) {
-            const int64_t i_lo = deltas_first_row<MODE>(b, T_out, offsets, s_cum);
-            const int64_t i_hi = deltas_first_row<MODE>(b + 1, T_out, offsets, s_cum);
+            const int64_t i_lo = first_of(b), i_hi = first_of(b + 1);
             if (i_lo >= c_hi) break;
             const int64_t p_lo = i_lo > c_lo ? i_lo : c_lo, p_hi = i_hi < c_hi ? i_hi : c_hi;
             if (p_hi <= p_lo) continue;                        // an empty item
             // the item: uniform for the workgroup
             int64_t first, len;
-            if (offsets) {
-                first = offsets[b];
-                len = offsets[b + 1] - first;
-            } else {
-                first = (int64_t)b * T_in;
-                len = seq_len[b];
-                if (len > T_in) len = T_in;
-            }
+            mg_item_rows(offsets, seq_len, T_in, b, first, len);
             if (MODE == DELTAS_TO_PADDED && len > T_out) len = T_out;      // cut to T_out frames, as mg_pad_normalise_f32 cuts it
-            if (len < 0) len = 0;
             const float* src = x + first * D;
             const float *q0 = p0, *q1 = p1;
-            bool row_ok = true;
-            if (norm_out && item_row) {                        // a bad row index never becomes an index: NaN in the valid frames
-                const int row = item_row[b];
-                row_ok = row >= 0 && row < S;
-                const int64_t at = row_ok ? (int64_t)row * WD : 0;
-                q0 += at;
-                q1 += at;
-            }
+            const bool row_ok = !norm_out || mg_item_param_rows(item_row, b, S, WD, q0, q1);      // false: NaN in the valid frames
             const int64_t t0 = p_lo - i_lo;
             const int64_t n_el = (p_hi - p_lo) * D;
             int64_t e = (int64_t)tid * VEC;
@@ -217,8 +195,7 @@ int mg_deltas_chunk_rows(int D) { return D > 0 ? deltas_chunk_rows(D) : 0; }
 int mg_deltas_f32(const float* x, int D, int B, const int64_t* offsets, const int64_t* seq_len, int T_in, int n_windows, const int* win_l,
                   const int* win_u, const double* win_coeff, int edge, const float* p0, const float* p1, const int32_t* item_row, int S,
                   int kind, int out_form, int64_t out_rows, float* raw_out, float* norm_out, void* stream) {
-    MG_CHECK_ARG((offsets != NULL) != (seq_len != NULL),
-                 "mg_deltas_f32: exactly one of offsets (packed rows) and seq_len (padded (B, T_in, D)) must be given");
+    MG_CHECK_ONE_LAYOUT("mg_deltas_f32", offsets, seq_len, "(B, T_in, D)");
     MG_CHECK_ARG(D > 0, "mg_deltas_f32: D=%d must be positive", D);
     MG_CHECK_ARG(B >= 0, "mg_deltas_f32: B=%d must not be negative", B);
     MG_CHECK_ARG(n_windows > 0 && n_windows <= DELTAS_MAX_WINDOWS, "mg_deltas_f32: 1..%d windows supported, got %d", DELTAS_MAX_WINDOWS,
@@ -245,9 +222,8 @@ int mg_deltas_f32(const float* x, int D, int B, const int64_t* offsets, const in
                  "mg_deltas_f32: out_rows=%lld (padded: frames per item, packed: rows) out of range", (long long)out_rows);
     MG_CHECK_ARG(offsets || T_in >= 0, "mg_deltas_f32: T_in=%d must not be negative", T_in);
     MG_CHECK_ARG(raw_out || norm_out, "mg_deltas_f32: no output requested");
-    MG_CHECK_ARG(!norm_out || (p0 && p1 && (kind == MG_NORM_MVN || kind == MG_NORM_MINMAX)),
-                 "mg_deltas_f32: a normalised output needs parameters and kind MG_NORM_MVN or MG_NORM_MINMAX (kind=%d)", kind);
-    MG_CHECK_ARG(!item_row || S > 0, "mg_deltas_f32: S=%d parameter rows", S);
+    MG_CHECK_NORM_TWIN("mg_deltas_f32", norm_out, p0, p1, kind);
+    MG_CHECK_PARAM_ROWS("mg_deltas_f32", "S", item_row, S);
     const int64_t WD = (int64_t)n_windows * D;
     int64_t total = out_rows;                                 // destination rows of the launch
     if (out_form == MG_DELTAS_OUT_PADDED) {

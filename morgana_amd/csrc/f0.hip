@@ -11,7 +11,8 @@
 //   vuv[t]    = voiced[t] ? 1 : 0
 //
 // all in float64 in exactly this order, rounded once; floating-point contraction is off, as the NumPy restatement
-// (data.continuous_lf0 on an array) has none.  The normalised twin is mg_normalise_f32's float arithmetic on the rounded value.
+// (data.continuous_lf0 on an array) has none.  The normalised twin is mg_normalise_f32's float arithmetic (csrc/item_norm.h) on the
+// rounded value.
 //
 // Mapping.  ONE WORKGROUP PER ITEM (grid-stride over the items); its four waves take the item column by column in trips of
 // F0_CHUNK_ROWS = 4 x 64 frames, one wave per 64-frame segment, lane = frame.  A wave ballots `voiced` over its segment; a lane finds
@@ -38,13 +39,7 @@
 #define F0_CHUNK_ROWS (F0_WAVES * F0_WAVE)
 #define F0_MAX_BLOCKS 65536
 
-// the normaliser arithmetic of normalise_kernel (csrc/loss_norm.hip), kind MG_NORM_MVN or MG_NORM_MINMAX
-__device__ __forceinline__ float f0_norm(float v, float a, float b, int kind) {
-    if (kind == MG_NORM_MVN) return (v - a) / (b + 1e-8f);
-    float scale = b - a;
-    if (fabsf(scale) <= 1e-8f) scale = 1.f;
-    return (v - a) / scale;
-}
+#include "item_norm.h"      // after the pragma: a forward kind is a subtraction and a division, nothing to contract
 
 __device__ __forceinline__ double f0_log(float x, int log_input) { return log_input ? (double)x : log((double)x); }
 
@@ -62,43 +57,28 @@ __global__ __launch_bounds__(F0_THREADS) void continuous_lf0_kernel(const float*
     const bool want_packed_rows = packed_out || (vuv_out && vuv_packed);
     for (int b = blockIdx.x; b < B; b += gridDim.x) {
         // the item: uniform for the workgroup
-        int64_t first, len, pfirst = 0;
-        if (offsets) {
-            first = offsets[b];
-            len = offsets[b + 1] - first;
-            pfirst = first;
-        } else {
-            first = (int64_t)b * T_in;
-            len = seq_len[b];
-            if (len > T_in) len = T_in;
-            if (want_packed_rows) {                            // its first packed row: the clamped lengths in front of it
-                int64_t part = 0;
-                for (int i = tid; i < b; i += F0_THREADS) {
-                    int64_t n = seq_len[i];
-                    if (n > T_in) n = T_in;
-                    if (n > 0) part += n;
-                }
-                __syncthreads();                               // (the previous item's readers of s_part are done)
-                s_part[tid] = part;
-                __syncthreads();
-                for (int half = F0_THREADS / 2; half > 0; half >>= 1) {
-                    if (tid < half) s_part[tid] += s_part[tid + half];
-                    __syncthreads();
-                }
-                pfirst = s_part[0];
+        int64_t first, len;
+        mg_item_rows(offsets, seq_len, T_in, b, first, len);
+        int64_t pfirst = offsets ? first : 0;
+        if (!offsets && want_packed_rows) {                    // a padded item's first packed row: the clamped lengths in front of it
+            int64_t part = 0;
+            for (int i = tid; i < b; i += F0_THREADS) {
+                int64_t n = seq_len[i];
+                if (n > T_in) n = T_in;
+                if (n > 0) part += n;
             }
+            __syncthreads();                                   // (the previous item's readers of s_part are done)
+            s_part[tid] = part;
+            __syncthreads();
+            for (int half = F0_THREADS / 2; half > 0; half >>= 1) {
+                if (tid < half) s_part[tid] += s_part[tid + half];
+                __syncthreads();
+            }
+            pfirst = s_part[0];
         }
-        if (len < 0) len = 0;
         const float* src = x + first * D;
         const float *q0 = p0, *q1 = p1;
-        bool row_ok = true;
-        if (norm_out && item_row) {                            // a bad row index never becomes an index: NaN in the valid frames
-            const int row = item_row[b];
-            row_ok = row >= 0 && row < S;
-            const int64_t at = row_ok ? (int64_t)row * D : 0;
-            q0 += at;
-            q1 += at;
-        }
+        const bool row_ok = !norm_out || mg_item_param_rows(item_row, b, S, D, q0, q1);      // false: NaN in the valid frames
         const int64_t n_seg = (len + F0_WAVE - 1) / F0_WAVE;
         for (int d = 0; d < D; ++d) {
             for (int64_t s = wave; s < n_seg; s += F0_WAVES) {       // uniform for the wave: every ballot below is taken by all 64 lanes
@@ -159,7 +139,7 @@ __global__ __launch_bounds__(F0_THREADS) void continuous_lf0_kernel(const float*
                 const int64_t at_packed = (pfirst + t) * D + d, at_padded = ((int64_t)b * out_rows + t) * D + d;
                 if (packed_out && in_packed) packed_out[at_packed] = v;
                 if (padded_out && in_padded) padded_out[at_padded] = v;
-                if (norm_out && in_padded) norm_out[at_padded] = row_ok ? f0_norm(v, q0[d], q1[d], kind) : __builtin_nanf("");
+                if (norm_out && in_padded) norm_out[at_padded] = row_ok ? mg_norm_forward(v, q0[d], q1[d], kind) : __builtin_nanf("");
                 if (vuv_out) {
                     if (vuv_packed) {
                         if (in_packed) vuv_out[at_packed] = flag;
@@ -189,8 +169,7 @@ int mg_continuous_lf0_f32(const float* x, int D, int B, const int64_t* offsets, 
                           float voiced_above, float fill, const float* p0, const float* p1, const int32_t* item_row, int S, int kind,
                           int64_t out_rows, int64_t packed_rows, float* packed_out, float* padded_out, float* norm_out, float* vuv_out,
                           int vuv_form, void* stream) {
-    MG_CHECK_ARG((offsets != NULL) != (seq_len != NULL),
-                 "mg_continuous_lf0_f32: exactly one of offsets (packed rows) and seq_len (padded (B, T_in, D)) must be given");
+    MG_CHECK_ONE_LAYOUT("mg_continuous_lf0_f32", offsets, seq_len, "(B, T_in, D)");
     MG_CHECK_ARG(D > 0, "mg_continuous_lf0_f32: D=%d must be positive", D);
     MG_CHECK_ARG(B >= 0, "mg_continuous_lf0_f32: B=%d must not be negative", B);
     MG_CHECK_ARG(offsets || T_in >= 0, "mg_continuous_lf0_f32: T_in=%d must not be negative", T_in);
@@ -204,9 +183,8 @@ int mg_continuous_lf0_f32(const float* x, int D, int B, const int64_t* offsets, 
                  "mg_continuous_lf0_f32: out_rows=%lld (frames per item of the padded outputs) out of range", (long long)out_rows);
     MG_CHECK_ARG(!any_packed || (packed_rows >= 0 && packed_rows <= INT64_MAX / 4 / D),
                  "mg_continuous_lf0_f32: packed_rows=%lld (rows of the packed outputs) out of range", (long long)packed_rows);
-    MG_CHECK_ARG(!norm_out || (p0 && p1 && (kind == MG_NORM_MVN || kind == MG_NORM_MINMAX)),
-                 "mg_continuous_lf0_f32: a normalised output needs parameters and kind MG_NORM_MVN or MG_NORM_MINMAX (kind=%d)", kind);
-    MG_CHECK_ARG(!item_row || S > 0, "mg_continuous_lf0_f32: S=%d parameter rows", S);
+    MG_CHECK_NORM_TWIN("mg_continuous_lf0_f32", norm_out, p0, p1, kind);
+    MG_CHECK_PARAM_ROWS("mg_continuous_lf0_f32", "S", item_row, S);
     MG_CHECK_ARG(!any_padded || B == 0 || out_rows == 0 || out_rows <= INT64_MAX / 4 / D / B,
                  "mg_continuous_lf0_f32: B=%d x T=%lld x D=%d overflow 64 bits", B, (long long)out_rows, D);
     MG_CHECK_ARG(offsets || B == 0 || T_in == 0 || (int64_t)T_in <= INT64_MAX / 4 / D / B,

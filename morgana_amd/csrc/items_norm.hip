@@ -5,9 +5,9 @@
 // item_row[b].  One kernel family (items_kernel) serves
 //   mg_normalise_items_f32       x (B, R, D) -> out, the four kinds of mg_normalise_f32;  grad_mode: d out / d x applied to a gradient
 //   mg_pad_normalise_items_f32   the device loader's pass (mg_pad_normalise_f32) with a row per utterance
-// with the per-element arithmetic of normalise_kernel / pad_normalise_kernel (csrc/loss_norm.hip): the same float operations in the
-// same order, so an item on speaker s gets bit for bit what mg_normalise_f32 gives with row s.  mg_item_rows_f32 gathers the rows
-// themselves ((B, D): what the per-item mode of mg_mlpg_f32 reads as variances' square roots).
+// with the per-element arithmetic of normalise_kernel / pad_normalise_kernel (csrc/loss_norm.hip): both files take the factor and the
+// element map from csrc/item_norm.h, so an item on speaker s gets bit for bit what mg_normalise_f32 gives with row s.
+// mg_item_rows_f32 gathers the rows themselves ((B, D): what the per-item mode of mg_mlpg_f32 reads as variances' square roots).
 //
 // Memory bound: one read and one write of x.  grid (chunks, B): a workgroup works on ONE item, so the item's two parameter rows
 // are staged once per workgroup in LDS as (offset, factor) - factor = the divisor or multiplier the kind derives from the row
@@ -17,6 +17,7 @@
 // An item_row entry outside [0, S) never indexes the tables: the workgroup stages NaN instead, so that item's output is NaN (the
 // host cannot look at a device index without a synchronisation).
 #include "common.h"
+#include "item_norm.h"      // no fp pragma in front of it, on purpose: the inverse kinds stay one fma, as in loss_norm.hip
 
 #define ITEMS_MAX_D 8192          // 2 x D floats of dynamic LDS (64 KB)
 #define ITEMS_CHUNK 4096          // elements of one item per workgroup and grid-stride step: 256 threads x 16
@@ -27,26 +28,12 @@ __device__ __forceinline__ void items_stage(const float* __restrict__ p0, const 
     for (int d = threadIdx.x; d < D; d += 256) {
         float off = __builtin_nanf(""), fac = __builtin_nanf("");
         if (row_ok) {
-            const float a = p0[d], b = p1[d];
-            off = a;
-            if (kind == MG_NORM_MVN) {
-                fac = b + 1e-8f;
-            } else if (kind == MG_DENORM_MVN) {
-                fac = b;
-            } else {
-                float scale = b - a;
-                if (fabsf(scale) <= 1e-8f) scale = 1.f;
-                fac = scale;
-            }
-            if (grad_mode) off = 0.f;
+            off = grad_mode ? 0.f : p0[d];
+            fac = mg_norm_factor(p0[d], p1[d], kind);
         }
         s_off[d] = off;
         s_fac[d] = fac;
     }
-}
-
-__device__ __forceinline__ float items_elem(float v, float off, float fac, bool inverse) {
-    return inverse ? v * fac + off : (v - off) / fac;
 }
 
 // PAD: x is the packed feature and offsets (B + 1) its utterances' first rows; frames past an utterance's length are zero in both
@@ -60,20 +47,18 @@ __global__ __launch_bounds__(256) void items_kernel(const float* __restrict__ x,
     float* s_off = s_par;
     float* s_fac = s_par + D;
     const int b = blockIdx.y;
-    const int row = item_row[b];
-    const int row_ok = row >= 0 && row < S;
-    const size_t at = row_ok ? (size_t)row * D : 0;
-    items_stage(p0 + at, p1 + at, row_ok, D, kind, grad_mode, s_off, s_fac);
+    const float *q0 = p0, *q1 = p1;
+    const bool row_ok = mg_item_param_rows(item_row, b, S, D, q0, q1);
+    items_stage(q0, q1, row_ok, D, kind, grad_mode, s_off, s_fac);
     __syncthreads();
-    const bool inverse = kind == MG_DENORM_MVN || kind == MG_DENORM_MINMAX;
+    const bool inverse = mg_norm_inverse(kind);
     const int64_t row_elems = R * D;
     int64_t valid = row_elems;
     const float* src = x + (size_t)b * row_elems;
     if (PAD) {
-        const int64_t lo = offsets[b];
-        int64_t len = offsets[b + 1] - lo;
+        int64_t lo, len;
+        mg_item_rows(offsets, nullptr, 0, b, lo, len);
         if (len > R) len = R;
-        if (len < 0) len = 0;
         valid = len * D;
         src = x + lo * D;
     }
@@ -92,7 +77,7 @@ __global__ __launch_bounds__(256) void items_kernel(const float* __restrict__ x,
                     const f32x4 off = *reinterpret_cast<const f32x4*>(s_off + d);
                     const f32x4 fac = *reinterpret_cast<const f32x4*>(s_fac + d);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) r[j] = items_elem(v[j], off[j], fac[j], inverse);
+                    for (int j = 0; j < 4; ++j) r[j] = mg_norm_elem(v[j], off[j], fac[j], inverse);
                 }
                 if (PAD && raw_out) *reinterpret_cast<f32x4*>(raw_out + base + e) = v;
                 *reinterpret_cast<f32x4*>(out + base + e) = r;
@@ -107,7 +92,7 @@ __global__ __launch_bounds__(256) void items_kernel(const float* __restrict__ x,
                 float v = 0.f, r = 0.f;
                 if (e < valid) {
                     v = src[e];
-                    r = items_elem(v, s_off[d], s_fac[d], inverse);
+                    r = mg_norm_elem(v, s_off[d], s_fac[d], inverse);
                 }
                 if (PAD && raw_out) raw_out[base + e] = v;
                 out[base + e] = r;
@@ -121,9 +106,8 @@ __global__ __launch_bounds__(256) void items_kernel(const float* __restrict__ x,
 __global__ __launch_bounds__(256) void item_rows_kernel(const float* __restrict__ table, int S, int D, const int32_t* __restrict__ item_row,
                                                         float* __restrict__ out) {
     const int b = blockIdx.x;
-    const int row = item_row[b];
-    const bool row_ok = row >= 0 && row < S;
-    for (int d = threadIdx.x; d < D; d += 256) out[(size_t)b * D + d] = row_ok ? table[(size_t)row * D + d] : __builtin_nanf("");
+    const int row = mg_item_row(item_row, b, S);
+    for (int d = threadIdx.x; d < D; d += 256) out[(size_t)b * D + d] = row >= 0 ? table[(size_t)row * D + d] : __builtin_nanf("");
 }
 
 template <bool PAD>
@@ -150,7 +134,7 @@ int mg_normalise_items_f32(const float* x, float* out, const float* p0, const fl
     MG_CHECK_ARG(x && out && p0 && p1 && item_row, "mg_normalise_items_f32: null argument");
     MG_CHECK_ARG(B > 0 && B <= 65535 && rows_per_item >= 0, "mg_normalise_items_f32: bad shape (B=%d rows_per_item=%lld)", B,
                  (long long)rows_per_item);
-    MG_CHECK_ARG(S > 0, "mg_normalise_items_f32: S=%d parameter rows", S);
+    MG_CHECK_PARAM_ROWS("mg_normalise_items_f32", "S", item_row, S);
     MG_CHECK_ARG(D > 0 && D <= ITEMS_MAX_D, "mg_normalise_items_f32: D=%d not in 1..%d", D, ITEMS_MAX_D);
     MG_CHECK_ARG(kind >= MG_NORM_MVN && kind <= MG_DENORM_MINMAX, "mg_normalise_items_f32: unknown kind %d", kind);
     if (rows_per_item == 0) return MG_OK;
@@ -163,7 +147,7 @@ int mg_pad_normalise_items_f32(const float* packed, const int64_t* offsets, int 
                                const int32_t* item_row, int S, int kind, float* raw_out, float* norm_out, void* stream) {
     MG_CHECK_ARG(packed && offsets && p0 && p1 && item_row && norm_out, "mg_pad_normalise_items_f32: null argument");
     MG_CHECK_ARG(B > 0 && B <= 65535 && T >= 0, "mg_pad_normalise_items_f32: bad shape (B=%d T=%d)", B, T);
-    MG_CHECK_ARG(S > 0, "mg_pad_normalise_items_f32: S=%d parameter rows", S);
+    MG_CHECK_PARAM_ROWS("mg_pad_normalise_items_f32", "S", item_row, S);
     MG_CHECK_ARG(D > 0 && D <= ITEMS_MAX_D, "mg_pad_normalise_items_f32: D=%d not in 1..%d", D, ITEMS_MAX_D);
     MG_CHECK_ARG(kind == MG_NORM_MVN || kind == MG_NORM_MINMAX, "mg_pad_normalise_items_f32: kind %d is not MG_NORM_MVN or MG_NORM_MINMAX",
                  kind);

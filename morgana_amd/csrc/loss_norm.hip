@@ -7,6 +7,7 @@
 // writes the gradient, a second tiny pass finishes the per-utterance normalisation in a fixed order (deterministic).
 // Algorithmic bytes for K4: B*T*D*(4+4) read + B*T*D*4 written.
 #include "common.h"
+#include "item_norm.h"      // no fp pragma in front of it, on purpose: the inverse kinds stay one fma
 #include "seq_reduce.h"
 
 #define MSE_CHUNK 8192  // elements of one utterance handled by one workgroup (256 threads x 32)
@@ -106,19 +107,7 @@ __global__ __launch_bounds__(256) void normalise_kernel(const float* __restrict_
     int d = (int)(i % D);
     const int step = (int)(stride % D);
     for (; i < n; i += stride) {
-        const float a = p0[d], b = p1[d];
-        const float v = x[i];
-        float r;
-        if (kind == MG_NORM_MVN) {
-            r = (v - a) / (b + 1e-8f);
-        } else if (kind == MG_DENORM_MVN) {
-            r = v * b + a;
-        } else {
-            float scale = b - a;
-            if (fabsf(scale) <= 1e-8f) scale = 1.f;
-            r = kind == MG_NORM_MINMAX ? (v - a) / scale : v * scale + a;
-        }
-        out[i] = r;
+        out[i] = mg_norm_any(x[i], p0[d], p1[d], kind);
         d += step;
         if (d >= D) d -= D;
     }
@@ -202,8 +191,8 @@ __global__ __launch_bounds__(256) void pad_normalise_kernel(const float* __restr
                                                             int T, int D, const float* __restrict__ p0, const float* __restrict__ p1,
                                                             int kind, float* __restrict__ raw_out, float* __restrict__ norm_out) {
     const int b = blockIdx.y;
-    const int64_t lo = offsets[b];
-    int64_t len = offsets[b + 1] - lo;
+    int64_t lo, len;
+    mg_item_rows(offsets, nullptr, 0, b, lo, len);
     if (len > T) len = T;
     const int64_t row_elems = (int64_t)T * D, valid = len * D;
     const float* src = packed + lo * D;
@@ -214,14 +203,7 @@ __global__ __launch_bounds__(256) void pad_normalise_kernel(const float* __restr
             v = src[e];
             if (norm_out) {
                 const int d = (int)(e % D);
-                const float a = p0[d], c = p1[d];
-                if (kind == MG_NORM_MVN) {
-                    r = (v - a) / (c + 1e-8f);
-                } else {
-                    float scale = c - a;
-                    if (fabsf(scale) <= 1e-8f) scale = 1.f;
-                    r = (v - a) / scale;
-                }
+                r = mg_norm_forward(v, p0[d], p1[d], kind);
             }
         }
         if (raw_out) raw_out[base + e] = v;
@@ -246,8 +228,8 @@ __global__ __launch_bounds__(256) void pad_normalise_bf16_kernel(const float* __
         for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) dst[e] = 0;
         return;
     }
-    const int64_t lo = offsets[b];
-    int64_t len = offsets[b + 1] - lo;
+    int64_t lo, len;
+    mg_item_rows(offsets, nullptr, 0, b, lo, len);
     if (len > T) len = T;
     const float* src = packed + lo * D;
     const size_t base = (size_t)b * T * D, bf_base = (size_t)b * T * ldb;
@@ -258,14 +240,7 @@ __global__ __launch_bounds__(256) void pad_normalise_bf16_kernel(const float* __
         float v = 0.f, r = 0.f;
         if (d < D && t < len) {
             v = src[t * D + d];
-            const float a = p0[d], c = p1[d];
-            if (kind == MG_NORM_MVN) {
-                r = (v - a) / (c + 1e-8f);
-            } else {
-                float scale = c - a;
-                if (fabsf(scale) <= 1e-8f) scale = 1.f;
-                r = (v - a) / scale;
-            }
+            r = mg_norm_forward(v, p0[d], p1[d], kind);
         }
         if (d < D) {
             if (raw_out) raw_out[base + t * D + d] = v;
@@ -373,8 +348,7 @@ int mg_pad_normalise_f32(const float* packed, const int64_t* offsets, int B, int
                          int kind, float* raw_out, float* norm_out, void* stream) {
     MG_CHECK_ARG(packed && offsets && B > 0 && T >= 0 && D > 0, "mg_pad_normalise_f32: bad arguments (B=%d T=%d D=%d)", B, T, D);
     MG_CHECK_ARG(raw_out || norm_out, "mg_pad_normalise_f32: no output requested");
-    MG_CHECK_ARG(!norm_out || (p0 && p1 && (kind == MG_NORM_MVN || kind == MG_NORM_MINMAX)),
-                 "mg_pad_normalise_f32: a normalised output needs parameters and kind MG_NORM_MVN or MG_NORM_MINMAX (kind=%d)", kind);
+    MG_CHECK_NORM_TWIN("mg_pad_normalise_f32", norm_out, p0, p1, kind);
     MG_CHECK_ARG(B <= 65535, "mg_pad_normalise_f32: B=%d exceeds 65535", B);
     if (T == 0) return MG_OK;
     int64_t chunks = mg_ceil_div((int64_t)T * D, 256 * 8);

@@ -8,6 +8,7 @@
 // one piece are contiguous, so the piece is copied at the widest access their RELATIVE alignment allows (16, 4 or 1 bytes), with the
 // few bytes in front of and behind the aligned body moved one by one.
 #include "common.h"
+#include "item_norm.h"
 #include "seq_reduce.h"
 
 #define UNPAD_THREADS 256
@@ -59,11 +60,7 @@ __global__ __launch_bounds__(UNPAD_THREADS) void unpad_rows_kernel(UnpadBatch ba
     for (int64_t c_lo = (int64_t)blockIdx.x * UNPAD_CHUNK; c_lo < n_bytes; c_lo += (int64_t)gridDim.x * UNPAD_CHUNK) {
         const int64_t c_hi = c_lo + UNPAD_CHUNK < n_bytes ? c_lo + UNPAD_CHUNK : n_bytes;
         // the item that holds byte c_lo: the largest b with s_off[b] * rb <= c_lo < s_off[b + 1] * rb
-        int b = 0, top = B;
-        while (b < top) {
-            const int mid = (b + top) >> 1;
-            if (s_off[mid + 1] * rb <= c_lo) b = mid + 1; else top = mid;
-        }
+        int b = mg_item_at(B, c_lo, [&](int i) { return s_off[i] * rb; });
         for (; b < B; ++b) {
             const int64_t i_lo = s_off[b] * rb, i_hi = s_off[b + 1] * rb;
             if (i_lo >= c_hi) break;

@@ -575,6 +575,49 @@ def _host_deltas(feature, spec):
     return out
 
 
+def _not_an_array(what, x):
+    """``x`` is no NumPy array: it must be a tensor ..."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError('%s takes a NumPy array or a device tensor, got %s' % (what, type(x)))
+
+
+def _on_device(what, x):
+    """... and, once its shape has been checked, on the device."""
+    if not x.is_cuda:
+        from ._lib import MorganaHipError
+        raise MorganaHipError('%s takes NumPy arrays (host) or device tensors; got a tensor on %s (no CPU fallback for the '
+                              'device path)' % (what, x.device))
+
+
+def _device_lengths(lengths, device):
+    return lengths.to(device=device, dtype=torch.int64).reshape(-1)
+
+
+def _host_or_batched(what, x, seq_len, noun):
+    """The argument of an operator with a host form and a device form -> (batched, seq_len, single).  A NumPy array is one whole item
+    for the host form: (None, None, True).  A device tensor (frames, features) or (batch, frames, features) comes back as a batch with
+    its int64 lengths on its device (every frame, without ``seq_len``); ``single``: the caller strips the batch dimension again."""
+    if isinstance(x, np.ndarray):
+        if seq_len is not None:
+            raise ValueError('%s: seq_len goes with a batched device tensor; a host array is one whole item' % what)
+        return None, None, True
+    _not_an_array(what, x)
+    if x.requires_grad:
+        raise RuntimeError('%s has no backward: detach the %s first' % (what, noun))
+    if x.dim() not in (2, 3):
+        raise ValueError('%s: a tensor must be (frames, features) or (batch, frames, features), got %s' % (what, tuple(x.shape)))
+    single = x.dim() == 2
+    if single and seq_len is not None:
+        raise ValueError('%s: seq_len goes with a batched (batch, frames, features) tensor' % what)
+    _on_device(what, x)
+    batched = x[None] if single else x
+    if seq_len is None:
+        seq_len = torch.full((batched.shape[0],), batched.shape[1], dtype=torch.int64, device=batched.device)
+    else:
+        seq_len = _device_lengths(seq_len, batched.device)
+    return batched, seq_len, single
+
+
 def compute_deltas(feature, windows=None, edge='replicate', seq_len=None):
     """Delta features ``[window 0 | window 1 | ...]`` of a feature: column ``w*D + d`` at frame t is ``sum_k coeff[w][k] x[t - l_w + k, d]``,
     row t of the window matrix ``W_w`` that MLPG inverts (morgana/viz/synthesis.py:8-36).  ``windows`` defaults to
@@ -590,28 +633,9 @@ def compute_deltas(feature, windows=None, edge='replicate', seq_len=None):
     ``{name}_deltas`` files of ``tts_data_tools`` were written with could not be verified - the package is not vendored with the
     reference - so it stays an argument."""
     spec = DeltaSpec(windows, edge)
-    if isinstance(feature, np.ndarray):
-        if seq_len is not None:
-            raise ValueError('compute_deltas: seq_len goes with a batched device tensor; a host array is one whole item')
+    batched, seq_len, single = _host_or_batched('compute_deltas', feature, seq_len, 'feature')
+    if batched is None:
         return _host_deltas(feature, spec)
-    if not isinstance(feature, torch.Tensor):
-        raise TypeError('compute_deltas takes a NumPy array or a device tensor, got %s' % type(feature))
-    if feature.requires_grad:
-        raise RuntimeError('compute_deltas has no backward: detach the feature first')
-    if feature.dim() not in (2, 3):
-        raise ValueError('compute_deltas: a tensor must be (frames, features) or (batch, frames, features), got %s' % (tuple(feature.shape),))
-    single = feature.dim() == 2
-    if single and seq_len is not None:
-        raise ValueError('compute_deltas: seq_len goes with a batched (batch, frames, features) tensor')
-    batched = feature[None] if single else feature
-    if not batched.is_cuda:
-        from ._lib import MorganaHipError
-        raise MorganaHipError('compute_deltas takes NumPy arrays (host) or device tensors; got a tensor on %s (no CPU fallback for the '
-                              'device path)' % feature.device)
-    if seq_len is None:
-        seq_len = torch.full((batched.shape[0],), batched.shape[1], dtype=torch.int64, device=batched.device)
-    else:
-        seq_len = seq_len.to(device=batched.device, dtype=torch.int64).reshape(-1)
     out, _ = ops.deltas(batched, spec.windows, seq_len=seq_len, edge=spec.edge, t=batched.shape[1])
     return out[0] if single else out
 
@@ -693,28 +717,9 @@ def continuous_lf0(f0, seq_len=None, log_input=False, voiced_above=None, fill=0.
     Holding the edge values is ``np.interp``'s convention.  Whether the ``lf0`` files of ``tts_data_tools`` were written that way could
     not be verified - the package is not vendored with the reference - so this is a stated choice, not a matched one."""
     spec = F0Spec(log_input=log_input, voiced_above=voiced_above, fill=fill)
-    if isinstance(f0, np.ndarray):
-        if seq_len is not None:
-            raise ValueError('continuous_lf0: seq_len goes with a batched device tensor; a host array is one whole item')
+    batched, seq_len, single = _host_or_batched('continuous_lf0', f0, seq_len, 'track')
+    if batched is None:
         return _host_continuous_lf0(f0, spec)
-    if not isinstance(f0, torch.Tensor):
-        raise TypeError('continuous_lf0 takes a NumPy array or a device tensor, got %s' % type(f0))
-    if f0.requires_grad:
-        raise RuntimeError('continuous_lf0 has no backward: detach the track first')
-    if f0.dim() not in (2, 3):
-        raise ValueError('continuous_lf0: a tensor must be (frames, features) or (batch, frames, features), got %s' % (tuple(f0.shape),))
-    single = f0.dim() == 2
-    if single and seq_len is not None:
-        raise ValueError('continuous_lf0: seq_len goes with a batched (batch, frames, features) tensor')
-    batched = f0[None] if single else f0
-    if not batched.is_cuda:
-        from ._lib import MorganaHipError
-        raise MorganaHipError('continuous_lf0 takes NumPy arrays (host) or device tensors; got a tensor on %s (no CPU fallback for the '
-                              'device path)' % f0.device)
-    if seq_len is None:
-        seq_len = torch.full((batched.shape[0],), batched.shape[1], dtype=torch.int64, device=batched.device)
-    else:
-        seq_len = seq_len.to(device=batched.device, dtype=torch.int64).reshape(-1)
     lf0, _, vuv, _ = ops.continuous_lf0(batched, seq_len=seq_len, t=batched.shape[1], log_input=spec.log_input,
                                         voiced_above=spec.voiced_above, fill=spec.fill)
     return (lf0[0], vuv[0]) if single else (lf0, vuv)
@@ -843,22 +848,18 @@ def frame_counters(dur, kind='full', seq_len=None, n_phones=None, max_len=None):
         if seq_len is not None or n_phones is not None or max_len is not None:
             raise ValueError('frame_counters: seq_len, n_phones and max_len go with a batched device tensor; a host array is one whole item')
         return _host_frame_counters(dur, kind)
-    if not isinstance(dur, torch.Tensor):
-        raise TypeError('frame_counters takes a NumPy array or a device tensor, got %s' % type(dur))
+    _not_an_array('frame_counters', dur)
     if dur.is_floating_point() or dur.dtype == torch.bool:
         raise TypeError('frame_counters: durations must be an integer tensor, got %s' % dur.dtype)
     if dur.dim() not in (2, 3):
         raise ValueError('frame_counters: a tensor must be (batch, phones) or (batch, phones, states), got %s' % (tuple(dur.shape),))
-    if not dur.is_cuda:
-        from ._lib import MorganaHipError
-        raise MorganaHipError('frame_counters takes NumPy arrays (host) or device tensors; got a tensor on %s (no CPU fallback for the '
-                              'device path)' % dur.device)
+    _on_device('frame_counters', dur)
     dur = dur if dur.dtype == torch.int64 else dur.long()
     batch_size = dur.shape[0]
     if seq_len is not None:
-        seq_len = seq_len.to(device=dur.device, dtype=torch.int64).reshape(-1)
+        seq_len = _device_lengths(seq_len, dur.device)
     if n_phones is not None:
-        n_phones = n_phones.to(device=dur.device, dtype=torch.int64).reshape(-1)
+        n_phones = _device_lengths(n_phones, dur.device)
     if max_len is None:
         _, tmax = ops.upsample_lengths(dur.reshape(batch_size, -1))
         max_len = int(tmax.item())

@@ -825,10 +825,7 @@ def pad_normalise(packed, offsets, t, p0=None, p1=None, kind=None, want_raw=True
     raw = torch.empty((b, t, d), dtype=torch.float32, device=packed.device) if want_raw else None
     norm = None
     if kind is not None:
-        p0 = _require(p0, torch.float32, 'param0')
-        p1 = _require(p1, torch.float32, 'param1')
-        if p0.numel() != d or p1.numel() != d:
-            raise ValueError('normaliser parameters have %d / %d entries, feature dim is %d' % (p0.numel(), p1.numel(), d))
+        p0, p1 = _norm_vectors(p0, p1, d)
         norm = torch.empty((b, t, d), dtype=torch.float32, device=packed.device)
     if bf16_extra_rows is not None:
         if kind is None:
@@ -857,6 +854,52 @@ def _item_tables(p0, p1, item_row, b, d, what):
     if item_row.dim() != 1 or item_row.numel() != b:
         raise ValueError('%s: item_row %s must hold one row index for each of the %d batch items' % (what, tuple(item_row.shape), b))
     return p0, p1, item_row
+
+
+def _norm_vectors(p0, p1, width, columns=('feature dim is %d',)):
+    """The two (width,) parameter vectors of a normaliser; ``columns``: (format, values in front of ``width``), what the error says
+    ``width`` counts (formatted only when it is raised: these wrappers are timed per call)."""
+    p0 = _require(p0, torch.float32, 'param0')
+    p1 = _require(p1, torch.float32, 'param1')
+    if p0.numel() != width or p1.numel() != width:
+        raise ValueError('normaliser parameters have %d / %d entries, ' % (p0.numel(), p1.numel()) + columns[0] % (columns[1:] + (width,)))
+    return p0, p1
+
+
+def _norm_twin(what, kind, p0, p1, item_row, b, width, columns, kind_name='kind', want_raw=None):
+    """The normalised twin a data-path launch writes next to its raw output -> (p0, p1, item_row, parameter rows, kind code): vectors
+    (width,) and 0 rows, or with ``item_row`` (B,) int32 tables (S, width) and S rows; (None, None, None, 0, -1) without a ``kind``.
+    ``columns``: as ``_norm_vectors`` takes it.  ``want_raw``: the caller's flag where it has one - no raw output needs a kind too."""
+    if kind is None:
+        if want_raw is False or p0 is not None or p1 is not None or item_row is not None:
+            raise ValueError('%s: normaliser parameters%s go with a %s (NORM_MVN or NORM_MINMAX)' % (
+                what, ' and item_row' if want_raw is None else ', item_row and want_raw=False', kind_name))
+        return None, None, None, 0, -1
+    if kind not in (NORM_MVN, NORM_MINMAX):
+        raise ValueError('%s: %s %r is not NORM_MVN or NORM_MINMAX' % (what, kind_name, kind))
+    if item_row is None:
+        return _norm_vectors(p0, p1, width, columns) + (None, 0, kind)
+    p0, p1, item_row = _item_tables(p0, p1, item_row, b, width, what)
+    return p0, p1, item_row, p0.shape[0], kind
+
+
+def _ragged_input(what, x, offsets, seq_len, width=None):
+    """A float32 feature in exactly one layout -> (offsets, seq_len, B, T_in, D): ``offsets`` (B + 1,) int64 with x the packed rows
+    (N, D) (T_in = 0), or ``seq_len`` (B,) int64 with x padded (B, T_in, D).  ``width``: the D the caller expects."""
+    if (offsets is None) == (seq_len is None):
+        raise ValueError('%s: give exactly one of offsets (packed rows) and seq_len (padded batch)' % what)
+    cols = 'features' if width is None else '%d' % width
+    if offsets is not None:
+        offsets = _require(offsets, torch.int64, 'offsets')
+        if x.dim() != 2 or (width is not None and x.shape[1] != width) or offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError('%s: packed rows %s must be (rows, %s) and offsets %s (items + 1,)' % (
+                what, tuple(x.shape), cols, tuple(offsets.shape)))
+        return offsets, None, offsets.numel() - 1, 0, x.shape[1]
+    seq_len = _require(seq_len, torch.int64, 'seq_len')
+    if x.dim() != 3 or (width is not None and x.shape[2] != width) or seq_len.dim() != 1 or seq_len.numel() != x.shape[0]:
+        raise ValueError('%s: padded batch %s must be (items, frames, %s) and seq_len %s (items,)' % (
+            what, tuple(x.shape), cols, tuple(seq_len.shape)))
+    return (None, seq_len) + tuple(x.shape)
 
 
 def normalise_items(x, p0, p1, item_row, kind, grad=False):
@@ -923,24 +966,13 @@ def column_stats(state, x, *, offsets=None, seq_len=None, item_row=None, max_row
         raise ValueError('column_stats: state is updated in place and must be contiguous')
     state = _require(state, torch.float64, 'state')
     x = _require(x, torch.float32, 'feature')
-    if (offsets is None) == (seq_len is None):
-        raise ValueError('column_stats: give exactly one of offsets (packed rows) and seq_len (padded batch)')
     if state.dim() != 3 or state.shape[1] != _lib.MG_COLSTATS_FIELDS:
         raise ValueError('column_stats: state %s must be (groups, %d, features)' % (tuple(state.shape), _lib.MG_COLSTATS_FIELDS))
-    groups, d = state.shape[0], state.shape[2]
+    groups = state.shape[0]
+    offsets, seq_len, b, t, d = _ragged_input('column_stats', x, offsets, seq_len, width=state.shape[2])
     if offsets is not None:
-        offsets = _require(offsets, torch.int64, 'offsets')
-        if x.dim() != 2 or x.shape[1] != d or offsets.dim() != 1 or offsets.numel() < 1:
-            raise ValueError('column_stats: packed rows %s must be (rows, %d) and offsets %s (items + 1,)' % (
-                tuple(x.shape), d, tuple(offsets.shape)))
-        b, t = offsets.numel() - 1, 0
         rows = max(1, min(int(max_rows), x.shape[0])) if max_rows is not None else 1
     else:
-        seq_len = _require(seq_len, torch.int64, 'seq_len')
-        if x.dim() != 3 or x.shape[2] != d or seq_len.dim() != 1 or seq_len.numel() != x.shape[0]:
-            raise ValueError('column_stats: padded batch %s must be (items, frames, %d) and seq_len %s (items,)' % (
-                tuple(x.shape), d, tuple(seq_len.shape)))
-        b, t = x.shape[0], x.shape[1]
         rows = t
     if item_row is not None:
         item_row = _require(item_row, torch.int32, 'item_row')
@@ -960,11 +992,8 @@ def column_stats(state, x, *, offsets=None, seq_len=None, item_row=None, max_row
 def normalise(x, p0, p1, kind):
     lib = _lib.load()
     x = _require(x, torch.float32, 'feature')
-    p0 = _require(p0, torch.float32, 'param0')
-    p1 = _require(p1, torch.float32, 'param1')
     d = x.shape[-1]
-    if p0.numel() != d or p1.numel() != d:
-        raise ValueError('normaliser parameters have %d / %d entries, feature dim is %d' % (p0.numel(), p1.numel(), d))
+    p0, p1 = _norm_vectors(p0, p1, d)
     out = torch.empty_like(x)
     _lib.check(lib.mg_normalise_f32(_p(x), _p(out), _p(p0), _p(p1), x.numel() // d, d, kind, _stream()),
                'mg_normalise_f32')
@@ -3127,44 +3156,18 @@ def deltas(x, windows, *, offsets=None, seq_len=None, edge='replicate', t=None, 
     Returns (raw or None, normalised or None)."""
     lib = _lib.load()
     x = _require(x, torch.float32, 'feature')
-    if (offsets is None) == (seq_len is None):
-        raise ValueError('deltas: give exactly one of offsets (packed rows) and seq_len (padded batch)')
+    offsets, seq_len, b, t_in, d = _ragged_input('deltas', x, offsets, seq_len)
     if (t is None) == (packed_rows is None):
         raise ValueError('deltas: give exactly one of t (padded output) and packed_rows (packed output)')
     if edge not in DELTAS_EDGES:
         raise ValueError("deltas: edge must be 'replicate' or 'zero', got %r" % (edge,))
     win_l, win_u, win_c = _window_arrays(windows)
     n_win = len(windows)
-    if offsets is not None:
-        offsets = _require(offsets, torch.int64, 'offsets')
-        if x.dim() != 2 or offsets.dim() != 1 or offsets.numel() < 1:
-            raise ValueError('deltas: packed rows %s must be (rows, features) and offsets %s (items + 1,)' % (
-                tuple(x.shape), tuple(offsets.shape)))
-        b, t_in, d = offsets.numel() - 1, 0, x.shape[1]
-    else:
-        seq_len = _require(seq_len, torch.int64, 'seq_len')
-        if x.dim() != 3 or seq_len.dim() != 1 or seq_len.numel() != x.shape[0]:
-            raise ValueError('deltas: padded batch %s must be (items, frames, features) and seq_len %s (items,)' % (
-                tuple(x.shape), tuple(seq_len.shape)))
-        b, t_in, d = x.shape
     width = n_win * d
     if d == 0:
         raise ValueError('deltas: the feature has no columns')
-    if kind is None and (want_raw is False or p0 is not None or p1 is not None or item_row is not None):
-        raise ValueError('deltas: normaliser parameters, item_row and want_raw=False go with a kind (NORM_MVN or NORM_MINMAX)')
-    s = 0
-    if kind is not None:
-        if kind not in (NORM_MVN, NORM_MINMAX):
-            raise ValueError('deltas: kind %r is not NORM_MVN or NORM_MINMAX' % (kind,))
-        if item_row is not None:
-            p0, p1, item_row = _item_tables(p0, p1, item_row, b, width, 'deltas')
-            s = p0.shape[0]
-        else:
-            p0 = _require(p0, torch.float32, 'param0')
-            p1 = _require(p1, torch.float32, 'param1')
-            if p0.numel() != width or p1.numel() != width:
-                raise ValueError('normaliser parameters have %d / %d entries, %d windows of %d columns need %d' % (
-                    p0.numel(), p1.numel(), n_win, d, width))
+    p0, p1, item_row, s, code = _norm_twin('deltas', kind, p0, p1, item_row, b, width,
+                                           ('%d windows of %d columns need %d', n_win, d), want_raw=want_raw)
     if t is not None:
         form, rows, shape = _lib.MG_DELTAS_OUT_PADDED, int(t), (b, int(t), width)
     else:
@@ -3174,8 +3177,7 @@ def deltas(x, windows, *, offsets=None, seq_len=None, edge='replicate', t=None, 
     raw = torch.empty(shape, dtype=torch.float32, device=x.device) if want_raw else None
     norm = torch.empty(shape, dtype=torch.float32, device=x.device) if kind is not None else None
     _lib.check(lib.mg_deltas_f32(_p(x), d, b, _p(offsets), _p(seq_len), int(t_in), n_win, win_l, win_u, win_c, DELTAS_EDGES[edge], _p(p0),
-                                 _p(p1), _p(item_row), s, -1 if kind is None else kind, form, rows, _p(raw), _p(norm), _stream()),
-               'mg_deltas_f32')
+                                 _p(p1), _p(item_row), s, code, form, rows, _p(raw), _p(norm), _stream()), 'mg_deltas_f32')
     return raw, norm
 
 
@@ -3207,22 +3209,9 @@ def continuous_lf0(x, *, offsets=None, seq_len=None, t=None, packed_rows=None, w
     Returns (lf0 padded or None, normalised or None, vuv, lf0 packed or None)."""
     lib = _lib.load()
     x = _require(x, torch.float32, 'f0')
-    if (offsets is None) == (seq_len is None):
-        raise ValueError('continuous_lf0: give exactly one of offsets (packed rows) and seq_len (padded batch)')
-    if offsets is not None:
-        offsets = _require(offsets, torch.int64, 'offsets')
-        if x.dim() != 2 or offsets.dim() != 1 or offsets.numel() < 1:
-            raise ValueError('continuous_lf0: packed rows %s must be (rows, features) and offsets %s (items + 1,)' % (
-                tuple(x.shape), tuple(offsets.shape)))
-        b, t_in, d = offsets.numel() - 1, 0, x.shape[1]
-        if packed_rows is None and (t is None or want_packed):
-            packed_rows = x.shape[0]
-    else:
-        seq_len = _require(seq_len, torch.int64, 'seq_len')
-        if x.dim() != 3 or seq_len.dim() != 1 or seq_len.numel() != x.shape[0]:
-            raise ValueError('continuous_lf0: padded batch %s must be (items, frames, features) and seq_len %s (items,)' % (
-                tuple(x.shape), tuple(seq_len.shape)))
-        b, t_in, d = x.shape
+    offsets, seq_len, b, t_in, d = _ragged_input('continuous_lf0', x, offsets, seq_len)
+    if offsets is not None and packed_rows is None and (t is None or want_packed):
+        packed_rows = x.shape[0]
     if d == 0:
         raise ValueError('continuous_lf0: the feature has no columns')
     if t is None and packed_rows is None:
@@ -3233,22 +3222,9 @@ def continuous_lf0(x, *, offsets=None, seq_len=None, t=None, packed_rows=None, w
         raise ValueError('continuous_lf0: packed_rows next to t goes with want_packed=True')
     if (t is not None and int(t) < 0) or (packed_rows is not None and int(packed_rows) < 0):
         raise ValueError('continuous_lf0: a negative output size (t=%r, packed_rows=%r)' % (t, packed_rows))
-    if kind is None and (p0 is not None or p1 is not None or item_row is not None):
-        raise ValueError('continuous_lf0: normaliser parameters and item_row go with a kind (NORM_MVN or NORM_MINMAX)')
-    s = 0
-    if kind is not None:
-        if kind not in (NORM_MVN, NORM_MINMAX):
-            raise ValueError('continuous_lf0: kind %r is not NORM_MVN or NORM_MINMAX' % (kind,))
-        if t is None:
-            raise ValueError('continuous_lf0: the normalised twin is a padded output: give t')
-        if item_row is not None:
-            p0, p1, item_row = _item_tables(p0, p1, item_row, b, d, 'continuous_lf0')
-            s = p0.shape[0]
-        else:
-            p0 = _require(p0, torch.float32, 'param0')
-            p1 = _require(p1, torch.float32, 'param1')
-            if p0.numel() != d or p1.numel() != d:
-                raise ValueError('normaliser parameters have %d / %d entries, the feature has %d columns' % (p0.numel(), p1.numel(), d))
+    if kind is not None and t is None:
+        raise ValueError('continuous_lf0: the normalised twin is a padded output: give t')
+    p0, p1, item_row, s, code = _norm_twin('continuous_lf0', kind, p0, p1, item_row, b, d, ('the feature has %d columns',))
     threshold = f0_voiced_above(voiced_above, log_input)
     padded = norm = packed = None
     if t is not None:
@@ -3260,7 +3236,7 @@ def continuous_lf0(x, *, offsets=None, seq_len=None, t=None, packed_rows=None, w
     if t is None or want_packed:
         packed = torch.empty((int(packed_rows), d), dtype=torch.float32, device=x.device)
     _lib.check(lib.mg_continuous_lf0_f32(_p(x), d, b, _p(offsets), _p(seq_len), int(t_in), 1 if log_input else 0, threshold, float(fill),
-                                         _p(p0), _p(p1), _p(item_row), s, -1 if kind is None else kind, 0 if t is None else int(t),
+                                         _p(p0), _p(p1), _p(item_row), s, code, 0 if t is None else int(t),
                                          0 if packed_rows is None else int(packed_rows), _p(packed), _p(padded), _p(norm), _p(vuv),
                                          vuv_form, _stream()), 'mg_continuous_lf0_f32')
     return padded, norm, vuv, packed
@@ -3298,35 +3274,24 @@ def frame_counters(dur, *, t, kind='full', seq_len=None, n_phones=None, p0=None,
         raise ValueError('frame_counters: %d phones of %d states per utterance, the kernel takes 1..%d segments' % (p, s, MAX_PHONES))
     if min(strides) < 0:
         raise ValueError('frame_counters: dur has a negative stride %s' % (strides,))
-    if int(t) < 0:
+    frames = int(t)
+    if frames < 0:
         raise ValueError('frame_counters: a negative output size t=%r' % (t,))
     seq_len = _lengths(seq_len, b, 'frame_counters: ')
     if n_phones is not None:
         n_phones = _require(n_phones, torch.int64, 'n_phones')
         if tuple(n_phones.shape) != (b,):
             raise ValueError('frame_counters: n_phones must be (B,) = (%d,), got %s' % (b, tuple(n_phones.shape)))
-    if norm_kind is None and (want_raw is False or p0 is not None or p1 is not None or item_row is not None):
-        raise ValueError('frame_counters: normaliser parameters, item_row and want_raw=False go with a norm_kind (NORM_MVN or NORM_MINMAX)')
-    rows = 0
-    if norm_kind is not None:
-        if norm_kind not in (NORM_MVN, NORM_MINMAX):
-            raise ValueError('frame_counters: norm_kind %r is not NORM_MVN or NORM_MINMAX' % (norm_kind,))
-        if item_row is not None:
-            p0, p1, item_row = _item_tables(p0, p1, item_row, b, c, 'frame_counters')
-            rows = p0.shape[0]
-        else:
-            p0 = _require(p0, torch.float32, 'param0')
-            p1 = _require(p1, torch.float32, 'param1')
-            if p0.numel() != c or p1.numel() != c:
-                raise ValueError('normaliser parameters have %d / %d entries, %r counters have %d columns' % (p0.numel(), p1.numel(), kind, c))
+    p0, p1, item_row, rows, norm_code = _norm_twin('frame_counters', norm_kind, p0, p1, item_row, b, c,
+                                                   ('%r counters have %d columns', kind), kind_name='norm_kind', want_raw=want_raw)
     if blocks_per_item is not None and int(blocks_per_item) < 1:
         raise ValueError('frame_counters: blocks_per_item=%r must be positive' % (blocks_per_item,))
-    raw = torch.empty((b, int(t), c), dtype=torch.float32, device=dur.device) if want_raw else None
-    norm = torch.empty((b, int(t), c), dtype=torch.float32, device=dur.device) if norm_kind is not None else None
-    if b == 0 or int(t) == 0:           # empty outputs: no address to hand the library
+    raw = torch.empty((b, frames, c), dtype=torch.float32, device=dur.device) if want_raw else None
+    norm = torch.empty((b, frames, c), dtype=torch.float32, device=dur.device) if norm_kind is not None else None
+    if b == 0 or frames == 0:           # empty outputs: no address to hand the library
         return raw, norm
-    _lib.check(lib.mg_frame_counters_f32(_p(dur), b, p, s, strides[0], strides[1], strides[2], _p(n_phones), _p(seq_len), int(t), code,
-                                         _p(p0), _p(p1), _p(item_row), rows, -1 if norm_kind is None else norm_kind, _p(raw), _p(norm),
+    _lib.check(lib.mg_frame_counters_f32(_p(dur), b, p, s, strides[0], strides[1], strides[2], _p(n_phones), _p(seq_len), frames, code,
+                                         _p(p0), _p(p1), _p(item_row), rows, norm_code, _p(raw), _p(norm),
                                          0 if blocks_per_item is None else int(blocks_per_item), _stream()), 'mg_frame_counters_f32')
     return raw, norm
 
