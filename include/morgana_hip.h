@@ -1509,6 +1509,44 @@ int mg_frame_counters_f32(const int64_t* dur, int B, int P, int S, int64_t strid
                           const int64_t* seq_len, int T, int counters_kind, const float* p0, const float* p1, const int32_t* item_row, int n_rows,
                           int norm_kind, float* raw_out, float* norm_out, int blocks_per_item, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * K31 (csrc/durations.hip)  integer durations from a duration model's real-valued prediction: the quantiser between
+ *                           models.DurationModel and everything that takes `dur` (K30, the upsampling kernels, the acoustic models).
+ * pred f32, logical [B, P, S], read in place through its element strides (none negative): P phones of S sub-phone states, in the
+ * normalised space.  n_phones (B, int64) or NULL: the phones from n_phones[b] on are never read and their outputs are 0 (NULL: all P
+ * count).  p0 / p1 [S] (mean, std_dev of the `dur` normaliser) or NULL (pred is in frames already); with item_row (B, int32) non-NULL
+ * they are tables [n_rows, S] and item b takes row item_row[b]: an index outside [0, n_rows) is never used as one, the item's outputs
+ * are all 0 and its flags MG_DUR_FLAG_NO_ROW alone.  Segments i = 0 .. n-1 in (p, s) order over the item's valid phones:
+ *   x_i = (double)pred * (double)p1[s] + (double)p0[s]  (one rounding);  exp(x_i) if log_input;  x_i * scale;
+ *         a NaN, infinite or negative x_i becomes 0 and sets MG_DUR_FLAG_INVALID;  min(x_i, hi)
+ *   q_i = floor(x_i * 65536 + 0.5) as int64: 16 fractional bits, everything below is integer arithmetic
+ *   total (B, int64) non-NULL, the length to fit item b to:  Q = sum_i q_i;  if Q > 0 and total[b] > 0
+ *         q_i = min(floor((double)q_i * ((double)(total[b] << 16) / (double)Q) + 0.5), hi << 16),  else MG_DUR_FLAG_NO_FIT and no fit
+ *   MG_DUR_NEAREST  d_i = max(lo, (q_i + 32768) >> 16): every segment rounded on its own (Merlin's rule)
+ *   MG_DUR_CARRY    C_i = q_0 + .. + q_i,  R_i = (C_i + 32768) >> 16,  E_i = (i+1) lo + max(0, max_{j<=i}(R_j - (j+1) lo)),
+ *                   d_i = E_i - E_{i-1}, E_{-1} = 0: the closed form of "emit max(lo, R_i - the frames emitted so far)".
+ *                   lo <= d_i <= max(lo, hi).  Where every clamped x_i >= lo the total is (C_{n-1} + 32768) >> 16 and every boundary
+ *                   lies within half a frame of C_i / 65536; MG_DUR_FLAG_PUSHED: E_{n-1} differs from that total (the minimum
+ *                   pushed the length out).
+ * Outputs: dur int64 [B, P, S] contiguous, phone_dur int64 [B, P] = sum_s dur, n_frames int64 [B] = sum dur, flags int32 [B].
+ * One workgroup per item walks its segments in chunks of 256 with a carried int64 sum and maximum: integer scans, so the bits depend
+ * on the values alone.  One launch, no workspace, no atomics, no host read: the same bits on every call, capturable.
+ * Refused (MG_EINVAL, nothing launched): an unknown rounding, P < 1, S < 1, B > 65535, P * S >= 2^24, a negative size or stride,
+ * not 0 <= lo <= hi <= 2^20, a scale that is not positive and finite, one of p0 / p1 without the other, item_row without tables, a
+ * NULL or misaligned pointer where one is read or written.  B == 0: MG_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define MG_DUR_CARRY 0
+#define MG_DUR_NEAREST 1
+#define MG_DUR_FLAG_INVALID 1
+#define MG_DUR_FLAG_NO_FIT 2
+#define MG_DUR_FLAG_PUSHED 4
+#define MG_DUR_FLAG_NO_ROW 8
+#define MG_DUR_MAX_FRAMES 1048576
+int mg_quantise_durations_f32(const float* pred, int B, int P, int S, int64_t stride_b, int64_t stride_p, int64_t stride_s,
+                              const int64_t* n_phones, const float* p0, const float* p1, const int32_t* item_row, int n_rows, int log_input,
+                              double scale, int64_t lo, int64_t hi, int rounding, const int64_t* total, int64_t* dur, int64_t* phone_dur,
+                              int64_t* n_frames, int32_t* flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

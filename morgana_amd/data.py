@@ -866,6 +866,143 @@ def frame_counters(dur, kind='full', seq_len=None, n_phones=None, max_len=None):
     return ops.frame_counters(dur, t=int(max_len), kind=kind, seq_len=seq_len, n_phones=n_phones)[0]
 
 
+def _duration_operands(normaliser, speaker_index, device=None):
+    """(p0, p1, item_row) that take a normalised duration prediction back to frames: the mean and std_dev of a mean-variance
+    normaliser - float32 vectors (host: ``device`` None; ``speaker_index`` then names the one speaker of a speaker-dependent
+    normaliser), or on ``device`` vectors / the (speakers, S) tables with the batch's int32 row index.  Three Nones without one."""
+    if normaliser is None:
+        if speaker_index is not None:
+            raise ValueError('quantise_durations: speaker_index goes with a speaker-dependent normaliser')
+        return None, None, None
+    if not isinstance(normaliser, FeatureNormaliser) or normaliser.kind != 'mvn':
+        raise TypeError('quantise_durations: normaliser must be a MeanVarianceNormaliser or a SpeakerDependentMeanVarianceNormaliser, '
+                        'got %r' % (normaliser,))
+    dependent = isinstance(normaliser, _SpeakerDependentNormaliser)
+    if dependent and speaker_index is None:
+        raise KeyError("quantise_durations: the normaliser of %r is speaker-dependent: it needs speaker_index (features['%s'])"
+                       % (normaliser.name, SPEAKER_INDEX_KEY))
+    if not dependent and speaker_index is not None:
+        raise ValueError('quantise_durations: speaker_index goes with a speaker-dependent normaliser')
+    if device is None:
+        prm = normaliser.fetch_params(speaker_index, np.ndarray) if dependent else normaliser.fetch_params(np.ndarray)
+        if not prm:
+            raise RuntimeError('normaliser %r has no parameters: call load_params, set_params or fit_normalisers first' % normaliser.name)
+        mean, std_dev = (np.asarray(prm[n], dtype=np.float32) for n in _KINDS['mvn']['params'])
+        if mean.ndim != 1:
+            raise ValueError('quantise_durations: a host array is one item of one speaker, got %r' % (speaker_index,))
+        return mean, std_dev, None
+    if dependent:
+        p0, p1 = normaliser.tables(device)
+        return p0, p1, normaliser.speaker_index(speaker_index, device)
+    prm = normaliser.fetch_params(torch.Tensor)
+    if prm is None:
+        raise RuntimeError('normaliser %r has no parameters: call load_params, set_params or fit_normalisers first' % normaliser.name)
+    p0, p1 = (prm[n].to(device=device, dtype=torch.float32).reshape(-1) for n in _KINDS['mvn']['params'])
+    return p0, p1, None
+
+
+def _host_quantise_durations(pred, p0, p1, log_input, scale, lo, hi, carry, total):
+    """The arithmetic of mg_quantise_durations_f32 in NumPy for one item (P, S): one float64 rounding per step up to the 16-bit
+    fixed-point value, int64 from there on, the carry rule in its closed form -> (dur (P, S), phone_dur (P,), n_frames, flags)."""
+    n_states = pred.shape[1]
+    flags = 0
+    with np.errstate(all='ignore'):
+        x = pred.astype(np.float64)
+        if p0 is not None:
+            x = x * p1.astype(np.float64)[None, :] + p0.astype(np.float64)[None, :]
+        if log_input:
+            x = np.exp(x)
+        x = (x * np.float64(scale)).ravel()
+        bad = ~(x >= 0.) | np.isinf(x)
+        if bad.any():
+            flags |= ops.DUR_FLAG_INVALID
+        x = np.minimum(np.where(bad, 0., x), np.float64(hi))
+        q = np.floor(x * 65536. + .5).astype(np.int64)
+        if total is not None:
+            whole = int(q.sum())
+            if whole > 0 and total > 0:
+                ratio = np.float64(float(total << 16)) / np.float64(whole)
+                q = np.minimum(np.floor(q.astype(np.float64) * ratio + .5), np.float64(hi << 16)).astype(np.int64)
+            else:
+                flags |= ops.DUR_FLAG_NO_FIT
+    if carry:
+        rounded = (np.cumsum(q) + 32768) >> 16
+        floor = np.arange(1, q.size + 1, dtype=np.int64) * lo
+        ends = floor + np.maximum(np.maximum.accumulate(rounded - floor), 0) if q.size else floor
+        dur = np.diff(ends, prepend=np.int64(0))
+        if q.size and int(ends[-1]) != (int(q.sum()) + 32768) >> 16:
+            flags |= ops.DUR_FLAG_PUSHED
+    else:
+        dur = np.maximum((q + 32768) >> 16, lo)
+    dur = dur.astype(np.int64).reshape(-1, n_states)
+    return dur, dur.sum(axis=1), int(dur.sum()), flags
+
+
+def quantise_durations(pred, n_phones=None, normaliser=None, speaker_index=None, log_input=False, scale=1., min_frames=1, max_frames=None,
+                       rounding='carry', total=None):
+    """Integer durations in frames from a duration model's real-valued prediction - what ``upsample_to_repetitions``,
+    ``frame_counters`` and the acoustic models take as ``dur``.  ``pred[p, s]``: P phones of S sub-phone states, in the normalised space
+    of ``normaliser`` (a ``MeanVarianceNormaliser`` or, with ``speaker_index``, a ``SpeakerDependentMeanVarianceNormaliser``: the value in
+    frames is ``pred * std_dev + mean`` in float64), in frames without one.  ``log_input``: that value is a log-duration; ``scale``: a
+    speaking-rate factor on the durations.  A NaN, infinite or negative value counts as 0 (flag ``ops.DUR_FLAG_INVALID``), a value above
+    ``max_frames`` (default and largest: 2^20) as ``max_frames``.  Every value is then rounded to 16 fractional bits
+    (``floor(x * 65536 + 0.5)``), and the rest is integer arithmetic over the segments in (p, s) order:
+
+    ``rounding='nearest'``: ``max(min_frames, round(x))`` for every segment on its own, Merlin's rule.  The boundaries drift from the
+    predicted ones like a random walk and the utterance length is whatever the errors add up to.
+    ``rounding='carry'`` (default): the rounding error is carried along.  Segment i ends at ``max(the rounded predicted end, the previous
+    end + min_frames)``: where every value is at least ``min_frames`` every boundary lies within half a frame of the predicted one and
+    the length is the rounded predicted length; ``ops.DUR_FLAG_PUSHED`` says that the minimum pushed the length out.
+
+    ``total``: the length to fit the item to, for example its natural ``n_frames``: the values are scaled by ``total / their sum``
+    before the rounding, so that (with 'carry', where no scaled value lies below ``min_frames``) the durations add up to ``total``
+    exactly.  ``ops.DUR_FLAG_NO_FIT`` and no scaling where ``total <= 0`` or the values add up to 0.
+
+    A NumPy float array ``(P,)`` or ``(P, S)`` is one item computed on the host (``total`` an int, ``speaker_index`` the speaker's name)
+    and gives ``(dur shaped like pred, phone_dur (P,), n_frames, flags)`` with the last two python ints.  A device float32 tensor
+    ``(B, P)`` or ``(B, P, S)`` goes through the HIP kernel (csrc/durations.hip), read in place through its strides, with ``n_phones``
+    (B,) dropping the phones from ``n_phones[b]`` on (never read, durations 0), ``total`` (B,) int64 and ``speaker_index`` (B,) the
+    batch's ``features['speaker_index']``; it gives ``(dur int64 shaped like pred, phone_dur int64 (B, P), n_frames int64 (B,),
+    flags int32 (B,))``: the same bits, except that ``exp`` of a ``log_input`` may differ in its last place between the host's and the
+    device's library, which matters only for a value within 2^-49 (relative) of a rounding boundary.  There is no backward."""
+    scale, lo, hi, code = ops.duration_arguments('quantise_durations', scale, min_frames, max_frames, rounding)
+    if isinstance(pred, np.ndarray):
+        if n_phones is not None:
+            raise ValueError('quantise_durations: n_phones goes with a batched device tensor; a host array is one whole item')
+        if not np.issubdtype(pred.dtype, np.floating):
+            raise TypeError('quantise_durations: the prediction must be a float array, got %s' % pred.dtype)
+        if pred.ndim not in (1, 2) or (pred.ndim == 2 and pred.shape[1] == 0):
+            raise ValueError('quantise_durations: a host array must be (phones,) or (phones, states), got shape %s' % (pred.shape,))
+        if total is not None:
+            if isinstance(total, bool) or not isinstance(total, (int, np.integer)):
+                raise TypeError('quantise_durations: total of a host array must be an int, got %r' % (total,))
+            total = int(total)
+        p0, p1, _ = _duration_operands(normaliser, speaker_index)
+        item = pred.astype(np.float32).reshape(pred.shape[0], -1)
+        if p0 is not None and (p0.size != item.shape[1] or p1.size != item.shape[1]):
+            raise ValueError('quantise_durations: the normaliser has %d / %d parameters, the prediction %d states per phone'
+                             % (p0.size, p1.size, item.shape[1]))
+        dur, phone_dur, n_frames, flags = _host_quantise_durations(item, p0, p1, bool(log_input), scale, lo, hi, code == ops.DUR_ROUNDINGS['carry'],
+                                                                    total)
+        return dur.reshape(pred.shape), phone_dur, n_frames, flags
+    _not_an_array('quantise_durations', pred)
+    if pred.requires_grad:
+        raise RuntimeError('quantise_durations has no backward: detach the prediction first')
+    if pred.dim() not in (2, 3):
+        raise ValueError('quantise_durations: a tensor must be (batch, phones) or (batch, phones, states), got %s' % (tuple(pred.shape),))
+    _on_device('quantise_durations', pred)
+    pred = pred if pred.dtype == torch.float32 else pred.float()
+    if n_phones is not None:
+        n_phones = _device_lengths(n_phones, pred.device)
+    if total is not None:
+        if not isinstance(total, torch.Tensor):
+            raise TypeError('quantise_durations: total of a device batch must be a (batch,) tensor, got %s' % type(total))
+        total = _device_lengths(total, pred.device)
+    p0, p1, item_row = _duration_operands(normaliser, speaker_index, pred.device)
+    return ops.quantise_durations(pred, n_phones=n_phones, p0=p0, p1=p1, item_row=item_row, log_input=log_input, scale=scale, lo=lo, hi=hi,
+                                  rounding=rounding, total=total)
+
+
 def _counter_specs_of(utterances, counter_specs):
     """The {feature name: CountersSpec} a loader applies: the argument, or what the data sources of a ``FilesDataset`` ask for."""
     if counter_specs is None:

@@ -808,3 +808,158 @@ class VAEF0Model(StreamModel, BaseVAE):
         if self.mode in self.metrics.collections:
             self.metrics.accumulate(self.mode, kld=kld)
         return StreamModel.loss(self, features, output_features) + self.kld_weight * kld
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The first stage of the SPSS chain: the durations the acoustic models above read as ``dur`` / ``counters`` / ``n_frames``.
+# ---------------------------------------------------------------------------------------------------------------------------------
+class DurationModel(BaseSPSS):
+    """Phone-rate duration model: ``normalised_lab`` (B, P, input_dim) -> ``normalised_dur`` (B, P, n_states), the stack of the shipped
+    F0 model (Linear-256 / sigmoid / GRU-64 x 3 / Linear-64 / sigmoid / Linear-n_states) run once per phone with
+    ``seq_len=features['n_phones']``, masked MSE against ``features['normalised_dur']`` (what ``collate_to_device`` writes for the
+    ``dur`` normaliser the reference's shipped models list and never read).  ``n_states`` = 1 predicts phone durations, 5 HTS state
+    durations.  With ``speaker_id_list`` the ``dur`` normaliser is per speaker.
+
+    ``predict`` returns ``normalised_dur`` (with gradient) and - once the ``dur`` normaliser has parameters - the quantiser's detached
+    ``dur`` int64 (B, P, n_states), ``phone_dur`` (B, P), ``n_frames`` (B,) and ``dur_flags`` int32 (B,) (``data.quantise_durations``
+    with this model's ``rounding``, ``min_frames``, ``max_frames``: one launch).  After ``fit_to('n_frames')`` an ``eval()``-mode
+    ``predict`` fits every utterance to ``features['n_frames']`` frames, so that acoustic metrics can score a prediction made with
+    predicted durations against natural targets; ``train()`` mode never does.  Metric ``DUR_RMSE_frames``: RMSE in frames of the
+    de-normalised real-valued prediction against ``features['dur']`` over the valid phones.
+
+    The layers run through the wrappers one after the other (no ``max_len``: the three GRU-64 layers take the workgroup-local
+    recurrence of csrc/gru_small.hip, which admits any B and any T >= 1, not the cross-workgroup wavefront), eager."""
+
+    def __init__(self, input_dim=600, n_states=1, dropout_prob=0., precision=None, speaker_id_list=None, rounding='carry', min_frames=1,
+                 max_frames=None):
+        super(DurationModel, self).__init__()
+        if int(n_states) < 1:
+            raise ValueError('DurationModel: n_states must be at least 1, got %r' % (n_states,))
+        ops.duration_arguments('DurationModel', 1., min_frames, max_frames, rounding)
+        self.input_dim, self.n_states, self.speaker_id_list = input_dim, int(n_states), speaker_id_list
+        self.rounding, self.min_frames, self.max_frames = rounding, min_frames, max_frames
+        self.layers = _gru_f0_stack(input_dim, self.n_states, dropout_prob, precision)
+        self.metrics.add_metrics('all', DUR_RMSE_frames=metrics.RMSE())
+
+    def normaliser_sources(self):
+        dur = (data.SpeakerDependentMeanVarianceNormaliser('dur', self.speaker_id_list) if self.speaker_id_list is not None
+               else data.MeanVarianceNormaliser('dur'))
+        return {'lab': data.MinMaxNormaliser('lab'), 'dur': dur}
+
+    # -- fitting the utterance length ------------------------------------------------------------------------------------------------
+    _fit_key = None               # the feature an eval()-mode predict fits every utterance's length to
+
+    def fit_to(self, total_key='n_frames'):
+        """In ``eval()`` mode every ``predict`` from now on hands the quantiser ``total=features[total_key]``: the durations of
+        utterance b add up to that many frames (exactly, with 'carry' rounding, unless ``min_frames`` pushes the length out:
+        ``ops.DUR_FLAG_PUSHED`` in ``dur_flags``).  ``fit_to(None)`` restores the default, the rounded predicted length.  In ``train()``
+        mode nothing changes.  Returns the model."""
+        if total_key is not None and not isinstance(total_key, str):
+            raise TypeError('fit_to: total_key must be a feature name or None, got %r' % (total_key,))
+        self._fit_key = total_key
+        return self
+
+    # -- pieces ----------------------------------------------------------------------------------------------------------------------
+    def _dur_normaliser(self):
+        norm = self.normalisers.get('dur') if hasattr(self.normalisers, 'get') else None
+        return norm if norm is not None and norm.params else None
+
+    def _speaker_args(self, normaliser, features):
+        if not isinstance(normaliser, data._SpeakerDependentNormaliser):
+            return None
+        speaker_index = features.get(data.SPEAKER_INDEX_KEY)
+        if speaker_index is None:
+            raise KeyError("the normaliser of 'dur' is speaker-dependent: the batch needs features['%s'] (the loaders write it)"
+                           % data.SPEAKER_INDEX_KEY)
+        return speaker_index
+
+    # -- the plugin surface ----------------------------------------------------------------------------------------------------------
+    def predict(self, features):
+        lab = features['normalised_lab']
+        n_phones = features['n_phones'].reshape(-1)
+        pred, _ = self.layers(lab, seq_len=n_phones)
+        if pred.shape[1] != lab.shape[1]:                 # the wrappers crop to the longest item: back to the batch's phone axis
+            pred = nn.functional.pad(pred, (0, 0, 0, lab.shape[1] - pred.shape[1]))
+        outputs = {'normalised_dur': pred}
+        normaliser = self._dur_normaliser()
+        if normaliser is not None:
+            total = None
+            if self._fit_key is not None and not self.training:
+                total = features[self._fit_key].reshape(-1)
+            dur, phone_dur, n_frames, flags = data.quantise_durations(
+                pred.detach(), n_phones=n_phones, normaliser=normaliser, speaker_index=self._speaker_args(normaliser, features),
+                min_frames=self.min_frames, max_frames=self.max_frames, rounding=self.rounding, total=total)
+            outputs.update(dur=dur, phone_dur=phone_dur, n_frames=n_frames, dur_flags=flags)
+        return outputs
+
+    def loss(self, features, output_features):
+        pred = output_features['normalised_dur']
+        normaliser = self._dur_normaliser()
+        if normaliser is not None and 'dur' in features and self.mode in self.metrics.collections:
+            speaker_index = self._speaker_args(normaliser, features)
+            frames = normaliser.denormalise(pred.detach(), *(() if speaker_index is None else (speaker_index,)))
+            self.metrics.accumulate(self.mode, DUR_RMSE_frames=(features['dur'].reshape(frames.shape).to(torch.float32), frames,
+                                                                features['n_phones'].reshape(-1)))
+        return losses.mse(pred, features['normalised_dur'], features['n_phones'])
+
+
+_PHONE_LEVEL = ('lab',)
+
+
+def _is_phone_level(key):
+    base = key[len('normalised_'):] if key.startswith('normalised_') else key
+    for suffix in (data.BF16_TABLE_SUFFIX, data.X3_TABLE_SUFFIX):
+        if base.endswith(suffix):
+            base = base[:-len(suffix)]
+    return base in _PHONE_LEVEL
+
+
+def with_predicted_durations(features, duration_outputs, normalisers, counters_kind='full', max_len=None):
+    """The feature dict an acoustic ``StreamModel`` reads, built from a batch and a ``DurationModel``'s outputs for it: a NEW dict,
+    ``features`` is untouched.  Written from ``duration_outputs``: ``dur`` int64 (B, P, 1), the phone durations in the shape the
+    acoustic models read; with state durations (n_states > 1) ``state_dur`` int64 (B, P, S) as well; ``n_frames`` int64 (B,); and
+    ``counters`` / ``normalised_counters`` (B, T, C), the frame-level positional features of the state durations where there are any,
+    else of the phone durations (``ops.frame_counters``, ``counters_kind``; normalised with the operands of ``normalisers['counters']``,
+    plain or speaker dependent, when there is one): one launch.  Kept from ``features``: everything that is not a batched sequence -
+    names, ``n_phones``, ``speaker_index``, other per-item values - and the phone-level sequences (``lab`` / ``normalised_lab`` and their
+    operand tables).  Dropped: every other batched sequence - the frame-level corpus features (targets, ``vuv``, natural ``counters``),
+    which are as long as the natural durations - and ``normalised_dur``, ``n_frames_total``.
+
+    ``max_len``: T, the frame axis of the counters (frames past an utterance's ``n_frames`` are zeros, longer utterances are cut).
+    ``max_len=None`` takes the longest predicted utterance, which costs the one device -> host read of ``n_frames.max()``."""
+    missing = [key for key in ('dur', 'phone_dur', 'n_frames') if key not in duration_outputs]
+    if missing:
+        raise KeyError('with_predicted_durations: duration_outputs lacks %s (a DurationModel writes them once its \'dur\' normaliser has '
+                       'parameters)' % ', '.join(missing))
+    state_dur, phone_dur, n_frames = (duration_outputs[key].detach() for key in ('dur', 'phone_dur', 'n_frames'))
+    if state_dur.dim() == 2:
+        state_dur = state_dur.unsqueeze(-1)
+    batch_size = state_dur.shape[0]
+    written = ('dur', 'state_dur', data.FRAME_COUNT_KEY, data.FRAME_COUNT_KEY + '_total', 'counters', 'normalised_counters',
+               'normalised_dur')
+    out = {}
+    for key, value in features.items():
+        if key in written:
+            continue
+        sequence = (isinstance(value, torch.Tensor) and value.dim() >= 2 and value.shape[0] == batch_size and
+                    not (value.dim() == 2 and value.shape[1] == 1))
+        if not sequence or _is_phone_level(key):
+            out[key] = value
+    out['dur'] = phone_dur.unsqueeze(-1)
+    source = out['dur']
+    if state_dur.shape[2] > 1:
+        out['state_dur'] = source = state_dur
+    out[data.FRAME_COUNT_KEY] = n_frames
+    n_phones = features.get('n_phones')
+    if n_phones is not None:
+        n_phones = n_phones.reshape(-1).to(device=source.device, dtype=torch.int64)
+    normaliser = normalisers.get('counters') if normalisers is not None else None
+    kind, p0, p1, item_row = data._normaliser_operands(out, 'counters', normaliser, source.device)
+    if max_len is None:
+        max_len = int(n_frames.max().item())
+    raw, norm = ops.frame_counters(source, t=int(max_len), kind=counters_kind, seq_len=n_frames, n_phones=n_phones, p0=p0, p1=p1,
+                                   norm_kind=kind, item_row=item_row)
+    out['counters'] = raw
+    if norm is not None:
+        out['normalised_counters'] = norm
+    return out

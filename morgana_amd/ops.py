@@ -3296,6 +3296,93 @@ def frame_counters(dur, *, t, kind='full', seq_len=None, n_phones=None, p0=None,
     return raw, norm
 
 
+DUR_ROUNDINGS = {'carry': _lib.MG_DUR_CARRY, 'nearest': _lib.MG_DUR_NEAREST}
+DUR_FLAG_INVALID, DUR_FLAG_NO_FIT, DUR_FLAG_PUSHED, DUR_FLAG_NO_ROW = (_lib.MG_DUR_FLAG_INVALID, _lib.MG_DUR_FLAG_NO_FIT,
+                                                                       _lib.MG_DUR_FLAG_PUSHED, _lib.MG_DUR_FLAG_NO_ROW)
+DUR_MAX_FRAMES = _lib.MG_DUR_MAX_FRAMES
+DUR_MAX_ITEMS, DUR_MAX_SEGMENTS = 65535, 2 ** 24 - 1
+
+
+def duration_arguments(what, scale, lo, hi, rounding):
+    """The scalar arguments of the quantiser, checked -> (scale, lo, hi, rounding code); ``hi=None``: the largest the kernel takes."""
+    if rounding not in DUR_ROUNDINGS:
+        raise ValueError("%s: rounding must be 'carry' or 'nearest', got %r" % (what, rounding))
+    scale = float(scale)
+    if not 0. < scale < float('inf'):
+        raise ValueError('%s: scale must be positive and finite, got %r' % (what, scale))
+    if isinstance(lo, bool) or not isinstance(lo, numbers.Integral) or (hi is not None and (isinstance(hi, bool) or
+                                                                                             not isinstance(hi, numbers.Integral))):
+        raise TypeError('%s: the frame bounds must be integers, got %r and %r' % (what, lo, hi))
+    hi = DUR_MAX_FRAMES if hi is None else int(hi)
+    lo = int(lo)
+    if not 0 <= lo <= hi <= DUR_MAX_FRAMES:
+        raise ValueError('%s: need 0 <= lo <= hi <= %d frames, got lo=%d, hi=%d' % (what, DUR_MAX_FRAMES, lo, hi))
+    return scale, lo, hi, DUR_ROUNDINGS[rounding]
+
+
+def quantise_durations(pred, *, n_phones=None, p0=None, p1=None, item_row=None, log_input=False, scale=1., lo=1, hi=None, rounding='carry',
+                       total=None):
+    """Integer durations from a real-valued prediction (csrc/durations.hip, mg_quantise_durations_f32), one launch.  ``pred`` float32
+    (B, P) or (B, P, S) - P phones of S sub-phone states - is read in place through its strides (a column slice of a wider prediction and
+    a transposed view are not copied).  p0 / p1 (S,): the mean and std_dev that take ``pred`` back to frames (``pred * p1 + p0`` in
+    float64); with ``item_row`` (B,) int32 they are tables (rows, S) and item b takes row item_row[b] (an index outside [0, rows): the
+    item's outputs are 0 and its flags DUR_FLAG_NO_ROW); without them ``pred`` is in frames.  ``log_input``: the value is a log-duration;
+    ``scale``: a speaking-rate factor on the durations; a NaN, infinite or negative value counts as 0 (DUR_FLAG_INVALID), a value above
+    ``hi`` as ``hi``.  The values are rounded to 16 fractional bits and everything after is integer arithmetic:
+
+    ``rounding='nearest'``: every segment on its own, ``max(lo, round(x))``;
+    ``rounding='carry'``: the rounding error is carried along the item - every segment boundary is the rounded predicted boundary unless
+    the minimum ``lo`` pushes it out (DUR_FLAG_PUSHED when that changes the item's length).
+
+    ``total`` (B,) int64: every item's values are first scaled so that they add up to total[b] frames (DUR_FLAG_NO_FIT and no scaling
+    where total[b] <= 0 or the values add up to 0).  ``n_phones`` (B,) int64 drops the phones from n_phones[b] on: never read, outputs 0.
+    Returns (dur int64 shaped like pred, phone_dur int64 (B, P), n_frames int64 (B,), flags int32 (B,))."""
+    lib = _lib.load()
+    pred = _require(pred, torch.float32, 'pred', contiguous=False)
+    scale, lo, hi, code = duration_arguments('quantise_durations', scale, lo, hi, rounding)
+    if pred.dim() not in (2, 3):
+        raise ValueError('quantise_durations: pred must be (B, P) or (B, P, S), got %s' % (tuple(pred.shape),))
+    b, p = pred.shape[0], pred.shape[1]
+    s = pred.shape[2] if pred.dim() == 3 else 1
+    strides = (pred.stride(0), pred.stride(1), pred.stride(2) if pred.dim() == 3 else 0)
+    if p == 0 or s == 0 or p * s > DUR_MAX_SEGMENTS:
+        raise ValueError('quantise_durations: %d phones of %d states per utterance, the kernel takes 1..%d segments' % (p, s, DUR_MAX_SEGMENTS))
+    if b > DUR_MAX_ITEMS:
+        raise ValueError('quantise_durations: %d items, the kernel takes at most %d' % (b, DUR_MAX_ITEMS))
+    if min(strides) < 0:
+        raise ValueError('quantise_durations: pred has a negative stride %s' % (strides,))
+    if n_phones is not None:
+        n_phones = _require(n_phones, torch.int64, 'n_phones')
+        if tuple(n_phones.shape) != (b,):
+            raise ValueError('quantise_durations: n_phones must be (B,) = (%d,), got %s' % (b, tuple(n_phones.shape)))
+    if total is not None:
+        total = _require(total, torch.int64, 'total')
+        if tuple(total.shape) != (b,):
+            raise ValueError('quantise_durations: total must be (B,) = (%d,), got %s' % (b, tuple(total.shape)))
+    rows = 0
+    if p0 is None and p1 is None:
+        if item_row is not None:
+            raise ValueError('quantise_durations: item_row goes with the parameter tables p0 / p1')
+    elif p0 is None or p1 is None:
+        raise ValueError('quantise_durations: p0 and p1 go together')
+    elif item_row is None:
+        p0, p1 = _norm_vectors(p0, p1, s, ('the prediction has %d states per phone',))
+    else:
+        p0, p1, item_row = _item_tables(p0, p1, item_row, b, s, 'quantise_durations')
+        rows = p0.shape[0]
+    dev = pred.device
+    dur = torch.empty(tuple(pred.shape), dtype=torch.int64, device=dev)
+    phone_dur = torch.empty((b, p), dtype=torch.int64, device=dev)
+    n_frames = torch.empty((b,), dtype=torch.int64, device=dev)
+    flags = torch.empty((b,), dtype=torch.int32, device=dev)
+    if b == 0:                          # empty outputs: no address to hand the library
+        return dur, phone_dur, n_frames, flags
+    _lib.check(lib.mg_quantise_durations_f32(_p(pred), b, p, s, strides[0], strides[1], strides[2], _p(n_phones), _p(p0), _p(p1),
+                                             _p(item_row), rows, 1 if log_input else 0, scale, lo, hi, code, _p(total), _p(dur),
+                                             _p(phone_dur), _p(n_frames), _p(flags), _stream()), 'mg_quantise_durations_f32')
+    return dur, phone_dur, n_frames, flags
+
+
 # ---------------------------------------------------------------------------------------------- phone-rate first layer
 # MORGANA_PHONE_RATE=0: every product at frame rate (the reference's order of operations).  This is only the DEFAULT of a per-call
 # choice: utils.upsample_to_repetitions(..., phone_rate=) records the choice on the lazy sequence it returns, the layers that consume
