@@ -1547,6 +1547,70 @@ int mg_quantise_durations_f32(const float* pred, int B, int P, int S, int64_t st
                               double scale, int64_t lo, int64_t hi, int rounding, const int64_t* total, int64_t* dur, int64_t* phone_dur,
                               int64_t* n_frames, int32_t* flags, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * K32 (csrc/vocoder.hip)  vocoder features: the three arrays a WORLD-style synthesiser takes (f0, spectral envelope, aperiodicity)
+ *                         from what the acoustic models generate (lf0, vuv, mcep, bap) - models/RNN_SPSS.py:141-161 up to the
+ *                         call of the synthesiser, which stays the user's.
+ * All inputs are float32.  Input x of `width` floats per frame, exactly one of
+ *   offsets (B + 1, int64): packed [N, width] - the rows of item b are [offsets[b], offsets[b + 1]); T_in is unused,
+ *   seq_len (B, int64):     padded [B, T_in, width] - item b is rows [b T_in, b T_in + min(max(seq_len[b], 0), T_in)); later frames
+ *                           are never read; at most MG_VOC_MAX_ITEMS items (their first packed rows are scanned in LDS).
+ * Output out, PACKED [packed_rows, cols]: frame t of item b is row offsets[b] + t (packed input) or (the clamped lengths of the items
+ * before b) + t (padded input); rows that belong to no item, and rows from packed_rows on, are not written.  out_f64 == 0: float;
+ * else double, holding (double)value of the same float32 result (a vocoder's float64 arrays without a host conversion pass).
+ * B == 0 or packed_rows == 0: MG_OK, nothing launched.  One launch each, no workspace, no atomics, no host read: the same bits on
+ * every call, capturable.
+ *
+ * mg_mcep_spectrum_f32: mel-cepstrum (M = 1 .. MG_VOC_MAX_ORDER coefficients per frame) -> power spectrum, cols = K = F / 2 + 1,
+ *   F a power of two in [8, 8192]:
+ *     L[t,k]  = sum_{m < M} c[t,m] basis[m,k]          float32, fmaf in ascending m from 0 (one rounding per term)
+ *     sp[t,k] = expf(2 L[t,k]),  or 2 L[t,k] itself with log_out != 0
+ *   basis f32 [M, ldb], ldb >= K: the caller's table basis[m,k] = cos(m w~_k), w_k = 2 pi k / F,
+ *   w~ = w + 2 atan(alpha sin w / (1 - alpha cos w)) (the all-pass warp; alpha = 0: a plain cosine sum), built in float64 and rounded
+ *   once; the kernel computes no cosine.  This closed form agrees with SPTK's freqt(-alpha) followed by a cosine sum at order F / 2 to
+ *   1.5e-14 (checked on the host at (60, 0.77, 2048)); whether the un-vendored tts_data_tools called exactly that could not be verified.
+ *   Non-finite cepstra propagate by the formula.  |L^ - L| <= (M + 1) 2^-24 sum_m |c[t,m]|.
+ *   Lanes run along bins (a wave stores 64 consecutive bins), a thread holds its basis column in registers, a frame's cepstra are
+ *   wave-uniform scalar operands.  mg_vocoder_tile_frames() / mg_vocoder_tile_bins(): packed rows / bins of one tile.
+ *
+ * mg_bap_aperiodicity_f32: coded band aperiodicity in dB (Nb columns, band i centred at 3000 i Hz) -> full-band aperiodicity,
+ *   cols = K = F / 2 + 1; Nb >= 1 and 3000 Nb < fs / 2 (fs in Hz), anything else is refused.  Each coded value is clamped to [-60, 0]
+ *   (a NaN stays a NaN): above 0 dB the aperiodicity would exceed 1 and WORLD takes sqrt(1 - ap^2).  Anchors (0 Hz, -60 dB),
+ *   (3000 i Hz, bap[t,i-1]) for i = 1 .. Nb, (fs / 2, 0 dB); at f_k = k fs / F between anchors (f_lo, a) and (f_hi, b), the segment
+ *   min(floor(f_k / 3000), Nb):
+ *     w = (float)((f_k - f_lo) / (f_hi - f_lo))  in float64, rounded once
+ *     dB = fmaf(b - a, w, a);   ap[t,k] = expf(dB * (float)(ln 10 / 20))
+ *   Bin 0 is 10^-3, bin F / 2 is 1, a bin on an anchor returns that anchor's value.  This is WORLD's decode_aperiodicity (linear
+ *   interpolation of the coded dB values over frequency, floor -60 dB) as its source is remembered; it could not be checked against
+ *   pyworld, which is not installed where this was written.
+ *
+ * mg_smooth_f0_f32: log-F0 and voicing [.., D] -> a gated, smoothed F0, cols = D.  Per item of n frames and per column, in float64:
+ *     y[t] = exp((double)lf0[t]);   window = w odd in [1, MG_VOC_MAX_WINDOW], h = (w - 1) / 2
+ *     w >= 3 and n >= w:  h <= t < n - h:  s[t] = (y[t-h] + .. + y[t+h]) / w, summed in ascending order
+ *                         the first / last h frames, i = t - base with base = 0 / n - w and y_j = y[base + j]:
+ *                           s[t] = (sum_j y_j) / w + (i - h) * ((sum_j (j - h) y_j) / (sum_j (j - h)^2))
+ *                         which is scipy.signal.savgol_filter(y, w, 1) in its default 'interp' mode (checked to 2e-15)
+ *     w == 1 or n < w:    s[t] = y[t] (scipy raises there)
+ *     f0[t] = vuv[t] > threshold ? (float)s[t] : 0            (a NaN vuv is unvoiced; a NaN threshold is refused)
+ *   The window never reaches a neighbouring item.  One workgroup per item, chunks of mg_smooth_f0_chunk_rows() frames with a halo
+ *   of h frames in LDS.
+ * Refused (MG_EINVAL, nothing launched): both or neither of offsets and seq_len, F not a power of two in range, M outside
+ *   [1, MG_VOC_MAX_ORDER], ldb < K, 3000 Nb >= fs / 2, an even or out-of-range window, D < 1, a negative size, a NULL out, a NULL or
+ *   misaligned pointer where one is read or written.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define MG_VOC_MAX_ORDER 128
+#define MG_VOC_MAX_WINDOW 65
+#define MG_VOC_MAX_ITEMS 4096
+int mg_vocoder_tile_frames(void);
+int mg_vocoder_tile_bins(void);
+int mg_smooth_f0_chunk_rows(void);
+int mg_mcep_spectrum_f32(const float* mcep, int M, int B, const int64_t* offsets, const int64_t* seq_len, int T_in, const float* basis,
+                         int64_t ldb, int F, int log_out, int out_f64, int64_t packed_rows, void* out, void* stream);
+int mg_bap_aperiodicity_f32(const float* bap, int Nb, int B, const int64_t* offsets, const int64_t* seq_len, int T_in, int fs, int F,
+                            int out_f64, int64_t packed_rows, void* out, void* stream);
+int mg_smooth_f0_f32(const float* lf0, const float* vuv, int D, int B, const int64_t* offsets, const int64_t* seq_len, int T_in, int window,
+                     float threshold, int out_f64, int64_t packed_rows, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

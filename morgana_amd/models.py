@@ -632,12 +632,21 @@ class StreamModel(BaseSPSS):
                 total = total + losses.ce(output_features[st.output_key], self._target(features, st), n_frames)
         return total / float(len(self.streams)) if len(self.streams) > 1 else total
 
-    def analysis_for_valid_batch(self, features, output_features, out_dir, **kwargs):
+    def analysis_for_valid_batch(self, features, output_features, out_dir, sample_rate=16000, synthesiser=None, alpha=None, fft_size=None,
+                                 **kwargs):
         """Saves every stream's generated output per utterance under ``{out_dir}/feats/{stream}/{name}.npy``
         (``viz.io.save_batched_seqs``): the MLPG trajectory of a delta stream (present when the normalisers carry delta
         parameters, i.e. under ``ExperimentBuilder``), the probabilities of a 'sigmoid_bce' stream, the predicted classes of a 'ce'
-        stream.  models/RNN_SPSS.py:145-161 - without its WORLD waveform synthesis, which needs ``pyworld`` (not a dependency of
-        this package).  Nothing is written without an ``out_dir`` or without utterance names in ``features['name']``."""
+        stream.  Nothing is written without an ``out_dir`` or without utterance names in ``features['name']``.
+
+        models/RNN_SPSS.py:145-161 goes on to synthesise every utterance with WORLD.  Here everything up to the synthesiser runs on the
+        device (``viz.synthesis.world_features``: the smoothed, voicing-gated F0, the spectral envelope of the mel-cepstrum, the
+        full-band aperiodicity); the waveform synthesis itself is the caller's: ``synthesiser(f0, sp, ap, sample_rate) -> wav``, for
+        example ``pyworld.synthesize`` (``pyworld`` is not a dependency of this package).  With a synthesiser, and the streams ``lf0``,
+        ``vuv``, ``mcep`` and ``bap`` among the outputs, each utterance is written to ``{out_dir}/synth/{name}.wav`` at
+        ``sample_rate``; ``alpha`` and ``fft_size`` as ``world_features`` takes them.  ``synthesiser=None`` (the default) writes
+        exactly the feature files."""
+        kwargs['sample_rate'] = sample_rate                     # models/RNN_SPSS.py:142: the base hooks see it
         super(StreamModel, self).analysis_for_valid_batch(features, output_features, out_dir, **kwargs)
         names = [st.name for st in self.streams if st.name in output_features]
         if out_dir is None or not names or features.get('name') is None:
@@ -645,6 +654,19 @@ class StreamModel(BaseSPSS):
         # the classes of a categorical stream are (B, T): a trailing axis makes them a sequence feature that is cropped like the others
         outputs = [output_features[n].unsqueeze(-1) if output_features[n].ndim == 2 else output_features[n] for n in names]
         viz.io.save_batched_seqs(outputs, names=features['name'], out_dir=out_dir, seq_len=features['n_frames'], feat_names=names)
+        if synthesiser is None:
+            return
+        missing = [n for n in ('lf0', 'vuv', 'mcep', 'bap') if n not in output_features]
+        if missing:
+            raise KeyError('analysis_for_valid_batch(synthesiser=...) needs the generated streams lf0, vuv, mcep and bap; %s %s not '
+                           'among the outputs' % (', '.join(missing), 'is' if len(missing) == 1 else 'are'))
+        synth_dir = os.path.join(out_dir, 'synth')
+        os.makedirs(synth_dir, exist_ok=True)
+        per_utterance = viz.synthesis.world_features(output_features['lf0'], output_features['vuv'], output_features['mcep'],
+                                                     output_features['bap'], sample_rate, features['n_frames'], alpha=alpha,
+                                                     fft_size=fft_size)
+        for name, (f0, sp, ap) in zip(features['name'], per_utterance):
+            viz.io.save_wav(os.path.join(synth_dir, name + '.wav'), synthesiser(f0, sp, ap, sample_rate), sample_rate)
 
     def forward(self, features):
         if not self.fused_loss:

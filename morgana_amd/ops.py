@@ -3383,6 +3383,137 @@ def quantise_durations(pred, *, n_phones=None, p0=None, p1=None, item_row=None, 
     return dur, phone_dur, n_frames, flags
 
 
+# ---------------------------------------------------------------------------------------------- vocoder features (csrc/vocoder.hip)
+VOC_MAX_ORDER, VOC_MAX_WINDOW, VOC_MAX_ITEMS = _lib.MG_VOC_MAX_ORDER, _lib.MG_VOC_MAX_WINDOW, _lib.MG_VOC_MAX_ITEMS
+_mcep_bases = {}
+
+
+def spectrum_bins(fft_size, what='fft_size'):
+    """K = fft_size / 2 + 1 bins of a power-of-two FFT size in [8, 8192]; anything else is a ValueError."""
+    if isinstance(fft_size, bool) or not isinstance(fft_size, numbers.Integral) or not 8 <= fft_size <= 8192 or fft_size & (fft_size - 1):
+        raise ValueError('%s=%r must be a power of two in [8, 8192]' % (what, fft_size))
+    return int(fft_size) // 2 + 1
+
+
+def mcep_basis_table(order, alpha, fft_size):
+    """The (order, fft_size / 2 + 1) float32 table ``cos(m w~_k)`` of mg_mcep_spectrum_f32 as a host array: ``w_k = 2 pi k / fft_size``
+    warped by the all-pass of ``alpha``, ``w~ = w + 2 atan(alpha sin w / (1 - alpha cos w))``, evaluated in float64, rounded once."""
+    import numpy as np
+    k = spectrum_bins(fft_size)
+    if isinstance(order, bool) or not isinstance(order, numbers.Integral) or not 1 <= order <= VOC_MAX_ORDER:
+        raise ValueError('mcep_spectrum: %r cepstral coefficients per frame, outside [1, %d]' % (order, VOC_MAX_ORDER))
+    alpha = float(alpha)
+    if not -1. < alpha < 1.:
+        raise ValueError('mcep_spectrum: alpha=%r must lie inside (-1, 1)' % alpha)
+    w = 2. * np.pi * np.arange(k, dtype=np.float64) / float(fft_size)
+    warped = w + 2. * np.arctan2(alpha * np.sin(w), 1. - alpha * np.cos(w))
+    return np.cos(np.arange(int(order), dtype=np.float64)[:, None] * warped[None, :]).astype(np.float32)
+
+
+def mcep_basis(order, alpha, fft_size, device):
+    """``mcep_basis_table`` on ``device``, built once per (order, alpha, fft_size, device) and kept."""
+    device = torch.device(device)
+    key = (int(order), float(alpha), int(fft_size), device.type, device.index if device.index is not None else torch.cuda.current_device())
+    table = _mcep_bases.get(key)
+    if table is None:
+        table = _mcep_bases[key] = torch.from_numpy(mcep_basis_table(order, alpha, fft_size)).to(device)
+    return table
+
+
+def _vocoder_output(what, x, offsets, seq_len, cols, packed_rows, out, out_dtype, width=None):
+    """What the three vocoder wrappers share -> (offsets, seq_len, B, T_in, D, packed_rows, out, out_f64): the ragged input, the rows of
+    the packed output (default: the rows of a packed input, B * T of a padded one - an upper bound that needs no host read; the rows
+    behind the last item are then not written) and the output buffer, allocated here unless ``out`` is given."""
+    offsets, seq_len, b, t_in, d = _ragged_input(what, x, offsets, seq_len, width)
+    if d == 0:
+        raise ValueError('%s: the feature has no columns' % what)
+    if seq_len is not None and b > VOC_MAX_ITEMS:
+        raise ValueError('%s: a padded batch takes at most %d items, got %d (pack it and give offsets)' % (what, VOC_MAX_ITEMS, b))
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError('%s: out_dtype must be torch.float32 or torch.float64, got %s' % (what, out_dtype))
+    if packed_rows is None:
+        packed_rows = x.shape[0] if offsets is not None else b * t_in
+    if isinstance(packed_rows, bool) or not isinstance(packed_rows, numbers.Integral) or packed_rows < 0:
+        raise ValueError('%s: packed_rows=%r must be a non-negative integer' % (what, packed_rows))
+    n_cols = d if cols is None else cols
+    if out is None:
+        out = torch.empty((int(packed_rows), n_cols), dtype=out_dtype, device=x.device)
+    else:
+        out = _require(out, out_dtype, 'out', contiguous=False)
+        if out.dim() != 2 or out.shape[1] != n_cols or out.shape[0] < packed_rows or not out.is_contiguous() or out.device != x.device:
+            raise ValueError('%s: out %s must be a contiguous (at least %d, %d) tensor on the input\'s device' % (
+                what, tuple(out.shape), packed_rows, n_cols))
+    return offsets, seq_len, b, int(t_in), d, int(packed_rows), out, 1 if out_dtype == torch.float64 else 0
+
+
+def mcep_spectrum(mcep, alpha, fft_size, *, offsets=None, seq_len=None, packed_rows=None, log=False, out_dtype=torch.float32, out=None):
+    """Mel-cepstrum to power spectrum (csrc/vocoder.hip, mg_mcep_spectrum_f32), one launch: ``exp(2 L)`` with
+    ``L[t, k] = sum_m c[t, m] cos(m w~_k)`` over the ``fft_size / 2 + 1`` bins, ``w~`` the frequency warped by the all-pass of ``alpha``
+    (``log``: ``2 L`` itself).  The cosine table is ``mcep_basis`` (float64, rounded once, cached per order, alpha, size and device).
+
+    Input, exactly one of: ``offsets`` (B + 1,) int64 with mcep the packed rows (N, M), or ``seq_len`` (B,) int64 with mcep padded
+    (B, T, M) (frames past the length are never read).  Returns the PACKED (packed_rows, fft_size / 2 + 1) tensor of ``out_dtype``
+    (float64: the float32 result widened on the device); ``packed_rows`` defaults to N, or to B * T for a padded input (no host read;
+    rows behind the last item are not written).  ``out``: a buffer to write into - rows from ``packed_rows`` on are left alone."""
+    lib = _lib.load()
+    mcep = _require(mcep, torch.float32, 'mcep')
+    k = spectrum_bins(fft_size)
+    offsets, seq_len, b, t_in, m, packed_rows, out, f64 = _vocoder_output('mcep_spectrum', mcep, offsets, seq_len, k, packed_rows, out,
+                                                                          out_dtype)
+    if b == 0 or packed_rows == 0:          # nothing to write: no address to hand the library
+        return out
+    basis = mcep_basis(m, alpha, fft_size, mcep.device)
+    _lib.check(lib.mg_mcep_spectrum_f32(_p(mcep), m, b, _p(offsets), _p(seq_len), t_in, _p(basis), basis.shape[1], int(fft_size),
+                                        1 if log else 0, f64, packed_rows, _p(out), _stream()), 'mg_mcep_spectrum_f32')
+    return out
+
+
+def bap_aperiodicity(bap, sample_rate, fft_size, *, offsets=None, seq_len=None, packed_rows=None, out_dtype=torch.float32, out=None):
+    """Coded band aperiodicity (dB, one column per 3 kHz band) to full-band aperiodicity (csrc/vocoder.hip, mg_bap_aperiodicity_f32),
+    one launch: every value clamped to [-60, 0], interpolated linearly in dB between (0 Hz, -60), (3000 i Hz, band i) and
+    (sample_rate / 2, 0) at the ``fft_size / 2 + 1`` bin frequencies, then ``10 ** (dB / 20)``.  ``3000 * bands < sample_rate / 2``.
+    Layouts, ``packed_rows``, ``out_dtype`` and ``out`` as ``mcep_spectrum``."""
+    lib = _lib.load()
+    bap = _require(bap, torch.float32, 'bap')
+    k = spectrum_bins(fft_size)
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, numbers.Integral) or sample_rate <= 0:
+        raise ValueError('bap_aperiodicity: sample_rate=%r must be a positive integer (Hz)' % (sample_rate,))
+    offsets, seq_len, b, t_in, nb, packed_rows, out, f64 = _vocoder_output('bap_aperiodicity', bap, offsets, seq_len, k, packed_rows, out,
+                                                                           out_dtype)
+    if 6000 * nb >= sample_rate:
+        raise ValueError('bap_aperiodicity: %d bands of 3000 Hz do not end below sample_rate / 2 = %g Hz' % (nb, sample_rate / 2.))
+    if b == 0 or packed_rows == 0:          # nothing to write: no address to hand the library
+        return out
+    _lib.check(lib.mg_bap_aperiodicity_f32(_p(bap), nb, b, _p(offsets), _p(seq_len), t_in, int(sample_rate), int(fft_size), f64,
+                                           packed_rows, _p(out), _stream()), 'mg_bap_aperiodicity_f32')
+    return out
+
+
+def smooth_f0(lf0, vuv, *, offsets=None, seq_len=None, packed_rows=None, window=7, threshold=0.5, out_dtype=torch.float32, out=None):
+    """Log-F0 and voicing to the F0 track a vocoder takes (csrc/vocoder.hip, mg_smooth_f0_f32), one launch: per item and column
+    ``exp(lf0)`` in float64, smoothed by ``scipy.signal.savgol_filter(., window, 1)`` (a moving average of ``window`` frames; the first
+    and last ``window // 2`` frames on the least-squares line of the item's first / last ``window`` frames; an item shorter than the
+    window, and ``window=1``, unsmoothed), then 0 wherever ``vuv <= threshold``.  ``window`` is odd, at most VOC_MAX_WINDOW.
+    lf0 and vuv share one layout and shape; layouts, ``packed_rows``, ``out_dtype`` and ``out`` as ``mcep_spectrum``."""
+    lib = _lib.load()
+    lf0 = _require(lf0, torch.float32, 'lf0')
+    vuv = _require(vuv, torch.float32, 'vuv')
+    if vuv.shape != lf0.shape or vuv.device != lf0.device:
+        raise ValueError('smooth_f0: vuv %s on %s does not match lf0 %s on %s' % (tuple(vuv.shape), vuv.device, tuple(lf0.shape), lf0.device))
+    if isinstance(window, bool) or not isinstance(window, numbers.Integral) or window < 1 or window > VOC_MAX_WINDOW or window % 2 == 0:
+        raise ValueError('smooth_f0: window=%r must be an odd integer in [1, %d]' % (window, VOC_MAX_WINDOW))
+    threshold = ctypes.c_float(float(threshold)).value
+    if threshold != threshold:
+        raise ValueError('smooth_f0: threshold is NaN: no frame would be voiced')
+    offsets, seq_len, b, t_in, d, packed_rows, out, f64 = _vocoder_output('smooth_f0', lf0, offsets, seq_len, None, packed_rows, out,
+                                                                          out_dtype)
+    if b == 0 or packed_rows == 0:          # nothing to write: no address to hand the library
+        return out
+    _lib.check(lib.mg_smooth_f0_f32(_p(lf0), _p(vuv), d, b, _p(offsets), _p(seq_len), t_in, int(window), threshold, f64, packed_rows,
+                                    _p(out), _stream()), 'mg_smooth_f0_f32')
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- phone-rate first layer
 # MORGANA_PHONE_RATE=0: every product at frame rate (the reference's order of operations).  This is only the DEFAULT of a per-call
 # choice: utils.upsample_to_repetitions(..., phone_rate=) records the choice on the lazy sequence it returns, the layers that consume

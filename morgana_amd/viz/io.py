@@ -1,6 +1,7 @@
 """The file-writing side of ``morgana.viz.io``: ``save_batched_seqs`` keeps the reference's name, arguments and error behaviour
 (morgana/viz/io.py:10-56) and writes ``.npy`` files."""
 import os
+import wave
 
 import numpy as np
 
@@ -45,3 +46,20 @@ def save_batched_seqs(sequence_features, names, out_dir, seq_len=None, feat_name
         os.makedirs(feat_dir, exist_ok=True)
         for name, item in zip(names, items):
             np.save(os.path.join(feat_dir, name + '.npy'), item)
+
+
+def save_wav(path, wav, sample_rate):
+    """Writes a mono waveform as 16-bit PCM with the standard library's ``wave`` (the reference writes through
+    ``tts_data_tools.file_io.save_wav``, which is not a dependency here).  wav: 1-D samples - floating point in [-1, 1], scaled by
+    32767, rounded and clipped; integers are taken as PCM values and clipped to int16.  A NaN sample is written as 0."""
+    wav = np.asarray(wav)
+    if wav.ndim != 1:
+        raise ValueError('save_wav takes a 1-D (mono) waveform, got shape %s' % (wav.shape,))
+    if not np.issubdtype(wav.dtype, np.integer):
+        wav = np.rint(np.nan_to_num(wav.astype(np.float64), nan=0., posinf=1., neginf=-1.) * 32767.)
+    pcm = np.clip(wav, -32768, 32767).astype('<i2')
+    with wave.open(path, 'wb') as f:
+        f.setnchannels(1)
+        f.setsampwidth(2)
+        f.setframerate(int(sample_rate))
+        f.writeframes(pcm.tobytes())

@@ -111,6 +111,132 @@ def MLPG_GV(means, variances, gv_mean, gv_variance, windows=None, padding_size=0
     return out if as_tensor else out.cpu().numpy()
 
 
+# ---- vocoder features (csrc/vocoder.hip): models/RNN_SPSS.py:141-161 up to the call of the synthesiser
+# Frequency-warping coefficients of the mel-cepstral analysis by sample rate: the values Merlin's WORLD recipes use.  What a corpus
+# was analysed with is its owner's to know - pass ``alpha`` whenever it is known.
+MERLIN_ALPHA = {16000: 0.58, 22050: 0.65, 44100: 0.76, 48000: 0.77}
+
+
+def default_alpha(sample_rate):
+    """Merlin's all-pass constant for ``sample_rate`` (``MERLIN_ALPHA``); any other rate raises: there is no formula to guess from."""
+    try:
+        return MERLIN_ALPHA[int(sample_rate)]
+    except KeyError:
+        raise ValueError('no default alpha for a sample rate of %r Hz (known: %s): pass the alpha the corpus was analysed with'
+                         % (sample_rate, sorted(MERLIN_ALPHA)))
+
+
+def default_fft_size(sample_rate):
+    """WORLD's CheapTrick FFT size for ``sample_rate``: 2 ** ceil(log2(3 fs / 71 + 1)) (f0 floor 71 Hz) - 1024 at 16 kHz, 2048 at 48 kHz."""
+    return 2 ** int(np.ceil(np.log2(3. * float(sample_rate) / 71. + 1.)))
+
+
+def _upload(what, x, dtype, device):
+    """(tensor on the device, the inputs' device or None): a device tensor as it is, an array uploaded to the current device."""
+    if isinstance(x, torch.Tensor):
+        return x.detach().to(dtype=dtype)
+    if device is None:
+        if not torch.cuda.is_available():
+            raise _lib.MorganaHipError('%s runs only on an MI355X device (no CPU fallback)' % what)
+        device = torch.device('cuda', torch.cuda.current_device())
+    return torch.from_numpy(np.array(x)).to(device=device, dtype=dtype)
+
+
+def _batched(what, x, seq_len, *more):
+    """The padded (B, T, D) form of a feature (a single (T, D) sequence gains the batch axis), its (B,) int64 device lengths, the
+    (B + 1,) packed offsets and the rows of the packed output.  ``seq_len`` None: every item is whole, nothing is read; host lengths
+    (array, list) are exact without a device read; DEVICE lengths stay on the device and the packed output has B * T rows, of which
+    those from ``offsets[-1]`` on are not written."""
+    device = _device_of(x, *more)
+    tensors = [_upload(what, v, torch.float32, device) for v in (x,) + more]
+    tensors = [v[None] if v.dim() == 2 else v for v in tensors]
+    if tensors[0].dim() != 3:
+        raise ValueError('%s takes (batch_size, seq_len, feat_dim) or (seq_len, feat_dim), got %s' % (what, tuple(tensors[0].shape)))
+    b, t = tensors[0].shape[:2]
+    dev = tensors[0].device
+    if seq_len is None:
+        lengths = torch.full((b,), t, dtype=torch.int64, device=dev)
+        rows = b * t
+    elif isinstance(seq_len, torch.Tensor):
+        lengths = seq_len.detach().reshape(-1).to(device=dev, dtype=torch.int64).clamp(0, t)
+        rows = b * t
+    else:
+        host = np.clip(np.asarray(seq_len, dtype=np.int64).reshape(-1), 0, t)
+        lengths = torch.from_numpy(host).to(dev)
+        rows = int(host.sum())
+    if lengths.numel() != b:
+        raise ValueError('%s: seq_len holds %d lengths for %d items' % (what, lengths.numel(), b))
+    offsets = torch.zeros((b + 1,), dtype=torch.int64, device=dev)
+    torch.cumsum(lengths, 0, out=offsets[1:])
+    return tensors, lengths, offsets, rows
+
+
+def mcep_to_spectrum(mcep, alpha, fft_size, seq_len=None, log=False, dtype=torch.float32):
+    r"""Mel-cepstrum to power spectrum, the envelope a WORLD-style vocoder takes (``csrc/vocoder.hip``).
+
+    mcep : (batch_size, seq_len, order) or (seq_len, order); alpha : the all-pass constant of the analysis (``default_alpha``);
+    fft_size : a power of two (``default_fft_size``); seq_len : (batch_size,) lengths; log : return the log power spectrum;
+    dtype : torch.float32 or torch.float64 (the float32 result widened on the device).
+
+    ``sp[t, k] = exp(2 sum_m c[t, m] cos(m w~_k))`` at ``w_k = 2 pi k / fft_size`` warped by the all-pass of ``alpha``: in closed form
+    what SPTK's ``freqt(-alpha)`` to order ``fft_size / 2`` followed by a cosine sum gives (agreement 1.5e-14, checked on the host).
+    Whether the un-vendored ``tts_data_tools`` the reference calls did exactly that could not be verified: the package is not
+    available.  Returns (spectrum, offsets): the PACKED (rows, fft_size / 2 + 1) device tensor - utterance b is rows
+    ``offsets[b]:offsets[b + 1]`` - and the (batch_size + 1,) int64 device offsets.  NumPy arrays are uploaded (float32), as ``MLPG``
+    does; the results stay on the device.  There is no host implementation: without the HIP library this raises."""
+    (mcep,), lengths, offsets, rows = _batched('mcep_to_spectrum', mcep, seq_len)
+    return ops.mcep_spectrum(mcep, alpha, fft_size, seq_len=lengths, packed_rows=rows, log=log, out_dtype=dtype), offsets
+
+
+def bap_to_aperiodicity(bap, sample_rate, fft_size, seq_len=None, dtype=torch.float32):
+    r"""Coded band aperiodicity (dB, one column per 3 kHz band: 1 at 16 kHz, 5 at 48 kHz) to the full-band aperiodicity a WORLD-style
+    vocoder takes (``csrc/vocoder.hip``): values clamped to [-60, 0] dB, interpolated linearly in dB over frequency between
+    (0 Hz, -60 dB), the bands at 3000 i Hz and (sample_rate / 2, 0 dB), then ``10 ** (dB / 20)``.  This is WORLD's
+    ``decode_aperiodicity`` as remembered; it could not be checked against ``pyworld``.  Arguments and returns as ``mcep_to_spectrum``."""
+    (bap,), lengths, offsets, rows = _batched('bap_to_aperiodicity', bap, seq_len)
+    return ops.bap_aperiodicity(bap, int(sample_rate), fft_size, seq_len=lengths, packed_rows=rows, out_dtype=dtype), offsets
+
+
+def smooth_f0(lf0, vuv, seq_len=None, window=7, threshold=0.5, dtype=torch.float32):
+    r"""Log-F0 and voicing to the F0 track a vocoder takes (models/RNN_SPSS.py:154-157): ``exp``, then
+    ``scipy.signal.savgol_filter(f0, window, 1)`` per utterance (an utterance shorter than the window is left unsmoothed, where scipy
+    raises), then 0 on every frame whose ``vuv`` is not above ``threshold``.  lf0, vuv : (batch_size, seq_len, 1) or (seq_len, 1).
+    Returns (f0, offsets): the packed (rows, 1) device tensor and the offsets, as ``mcep_to_spectrum``."""
+    (lf0, vuv), lengths, offsets, rows = _batched('smooth_f0', lf0, seq_len, vuv)
+    return ops.smooth_f0(lf0, vuv, seq_len=lengths, packed_rows=rows, window=window, threshold=threshold, out_dtype=dtype), offsets
+
+
+def world_features(lf0, vuv, mcep, bap, sample_rate, seq_len, alpha=None, fft_size=None, f0_window=7, as_numpy=True):
+    r"""The three arrays a WORLD-style synthesiser takes for every utterance of a batch, from what an acoustic model generates.
+
+    lf0, vuv : (batch_size, seq_len, 1); mcep : (batch_size, seq_len, order); bap : (batch_size, seq_len, bands); seq_len : (batch_size,)
+    lengths; alpha : None looks the rate up in ``MERLIN_ALPHA`` (Merlin's WORLD values - what the corpus was analysed with is the
+    user's to know - and raises for any other rate); fft_size : None is WORLD's CheapTrick size (``default_fft_size``).
+
+    Returns a list of per-utterance ``(f0 (n,), sp (n, fft_size / 2 + 1), ap (n, fft_size / 2 + 1))``: float64, C-contiguous NumPy
+    arrays (``pyworld.synthesize`` takes exactly these), or with ``as_numpy=False`` views of the packed float64 device tensors.
+    ``seq_len`` is read once and each feature reaches the host in one copy."""
+    alpha = default_alpha(sample_rate) if alpha is None else alpha
+    fft_size = default_fft_size(sample_rate) if fft_size is None else fft_size
+    if isinstance(seq_len, torch.Tensor):
+        seq_len = seq_len.detach().reshape(-1).cpu().numpy()           # the one read of the lengths
+    seq_len = np.asarray(seq_len, dtype=np.int64).reshape(-1)
+    f0, _ = smooth_f0(lf0, vuv, seq_len, window=f0_window, dtype=torch.float64)
+    sp, _ = mcep_to_spectrum(mcep, alpha, fft_size, seq_len, dtype=torch.float64)
+    ap, _ = bap_to_aperiodicity(bap, sample_rate, fft_size, seq_len, dtype=torch.float64)
+    if f0.shape[1] != 1:
+        raise ValueError('world_features: lf0 and vuv must have one column, got %d' % f0.shape[1])
+    frames = f0.shape[0]
+    if sp.shape[0] != frames or ap.shape[0] != frames:
+        raise ValueError('world_features: the features disagree about the frames (%d, %d, %d)' % (frames, sp.shape[0], ap.shape[0]))
+    f0 = f0.reshape(-1)
+    if as_numpy:
+        f0, sp, ap = f0.cpu().numpy(), sp.cpu().numpy(), ap.cpu().numpy()
+    # each item's length as its feature sees it (clamped to that feature's own T): the three agree where the shapes do
+    ends = np.cumsum(np.clip(seq_len, 0, lf0.shape[-2]))
+    return [(f0[e - n:e], sp[e - n:e], ap[e - n:e]) for e, n in zip(ends, np.clip(seq_len, 0, lf0.shape[-2]))]
+
+
 def mlpg_trajectory(means, variances, windows=None, padding_size=0, seq_len=None, variance_grad=False):
     r"""``MLPG`` as a differentiable layer (trajectory / minimum-generation-error training; the reference's host MLPG has no gradient).
 
