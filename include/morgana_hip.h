@@ -1611,6 +1611,58 @@ int mg_bap_aperiodicity_f32(const float* bap, int Nb, int B, const int64_t* offs
 int mg_smooth_f0_f32(const float* lf0, const float* vuv, int D, int B, const int64_t* offsets, const int64_t* seq_len, int T_in, int window,
                      float threshold, int out_f64, int64_t packed_rows, void* out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * K33 (csrc/analysis.hip)  vocoder analysis, the opposite direction of K32: what an analyser such as WORLD gives per frame - a power
+ *                          spectrum and a full-band aperiodicity, K = F / 2 + 1 bins each - coded into the mel-cepstrum and the
+ *                          band aperiodicity the models are trained on.  The waveform analysis itself stays the user's.
+ * The input conventions are K32's: input x of K elements per frame, exactly one of offsets (B + 1, int64; packed [N, K]) and seq_len
+ * (B, int64; padded [B, T_in, K], at most MG_VOC_MAX_ITEMS items, frames past the clamped length are never read); output PACKED
+ * [packed_rows, cols], rows of no item and rows from packed_rows on are not written; B == 0 or packed_rows == 0: MG_OK, nothing
+ * launched.  One launch each, no workspace, no atomics, no host read: the same bits on every call, capturable.
+ * New in this family: the INPUT is float (in_f64 == 0) or double (in_f64 != 0) - analysers write float64; out_f64 chooses the output.
+ *
+ * mg_spectrum_mcep: power spectrum -> M = 1 .. MG_VOC_MAX_ORDER mel-cepstral coefficients, cols = M, F a power of two in [8, 8192]:
+ *     l[t,k] = 0.5 * log((double)sp[t,k])       (log_in != 0: 0.5 * (double)x[t,k]; x is what mg_mcep_spectrum_f32 writes with log_out)
+ *     c[t,m] = sum_{k < K} table[m,k] * l[t,k]   in float64; every product and every addition rounded at most once, in one fixed
+ *                                                order (the float64 matrix instruction, K taken in ascending groups of four)
+ *     out    = out_f64 ? c : (float)c            one rounding: the float32 output is bit for bit the float64 output rounded
+ *   |c^ - c| <= (2K + 8) 2^-53 sum_k |table[m,k]| |l[t,k]| (the dot product in any order, one rounding per table entry, 2 ulp of log).
+ *   table f64 [M, ldt], ldt >= K, is the caller's; the kernel computes no cosine and runs no recursion.  It is the composition of two
+ *   linear maps, built on the host in float64:
+ *     cepstrum   g_n = (kappa_n / F) [l_0 + (-1)^n l_{F/2} + 2 sum_{k=1}^{F/2-1} l_k cos(2 pi n k / F)],  n = 0 .. F/2,
+ *                kappa_n = 1 for n in {0, F/2}, else 2: the one-sided cepstrum, l_k = sum_n g_n cos(n w_k) exactly on the grid;
+ *     freqt      SPTK's frequency transform from order F/2 to order M - 1 with alpha: c~ = 0; for i = F/2 down to 0: d = c~;
+ *                c~_0 = g_i + alpha d_0;  c~_1 = (1 - alpha^2) d_0 + alpha d_1;  c~_j = d_{j-1} + alpha (d_j - c~_{j-1}) for j >= 2.
+ *   The composition is the left inverse of K32's basis, table . basis(M, alpha, F)^T = I_M, to 2e-15 at (60, .77, 2048), (25, .58,
+ *   1024), (60, .58, 1024), (40, .42, 512), and agrees with the two-step route (irfft, then the recursion per frame) to 4e-15;
+ *   max_m sum_k |table[m,k]| is about 1.3.  The identity does NOT hold where the warped series aliases - (128, .77, 2048): 6e-4,
+ *   (5, .58, 16): 0.65 - which is a property of the truncated transform, not an error: such settings are held to the two-step route.
+ *   This is pysptk.sp2mc as its source is remembered (irfft of the log power spectrum, c[0] halved, freqt); it could not be checked
+ *   against pysptk, which is not installed where this was written.
+ *   Non-finite and non-positive bins propagate by the formula (log(0) = -inf, log of a negative number is NaN): that frame's
+ *   coefficients come out non-finite and no other frame changes.  Nothing at or past sp[t, K) of a row is read as an operand: the
+ *   dead slots of the last group of four enter as exact zeros on both operands.
+ *   mg_analysis_tile_frames(): packed rows of one workgroup's tile (a wave owns 16 of them).
+ *
+ * mg_aperiodicity_bap: full-band aperiodicity -> Nb >= 1 coded bands in dB, cols = Nb, 3000 Nb < fs / 2 (fs in Hz): the constraints of
+ *   mg_bap_aperiodicity_f32.  Band b (0-based) is anchored at 3000 (b + 1) Hz, bin position 3000 (b + 1) F / fs: in integer arithmetic
+ *   k0 the quotient and r the remainder of that division, w = (double)r / (double)fs;
+ *     dB(k)    = min(max(20 * log10((double)ap[t,k]), -60), 0)      (a NaN stays a NaN; ap = 0 gives -60)
+ *     bap[t,b] = fma(dB(k0 + 1) - dB(k0), w, dB(k0))                in float64, rounded to float once (out_f64: the double itself)
+ *   This is WORLD's CodeAperiodicity as remembered (linear interpolation of the dB values at the coarse frequency axis); it could
+ *   not be checked against pyworld.  Where every anchor falls on a bin (16 kHz / 1024, 48 kHz / 2048) it inverts
+ *   mg_bap_aperiodicity_f32 exactly (1.4e-14 dB in float64); where none does (44.1 kHz / 2048, 22.05 kHz / 1024) the bin pair
+ *   straddles the decoder's kink and the round trip is off by up to 0.17 dB.
+ * Refused (MG_EINVAL, nothing launched): both or neither of offsets and seq_len, F not a power of two in range, M outside
+ *   [1, MG_VOC_MAX_ORDER], ldt < K, 3000 Nb >= fs / 2, a negative size, a NULL out or table, a NULL input where one is read, a
+ *   pointer misaligned for its element type.
+ * ---------------------------------------------------------------------------------------------------------------- */
+int mg_analysis_tile_frames(void);
+int mg_spectrum_mcep(const void* sp, int in_f64, int log_in, int F, int B, const int64_t* offsets, const int64_t* seq_len, int T_in,
+                     const double* table, int64_t ldt, int M, int out_f64, int64_t packed_rows, void* out, void* stream);
+int mg_aperiodicity_bap(const void* ap, int in_f64, int F, int fs, int Nb, int B, const int64_t* offsets, const int64_t* seq_len,
+                        int T_in, int out_f64, int64_t packed_rows, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

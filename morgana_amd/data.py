@@ -1058,9 +1058,10 @@ _STAGING = _Staging()
 HOST_PACK_THREADS = max(1, min(8, (os.cpu_count() or 2) // 2))
 
 
-def _pack_pinned(items, device, key):
-    """``np.concatenate(items)`` of 2-D float32 arrays into a pinned staging buffer (mg_host_pack: threaded memcpy), its asynchronous
-    copy to ``device`` and the row offsets (int64, ``len(items) + 1``) beside it.  Returns (packed device tensor, offsets device tensor)."""
+def _pack_pinned(items, device, key, dtype=np.float32):
+    """``np.concatenate(items)`` of 2-D float32 arrays (``dtype``: of another element type - mg_host_pack copies bytes) into a pinned
+    staging buffer (mg_host_pack: threaded memcpy), its asynchronous copy to ``device`` and the row offsets (int64, ``len(items) + 1``)
+    beside it.  Returns (packed device tensor, offsets device tensor, host lengths)."""
     import ctypes
     from . import _lib
     width = items[0].shape[1]
@@ -1068,13 +1069,16 @@ def _pack_pinned(items, device, key):
     total = int(lens.sum())
     n_off = len(items) + 1
     off_bytes = (n_off * 8 + 63) // 64 * 64
-    n_bytes = off_bytes + total * width * 4
+    dtype = np.dtype(dtype)
+    if dtype not in (np.float32, np.float64):
+        raise TypeError('_pack_pinned packs float32 or float64 rows, got %s' % dtype)
+    n_bytes = off_bytes + total * width * dtype.itemsize
     slot = _STAGING.take(str(device), key, n_bytes)
     host = slot[0]
     offsets_host = host[:n_off * 8].view(torch.int64)
     offsets_host[0] = 0
     offsets_host[1:] = torch.from_numpy(np.cumsum(lens))
-    arrays = [x if (x.flags['C_CONTIGUOUS'] and x.dtype == np.float32) else np.ascontiguousarray(x, dtype=np.float32) for x in items]
+    arrays = [x if (x.flags['C_CONTIGUOUS'] and x.dtype == dtype) else np.ascontiguousarray(x, dtype=dtype) for x in items]
     srcs = (ctypes.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
     sizes = (ctypes.c_int64 * len(arrays))(*[a.nbytes for a in arrays])
     lib = _lib.load()
@@ -1085,7 +1089,7 @@ def _pack_pinned(items, device, key):
     slot[1] = torch.cuda.Event()
     slot[1].record(torch.cuda.current_stream(device))
     offsets = staged[:n_off * 8].view(torch.int64)
-    packed = staged[off_bytes:].view(torch.float32).view(total, width)
+    packed = staged[off_bytes:].view(torch.float64 if dtype == np.float64 else torch.float32).view(total, width)
     return packed, offsets, lens
 
 
@@ -1848,3 +1852,205 @@ def fit_global_variance(utterances, names, device='cuda:0', batch_size=64, out_d
             normaliser.save_params(out_dir, data_root)
         fitted[name + GV_SUFFIX] = normaliser
     return fitted
+
+
+# ---- vocoder analysis (csrc/analysis.hip): from what an analyser such as WORLD writes (f0, sp, ap) to the features the models read.
+# The opposite direction of viz.synthesis.world_features.  The coding runs ONCE per corpus (extract_world_features), not in a loader:
+# re-coding 8 KB of spectrum per frame every epoch to get 240 B of features is the wrong trade.
+def _analysis_device(what, *values):
+    """The device of the first tensor among ``values``, else the current device; without one there is nothing to run on."""
+    from ._lib import MorganaHipError
+    for v in values:
+        if isinstance(v, torch.Tensor):
+            _on_device(what, v)
+            return v.device
+    if not torch.cuda.is_available():
+        raise MorganaHipError('%s runs only on an MI355X device (no CPU fallback)' % what)
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def _analysis_upload(what, x, device, dtype=None):
+    """A spectrum-like feature on the device in the float type it comes in (float32 or float64; anything else becomes float64), or
+    in ``dtype``: an array is uploaded, a device tensor taken as it is."""
+    if isinstance(x, torch.Tensor):
+        _on_device(what, x)
+        x = x.detach()
+    else:
+        x = torch.from_numpy(np.array(x)).to(device)
+    if dtype is None:
+        dtype = x.dtype if x.dtype in (torch.float32, torch.float64) else torch.float64
+    return x.to(dtype=dtype)
+
+
+def _analysis_batched(what, x, seq_len):
+    """(padded (B, T, K) device tensor in its own float type, (B,) device lengths, (B + 1,) device offsets, rows of the packed output)
+    of a feature given as (B, T, K) or (T, K) - the conventions of viz.synthesis.mcep_to_spectrum: host lengths are exact without a
+    device read, device lengths leave B * T rows of which those from ``offsets[-1]`` on are not written."""
+    x = _analysis_upload(what, x, _analysis_device(what, x, seq_len))
+    if x.dim() == 2:
+        x = x[None]
+    if x.dim() != 3:
+        raise ValueError('%s takes (batch_size, seq_len, bins) or (seq_len, bins), got %s' % (what, tuple(x.shape)))
+    b, t = x.shape[:2]
+    if seq_len is None:
+        lengths, rows = torch.full((b,), t, dtype=torch.int64, device=x.device), b * t
+    elif isinstance(seq_len, torch.Tensor):
+        lengths, rows = seq_len.detach().reshape(-1).to(device=x.device, dtype=torch.int64).clamp(0, t), b * t
+    else:
+        host = np.clip(np.asarray(seq_len, dtype=np.int64).reshape(-1), 0, t)
+        lengths, rows = torch.from_numpy(host).to(x.device), int(host.sum())
+    if lengths.numel() != b:
+        raise ValueError('%s: seq_len holds %d lengths for %d items' % (what, lengths.numel(), b))
+    offsets = torch.zeros((b + 1,), dtype=torch.int64, device=x.device)
+    torch.cumsum(lengths, 0, out=offsets[1:])
+    return x, lengths, offsets, rows
+
+
+def spectrum_to_mcep(sp, order, alpha, fft_size=None, seq_len=None, log_input=False, dtype=torch.float32):
+    r"""Power spectrum to mel-cepstrum (``csrc/analysis.hip``): ``c = table (0.5 log sp)`` per frame in float64, ``table`` the one-sided
+    cepstrum followed by SPTK's ``freqt(alpha)`` (``ops.mcep_analysis_table``) - ``pysptk.sp2mc`` as its source is remembered, which
+    could not be checked: the package is not available.  Where the warped series does not alias (every shipped setting) it is the left
+    inverse of ``viz.synthesis.mcep_to_spectrum``.
+
+    sp : (batch_size, seq_len, fft_size / 2 + 1) or (seq_len, fft_size / 2 + 1), float32 or float64 - a NumPy array is uploaded in
+    its own type, a device tensor taken as it is; order : coefficients per frame; fft_size : None is ``2 (bins - 1)``; log_input : sp is
+    a log power spectrum.  Returns (mcep, offsets): the PACKED (rows, order) device tensor of ``dtype`` and the (batch_size + 1,) int64
+    device offsets.  There is no host implementation: without the HIP library this raises."""
+    sp, lengths, offsets, rows = _analysis_batched('spectrum_to_mcep', sp, seq_len)
+    return ops.spectrum_mcep(sp, order, alpha, fft_size, seq_len=lengths, packed_rows=rows, log_input=log_input, out_dtype=dtype), offsets
+
+
+def aperiodicity_to_bap(ap, sample_rate, n_bands=None, fft_size=None, seq_len=None, dtype=torch.float32):
+    r"""Full-band aperiodicity to coded band aperiodicity in dB, one column per 3 kHz band (``csrc/analysis.hip``): ``20 log10(ap)``
+    clamped to [-60, 0] and interpolated linearly between the two bins around 3000 (b + 1) Hz - WORLD's ``CodeAperiodicity`` as
+    remembered; it could not be checked against ``pyworld``.  n_bands : None is WORLD's rule (1 at 16 kHz, 5 at 48 kHz).  Arguments and
+    returns as ``spectrum_to_mcep``."""
+    ap, lengths, offsets, rows = _analysis_batched('aperiodicity_to_bap', ap, seq_len)
+    return ops.aperiodicity_bap(ap, int(sample_rate), n_bands, fft_size, seq_len=lengths, packed_rows=rows, out_dtype=dtype), offsets
+
+
+def _analysis_items(what, x, seq_len, form):
+    """A feature of several utterances as a list of per-utterance (n, columns) views.  ``form``: 'list' - a list / tuple of arrays or
+    tensors, taken as it is; 'one' - one utterance, a list of one; 'padded' - a (B, T, ...) batch cut to the host lengths ``seq_len``."""
+    if form == 'list':
+        if not isinstance(x, (list, tuple)):
+            raise TypeError('%s: f0, sp and ap come in one form: lists of utterances, one utterance or padded batches' % what)
+        items = list(x)
+    elif form == 'one':
+        items = [x]
+    else:
+        if len(seq_len) != x.shape[0]:
+            raise ValueError('%s: seq_len holds %d lengths for %d items' % (what, len(seq_len), x.shape[0]))
+        items = [x[i, :max(int(n), 0)] for i, n in enumerate(seq_len)]
+    return [v.reshape(v.shape[0], -1) for v in items]
+
+
+def world_parameters(f0, sp, ap, sample_rate, n_mcep=60, alpha=None, n_bands=None, seq_len=None):
+    r"""The acoustic features of the shipped models from what a WORLD-style analyser gives: the inverse of
+    ``viz.synthesis.world_features``.
+
+    f0 : (n,), sp, ap : (n, fft_size / 2 + 1) of one utterance; or lists of those, one entry per utterance (what ``world_features``
+    returns, transposed: ``world_parameters(*zip(*features), sample_rate)``); or padded batches (B, T[, bins]) with seq_len (B,).  NumPy
+    arrays are uploaded in their own float type, device tensors taken as they are.  alpha : None looks the rate up in
+    ``viz.synthesis.MERLIN_ALPHA`` and raises for any other rate; n_bands : None is WORLD's rule (``ops.default_n_bands``).
+
+    Returns per utterance ``(lf0 (n, 1), vuv (n, 1), mcep (n, n_mcep), bap (n, n_bands))``, float32 NumPy arrays - one tuple for one
+    utterance, else a list of tuples.  ``lf0`` and ``vuv`` are ``continuous_lf0`` of ``f0``; ``mcep`` is ``spectrum_to_mcep``, ``bap`` is
+    ``aperiodicity_to_bap``.  Each feature reaches the host in one copy.  There is no host implementation."""
+    from .viz import synthesis
+    what = 'world_parameters'
+    if isinstance(seq_len, torch.Tensor):
+        seq_len = seq_len.detach().reshape(-1).cpu().numpy()
+    alpha = synthesis.default_alpha(sample_rate) if alpha is None else alpha
+    form = 'list' if isinstance(sp, (list, tuple)) else 'one' if sp.ndim == 2 else 'padded'
+    if (form == 'padded') != (seq_len is not None):
+        raise ValueError('%s: seq_len goes with padded (B, T, bins) batches, and those need it' % what)
+    single = form == 'one'
+    f0_items, sp_items, ap_items = (_analysis_items(what, v, seq_len, form) for v in (f0, sp, ap))
+    if not len(f0_items) == len(sp_items) == len(ap_items):
+        raise ValueError('%s: %d, %d and %d utterances of f0, sp and ap' % (what, len(f0_items), len(sp_items), len(ap_items)))
+    device = _analysis_device(what, *(f0_items + sp_items + ap_items))
+    lens = np.array([v.shape[0] for v in sp_items], dtype=np.int64)
+    for i, (a, b, c) in enumerate(zip(f0_items, sp_items, ap_items)):
+        if a.shape[0] != b.shape[0] or c.shape != b.shape or a.shape[1] != 1:
+            raise ValueError('%s: utterance %d has f0 %s, sp %s and ap %s' % (what, i, tuple(a.shape), tuple(b.shape), tuple(c.shape)))
+
+    def packed(items, dtype=None):
+        if all(isinstance(v, np.ndarray) for v in items):
+            return _analysis_upload(what, np.concatenate(items) if len(items) > 1 else items[0], device, dtype)
+        return torch.cat([_analysis_upload(what, v, device, dtype) for v in items])
+
+    offsets = torch.from_numpy(np.concatenate(([0], np.cumsum(lens)))).to(device)
+    _, _, vuv, lf0 = ops.continuous_lf0(packed(f0_items, torch.float32), offsets=offsets)
+    mcep = ops.spectrum_mcep(packed(sp_items), n_mcep, alpha, offsets=offsets)
+    bap = ops.aperiodicity_bap(packed(ap_items), int(sample_rate), n_bands, offsets=offsets)
+    lf0, vuv, mcep, bap = lf0.cpu().numpy(), vuv.cpu().numpy(), mcep.cpu().numpy(), bap.cpu().numpy()
+    ends = np.cumsum(lens)
+    out = [(lf0[e - n:e], vuv[e - n:e], mcep[e - n:e], bap[e - n:e]) for e, n in zip(ends, lens)]
+    return out[0] if single else out
+
+
+def extract_world_features(ids, in_dir, out_dir, sample_rate, n_mcep=60, alpha=None, n_bands=None, device='cuda:0',
+                           max_batch_bytes=256 << 20, overwrite=False):
+    r"""Code a corpus: for every id read ``{in_dir}/sp/{id}.npy`` and ``{in_dir}/ap/{id}.npy`` ((n, fft_size / 2 + 1), float32 or
+    float64, as an analyser wrote them) and write ``{out_dir}/mcep/{id}.npy`` (n, n_mcep) and ``{out_dir}/bap/{id}.npy`` (n, n_bands),
+    float32.  ``lf0``, ``vuv``, deltas and counters need no files: ``ContinuousLF0Source``, ``deltas='compute'`` and
+    ``FrameCountersSource`` make them from ``f0`` and ``dur`` at load time.
+
+    Utterances are batched by bytes (``max_batch_bytes`` of input per batch, at least one utterance), never by count.  Per batch and
+    feature the rows are packed into pinned memory and uploaded in ONE copy in the type they are stored in, coded in one launch
+    (``ops.spectrum_mcep``, ``ops.aperiodicity_bap``), and exactly the packed result comes back in one more copy.  alpha, n_bands : as
+    ``world_parameters``.  Refused, naming the id, before anything is written: an utterance whose sp and ap differ in length or width,
+    and an output file that exists unless ``overwrite=True``.  Returns the number of frames written."""
+    from ._lib import MorganaHipError
+    from .viz import synthesis
+    device = torch.device(device)
+    if device.type != 'cuda' or not torch.cuda.is_available():
+        raise MorganaHipError('extract_world_features runs on an MI355X device, got %s (there is no CPU fallback)' % device)
+    alpha = synthesis.default_alpha(sample_rate) if alpha is None else alpha
+    n_bands = ops.default_n_bands(sample_rate) if n_bands is None else n_bands
+    ids = list(ids)
+    paths = {name: os.path.join(out_dir, name) for name in ('mcep', 'bap')}
+    if not overwrite:
+        for utt in ids:
+            for name in ('mcep', 'bap'):
+                if os.path.exists(os.path.join(paths[name], '%s.npy' % utt)):
+                    raise FileExistsError('extract_world_features: %s of utterance %r exists (overwrite=True replaces it)' % (name, utt))
+    entries = []
+    for utt in ids:                                           # memory maps: the one read of the samples is the pack into pinned memory
+        sp = np.load(os.path.join(in_dir, 'sp', '%s.npy' % utt), mmap_mode='r')
+        ap = np.load(os.path.join(in_dir, 'ap', '%s.npy' % utt), mmap_mode='r')
+        if sp.ndim != 2 or ap.ndim != 2 or sp.shape != ap.shape:
+            raise ValueError('extract_world_features: utterance %r has sp %s and ap %s' % (utt, sp.shape, ap.shape))
+        for name, x in (('sp', sp), ('ap', ap)):
+            if x.dtype not in (np.float32, np.float64):
+                raise TypeError('extract_world_features: %s of utterance %r is %s, not float32 or float64' % (name, utt, x.dtype))
+        if entries and sp.shape[1] != entries[0][1].shape[1]:
+            raise ValueError('extract_world_features: utterance %r has %d bins, the first has %d' % (utt, sp.shape[1], entries[0][1].shape[1]))
+        entries.append((utt, sp, ap))
+    for path in paths.values():
+        os.makedirs(path, exist_ok=True)
+    frames, start = 0, 0
+    while start < len(entries):
+        stop, size = start, 0
+        while stop < len(entries):                            # by bytes; one element type per feature and batch
+            _, sp, ap = entries[stop]
+            if stop > start and (size + sp.nbytes + ap.nbytes > max_batch_bytes or sp.dtype != entries[start][1].dtype
+                                 or ap.dtype != entries[start][2].dtype):
+                break
+            size += sp.nbytes + ap.nbytes
+            stop += 1
+        chunk = entries[start:stop]
+        with torch.cuda.device(device):
+            sp_rows, offsets, lens = _pack_pinned([e[1] for e in chunk], device, 'extract:sp', chunk[0][1].dtype)
+            mcep = ops.spectrum_mcep(sp_rows, n_mcep, alpha, offsets=offsets)
+            ap_rows, offsets, _ = _pack_pinned([e[2] for e in chunk], device, 'extract:ap', chunk[0][2].dtype)
+            bap = ops.aperiodicity_bap(ap_rows, int(sample_rate), n_bands, offsets=offsets)
+            mcep, bap = mcep.cpu().numpy(), bap.cpu().numpy()
+        ends = np.cumsum(lens)
+        for (utt, _, _), e, n in zip(chunk, ends, lens):
+            np.save(os.path.join(paths['mcep'], '%s.npy' % utt), mcep[e - n:e])
+            np.save(os.path.join(paths['bap'], '%s.npy' % utt), bap[e - n:e])
+        frames += int(lens.sum())
+        start = stop
+    return frames

@@ -3514,6 +3514,130 @@ def smooth_f0(lf0, vuv, *, offsets=None, seq_len=None, packed_rows=None, window=
     return out
 
 
+# ---------------------------------------------------------------------------------------------- vocoder analysis (csrc/analysis.hip)
+_mcep_analysis = {}
+
+
+def mcep_analysis_table(order, alpha, fft_size):
+    """The (order, fft_size / 2 + 1) float64 table of mg_spectrum_mcep as a host array: ``c = table @ l`` takes the half log power
+    spectrum ``l = 0.5 log(sp)`` of a frame to its mel-cepstrum.  It is the composition of the one-sided cepstrum on the FFT grid,
+    ``g_n = (kappa_n / F) [l_0 + (-1)^n l_{F/2} + 2 sum_k l_k cos(2 pi n k / F)]``, and SPTK's ``freqt`` recursion from order F / 2 to
+    ``order - 1`` with ``alpha``, run once for all K unit spectra side by side: F / 2 + 1 steps of ``order`` vector operations.  Where the
+    warped series does not alias it is the left inverse of ``mcep_basis_table`` (``table @ basis.T = I`` to 2e-15)."""
+    import numpy as np
+    k = spectrum_bins(fft_size)
+    if isinstance(order, bool) or not isinstance(order, numbers.Integral) or not 1 <= order <= VOC_MAX_ORDER:
+        raise ValueError('spectrum_mcep: %r cepstral coefficients per frame, outside [1, %d]' % (order, VOC_MAX_ORDER))
+    alpha = float(alpha)
+    if not -1. < alpha < 1.:
+        raise ValueError('spectrum_mcep: alpha=%r must lie inside (-1, 1)' % alpha)
+    order, f, half = int(order), int(fft_size), int(fft_size) // 2
+    cosines = np.cos(2. * np.pi * np.arange(f, dtype=np.float64) / float(f))      # cos(2 pi n k / F) = cosines[n k mod F]
+    bins = np.arange(k, dtype=np.int64)
+    weight = np.full(k, 2. / f)
+    weight[0] = weight[half] = 1. / f
+    table = np.zeros((order, k), dtype=np.float64)
+    beta = 1. - alpha * alpha
+    for i in range(half, -1, -1):
+        g = (1. if i in (0, half) else 2.) * weight * cosines[(i * bins) % f]    # row i of the cepstrum map
+        d = table.copy()
+        table[0] = g + alpha * d[0]
+        if order > 1:
+            table[1] = beta * d[0] + alpha * d[1]
+        for j in range(2, order):
+            table[j] = d[j - 1] + alpha * (d[j] - table[j - 1])
+    return table
+
+
+def mcep_analysis_matrix(order, alpha, fft_size, device):
+    """``mcep_analysis_table`` on ``device`` (float64), built once per (order, alpha, fft_size, device) and kept."""
+    device = torch.device(device)
+    key = (int(order), float(alpha), int(fft_size), device.type, device.index if device.index is not None else torch.cuda.current_device())
+    table = _mcep_analysis.get(key)
+    if table is None:
+        table = _mcep_analysis[key] = torch.from_numpy(mcep_analysis_table(order, alpha, fft_size)).to(device)
+    return table
+
+
+def default_n_bands(sample_rate):
+    """WORLD's number of coded aperiodicity bands: floor(min(15000, fs / 2 - 3000) / 3000) - 1 at 16 kHz, 2 at 22.05 kHz, 5 at 44.1 and
+    48 kHz.  A rate too low for one band raises."""
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, numbers.Integral) or sample_rate <= 0:
+        raise ValueError('sample_rate=%r must be a positive integer (Hz)' % (sample_rate,))
+    bands = int(min(15000., sample_rate / 2. - 3000.) // 3000)
+    if bands < 1:
+        raise ValueError('a sample rate of %d Hz has no 3000 Hz band below fs / 2 - 3000 Hz' % sample_rate)
+    return bands
+
+
+def _analysis_input(what, x, name, fft_size):
+    """A spectrum-like input of the analysis family: a float32 or float64 device tensor whose last dimension is the fft_size / 2 + 1
+    bins -> (tensor contiguous, fft_size, K, in_f64)."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError('%s must be a torch.Tensor, got %s' % (name, type(x)))
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError('%s: %s must be torch.float32 or torch.float64, got %s' % (what, name, x.dtype))
+    x = _require(x, x.dtype, name)
+    if x.dim() not in (2, 3):
+        raise ValueError('%s: %s must be packed (rows, bins) or padded (items, frames, bins), got %s' % (what, name, tuple(x.shape)))
+    if fft_size is None:
+        fft_size = 2 * (x.shape[-1] - 1)
+    k = spectrum_bins(fft_size)
+    if x.shape[-1] != k:
+        raise ValueError('%s: %s has %d bins per frame, fft_size=%d has %d' % (what, name, x.shape[-1], fft_size, k))
+    return x, int(fft_size), k, 1 if x.dtype == torch.float64 else 0
+
+
+def spectrum_mcep(sp, order, alpha, fft_size=None, *, offsets=None, seq_len=None, packed_rows=None, log_input=False,
+                  out_dtype=torch.float32, out=None):
+    """Power spectrum to mel-cepstrum (csrc/analysis.hip, mg_spectrum_mcep), one launch: ``c = table @ (0.5 log(sp))`` per frame in
+    float64 on the matrix unit, the logarithm taken once per bin.  ``table`` is ``mcep_analysis_matrix`` (the one-sided cepstrum followed
+    by SPTK's ``freqt``; float64, cached per order, alpha, size and device); where the warped series does not alias this is the left
+    inverse of ``mcep_spectrum``.  ``sp`` is float32 or float64 (what analysers write) and is read as it is; ``fft_size`` None is
+    ``2 (bins - 1)``; ``log_input``: ``sp`` is the log power spectrum (``mcep_spectrum(..., log=True)``).  A frame with a zero, negative
+    or non-finite bin comes out non-finite; no other frame changes.
+
+    Input, exactly one of: ``offsets`` (B + 1,) int64 with sp the packed rows (N, K), or ``seq_len`` (B,) int64 with sp padded (B, T, K)
+    (frames past the length are never read).  Returns the PACKED (packed_rows, order) tensor of ``out_dtype`` (float32: the float64
+    result rounded once); ``packed_rows`` and ``out`` as ``mcep_spectrum``."""
+    lib = _lib.load()
+    sp, fft_size, k, in_f64 = _analysis_input('spectrum_mcep', sp, 'sp', fft_size)
+    if isinstance(order, bool) or not isinstance(order, numbers.Integral) or not 1 <= order <= VOC_MAX_ORDER:
+        raise ValueError('spectrum_mcep: %r cepstral coefficients per frame, outside [1, %d]' % (order, VOC_MAX_ORDER))
+    offsets, seq_len, b, t_in, _, packed_rows, out, f64 = _vocoder_output('spectrum_mcep', sp, offsets, seq_len, int(order), packed_rows,
+                                                                          out, out_dtype)
+    if b == 0 or packed_rows == 0:          # nothing to write: no address to hand the library
+        return out
+    table = mcep_analysis_matrix(order, alpha, fft_size, sp.device)
+    _lib.check(lib.mg_spectrum_mcep(_p(sp), in_f64, 1 if log_input else 0, fft_size, b, _p(offsets), _p(seq_len), t_in, _p(table),
+                                    table.shape[1], int(order), f64, packed_rows, _p(out), _stream()), 'mg_spectrum_mcep')
+    return out
+
+
+def aperiodicity_bap(ap, sample_rate, n_bands=None, fft_size=None, *, offsets=None, seq_len=None, packed_rows=None,
+                     out_dtype=torch.float32, out=None):
+    """Full-band aperiodicity to coded band aperiodicity in dB (csrc/analysis.hip, mg_aperiodicity_bap), one launch: band b is
+    ``20 log10(ap)`` clamped to [-60, 0], interpolated linearly between the two bins around 3000 (b + 1) Hz, in float64.  ``ap`` is
+    float32 or float64 and is read as it is; ``n_bands`` None is WORLD's rule (``default_n_bands``); ``fft_size`` None is
+    ``2 (bins - 1)``.  Where every anchor is a bin (16 kHz / 1024, 48 kHz / 2048) this inverts ``bap_aperiodicity``; elsewhere the round
+    trip is off by up to 0.17 dB.  Layouts, ``packed_rows``, ``out_dtype`` and ``out`` as ``spectrum_mcep``."""
+    lib = _lib.load()
+    ap, fft_size, k, in_f64 = _analysis_input('aperiodicity_bap', ap, 'ap', fft_size)
+    if n_bands is None:
+        n_bands = default_n_bands(sample_rate)
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, numbers.Integral) or sample_rate <= 0:
+        raise ValueError('aperiodicity_bap: sample_rate=%r must be a positive integer (Hz)' % (sample_rate,))
+    if isinstance(n_bands, bool) or not isinstance(n_bands, numbers.Integral) or n_bands < 1 or 6000 * n_bands >= sample_rate:
+        raise ValueError('aperiodicity_bap: %r bands of 3000 Hz do not end below sample_rate / 2 = %g Hz' % (n_bands, sample_rate / 2.))
+    offsets, seq_len, b, t_in, _, packed_rows, out, f64 = _vocoder_output('aperiodicity_bap', ap, offsets, seq_len, int(n_bands),
+                                                                          packed_rows, out, out_dtype)
+    if b == 0 or packed_rows == 0:          # nothing to write: no address to hand the library
+        return out
+    _lib.check(lib.mg_aperiodicity_bap(_p(ap), in_f64, fft_size, int(sample_rate), int(n_bands), b, _p(offsets), _p(seq_len), t_in, f64,
+                                       packed_rows, _p(out), _stream()), 'mg_aperiodicity_bap')
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- phone-rate first layer
 # MORGANA_PHONE_RATE=0: every product at frame rate (the reference's order of operations).  This is only the DEFAULT of a per-call
 # choice: utils.upsample_to_repetitions(..., phone_rate=) records the choice on the lazy sequence it returns, the layers that consume

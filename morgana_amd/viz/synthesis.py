@@ -215,7 +215,8 @@ def world_features(lf0, vuv, mcep, bap, sample_rate, seq_len, alpha=None, fft_si
 
     Returns a list of per-utterance ``(f0 (n,), sp (n, fft_size / 2 + 1), ap (n, fft_size / 2 + 1))``: float64, C-contiguous NumPy
     arrays (``pyworld.synthesize`` takes exactly these), or with ``as_numpy=False`` views of the packed float64 device tensors.
-    ``seq_len`` is read once and each feature reaches the host in one copy."""
+    ``seq_len`` is read once and each feature reaches the host in one copy.  The opposite direction - an analyser's ``f0``, ``sp``,
+    ``ap`` to ``lf0``, ``vuv``, ``mcep``, ``bap`` - is ``data.world_parameters``."""
     alpha = default_alpha(sample_rate) if alpha is None else alpha
     fft_size = default_fft_size(sample_rate) if fft_size is None else fft_size
     if isinstance(seq_len, torch.Tensor):
