@@ -471,7 +471,8 @@ int mg_expand_column_reduce_f32(const float* table, const int32_t* rows, int64_t
                                 int extra, const float* slab, int64_t n, int64_t stride, int S, float* dst, void* stream);
 size_t mg_phone_target_stats_workspace_bytes(int R, int extra);
 /* loss_const may be NULL: then mg_phone_loss_const_add(workspace, R, extra, loss) adds the constant to a loss in place later on
- * (the workspace must be left untouched in between). */
+ * (the workspace must be left untouched in between).  mg_phone_target_stats and mg_phone_front refuse extra = 0 (MG_EINVAL): the
+ * padding frames' loss terms live in the extra rows, and without one they would be lost silently. */
 int mg_phone_loss_const_add(const void* workspace, int R, int extra, float* loss, void* stream);
 int mg_phone_target_stats(const float* target, const int32_t* rows, int64_t M, const int32_t* seg_start, const int32_t* seg_end,
                           const int64_t* seq_len, int B, int T, int R, int extra, float* ybar, float* weight, float* loss_const,

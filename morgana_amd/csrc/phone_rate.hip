@@ -595,12 +595,16 @@ size_t mg_phone_target_stats_workspace_bytes(int R, int extra) {
     return (size_t)(mg_ceil_div(R, 16) + mg_ceil_div(extra, 4)) * sizeof(float);
 }
 
+// extra = 0 is REFUSED: the loss terms of the padding frames (those below seq_len count in the masked MSE) live in the extra rows and
+// in their partial sums; without an extra row they would go nowhere and the loss would silently miss them.  (mg_segment_sum takes
+// extra = 0: there the padding frames' gradients are simply not collected.)
 int mg_phone_target_stats(const float* target, const int32_t* rows, int64_t M, const int32_t* seg_start, const int32_t* seg_end,
                           const int64_t* seq_len, int B, int T, int R, int extra, float* ybar, float* weight, float* loss_const,
                           void* workspace, size_t workspace_bytes, void* stream) {
     MG_CHECK_ARG(target && rows && seg_start && seg_end && ybar && weight && B > 0 && T > 0 && R > 0 && extra >= 0 &&
                      M == (int64_t)B * T,
                  "mg_phone_target_stats: bad arguments (M=%lld B=%d T=%d R=%d extra=%d)", (long long)M, B, T, R, extra);
+    MG_CHECK_ARG(extra > 0, "mg_phone_target_stats: extra=%d: at least one extra row must take the padding frames' loss terms", extra);
     if (!workspace || workspace_bytes < mg_phone_target_stats_workspace_bytes(R, extra)) {
         mg_set_error("mg_phone_target_stats: workspace of %zu bytes needed, got %zu", mg_phone_target_stats_workspace_bytes(R, extra),
                      workspace_bytes);
@@ -621,7 +625,7 @@ int mg_phone_target_stats(const float* target, const int32_t* rows, int64_t M, c
 int mg_phone_front_check(const int64_t* dur, int B, int P, int T, const float* target, int extra, const int32_t* rows32,
                          const int32_t* rows_mapped, const int32_t* seg_start, const int32_t* seg_end, const float* ybar, const float* weight,
                          const void* workspace, size_t workspace_bytes, const char* who) {
-    if (!(dur && target && rows32 && rows_mapped && seg_start && seg_end && ybar && weight && B > 0 && P > 0 && T > 0 && extra >= 0)) {
+    if (!(dur && target && rows32 && rows_mapped && seg_start && seg_end && ybar && weight && B > 0 && P > 0 && T > 0 && extra > 0)) {   // extra = 0: as mg_phone_target_stats
         mg_set_error("%s: bad arguments (B=%d P=%d T=%d extra=%d)", who, B, P, T, extra);
         return MG_EINVAL;
     }

@@ -2204,6 +2204,8 @@ def phone_target_stats(target, rows, seg, seq_len, b, t, n_table_rows, extra):
     the per-block sums of the loss's constant term for ``phone_loss_const_add``."""
     lib = _lib.load()
     target = _require(target, torch.float32, 'targets')
+    if extra < 1:
+        raise ValueError('phone_target_stats: extra=%d: at least one extra row must take the padding frames\' loss terms' % extra)
     stats = torch.empty((2, n_table_rows + extra), dtype=torch.float32, device=target.device)
     ws = torch.empty(lib.mg_phone_target_stats_workspace_bytes(n_table_rows, extra), dtype=torch.uint8, device=target.device)
     _lib.check(lib.mg_phone_target_stats(_p(target), _p(rows), rows.numel(), _p(seg[0]), _p(seg[1]), _p(seq_len), b, t, n_table_rows,
@@ -3707,6 +3709,8 @@ def segment_sum_feat(g, rows, seg, n_table_rows, n, feat, extra=PHONE_RATE_EXTRA
     lib = _lib.load()
     g = _require(g, torch.bfloat16, 'gradient')
     feat = _require(feat, torch.float32, 'frame features')
+    if g.data_ptr() % 16:
+        raise ValueError('segment_sum_feat: the gradient must start on a 16-byte boundary')
     c = feat.shape[1]
     out = torch.empty((n_table_rows + extra, g.shape[1]), dtype=g.dtype, device=g.device)
     nbytes = lib.mg_segment_sum_feat_workspace_bytes(c, out.shape[1])
@@ -3727,6 +3731,8 @@ def segment_sum(g, rows, seg, n_table_rows, n, extra=PHONE_RATE_EXTRA):
     lib = _lib.load()
     bf16 = g.dtype == torch.bfloat16
     g = _require(g, torch.bfloat16 if bf16 else torch.float32, 'gradient')
+    if g.data_ptr() % 16:
+        raise ValueError('segment_sum: the gradient must start on a 16-byte boundary (the kernel reads 16 bytes per lane)')
     out = torch.empty((n_table_rows + extra, g.shape[1]), dtype=g.dtype, device=g.device)
     _lib.check(lib.mg_segment_sum(_p(g), g.shape[1], int(bf16), _p(rows), rows.numel(), _p(seg[0]), _p(seg[1]), n_table_rows, extra, n,
                                   _p(out), out.shape[1], _stream()), 'mg_segment_sum')
