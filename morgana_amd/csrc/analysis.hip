@@ -25,13 +25,12 @@
 // consecutive coefficients of four frames.
 //
 // Rows.  As K32: a packed input's tile reads its own rows, [offsets[0], offsets[B]); a padded input's tile finds the source frame of
-// each packed row by a binary search in the scanned clamped lengths, held in LDS (B <= MG_VOC_MAX_ITEMS).  The few helpers are
-// restated here rather than moved out of vocoder.hip, whose code this family leaves as it is.
+// each packed row by a binary search in the scanned clamped lengths, held in LDS (B <= MG_VOC_MAX_ITEMS): the helpers of
+// csrc/packed_rows.h.
 //
 // Aperiodicity mapping.  One thread per (packed row, band), grid-stride: two strided loads, two log10, one store.
 #include "common.h"
-#include "item_norm.h"
-#include "seq_reduce.h"
+#include "packed_rows.h"
 
 #define ANA_THREADS 256
 #define ANA_TILE_FRAMES 64             // packed rows of a workgroup's tile: 16 per wave
@@ -42,33 +41,6 @@
 #define ANA_BAP_MAX_BLOCKS 4096
 
 typedef double ana_double4 __attribute__((ext_vector_type(4)));
-
-// first packed row of item b (b == B: all rows)
-__device__ __forceinline__ int64_t ana_first_row(int b, const int64_t* __restrict__ offsets, const int64_t* s_cum) {
-    return offsets ? offsets[b] : s_cum[b];
-}
-
-// the source frame (row of the input as the item's layout counts it) of packed row r, or -1: no item holds it
-__device__ __forceinline__ int64_t ana_source_row(int64_t r, int64_t rows_end, int B, const int64_t* __restrict__ offsets,
-                                                  const int64_t* __restrict__ seq_len, int64_t T_in, const int64_t* s_cum) {
-    if (r >= rows_end) return -1;
-    if (offsets) return r >= offsets[0] ? r : -1;              // packed rows are their own source: [offsets[0], offsets[B]), no search
-    const auto first_of = [&](int b) { return ana_first_row(b, offsets, s_cum); };
-    const int b = mg_item_at(B, r, first_of);
-    if (b >= B) return -1;
-    int64_t first, len;
-    mg_item_rows(offsets, seq_len, T_in, b, first, len);
-    const int64_t t = r - first_of(b);
-    return t >= 0 && t < len ? first + t : -1;
-}
-
-// The prologue both kernels share: the scan of a padded input, then the end of the rows any tile has to look at.
-__device__ __forceinline__ int64_t ana_rows_end(const int64_t* __restrict__ offsets, const int64_t* __restrict__ seq_len, int64_t T_in, int B,
-                                                int64_t packed_rows, int64_t* s_cum) {
-    if (!offsets) mg_clamped_length_scan(seq_len, B, T_in, s_cum, s_cum + B + 1);
-    const int64_t all = ana_first_row(B, offsets, s_cum);
-    return all < packed_rows ? all : packed_rows;
-}
 
 template <int MT, typename InT, typename OutT>
 __global__ __launch_bounds__(ANA_THREADS) void spectrum_mcep_kernel(const InT* __restrict__ sp, const double* __restrict__ table, int64_t ldt,
@@ -81,7 +53,7 @@ __global__ __launch_bounds__(ANA_THREADS) void spectrum_mcep_kernel(const InT* _
     __shared__ int64_t s_src[ANA_TILE_FRAMES];
     const int tid = threadIdx.x;
     const int lane = tid & (MG_WAVE - 1), wave = tid / MG_WAVE;
-    const int64_t rows_end = ana_rows_end(offsets, seq_len, T_in, B, packed_rows, s_ana);
+    const int64_t rows_end = mg_packed_rows_end(offsets, seq_len, T_in, B, packed_rows, s_ana);
     const int64_t n_tiles = (rows_end + ANA_TILE_FRAMES - 1) / ANA_TILE_FRAMES;
     const int n_chunks = (K + ANA_KC - 1) / ANA_KC;
 
@@ -93,7 +65,7 @@ __global__ __launch_bounds__(ANA_THREADS) void spectrum_mcep_kernel(const InT* _
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t r_lo = tile * ANA_TILE_FRAMES;
         __syncthreads();                                       // the previous tile's readers of s_src, s_l and s_t are done
-        if (tid < ANA_TILE_FRAMES) s_src[tid] = ana_source_row(r_lo + tid, rows_end, B, offsets, seq_len, T_in, s_ana);
+        if (tid < ANA_TILE_FRAMES) s_src[tid] = mg_packed_source_row(r_lo + tid, rows_end, B, offsets, seq_len, T_in, s_ana);
         __syncthreads();
         const InT* __restrict__ xrow[ANA_ROWS_PER_THREAD];
 #pragma unroll
@@ -168,12 +140,12 @@ __global__ __launch_bounds__(ANA_THREADS) void aperiodicity_bap_kernel(const InT
                                                                        const int64_t* __restrict__ seq_len, int64_t T_in, int B, int Nb, int fs,
                                                                        int F, int K, int64_t packed_rows, OutT* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) int64_t s_ana[];
-    const int64_t rows_end = ana_rows_end(offsets, seq_len, T_in, B, packed_rows, s_ana);
+    const int64_t rows_end = mg_packed_rows_end(offsets, seq_len, T_in, B, packed_rows, s_ana);
     const int64_t n = rows_end * Nb;
     for (int64_t e = (int64_t)blockIdx.x * ANA_THREADS + threadIdx.x; e < n; e += (int64_t)gridDim.x * ANA_THREADS) {
         const int64_t r = e / Nb;
         const int b = (int)(e - r * Nb);
-        const int64_t src = ana_source_row(r, rows_end, B, offsets, seq_len, T_in, s_ana);
+        const int64_t src = mg_packed_source_row(r, rows_end, B, offsets, seq_len, T_in, s_ana);
         if (src < 0) continue;
         const int64_t pos = (int64_t)3000 * (b + 1) * F;       // the anchor's bin position times fs: below 2^30 * 2^13
         const int64_t k0 = pos / fs;                          // k0 + 1 <= F / 2: the anchor lies below fs / 2
@@ -184,56 +156,14 @@ __global__ __launch_bounds__(ANA_THREADS) void aperiodicity_bap_kernel(const InT
     }
 }
 
-static size_t ana_scan_bytes(const int64_t* offsets, int B) { return offsets ? 0 : ((size_t)B + 1 + ANA_THREADS) * sizeof(int64_t); }
-
-// The argument checks the two entry points share: one layout, the sizes, the output, the alignment.  `width`: elements per input row.
-#define ANA_CHECK_COMMON(name, x, width, cols)                                                                                          \
-    MG_CHECK_ONE_LAYOUT(name, offsets, seq_len, "(B, T_in, K)");                                                                        \
-    MG_CHECK_ARG(B >= 0, name ": B=%d must not be negative", B);                                                                        \
-    MG_CHECK_ARG(offsets || T_in >= 0, name ": T_in=%d must not be negative", T_in);                                                    \
-    MG_CHECK_ARG(offsets || B <= MG_VOC_MAX_ITEMS, name ": a padded input takes at most %d items, got B=%d", MG_VOC_MAX_ITEMS, B);      \
-    MG_CHECK_ARG(out, name ": out must not be NULL");                                                                                   \
-    MG_CHECK_ARG(packed_rows >= 0 && packed_rows <= INT64_MAX / 8 / ((width) > (cols) ? (width) : (cols)),                              \
-                 name ": packed_rows=%lld out of range", (long long)packed_rows);                                                       \
-    MG_CHECK_ARG(offsets || B == 0 || T_in == 0 || (int64_t)T_in <= INT64_MAX / 8 / (width) / B,                                        \
-                 name ": B=%d x T_in=%d x %d overflow 64 bits", B, T_in, (int)(width));                                                 \
-    if (B == 0 || packed_rows == 0) return MG_OK;                                                                                       \
-    MG_CHECK_ARG(x, name ": the input must not be NULL");                                                                               \
-    MG_CHECK_ARG(((uintptr_t)(x) & (in_f64 ? 7u : 3u)) == 0 && ((uintptr_t)out & (out_f64 ? 7u : 3u)) == 0 &&                           \
-                     (((uintptr_t)offsets | (uintptr_t)seq_len) & 7u) == 0,                                                             \
-                 name ": the input must be 4-byte (8-byte with in_f64), out 4-byte (8-byte with out_f64), offsets and seq_len 8-byte "   \
-                      "aligned")
-
-template <int MT, typename InT>
-static void ana_launch_mcep(dim3 grid, size_t lds, hipStream_t stream, const void* sp, const double* table, int64_t ldt, const int64_t* offsets,
-                            const int64_t* seq_len, int T_in, int B, int M, int K, int log_in, int out_f64, int64_t packed_rows, void* out) {
-    if (out_f64)
-        hipLaunchKernelGGL((spectrum_mcep_kernel<MT, InT, double>), grid, dim3(ANA_THREADS), lds, stream, (const InT*)sp, table, ldt, offsets,
-                           seq_len, (int64_t)T_in, B, M, K, log_in ? 1 : 0, packed_rows, (double*)out);
-    else
-        hipLaunchKernelGGL((spectrum_mcep_kernel<MT, InT, float>), grid, dim3(ANA_THREADS), lds, stream, (const InT*)sp, table, ldt, offsets,
-                           seq_len, (int64_t)T_in, B, M, K, log_in ? 1 : 0, packed_rows, (float*)out);
-}
-
 template <int MT>
-static void ana_launch_mcep_in(int in_f64, dim3 grid, size_t lds, hipStream_t stream, const void* sp, const double* table, int64_t ldt,
-                               const int64_t* offsets, const int64_t* seq_len, int T_in, int B, int M, int K, int log_in, int out_f64,
-                               int64_t packed_rows, void* out) {
-    if (in_f64)
-        ana_launch_mcep<MT, double>(grid, lds, stream, sp, table, ldt, offsets, seq_len, T_in, B, M, K, log_in, out_f64, packed_rows, out);
-    else
-        ana_launch_mcep<MT, float>(grid, lds, stream, sp, table, ldt, offsets, seq_len, T_in, B, M, K, log_in, out_f64, packed_rows, out);
-}
-
-template <typename InT>
-static void ana_launch_bap(dim3 grid, size_t lds, hipStream_t stream, const void* ap, const int64_t* offsets, const int64_t* seq_len, int T_in,
-                           int B, int Nb, int fs, int F, int K, int out_f64, int64_t packed_rows, void* out) {
-    if (out_f64)
-        hipLaunchKernelGGL((aperiodicity_bap_kernel<InT, double>), grid, dim3(ANA_THREADS), lds, stream, (const InT*)ap, offsets, seq_len,
-                           (int64_t)T_in, B, Nb, fs, F, K, packed_rows, (double*)out);
-    else
-        hipLaunchKernelGGL((aperiodicity_bap_kernel<InT, float>), grid, dim3(ANA_THREADS), lds, stream, (const InT*)ap, offsets, seq_len,
-                           (int64_t)T_in, B, Nb, fs, F, K, packed_rows, (float*)out);
+static void ana_launch_mcep(int in_f64, dim3 grid, size_t lds, hipStream_t stream, const void* sp, const double* table, int64_t ldt,
+                            const int64_t* offsets, const int64_t* seq_len, int T_in, int B, int M, int K, int log_in, int out_f64,
+                            int64_t packed_rows, void* out) {
+#define ANA_GO hipLaunchKernelGGL((spectrum_mcep_kernel<MT, InT, OutT>), grid, dim3(ANA_THREADS), lds, stream, (const InT*)sp, table, ldt, \
+                                  offsets, seq_len, (int64_t)T_in, B, M, K, log_in ? 1 : 0, packed_rows, (OutT*)out)
+    MG_SWITCH_F64(in_f64, InT, MG_SWITCH_F64(out_f64, OutT, ANA_GO));
+#undef ANA_GO
 }
 
 extern "C" {
@@ -246,17 +176,17 @@ int mg_spectrum_mcep(const void* sp, int in_f64, int log_in, int F, int B, const
     MG_CHECK_ARG(M >= 1 && M <= MG_VOC_MAX_ORDER, "mg_spectrum_mcep: M=%d coefficients outside [1, %d]", M, MG_VOC_MAX_ORDER);
     const int K = F / 2 + 1;
     MG_CHECK_ARG(ldt >= K, "mg_spectrum_mcep: ldt=%lld is below the F / 2 + 1 = %d bins of a table row", (long long)ldt, K);
-    ANA_CHECK_COMMON("mg_spectrum_mcep", sp, K, M);
+    MG_CHECK_PACKED_IO("mg_spectrum_mcep", "(B, T_in, K)", sp, in_f64, K, M);
     MG_CHECK_ARG(table && ((uintptr_t)table & 7u) == 0, "mg_spectrum_mcep: table must not be NULL and 8-byte aligned");
     const int64_t n_tiles = (packed_rows + ANA_TILE_FRAMES - 1) / ANA_TILE_FRAMES;
     const dim3 grid((unsigned)(n_tiles < ANA_MAX_BLOCKS ? n_tiles : ANA_MAX_BLOCKS));
-    const size_t lds = ana_scan_bytes(offsets, B);
+    const size_t lds = mg_packed_scan_bytes(offsets, B, ANA_THREADS);
     const hipStream_t s = (hipStream_t)stream;
     const int mt = (M + 15) / 16;
-    if (mt <= 1) ana_launch_mcep_in<1>(in_f64, grid, lds, s, sp, table, ldt, offsets, seq_len, T_in, B, M, K, log_in, out_f64, packed_rows, out);
-    else if (mt <= 2) ana_launch_mcep_in<2>(in_f64, grid, lds, s, sp, table, ldt, offsets, seq_len, T_in, B, M, K, log_in, out_f64, packed_rows, out);
-    else if (mt <= 4) ana_launch_mcep_in<4>(in_f64, grid, lds, s, sp, table, ldt, offsets, seq_len, T_in, B, M, K, log_in, out_f64, packed_rows, out);
-    else ana_launch_mcep_in<8>(in_f64, grid, lds, s, sp, table, ldt, offsets, seq_len, T_in, B, M, K, log_in, out_f64, packed_rows, out);
+    if (mt <= 1) ana_launch_mcep<1>(in_f64, grid, lds, s, sp, table, ldt, offsets, seq_len, T_in, B, M, K, log_in, out_f64, packed_rows, out);
+    else if (mt <= 2) ana_launch_mcep<2>(in_f64, grid, lds, s, sp, table, ldt, offsets, seq_len, T_in, B, M, K, log_in, out_f64, packed_rows, out);
+    else if (mt <= 4) ana_launch_mcep<4>(in_f64, grid, lds, s, sp, table, ldt, offsets, seq_len, T_in, B, M, K, log_in, out_f64, packed_rows, out);
+    else ana_launch_mcep<8>(in_f64, grid, lds, s, sp, table, ldt, offsets, seq_len, T_in, B, M, K, log_in, out_f64, packed_rows, out);
     MG_CHECK_LAUNCH("mg_spectrum_mcep");
     return MG_OK;
 }
@@ -268,14 +198,14 @@ int mg_aperiodicity_bap(const void* ap, int in_f64, int F, int fs, int Nb, int B
     MG_CHECK_ARG(Nb >= 1 && (int64_t)6000 * Nb < (int64_t)fs,
                  "mg_aperiodicity_bap: Nb=%d bands of 3000 Hz must end below fs / 2 = %g Hz (and Nb >= 1)", Nb, 0.5 * fs);
     const int K = F / 2 + 1;
-    ANA_CHECK_COMMON("mg_aperiodicity_bap", ap, K, Nb);
+    MG_CHECK_PACKED_IO("mg_aperiodicity_bap", "(B, T_in, K)", ap, in_f64, K, Nb);
     const int64_t n_blocks = (packed_rows * Nb + ANA_THREADS - 1) / ANA_THREADS;
     const dim3 grid((unsigned)(n_blocks < ANA_BAP_MAX_BLOCKS ? n_blocks : ANA_BAP_MAX_BLOCKS));
-    const size_t lds = ana_scan_bytes(offsets, B);
-    if (in_f64)
-        ana_launch_bap<double>(grid, lds, (hipStream_t)stream, ap, offsets, seq_len, T_in, B, Nb, fs, F, K, out_f64, packed_rows, out);
-    else
-        ana_launch_bap<float>(grid, lds, (hipStream_t)stream, ap, offsets, seq_len, T_in, B, Nb, fs, F, K, out_f64, packed_rows, out);
+    const size_t lds = mg_packed_scan_bytes(offsets, B, ANA_THREADS);
+#define ANA_GO hipLaunchKernelGGL((aperiodicity_bap_kernel<InT, OutT>), grid, dim3(ANA_THREADS), lds, (hipStream_t)stream, (const InT*)ap, \
+                                  offsets, seq_len, (int64_t)T_in, B, Nb, fs, F, K, packed_rows, (OutT*)out)
+    MG_SWITCH_F64(in_f64, InT, MG_SWITCH_F64(out_f64, OutT, ANA_GO));
+#undef ANA_GO
     MG_CHECK_LAUNCH("mg_aperiodicity_bap");
     return MG_OK;
 }

@@ -30,25 +30,24 @@ typedef __bf16 bfv4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bfv2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-// LDS-DMA of 64 x 16 bytes: lane l's 16 bytes land at LDS byte address (lds_addr + 16 l); lds_addr = the wave-uniform LDS address
-// (an integer: casting a generic pointer back to the LDS address space inside the step loop made hipcc emit a null check that does
-// not assemble).  M0 saved / restored inside the statement; completion counted by vmcnt.
-__device__ __forceinline__ void wglds16(const void* src, unsigned lds_addr) {
-    const unsigned lds_uni = __builtin_amdgcn_readfirstlane(lds_addr);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(src), "s"(lds_uni)
-                 : "memory");
-}
-
-// The same with a wave-uniform base and a 32-bit per-lane byte offset (no 64-bit address arithmetic in vector registers).
+// mg_glds16_at (common.h) with a wave-uniform base and a 32-bit per-lane byte offset (no 64-bit address arithmetic in vector
+// registers).
 __device__ __forceinline__ void wglds16_off(const void* base_uniform, unsigned byte_off, unsigned lds_addr) {
     const unsigned lds_uni = __builtin_amdgcn_readfirstlane(lds_addr);
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep)
                  : "v"(byte_off), "s"(base_uniform), "s"(lds_uni)
+                 : "memory");
+}
+
+// ... and 64 x 4 bytes: lane l's dword lands at LDS byte address (lds_addr + 4 l).  The row-index fetch of the three kernels.
+__device__ __forceinline__ void wglds4(const void* src, unsigned lds_addr) {
+    const unsigned lds_uni = __builtin_amdgcn_readfirstlane(lds_addr);
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(src), "s"(lds_uni)
                  : "memory");
 }
 
@@ -132,13 +131,7 @@ __global__ __launch_bounds__(512) void wgrad_fused64_kernel(const uint16_t* __re
         const int f = u * W_F + lane;
         int64_t m = m_lo + min(f, max(n_rows - 1, 0));
         if (m > M - 1) m = M - 1;
-        const int32_t* src = rows + m;
-        const unsigned lds_uni = __builtin_amdgcn_readfirstlane(smem_lds + L::ROWS + (u % 3) * 256);
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(src), "s"(lds_uni)
-                     : "memory");
+        wglds4(rows + m, smem_lds + L::ROWS + (u % 3) * 256);
     };
     auto read_rows = [&](int u) -> int {
         const int lane = opaque_lane();
@@ -193,7 +186,7 @@ __global__ __launch_bounds__(512) void wgrad_fused64_kernel(const uint16_t* __re
             if (run >= n_runs || src < 0) src = 0;
             int rg = rp + gl;
             rg -= (rg >= NG) ? NG : 0;
-            wglds16((const void*)(a_ptr + (unsigned long long)(unsigned)src * lda_bytes + (unsigned)xo), smem_lds + L::X + rg * W_GROUP + i * 1024);
+            mg_glds16_at((const void*)(a_ptr + (unsigned long long)(unsigned)src * lda_bytes + (unsigned)xo), smem_lds + L::X + rg * W_GROUP + i * 1024);
         }
     };
 
@@ -625,7 +618,7 @@ __global__ __launch_bounds__(512) void wgrad_fused3_kernel(const uint16_t* __res
         const int kt = p >> 3;
         const int row = 16 * (p & 7) + (lane >> 2);
         const int c = (lane & 3) ^ (((row >> 3) & 1) << 1);
-        wglds16(W2T + (size_t)(n0 + row) * ldwt + 32 * kt + 8 * c, smem_lds + L::W2T + p * 1024);
+        mg_glds16_at(W2T + (size_t)(n0 + row) * ldwt + 32 * kt + 8 * c, smem_lds + L::W2T + p * 1024);
     }
 
     // ---- run structure of a step: every wave derives it from the step's 64 row indices (lane = frame) ---------------------------------
@@ -643,13 +636,7 @@ __global__ __launch_bounds__(512) void wgrad_fused3_kernel(const uint16_t* __res
         const int f = u * W_F + lane;
         int64_t m = m_lo + min(f, max(n_rows - 1, 0));
         if (m > M - 1) m = M - 1;
-        const int32_t* src = rows + m;
-        const unsigned lds_uni = __builtin_amdgcn_readfirstlane(smem_lds + L::ROWS + (u % 3) * 256);
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(src), "s"(lds_uni)
-                     : "memory");
+        wglds4(rows + m, smem_lds + L::ROWS + (u % 3) * 256);
     };
     auto read_rows = [&](int u) -> int {
         const int lane = opaque_lane();
@@ -704,7 +691,7 @@ __global__ __launch_bounds__(512) void wgrad_fused3_kernel(const uint16_t* __res
             if (run >= n_runs || src < 0) src = 0;
             int rg = rp + gl;
             rg -= (rg >= NG) ? NG : 0;
-            wglds16((const void*)(a_ptr + (unsigned long long)(unsigned)src * lda_bytes + (unsigned)xo), smem_lds + L::X + rg * W_GROUP + i * 1024);
+            mg_glds16_at((const void*)(a_ptr + (unsigned long long)(unsigned)src * lda_bytes + (unsigned)xo), smem_lds + L::X + rg * W_GROUP + i * 1024);
         }
     };
 
@@ -1236,7 +1223,7 @@ __global__ __launch_bounds__(512) void wgrad_fused64w_kernel(const uint16_t* __r
         const int kt = p >> 3;
         const int row = 16 * (p & 7) + (lane >> 2);
         const int c = (lane & 3) ^ (((row >> 3) & 1) << 1);
-        wglds16(W2T + (size_t)(n0 + row) * ldwt + 32 * kt + 8 * c, smem_lds + L::W2T + p * 1024);
+        mg_glds16_at(W2T + (size_t)(n0 + row) * ldwt + 32 * kt + 8 * c, smem_lds + L::W2T + p * 1024);
     }
 
     auto issue_rows = [&](int u) {                        // wave 0 only: the row indices of step u into slot u % 3
@@ -1244,13 +1231,7 @@ __global__ __launch_bounds__(512) void wgrad_fused64w_kernel(const uint16_t* __r
         const int f = u * W_F + lane;
         int64_t m = m_lo + min(f, max(n_rows - 1, 0));
         if (m > M - 1) m = M - 1;
-        const int32_t* src = rows + m;
-        const unsigned lds_uni = __builtin_amdgcn_readfirstlane(smem_lds + L::ROWS + (u % 3) * 256);
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(src), "s"(lds_uni)
-                     : "memory");
+        wglds4(rows + m, smem_lds + L::ROWS + (u % 3) * 256);
     };
     auto read_rows_raw = [&](int u) -> int {
         const int lane = opaque_lane();
@@ -1298,7 +1279,7 @@ __global__ __launch_bounds__(512) void wgrad_fused64w_kernel(const uint16_t* __r
         if (run >= n_runs || src < 0) src = 0;
         int rg = rp + gl;
         rg -= (rg >= NG) ? NG : 0;
-        wglds16((const void*)(a_ptr + (unsigned long long)(unsigned)src * lda_bytes + (unsigned)xo), smem_lds + L::X + rg * W_GROUP + i * 1024);
+        mg_glds16_at((const void*)(a_ptr + (unsigned long long)(unsigned)src * lda_bytes + (unsigned)xo), smem_lds + L::X + rg * W_GROUP + i * 1024);
     };
     auto issue_x = [&](int rr, const StepMasks& mk, int rp, int g_first, int g_cnt, int rot) {      // the slow paths: all pieces at once
         const int n_pieces = 5 * g_cnt;

@@ -30,16 +30,6 @@ MG_STAMP_DECL(g_stamps_fz);
 #define FZ_ELEMS 16384
 __device__ uint16_t g_fused_zero_row[FZ_ELEMS];
 
-__device__ __forceinline__ void fglds16(const uint16_t* src, unsigned char* lds_wave_base) {
-    const unsigned lds_off = (unsigned)(unsigned long long)((__attribute__((address_space(3))) unsigned char*)lds_wave_base);
-    const unsigned lds_uni = __builtin_amdgcn_readfirstlane(lds_off);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(src), "s"(lds_uni)
-                 : "memory");
-}
-
 #define F_BNT 128
 #define F_BKT 640
 #define F_N2 128
@@ -135,7 +125,7 @@ __global__ __launch_bounds__(512) void wgrad_fused_kernel(const uint16_t* __rest
         const int kt = p >> 3;
         const int row = 16 * (p & 7) + (lane >> 2);
         const int c = (lane & 3) ^ ((row >> 2) & 3);
-        fglds16(W2T + (size_t)(n0 + row) * ldwt + 32 * kt + 8 * c, smem + F_W2T + p * 1024);
+        mg_glds16(W2T + (size_t)(n0 + row) * ldwt + 32 * kt + 8 * c, smem + F_W2T + p * 1024);
     }
 
     // ---- DMA slots ----------------------------------------------------------------------------------------------------------
@@ -168,7 +158,7 @@ __global__ __launch_bounds__(512) void wgrad_fused_kernel(const uint16_t* __rest
         }
 #pragma unroll
         for (int i = 0; i < NX; ++i)
-            fglds16(pick(a_ptr + (unsigned long long)(unsigned)rr[i] * lda_bytes + (unsigned)x_off[i], rr[i]), st + i * 1024);
+            mg_glds16(pick(a_ptr + (unsigned long long)(unsigned)rr[i] * lda_bytes + (unsigned)x_off[i], rr[i]), st + i * 1024);
     };
     int g_issued = 0;                                     // groups 0 .. g_issued - 1 are in flight or landed (wave-uniform)
     auto issue_upto = [&](int g_last) {
@@ -187,8 +177,8 @@ __global__ __launch_bounds__(512) void wgrad_fused_kernel(const uint16_t* __rest
     const int h1_col = n0 + 8 * ((lane & 15) ^ (h1_row & 15));
     auto issue_small = [&](int step) {
         const int mz = step * 32 + dz_row, mh = step * 32 + h1_row;
-        fglds16(pick((unsigned long long)(dZ2 + (size_t)(m_lo + mz) * lddz + dz_col), n_rows - 1 - mz), smem + F_DZ + wave * 1024);
-        fglds16(pick((unsigned long long)(H1 + (size_t)(m_lo + mh) * ldh + h1_col), n_rows - 1 - mh), smem + F_H1 + wave * 1024);
+        mg_glds16(pick((unsigned long long)(dZ2 + (size_t)(m_lo + mz) * lddz + dz_col), n_rows - 1 - mz), smem + F_DZ + wave * 1024);
+        mg_glds16(pick((unsigned long long)(H1 + (size_t)(m_lo + mh) * ldh + h1_col), n_rows - 1 - mh), smem + F_H1 + wave * 1024);
     };
 
     f32x16 acc[2][TKT];
@@ -511,7 +501,7 @@ __global__ __launch_bounds__(512) void wgrad_fused_pipe_kernel(const uint16_t* _
         }
 #pragma unroll
         for (int i = 0; i < NX; ++i)
-            fglds16(pick(a_ptr + (unsigned long long)(unsigned)rr[i] * lda_bytes + (unsigned)xo[i], rr[i]), st + i * 1024);
+            mg_glds16(pick(a_ptr + (unsigned long long)(unsigned)rr[i] * lda_bytes + (unsigned)xo[i], rr[i]), st + i * 1024);
     };
     int g_issued = 0;                                     // groups 0 .. g_issued - 1 are in flight or landed (wave-uniform)
     auto issue_upto = [&](int g_last) {
@@ -528,9 +518,9 @@ __global__ __launch_bounds__(512) void wgrad_fused_pipe_kernel(const uint16_t* _
     const int h1_col = n0 + 8 * ((lane & 15) ^ (h1_row & 15));
     auto issue_small = [&](int step, int buf) {           // tiles of `step` into buffer buf (= step % 3)
         const int mz = step * 32 + dz_row, mh = step * 32 + h1_row;
-        fglds16(pick((unsigned long long)(dZ2 + (size_t)(m_lo + mz) * lddz + dz_col), n_rows - 1 - mz),
+        mg_glds16(pick((unsigned long long)(dZ2 + (size_t)(m_lo + mz) * lddz + dz_col), n_rows - 1 - mz),
                 smem + P_DZ + buf * 8192 + wave * 1024);
-        fglds16(pick((unsigned long long)(H1 + (size_t)(m_lo + mh) * ldh + h1_col), n_rows - 1 - mh),
+        mg_glds16(pick((unsigned long long)(H1 + (size_t)(m_lo + mh) * ldh + h1_col), n_rows - 1 - mh),
                 smem + P_H1 + buf * 8192 + wave * 1024);
     };
 
@@ -909,7 +899,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_fused_solo_kernel(const uint16_t
         }
 #pragma unroll
         for (int i = 0; i < NX; ++i)
-            fglds16(pick(a_ptr + (unsigned long long)(unsigned)rr[i] * lda_bytes + (unsigned)xo[i], rr[i]), st + i * 1024);
+            mg_glds16(pick(a_ptr + (unsigned long long)(unsigned)rr[i] * lda_bytes + (unsigned)xo[i], rr[i]), st + i * 1024);
     };
     int g_issued = 0;
     auto issue_upto = [&](int g_last) {
@@ -934,9 +924,9 @@ __global__ __launch_bounds__(256, 1) void wgrad_fused_solo_kernel(const uint16_t
         for (int u = 0; u < 2; ++u) {
             const int pp = wave + 4 * u;
             const int mz = step * 32 + dz_row[u], mh = step * 32 + h1_row[u];
-            fglds16(pick((unsigned long long)(dZ2 + (size_t)(m_lo + mz) * lddz + dz_col[u]), n_rows - 1 - mz),
+            mg_glds16(pick((unsigned long long)(dZ2 + (size_t)(m_lo + mz) * lddz + dz_col[u]), n_rows - 1 - mz),
                     smem + P_DZ + buf * 8192 + pp * 1024);
-            fglds16(pick((unsigned long long)(H1 + (size_t)(m_lo + mh) * ldh + h1_col[u]), n_rows - 1 - mh),
+            mg_glds16(pick((unsigned long long)(H1 + (size_t)(m_lo + mh) * ldh + h1_col[u]), n_rows - 1 - mh),
                     smem + P_H1 + buf * 8192 + pp * 1024);
         }
     };

@@ -24,6 +24,36 @@ void mg_set_error(const char* fmt, ...);
 #define MG_CHECK_ONE_LAYOUT(name, offsets, seq_len, padded)          \
     MG_CHECK_ARG(((offsets) != NULL) != ((seq_len) != NULL),         \
                  name ": exactly one of offsets (packed rows) and seq_len (padded " padded ") must be given")
+// The checks of an entry point that maps a ragged input `x` (`width` elements per row, 8-byte with in_f64, else 4-byte) to packed
+// rows of `cols` elements in `out` (8-byte with out_f64): one layout, the sizes, the output, the alignment.  It reads the entry
+// point's B, offsets, seq_len, T_in, packed_rows, out and out_f64 by name, and returns MG_OK itself where there is nothing to do.
+#define MG_CHECK_PACKED_IO(name, padded, x, in_f64, width, cols)                                                                        \
+    MG_CHECK_ONE_LAYOUT(name, offsets, seq_len, padded);                                                                                \
+    MG_CHECK_ARG(B >= 0, name ": B=%d must not be negative", B);                                                                        \
+    MG_CHECK_ARG(offsets || T_in >= 0, name ": T_in=%d must not be negative", T_in);                                                    \
+    MG_CHECK_ARG(offsets || B <= MG_VOC_MAX_ITEMS, name ": a padded input takes at most %d items, got B=%d", MG_VOC_MAX_ITEMS, B);      \
+    MG_CHECK_ARG(out, name ": out must not be NULL");                                                                                   \
+    MG_CHECK_ARG(packed_rows >= 0 && packed_rows <= INT64_MAX / 8 / ((width) > (cols) ? (width) : (cols)),                              \
+                 name ": packed_rows=%lld out of range", (long long)packed_rows);                                                       \
+    MG_CHECK_ARG(offsets || B == 0 || T_in == 0 || (int64_t)T_in <= INT64_MAX / 8 / (width) / B,                                        \
+                 name ": B=%d x T_in=%d x %d overflow 64 bits", B, T_in, (int)(width));                                                 \
+    if (B == 0 || packed_rows == 0) return MG_OK;                                                                                       \
+    MG_CHECK_ARG(x, name ": the input must not be NULL");                                                                               \
+    MG_CHECK_ARG(((uintptr_t)(x) & ((in_f64) ? 7u : 3u)) == 0 && ((uintptr_t)out & (out_f64 ? 7u : 3u)) == 0 &&                         \
+                     (((uintptr_t)offsets | (uintptr_t)seq_len) & 7u) == 0,                                                             \
+                 name ": the input must be 4-byte (8-byte with in_f64), out 4-byte (8-byte with out_f64), offsets and seq_len 8-byte "   \
+                      "aligned")
+// One launch statement per element type: T names double where `f64` is set and float where it is not, in STMT.
+#define MG_SWITCH_F64(f64, T, STMT)     \
+    do {                                \
+        if (f64) {                      \
+            using T = double;           \
+            STMT;                       \
+        } else {                        \
+            using T = float;            \
+            STMT;                       \
+        }                               \
+    } while (0)
 // A normalised twin needs both parameter operands and a forward kind.
 #define MG_CHECK_NORM_TWIN(name, norm_out, p0, p1, kind)                                                          \
     MG_CHECK_ARG(!(norm_out) || ((p0) && (p1) && ((kind) == MG_NORM_MVN || (kind) == MG_NORM_MINMAX)),            \
@@ -176,18 +206,25 @@ __device__ __forceinline__ f32x16 mg_mfma_32x32x16(mg_bfv8 a, mg_bfv8 b, f32x16 
 }
 #endif
 
-// LDS-DMA of 64 x 16 bytes: lane l's 16 bytes (from its own address `src`) land at LDS byte (lds_wave_base + 16 l); no VGPR staging,
-// completion counted by vmcnt.  Inline asm on purpose: hipcc keeps no record of the pending LDS write (its own waits stay
-// conservative - a wait for a tracked load also covers every older DMA); the caller drains vmcnt before the barrier in front of the
-// first read.  M0 is saved and restored inside the statement (cdna_hip_programming.md section 5.7).
-__device__ __forceinline__ void mg_glds16(const void* src, unsigned char* lds_wave_base) {
-    const unsigned lds_off = (unsigned)(unsigned long long)((__attribute__((address_space(3))) unsigned char*)lds_wave_base);
-    const unsigned lds_uni = __builtin_amdgcn_readfirstlane(lds_off);
+// LDS-DMA of 64 x 16 bytes: lane l's 16 bytes (from its own address `src`) land at LDS byte (wave-uniform address + 16 l); no VGPR
+// staging, no ds_write, completion counted by vmcnt.  The one statement of this form in the library.  Inline asm on purpose: hipcc
+// keeps no record of the pending LDS write, so it drains vmcnt neither in front of the fragment reads (it does for
+// ds_read_b64_tr_b16 behind the builtin form: one s_waitcnt vmcnt(0) per step, measured) nor in front of __syncthreads; its own waits
+// stay conservative - a wait for a tracked load also covers every older DMA.  What the caller owes: it drains vmcnt, with a counted
+// wait of its own, before the barrier in front of the first read.  M0 is saved and restored inside the statement
+// (cdna_hip_programming.md section 5.7).
+//   mg_glds16_at takes the LDS address as an integer: casting a generic pointer back to the LDS address space inside a step loop
+//   made hipcc emit a null check that does not assemble.  mg_glds16 takes the pointer, where that cast is harmless.
+__device__ __forceinline__ void mg_glds16_at(const void* src, unsigned lds_addr) {
+    const unsigned lds_uni = __builtin_amdgcn_readfirstlane(lds_addr);
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep)
                  : "v"(src), "s"(lds_uni)
                  : "memory");
+}
+__device__ __forceinline__ void mg_glds16(const void* src, unsigned char* lds_wave_base) {
+    mg_glds16_at(src, (unsigned)(unsigned long long)((__attribute__((address_space(3))) unsigned char*)lds_wave_base));
 }
 
 // Write-through stores (mg_wt_mask above): the value goes to memory with the sc1 bit, the line does not stay dirty in L2.

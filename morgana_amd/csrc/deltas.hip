@@ -19,7 +19,7 @@
 // (B <= MG_DELTAS_MAX_SCAN_ITEMS), the only use of LDS here.
 #include "common.h"
 #include "item_norm.h"
-#include "seq_reduce.h"
+#include "packed_rows.h"
 
 #define DELTAS_THREADS 256
 #define DELTAS_CHUNK_ELEMS 2048      // input elements (rows x D) of one chunk when D % 4 == 0: two 16-byte trips per thread
@@ -249,7 +249,7 @@ int mg_deltas_f32(const float* x, int D, int B, const int64_t* offsets, const in
     const bool vec = D % 4 == 0 && bits % 16 == 0;
     const int64_t chunks = mg_ceil_div(total, deltas_chunk_rows(D));
     const unsigned blocks = (unsigned)(chunks < DELTAS_MAX_BLOCKS ? chunks : DELTAS_MAX_BLOCKS);
-    const size_t lds = scan ? ((size_t)B + 1 + DELTAS_THREADS) * sizeof(int64_t) : 0;
+    const size_t lds = scan ? mg_packed_scan_bytes(NULL, B, DELTAS_THREADS) : 0;
     hipStream_t st = (hipStream_t)stream;
 #define DELTAS_GO(VEC, MODE) \
     deltas_launch<VEC, MODE>(blocks, lds, st, x, offsets, seq_len, T_in, B, D, win, edge, p0, p1, item_row, S, kind, out_rows, total, raw_out, norm_out)

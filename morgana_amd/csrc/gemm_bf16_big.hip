@@ -28,22 +28,7 @@ typedef __bf16 bfv4 __attribute__((ext_vector_type(4)));
 #define MG_ZERO_ELEMS 16384
 __device__ uint16_t g_zero_row[MG_ZERO_ELEMS];   // zero-initialised: source of pad rows / out-of-range rows
 
-// LDS-DMA of 64 x 16 bytes: lane l's 16 bytes land at LDS byte (lds_wave_base + 16 l).  Issued from inline asm on
-// purpose: hipcc then keeps no record of a pending LDS write, so it neither drains vmcnt in front of the fragment reads
-// (it does for ds_read_b64_tr_b16 behind the builtin form: one s_waitcnt vmcnt(0) per step, measured) nor in front of
-// __syncthreads; completion is tracked by the counted waits of WAIT_VM_BARRIER below.  M0 is saved and restored inside
-// the statement (cdna_hip_programming.md section 5.7).
-__device__ __forceinline__ void glds16(const uint16_t* src, unsigned char* lds_wave_base) {
-    const unsigned lds_off = (unsigned)(unsigned long long)((__attribute__((address_space(3))) unsigned char*)lds_wave_base);
-    const unsigned lds_uni = __builtin_amdgcn_readfirstlane(lds_off);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(src), "s"(lds_uni)
-                 : "memory");
-}
-
-
+// LDS-DMA (mg_glds16 of common.h) is issued from inline asm: completion is tracked by the counted waits of WAIT_VM_BARRIER below.
 #define WAIT_VM_BARRIER(N) asm volatile("s_waitcnt vmcnt(" #N ")\n\ts_barrier" ::: "memory")
 #define WAIT_LGKM_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
@@ -167,9 +152,9 @@ __device__ __forceinline__ void gemm_nt_big_body(unsigned char* __restrict__ sme
             kb = w + (pass == 1 ? b_lo : 0);
         }
 #pragma unroll
-        for (int i = 0; i < GA; ++i) glds16(asrc[i] + ka, st + (wave * GA + i) * 1024);
+        for (int i = 0; i < GA; ++i) mg_glds16(asrc[i] + ka, st + (wave * GA + i) * 1024);
 #pragma unroll
-        for (int i = 0; i < GB; ++i) glds16(bsrc[i] + kb, st + A_BYTES + (wave * GB + i) * 1024);
+        for (int i = 0; i < GB; ++i) mg_glds16(bsrc[i] + kb, st + A_BYTES + (wave * GB + i) * 1024);
     };
 
     // acc[i][j] holds C^T of the (i, j) 32 x 32 sub-tile: lane&31 = frame row, registers = output columns.
@@ -600,19 +585,19 @@ __device__ __forceinline__ void gemm_nt_persist_body(unsigned char* __restrict__
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
 #pragma unroll
-                for (int g = 0; g < GA; ++g) glds16(asrc[g] + ka + pl * a_lo, st + pl * PLANE + (wave * GA + g) * 1024);
+                for (int g = 0; g < GA; ++g) mg_glds16(asrc[g] + ka + pl * a_lo, st + pl * PLANE + (wave * GA + g) * 1024);
 #pragma unroll
-                for (int g = 0; g < GB; ++g) glds16(bsrc[g] + kb + pl * b_lo, st + pl * PLANE + A_BYTES + (wave * GB + g) * 1024);
+                for (int g = 0; g < GB; ++g) mg_glds16(bsrc[g] + kb + pl * b_lo, st + pl * PLANE + A_BYTES + (wave * GB + g) * 1024);
             }
         } else
         // probe bits (timing experiments, results garbage): 1 = no A pieces, 2 = no B pieces, 4 = no fragment reads, 8 = no MFMAs, 16 = no epilogue
         for (int rep = 0; rep < reps; ++rep) {
 #pragma unroll
         for (int g = 0; g < GA; ++g)
-            if (!(probe & 1)) glds16(asrc[g] + ka, st + (wave * GA + g) * 1024);
+            if (!(probe & 1)) mg_glds16(asrc[g] + ka, st + (wave * GA + g) * 1024);
 #pragma unroll
         for (int g = 0; g < GB; ++g)
-            if (!(probe & 2)) glds16(bsrc[g] + kb, st + A_BYTES + (wave * GB + g) * 1024);
+            if (!(probe & 2)) mg_glds16(bsrc[g] + kb, st + A_BYTES + (wave * GB + g) * 1024);
         }
         i_s = (i_s + 1 == NS) ? 0 : i_s + 1;
         if (X3 == 1 && ++i_p == 3) {              // pass fastest: an operand's k-tile is read again while the XCD's L2 still holds it
@@ -630,8 +615,8 @@ __device__ __forceinline__ void gemm_nt_persist_body(unsigned char* __restrict__
     auto issue_piece = [&](int q) {               // SPREAD: piece q of the next stage; advance_stage() after the last
         if (i_t >= n_my) return;
         unsigned char* st = smem + i_s * STAGE;
-        if (q < GA) glds16(asrc[q < GA ? q : 0] + i_k * BK, st + (wave * GA + q) * 1024);
-        else glds16(bsrc[q < GA ? 0 : q - GA] + i_k * BK, st + A_BYTES + (wave * GB + (q - GA)) * 1024);
+        if (q < GA) mg_glds16(asrc[q < GA ? q : 0] + i_k * BK, st + (wave * GA + q) * 1024);
+        else mg_glds16(bsrc[q < GA ? 0 : q - GA] + i_k * BK, st + A_BYTES + (wave * GB + (q - GA)) * 1024);
     };
     auto advance_stage = [&]() {
         if (i_t >= n_my) return;
@@ -1207,7 +1192,7 @@ __device__ __forceinline__ void wgrad_big_body(unsigned char* __restrict__ smem,
                 for (int i = 0; i < NY; ++i) {
                     const int ml = step * 32 + y_row[i];
                     const uint16_t* p = (ml < n_rows) ? dY + (size_t)(m_lo + ml) * lddy + pl * (lddy >> 1) + n0 + y_c[i] * 8 : g_zero_row;
-                    glds16(p, st + pl * STAGE + (wave * NY + i) * 1024);
+                    mg_glds16(p, st + pl * STAGE + (wave * NY + i) * 1024);
                 }
                 int rn[NX];
 #pragma unroll
@@ -1215,7 +1200,7 @@ __device__ __forceinline__ void wgrad_big_body(unsigned char* __restrict__ smem,
 #pragma unroll
                 for (int i = 0; i < NX; ++i) {
                     const uint16_t* p = (rn[i] >= 0 && x_off[i] >= 0) ? A + (size_t)rn[i] * lda + pl * (lda >> 1) + x_off[i] : g_zero_row;
-                    glds16(p, st + pl * STAGE + Y_BYTES + (wave * NX + i) * 1024);
+                    mg_glds16(p, st + pl * STAGE + Y_BYTES + (wave * NX + i) * 1024);
                 }
             }
             return;
@@ -1231,11 +1216,11 @@ __device__ __forceinline__ void wgrad_big_body(unsigned char* __restrict__ smem,
             if (DYR) {
                 const int ry = dyrow_lds[step * 32 + y_row[i]];
                 const uint16_t* p = ry >= 0 ? dY + (size_t)ry * lddy + n0 + y_c[i] * 8 : g_zero_row;
-                glds16(p, st + (wave * NY + i) * 1024);
+                mg_glds16(p, st + (wave * NY + i) * 1024);
             } else {
                 const int ml = step * 32 + y_row[i];
                 const uint16_t* p = (ml < n_rows) ? dY + (size_t)(m_lo + ml) * lddy + y_plane + n0 + y_c[i] * 8 : g_zero_row;
-                glds16(p, st + (wave * NY + i) * 1024);
+                mg_glds16(p, st + (wave * NY + i) * 1024);
             }
         }
         int rr[NX];
@@ -1244,7 +1229,7 @@ __device__ __forceinline__ void wgrad_big_body(unsigned char* __restrict__ smem,
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
             const uint16_t* p = (rr[i] >= 0 && x_off[i] >= 0) ? A + (size_t)rr[i] * lda + a_plane + x_off[i] : g_zero_row;
-            glds16(p, st + Y_BYTES + (wave * NX + i) * 1024);
+            mg_glds16(p, st + Y_BYTES + (wave * NX + i) * 1024);
         }
     };
 

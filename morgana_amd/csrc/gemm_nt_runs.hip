@@ -29,16 +29,6 @@ typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 __device__ uint16_t g_nr_zero_row[NR_ZERO_ELEMS];      // source of pad rows / unused run slots / out-of-range weight rows
 __device__ uint16_t g_nr_sink[64 * 8];                  // where the stores of rows past M go: every wave issues exactly NST stores
 
-__device__ __forceinline__ void nr_glds16(const uint16_t* src, unsigned char* lds_wave_base) {
-    const unsigned lds_off = (unsigned)(unsigned long long)((__attribute__((address_space(3))) unsigned char*)lds_wave_base);
-    const unsigned lds_uni = __builtin_amdgcn_readfirstlane(lds_off);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(src), "s"(lds_uni)
-                 : "memory");
-}
-
 #define NR_WAIT(N) asm volatile("s_waitcnt vmcnt(" #N ") lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #define NR_WAIT_CASE(N) case N: NR_WAIT(N); break;
 
@@ -191,9 +181,9 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_runs_kernel(const uint16_t* __
         }
         ++issued;
         unsigned char* st = smem + i_s * NR_STAGE;
-        nr_glds16(asrc + i_k * BK, st + wave * 1024);
-        nr_glds16(bsrc[0] + i_k * BK, st + NR_A_BYTES + (wave * 2) * 1024);
-        nr_glds16(bsrc[1] + i_k * BK, st + NR_A_BYTES + (wave * 2 + 1) * 1024);
+        mg_glds16(asrc + i_k * BK, st + wave * 1024);
+        mg_glds16(bsrc[0] + i_k * BK, st + NR_A_BYTES + (wave * 2) * 1024);
+        mg_glds16(bsrc[1] + i_k * BK, st + NR_A_BYTES + (wave * 2 + 1) * 1024);
         i_s = (i_s + 1 == NS) ? 0 : i_s + 1;
         if (++i_k == n_kt) {
             i_k = 0;

@@ -1,9 +1,10 @@
-// What the data-path kernels share (loss_norm's normalisers and pad passes, items_norm, colstats, unpad, deltas, f0, counters, durations): the
-// normaliser arithmetic, the guarded parameter row of an item, the rows of an item and the search from a chunk of destination rows to
-// its first item.  Each is a fixed order of operations on its arguments alone, so "the same bits as mg_normalise_f32" is
-// kept here, once.  The header carries no floating-point pragma: it is compiled under whatever its includer has set at that point
-// (f0.hip, counters.hip and durations.hip include it after their `fp contract(off)`; loss_norm.hip and items_norm.hip set nothing, and there the
-// inverse kinds' `v * fac + off` is contracted into one fma).
+// What the data-path kernels share (loss_norm's normalisers and pad passes, items_norm, colstats, f0, counters, durations, and - through
+// packed_rows.h, which includes this header - unpad, deltas, vocoder, analysis): the normaliser arithmetic, the guarded parameter row
+// of an item, the rows of an item and the search from a chunk of destination rows to its first item.  Each is a fixed order of
+// operations on its arguments alone, so "the same bits as mg_normalise_f32" is kept here, once.  The header carries no floating-point
+// pragma: it is compiled under whatever its includer has set at that point (f0.hip, counters.hip and durations.hip include it after
+// their `fp contract(off)`; loss_norm.hip and items_norm.hip set nothing, and there the inverse kinds' `v * fac + off` is contracted
+// into one fma).
 #pragma once
 
 // ---- the normaliser arithmetic (reference: morgana/data.py:533-538, 579-590)

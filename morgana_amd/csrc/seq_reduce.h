@@ -1,7 +1,8 @@
-// What the one-pass loss and statistics kernels share (ce, mdn, gv, seqmean, clip, the masked losses of loss_norm, unpad, deltas):
-// the valid-frame count of an utterance, the wave and workgroup reductions and the scan of the clamped lengths.  Each is a fixed
-// order of operations on its arguments alone - "the same bits on every call" is kept here, once.  Workgroups are 256 threads (four
-// waves of 64).  The header carries no floating-point pragma: it is compiled under whatever its includer has set at that point.
+// What the one-pass loss and statistics kernels share (ce, mdn, gv, vq, seqmean, segpool, clip, the masked losses of loss_norm):
+// the valid-frame count of an utterance and the wave and workgroup reductions.  Each is a fixed order of operations on its arguments
+// alone - "the same bits on every call" is kept here, once.  Workgroups are 256 threads (four waves of 64).  The header carries no
+// floating-point pragma: it is compiled under whatever its includer has set at that point.  (The scan of the clamped lengths, which
+// only the data-path kernels use, is in packed_rows.h.)
 #pragma once
 
 // n_b = min(max(seq_len[b], 0), T); without seq_len every frame is valid
@@ -64,34 +65,4 @@ __device__ __forceinline__ float mg_utterance_mean_sum(const float* __restrict__
         __syncthreads();
     }
     return red[0];
-}
-
-// Exclusive scan of len_b = min(max(seq_len[b], 0), T) over the workgroup: s_off[b] = sum of the lengths before item b,
-// s_off[B] = all of them.  Thread t owns items [t per, (t + 1) per).  s_off: B + 1, s_part: 256 entries of LDS.
-__device__ __forceinline__ void mg_clamped_length_scan(const int64_t* __restrict__ seq_len, int B, int64_t T, int64_t* s_off,
-                                                       int64_t* s_part) {
-    const int tid = threadIdx.x;
-    const int per = (B + 255) / 256;
-    const int lo = tid * per < B ? tid * per : B, hi = lo + per < B ? lo + per : B;
-    int64_t sum = 0;
-    for (int b = lo; b < hi; ++b) {
-        const int64_t len = seq_len[b];
-        sum += len < 0 ? 0 : len > T ? T : len;
-    }
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const int64_t v = tid >= off ? s_part[tid - off] : 0;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    int64_t run = s_part[tid] - sum;
-    for (int b = lo; b < hi; ++b) {
-        const int64_t len = seq_len[b];
-        s_off[b] = run;
-        run += len < 0 ? 0 : len > T ? T : len;
-    }
-    if (tid == 255) s_off[B] = s_part[tid];
-    __syncthreads();
 }

@@ -9,7 +9,7 @@
 // few bytes in front of and behind the aligned body moved one by one.
 #include "common.h"
 #include "item_norm.h"
-#include "seq_reduce.h"
+#include "packed_rows.h"
 
 #define UNPAD_THREADS 256
 #define UNPAD_CHUNK (UNPAD_THREADS * 16 * 4)        // destination bytes per chunk: four 16-byte trips per thread

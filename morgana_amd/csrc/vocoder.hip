@@ -24,8 +24,8 @@
 // term.
 //
 // Rows.  A row tile of a packed input reads its own rows, [offsets[0], offsets[B]).  A padded input's tile finds the source frame of
-// each of its packed rows by a binary search in the items' first packed rows (mg_item_at of csrc/item_norm.h): the scanned clamped
-// lengths, held in LDS, B <= MG_VOC_MAX_ITEMS.  A packed row that belongs to no item, and every row from packed_rows on, is not
+// each of its packed rows by a binary search in the items' first packed rows (mg_packed_source_row of csrc/packed_rows.h): the scanned
+// clamped lengths, held in LDS, B <= MG_VOC_MAX_ITEMS.  A packed row that belongs to no item, and every row from packed_rows on, is not
 // written; a frame past its item's length is never read.
 //
 // Smoothing mapping.  One workgroup per item (grid-stride), as csrc/f0.hip; per column the item is taken in chunks of VOC_F0_CHUNK
@@ -34,7 +34,7 @@
 // last `window` frames, recomputed from memory by the few threads that own them (the same function of the same input).
 #include "common.h"
 #include "item_norm.h"
-#include "seq_reduce.h"
+#include "packed_rows.h"
 
 #define VOC_THREADS 256
 #define VOC_TILE_BINS VOC_THREADS
@@ -57,33 +57,6 @@ __device__ __forceinline__ int64_t voc_uniform(int64_t v) {      // a value ever
 // operands of a plain fma, would each be copied into one first.
 __device__ __forceinline__ void voc_chain_fence(float& done, float& next) { asm volatile("" : "+v"(done), "+v"(next)); }
 
-// first packed row of item b (b == B: all rows)
-__device__ __forceinline__ int64_t voc_first_row(int b, const int64_t* __restrict__ offsets, const int64_t* s_cum) {
-    return offsets ? offsets[b] : s_cum[b];
-}
-
-// the source frame (row of the input as the item's layout counts it) of packed row r, or -1: no item holds it
-__device__ __forceinline__ int64_t voc_source_row(int64_t r, int64_t rows_end, int B, const int64_t* __restrict__ offsets,
-                                                  const int64_t* __restrict__ seq_len, int64_t T_in, const int64_t* s_cum) {
-    if (r >= rows_end) return -1;
-    if (offsets) return r >= offsets[0] ? r : -1;              // packed rows are their own source: [offsets[0], offsets[B]), no search
-    const auto first_of = [&](int b) { return voc_first_row(b, offsets, s_cum); };
-    const int b = mg_item_at(B, r, first_of);
-    if (b >= B) return -1;
-    int64_t first, len;
-    mg_item_rows(offsets, seq_len, T_in, b, first, len);
-    const int64_t t = r - first_of(b);
-    return t >= 0 && t < len ? first + t : -1;
-}
-
-// The prologue the two tiled kernels share: the scan of a padded input, then the end of the rows any tile has to look at.
-__device__ __forceinline__ int64_t voc_rows_end(const int64_t* __restrict__ offsets, const int64_t* __restrict__ seq_len, int64_t T_in, int B,
-                                                int64_t packed_rows, int64_t* s_cum) {
-    if (!offsets) mg_clamped_length_scan(seq_len, B, T_in, s_cum, s_cum + B + 1);
-    const int64_t all = voc_first_row(B, offsets, s_cum);
-    return all < packed_rows ? all : packed_rows;
-}
-
 template <int MC, typename OutT>
 __global__ __launch_bounds__(VOC_THREADS) void mcep_spectrum_kernel(const float* __restrict__ c, const float* __restrict__ basis, int64_t ldb,
                                                                     const int64_t* __restrict__ offsets, const int64_t* __restrict__ seq_len,
@@ -92,7 +65,7 @@ __global__ __launch_bounds__(VOC_THREADS) void mcep_spectrum_kernel(const float*
     extern __shared__ __attribute__((aligned(16))) int64_t s_voc[];      // a padded input only: [B + 1] first rows, [256] partials
     __shared__ int64_t s_src[VOC_TILE_FRAMES];
     const int tid = threadIdx.x;
-    const int64_t rows_end = voc_rows_end(offsets, seq_len, T_in, B, packed_rows, s_voc);
+    const int64_t rows_end = mg_packed_rows_end(offsets, seq_len, T_in, B, packed_rows, s_voc);
     const int64_t n_tiles = (rows_end + VOC_TILE_FRAMES - 1) / VOC_TILE_FRAMES;
 
     const int bin = blockIdx.x * VOC_TILE_BINS + tid;
@@ -116,7 +89,7 @@ __global__ __launch_bounds__(VOC_THREADS) void mcep_spectrum_kernel(const float*
     for (int64_t tile = blockIdx.y; tile < n_tiles; tile += gridDim.y) {
         const int64_t r_lo = tile * VOC_TILE_FRAMES;
         __syncthreads();                                       // the previous tile's readers of s_src are done
-        if (tid < VOC_TILE_FRAMES) s_src[tid] = voc_source_row(r_lo + tid, rows_end, B, offsets, seq_len, T_in, s_voc);
+        if (tid < VOC_TILE_FRAMES) s_src[tid] = mg_packed_source_row(r_lo + tid, rows_end, B, offsets, seq_len, T_in, s_voc);
         __syncthreads();
         if (!wave_live) continue;
         for (int r = 0; r < VOC_TILE_FRAMES; r += VOC_FRAMES) {
@@ -199,7 +172,7 @@ __global__ __launch_bounds__(VOC_THREADS) void bap_aperiodicity_kernel(const flo
     extern __shared__ __attribute__((aligned(16))) int64_t s_voc[];
     __shared__ int64_t s_src[VOC_TILE_FRAMES];
     const int tid = threadIdx.x;
-    const int64_t rows_end = voc_rows_end(offsets, seq_len, T_in, B, packed_rows, s_voc);
+    const int64_t rows_end = mg_packed_rows_end(offsets, seq_len, T_in, B, packed_rows, s_voc);
     const int64_t n_tiles = (rows_end + VOC_TILE_FRAMES - 1) / VOC_TILE_FRAMES;
 
     const int bin = blockIdx.x * VOC_TILE_BINS + tid;
@@ -215,7 +188,7 @@ __global__ __launch_bounds__(VOC_THREADS) void bap_aperiodicity_kernel(const flo
     for (int64_t tile = blockIdx.y; tile < n_tiles; tile += gridDim.y) {
         const int64_t r_lo = tile * VOC_TILE_FRAMES;
         __syncthreads();
-        if (tid < VOC_TILE_FRAMES) s_src[tid] = voc_source_row(r_lo + tid, rows_end, B, offsets, seq_len, T_in, s_voc);
+        if (tid < VOC_TILE_FRAMES) s_src[tid] = mg_packed_source_row(r_lo + tid, rows_end, B, offsets, seq_len, T_in, s_voc);
         __syncthreads();
         if (!live) continue;
 #pragma unroll 4
@@ -245,7 +218,7 @@ __global__ __launch_bounds__(VOC_THREADS) void smooth_f0_kernel(const float* __r
         // the item: uniform for the workgroup
         int64_t first, len;
         mg_item_rows(offsets, seq_len, T_in, b, first, len);
-        const int64_t pfirst = voc_first_row(b, offsets, s_voc);
+        const int64_t pfirst = mg_packed_first_row(b, offsets, s_voc);
         const bool smooth = window > 1 && len >= window;
         const int h = smooth ? (window - 1) / 2 : 0;
         const double den = (double)h * (double)(h + 1) * (double)(2 * h + 1) / 3.0;      // sum_j (j - h)^2, an integer
@@ -285,25 +258,6 @@ __global__ __launch_bounds__(VOC_THREADS) void smooth_f0_kernel(const float* __r
     }
 }
 
-static size_t voc_scan_bytes(const int64_t* offsets, int B) { return offsets ? 0 : ((size_t)B + 1 + VOC_THREADS) * sizeof(int64_t); }
-
-// The argument checks the three entry points share: one layout, the sizes, the output, the alignment.  `width`: floats per input row.
-#define VOC_CHECK_COMMON(name, x, width, cols)                                                                                          \
-    MG_CHECK_ONE_LAYOUT(name, offsets, seq_len, "(B, T_in, D)");                                                                        \
-    MG_CHECK_ARG(B >= 0, name ": B=%d must not be negative", B);                                                                        \
-    MG_CHECK_ARG(offsets || T_in >= 0, name ": T_in=%d must not be negative", T_in);                                                    \
-    MG_CHECK_ARG(offsets || B <= MG_VOC_MAX_ITEMS, name ": a padded input takes at most %d items, got B=%d", MG_VOC_MAX_ITEMS, B);      \
-    MG_CHECK_ARG(out, name ": out must not be NULL");                                                                                   \
-    MG_CHECK_ARG(packed_rows >= 0 && packed_rows <= INT64_MAX / 8 / (cols), name ": packed_rows=%lld out of range",                     \
-                 (long long)packed_rows);                                                                                               \
-    MG_CHECK_ARG(offsets || B == 0 || T_in == 0 || (int64_t)T_in <= INT64_MAX / 4 / (width) / B,                                        \
-                 name ": B=%d x T_in=%d x %d overflow 64 bits", B, T_in, (int)(width));                                                 \
-    if (B == 0 || packed_rows == 0) return MG_OK;                                                                                       \
-    MG_CHECK_ARG(x, name ": the input must not be NULL");                                                                               \
-    MG_CHECK_ARG(((uintptr_t)(x) & 3u) == 0 && ((uintptr_t)out & (out_f64 ? 7u : 3u)) == 0 &&                                           \
-                     (((uintptr_t)offsets | (uintptr_t)seq_len) & 7u) == 0,                                                             \
-                 name ": the input must be 4-byte, out 4-byte (8-byte with out_f64), offsets and seq_len 8-byte aligned")
-
 static dim3 voc_tile_grid(int K, int64_t packed_rows) {
     const unsigned nbt = (unsigned)((K + VOC_TILE_BINS - 1) / VOC_TILE_BINS);
     const int64_t n_tiles = (packed_rows + VOC_TILE_FRAMES - 1) / VOC_TILE_FRAMES;
@@ -317,12 +271,9 @@ template <int MC>
 static void voc_launch_spectrum(dim3 grid, size_t lds, hipStream_t stream, const float* mcep, const float* basis, int64_t ldb,
                                 const int64_t* offsets, const int64_t* seq_len, int T_in, int B, int M, int K, int log_out, int out_f64,
                                 int64_t packed_rows, void* out) {
-    if (out_f64)
-        hipLaunchKernelGGL((mcep_spectrum_kernel<MC, double>), grid, dim3(VOC_THREADS), lds, stream, mcep, basis, ldb, offsets, seq_len,
-                           (int64_t)T_in, B, M, K, log_out ? 1 : 0, packed_rows, (double*)out);
-    else
-        hipLaunchKernelGGL((mcep_spectrum_kernel<MC, float>), grid, dim3(VOC_THREADS), lds, stream, mcep, basis, ldb, offsets, seq_len,
-                           (int64_t)T_in, B, M, K, log_out ? 1 : 0, packed_rows, (float*)out);
+    MG_SWITCH_F64(out_f64, OutT,
+                  hipLaunchKernelGGL((mcep_spectrum_kernel<MC, OutT>), grid, dim3(VOC_THREADS), lds, stream, mcep, basis, ldb, offsets, seq_len,
+                                     (int64_t)T_in, B, M, K, log_out ? 1 : 0, packed_rows, (OutT*)out));
 }
 
 extern "C" {
@@ -337,10 +288,10 @@ int mg_mcep_spectrum_f32(const float* mcep, int M, int B, const int64_t* offsets
     MG_CHECK_ARG(M >= 1 && M <= MG_VOC_MAX_ORDER, "mg_mcep_spectrum_f32: M=%d cepstra outside [1, %d]", M, MG_VOC_MAX_ORDER);
     const int K = F / 2 + 1;
     MG_CHECK_ARG(ldb >= K, "mg_mcep_spectrum_f32: ldb=%lld is below the F / 2 + 1 = %d bins of a basis row", (long long)ldb, K);
-    VOC_CHECK_COMMON("mg_mcep_spectrum_f32", mcep, M, K);
+    MG_CHECK_PACKED_IO("mg_mcep_spectrum_f32", "(B, T_in, D)", mcep, 0, M, K);
     MG_CHECK_ARG(basis && ((uintptr_t)basis & 3u) == 0, "mg_mcep_spectrum_f32: basis must not be NULL and 4-byte aligned");
     const dim3 grid = voc_tile_grid(K, packed_rows);
-    const size_t lds = voc_scan_bytes(offsets, B);
+    const size_t lds = mg_packed_scan_bytes(offsets, B, VOC_THREADS);
     switch ((M + 31) / 32) {
         case 1: voc_launch_spectrum<1>(grid, lds, (hipStream_t)stream, mcep, basis, ldb, offsets, seq_len, T_in, B, M, K, log_out, out_f64, packed_rows, out); break;
         case 2: voc_launch_spectrum<2>(grid, lds, (hipStream_t)stream, mcep, basis, ldb, offsets, seq_len, T_in, B, M, K, log_out, out_f64, packed_rows, out); break;
@@ -358,15 +309,12 @@ int mg_bap_aperiodicity_f32(const float* bap, int Nb, int B, const int64_t* offs
     MG_CHECK_ARG(Nb >= 1 && (int64_t)6000 * Nb < (int64_t)fs,
                  "mg_bap_aperiodicity_f32: Nb=%d bands of 3000 Hz must end below fs / 2 = %g Hz (and Nb >= 1)", Nb, 0.5 * fs);
     const int K = F / 2 + 1;
-    VOC_CHECK_COMMON("mg_bap_aperiodicity_f32", bap, Nb, K);
+    MG_CHECK_PACKED_IO("mg_bap_aperiodicity_f32", "(B, T_in, D)", bap, 0, Nb, K);
     const dim3 grid = voc_tile_grid(K, packed_rows);
-    const size_t lds = voc_scan_bytes(offsets, B);
-    if (out_f64)
-        hipLaunchKernelGGL(bap_aperiodicity_kernel<double>, grid, dim3(VOC_THREADS), lds, (hipStream_t)stream, bap, offsets, seq_len,
-                           (int64_t)T_in, B, Nb, fs, F, K, packed_rows, (double*)out);
-    else
-        hipLaunchKernelGGL(bap_aperiodicity_kernel<float>, grid, dim3(VOC_THREADS), lds, (hipStream_t)stream, bap, offsets, seq_len,
-                           (int64_t)T_in, B, Nb, fs, F, K, packed_rows, (float*)out);
+    const size_t lds = mg_packed_scan_bytes(offsets, B, VOC_THREADS);
+    MG_SWITCH_F64(out_f64, OutT,
+                  hipLaunchKernelGGL(bap_aperiodicity_kernel<OutT>, grid, dim3(VOC_THREADS), lds, (hipStream_t)stream, bap, offsets, seq_len,
+                                     (int64_t)T_in, B, Nb, fs, F, K, packed_rows, (OutT*)out));
     MG_CHECK_LAUNCH("mg_bap_aperiodicity_f32");
     return MG_OK;
 }
@@ -377,16 +325,13 @@ int mg_smooth_f0_f32(const float* lf0, const float* vuv, int D, int B, const int
     MG_CHECK_ARG(window >= 1 && window <= MG_VOC_MAX_WINDOW && (window & 1), "mg_smooth_f0_f32: window=%d must be odd and in [1, %d]", window,
                  MG_VOC_MAX_WINDOW);
     MG_CHECK_ARG(threshold == threshold, "mg_smooth_f0_f32: threshold is NaN: no frame would be voiced");
-    VOC_CHECK_COMMON("mg_smooth_f0_f32", lf0, D, D);
+    MG_CHECK_PACKED_IO("mg_smooth_f0_f32", "(B, T_in, D)", lf0, 0, D, D);
     MG_CHECK_ARG(vuv && ((uintptr_t)vuv & 3u) == 0, "mg_smooth_f0_f32: vuv must not be NULL and 4-byte aligned");
     const unsigned blocks = (unsigned)(B < VOC_F0_MAX_BLOCKS ? B : VOC_F0_MAX_BLOCKS);
-    const size_t lds = voc_scan_bytes(offsets, B);
-    if (out_f64)
-        hipLaunchKernelGGL(smooth_f0_kernel<double>, dim3(blocks), dim3(VOC_THREADS), lds, (hipStream_t)stream, lf0, vuv, offsets, seq_len,
-                           (int64_t)T_in, B, D, window, threshold, packed_rows, (double*)out);
-    else
-        hipLaunchKernelGGL(smooth_f0_kernel<float>, dim3(blocks), dim3(VOC_THREADS), lds, (hipStream_t)stream, lf0, vuv, offsets, seq_len,
-                           (int64_t)T_in, B, D, window, threshold, packed_rows, (float*)out);
+    const size_t lds = mg_packed_scan_bytes(offsets, B, VOC_THREADS);
+    MG_SWITCH_F64(out_f64, OutT,
+                  hipLaunchKernelGGL(smooth_f0_kernel<OutT>, dim3(blocks), dim3(VOC_THREADS), lds, (hipStream_t)stream, lf0, vuv, offsets,
+                                     seq_len, (int64_t)T_in, B, D, window, threshold, packed_rows, (OutT*)out));
     MG_CHECK_LAUNCH("mg_smooth_f0_f32");
     return MG_OK;
 }

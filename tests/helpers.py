@@ -4,7 +4,7 @@ all-reduce, LR schedules, the epoch loop) can be tested without a GPU.  The prod
 import numpy as np
 import torch
 
-from morgana_amd import base_models
+from morgana_amd import _lib, base_models
 from oracle import ref_torch
 
 
@@ -77,3 +77,27 @@ def g8_files_dataset(g8, root, device='cpu'):
     sources = {'n_frames': data.TextSource('n_frames'), 'dur': data.NumpyBinarySource('dur'), 'lab': data.NumpyBinarySource('lab'),
                'lf0': data.NumpyBinarySource('lf0')}
     return data.FilesDataset(sources, 'train', 'train_file_id_list.scp', normalisers, data_root=root)
+
+
+# ------------------------------------------------------------------------------------------------- the C ABI without a GPU
+# Fake device addresses for the host-side argument checks: never dereferenced, because every call made with them is refused on the host
+# (or has nothing to do) before a launch.
+X, OFF, SEQ, OUT, TAB = 1 << 20, 2 << 20, 3 << 20, 4 << 20, 5 << 20
+
+
+def abi_caller(name, names, ok):
+    """(call, refused) for the entry point ``name``: ``call(**changed)`` passes the accepted arguments ``ok`` (in the order of
+    ``names``) with some replaced; ``refused(message, **changed)``: the call returned MG_EINVAL and the error names the entry point
+    and contains ``message``."""
+    lib = _lib.load()
+    assert len(names) == len(_lib.SIGNATURES[name][1])
+
+    def call(**changed):
+        args = dict(zip(names, ok))
+        args.update(changed)
+        return getattr(lib, name)(*[args[n] for n in names])
+
+    def refused(message, **changed):
+        return call(**changed) == _lib.MG_EINVAL and name in _lib.last_error() and message in _lib.last_error()
+
+    return call, refused

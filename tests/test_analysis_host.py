@@ -7,6 +7,7 @@ import torch
 
 import analysis_ref64 as ref
 import vocoder_ref64 as voc
+from helpers import OFF, OUT, SEQ, TAB, X, abi_caller as _caller
 from morgana_amd import _lib, data, ops
 
 IDENTITY_SETTINGS = ((60, 0.77, 2048), (25, 0.58, 1024), (60, 0.58, 1024), (40, 0.42, 512))
@@ -139,22 +140,8 @@ def test_wrappers_refuse_host_tensors_and_bad_arguments():
 
 
 # ------------------------------------------------------------------------------------------------------------------------- the C ABI
-X, OFF, SEQ, OUT, TAB = 1 << 20, 2 << 20, 3 << 20, 4 << 20, 5 << 20      # never dereferenced: every call below is refused on the host
-
-
-def _caller(name, names, ok):
-    lib = _lib.load()
-    assert len(names) == len(_lib.SIGNATURES[name][1])
-
-    def call(**changed):
-        args = dict(zip(names, ok))
-        args.update(changed)
-        return getattr(lib, name)(*[args[n] for n in names])
-
-    def refused(message, **changed):
-        return call(**changed) == _lib.MG_EINVAL and name in _lib.last_error() and message in _lib.last_error()
-
-    return call, refused
+# The addresses X, OFF, SEQ, OUT and TAB are fake: every call below must be one that is refused on the host, or has nothing to do.
+INT64_MAX = 2 ** 63 - 1
 
 
 def test_tile_and_signatures():
@@ -200,3 +187,14 @@ def test_bap_entry_point_refuses_bad_arguments_without_a_gpu():
     assert refused('input must not be NULL', ap=None)
     assert refused('aligned', ap=X + 1) and refused('aligned', ap=X + 4, in_f64=1) and refused('aligned', out=OUT + 4, out_f64=1)
     assert call(B=0) == 0 and call(Nb=7, B=0) == 0 and call(Nb=2, fs=16000, B=0) == 0 and call(packed_rows=0) == 0
+
+
+def test_packed_rows_overflow_guard_refuses_its_first_value_without_a_gpu():
+    """The byte count packed_rows x max(width, cols) must fit 64 bits.  Only the refused side of the guard is called: the value below
+    it would launch.  (The guard on B x T_in x width cannot be reached here: T_in is an int, and at most MG_VOC_MAX_ITEMS = 4096 items
+    of at most 4097 bins leave it 2^37 frames.)"""
+    names = ('sp', 'in_f64', 'log_in', 'F', 'B', 'offsets', 'seq_len', 'T_in', 'table', 'ldt', 'M', 'out_f64', 'packed_rows', 'out', 'stream')
+    ok = (X, 1, 0, 8, 3, OFF, None, 0, TAB, 5, 2, 0, 30, OUT, None)
+    _, refused = _caller('mg_spectrum_mcep', names, ok)
+    assert refused('packed_rows=', packed_rows=INT64_MAX // 8 // max(5, 2) + 1)
+    assert INT64_MAX // 4 // 4097 // _lib.MG_VOC_MAX_ITEMS + 1 >= 2 ** 31

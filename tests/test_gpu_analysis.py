@@ -350,3 +350,36 @@ def test_extract_world_features_writes_what_the_ops_return(tmp_path):
     with pytest.raises(ValueError, match="'b'"):
         data.extract_world_features(ids, in_dir, str(tmp_path / 'other'), 16000, n_mcep=25, device=DEV)
     assert not os.path.exists(str(tmp_path / 'other'))
+
+
+# ---------------------------------------------------------------------------------- a packed input whose items do not start at row 0
+@pytest.mark.parametrize('entry', ['spectrum_mcep', 'aperiodicity_bap'])
+def test_packed_items_between_rows_of_no_item(entry):
+    """Items [tile - 1, 0, 2] whose offsets start at tile + 1 - the first row tile holds no item - and end 3 rows before packed_rows:
+    the rows in front of the first item and behind the last keep the canary, the rows between are the bits of the same items packed
+    from row 0.  The input rows of no item are NaN: nothing of them reaches an item."""
+    tile = _tile()
+    offsets = _offsets([tile - 1, 0, 2]) + (tile + 1)
+    lo, hi = int(offsets[0]), int(offsets[-1])
+    rows = hi + 3
+    x = np.full((rows, 5), np.nan)                               # fft_size 8
+    x[lo:hi] = np.random.RandomState(tile).uniform(1e-3, 1.0, size=(hi - lo, 5))
+    x = _dev(x)
+    if entry == 'spectrum_mcep':
+        cols = 2
+
+        def run(rows_of, off, **kwargs):
+            return ops.spectrum_mcep(x[rows_of], 2, 0.42, offsets=off, **kwargs)
+    else:
+        cols = 1
+
+        def run(rows_of, off, **kwargs):
+            return ops.aperiodicity_bap(x[rows_of], 16000, 1, offsets=off, **kwargs)
+
+    out = _with_canary(rows, cols)
+    run(slice(None), _dev(offsets), out=out, packed_rows=rows)
+    want = run(slice(lo, hi), _dev(offsets - lo))
+    assert want.shape == (hi - lo, cols) and bool(torch.isfinite(want).all())
+    assert torch.all(out[:lo] == CANARY), 'rows in front of the first item were written'
+    assert torch.all(out[hi:] == CANARY), 'rows behind the last item were written'
+    assert torch.equal(out[lo:hi], want), 'the items moved to row 0 give other bits'

@@ -358,3 +358,45 @@ def test_model_hook_hands_world_features_to_the_synthesiser(tmp_path):
                                        synthesiser=synthesiser)
     with pytest.raises(ValueError, match='no default alpha'):
         model.analysis_for_valid_batch(feats, outputs, out_dir=synth, sample_rate=32000, synthesiser=synthesiser)
+
+
+# ---------------------------------------------------------------------------------- a packed input whose items do not start at row 0
+@pytest.mark.parametrize('entry', ['mcep_spectrum', 'bap_aperiodicity', 'smooth_f0'])
+def test_packed_items_between_rows_of_no_item(entry):
+    """Items [tile - 1, 0, 2] whose offsets start at tile + 1 - the first row tile holds no item - and end 3 rows before packed_rows:
+    the rows in front of the first item and behind the last keep the canary, the rows between are the bits of the same items packed
+    from row 0.  The input rows of no item are NaN: nothing of them reaches an item."""
+    tile = _tile()
+    offsets = _offsets([tile - 1, 0, 2]) + (tile + 1)
+    lo, hi = int(offsets[0]), int(offsets[-1])
+    rows = hi + 3
+    rng = np.random.RandomState(tile)
+
+    def packed(low, high, width):
+        x = np.full((rows, width), np.nan, dtype=np.float32)
+        x[lo:hi] = rng.uniform(low, high, size=(hi - lo, width))
+        return torch.from_numpy(x).to(DEV)
+
+    if entry == 'mcep_spectrum':
+        mcep, cols = packed(-1.0, 1.0, 2), 5
+
+        def run(rows_of, off, **kwargs):
+            return ops.mcep_spectrum(mcep[rows_of], 0.42, 8, offsets=off, **kwargs)
+    elif entry == 'bap_aperiodicity':
+        bap, cols = packed(-70.0, 5.0, 1), 5
+
+        def run(rows_of, off, **kwargs):
+            return ops.bap_aperiodicity(bap[rows_of], 16000, 8, offsets=off, **kwargs)
+    else:
+        lf0, vuv, cols = packed(4.0, 6.0, 1), packed(0.0, 1.0, 1), 1
+
+        def run(rows_of, off, **kwargs):
+            return ops.smooth_f0(lf0[rows_of], vuv[rows_of], offsets=off, **kwargs)
+
+    out = _with_canary(rows, cols)
+    run(slice(None), torch.from_numpy(offsets).to(DEV), out=out, packed_rows=rows)
+    want = run(slice(lo, hi), torch.from_numpy(offsets - lo).to(DEV))
+    assert want.shape == (hi - lo, cols) and bool(torch.isfinite(want).all())
+    assert torch.all(out[:lo] == CANARY), 'rows in front of the first item were written'
+    assert torch.all(out[hi:] == CANARY), 'rows behind the last item were written'
+    assert torch.equal(out[lo:hi], want), 'the items moved to row 0 give other bits'

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import vocoder_ref64 as ref
+from helpers import OFF, OUT, SEQ, TAB, X, abi_caller as _caller
 from morgana_amd import _lib, ops, viz
 
 SETTINGS = ((1, 8, 0.0), (2, 8, 0.42), (25, 512, 0.42), (60, 2048, 0.77), (61, 1024, 0.58), (128, 64, 0.3))
@@ -108,22 +109,8 @@ def test_aperiodicity_at_exact_anchors():
 
 
 # ------------------------------------------------------------------------------------------------------------------------- the C ABI
-X, OFF, SEQ, OUT, TAB = 1 << 20, 2 << 20, 3 << 20, 4 << 20, 5 << 20      # never dereferenced: every call below is refused on the host
-
-
-def _caller(name, names, ok):
-    lib = _lib.load()
-    assert len(names) == len(_lib.SIGNATURES[name][1])
-
-    def call(**changed):
-        args = dict(zip(names, ok))
-        args.update(changed)
-        return getattr(lib, name)(*[args[n] for n in names])
-
-    def refused(message, **changed):
-        return call(**changed) == _lib.MG_EINVAL and name in _lib.last_error() and message in _lib.last_error()
-
-    return call, refused
+# The addresses X, OFF, SEQ, OUT and TAB are fake: every call below must be one that is refused on the host, or has nothing to do.
+INT64_MAX = 2 ** 63 - 1
 
 
 def test_limits_and_tiles():
@@ -182,6 +169,23 @@ def test_smoothing_entry_point_refuses_bad_arguments_without_a_gpu():
     assert refused('out must not be NULL', out=None)
     assert refused('input must not be NULL', lf0=None) and refused('vuv', vuv=None)
     assert call(B=0) == 0 and call(B=0, window=1) == 0 and call(B=0, window=65) == 0
+
+
+def test_overflow_guards_refuse_their_first_value_without_a_gpu():
+    """The byte counts packed_rows x max(width, cols) and B x T_in x width must fit 64 bits.  Only the refused side of either guard is
+    called: the value below it would launch."""
+    names = ('mcep', 'M', 'B', 'offsets', 'seq_len', 'T_in', 'basis', 'ldb', 'F', 'log_out', 'out_f64', 'packed_rows', 'out', 'stream')
+    ok = (X, 2, 3, OFF, None, 0, TAB, 5, 8, 0, 0, 30, OUT, None)
+    _, refused = _caller('mg_mcep_spectrum_f32', names, ok)
+    assert refused('packed_rows=', packed_rows=INT64_MAX // 8 // max(2, 5) + 1)
+    # T_in is an int: only a wide row brings the guard into its range
+    names = ('lf0', 'vuv', 'D', 'B', 'offsets', 'seq_len', 'T_in', 'window', 'threshold', 'out_f64', 'packed_rows', 'out', 'stream')
+    width, items = 2 ** 31 - 1, 1
+    ok = (X, TAB, width, items, None, SEQ, 4, 7, 0.5, 0, 1, OUT, None)
+    _, refused = _caller('mg_smooth_f0_f32', names, ok)
+    t_in = INT64_MAX // 4 // width // items + 1
+    assert t_in < 2 ** 31
+    assert refused('overflow 64 bits', T_in=t_in)
 
 
 def test_wrappers_refuse_host_tensors_and_bad_arguments():
