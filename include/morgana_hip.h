@@ -1664,6 +1664,72 @@ int mg_spectrum_mcep(const void* sp, int in_f64, int log_in, int F, int B, const
 int mg_aperiodicity_bap(const void* ap, int in_f64, int F, int fs, int Nb, int B, const int64_t* offsets, const int64_t* seq_len,
                         int T_in, int out_f64, int64_t packed_rows, void* out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * K34 (csrc/synth.hip)  WORLD-style waveform synthesis: f0 [n], power spectrum sp [n, K] and aperiodicity ap [n, K] in [0, 1],
+ *                       K = F / 2 + 1, F a power of two in [MG_SYNTH_MIN_FFT, MG_SYNTH_MAX_FFT], to N samples per utterance.
+ * This is WORLD's synthesis.cpp as remembered - pulse positions from the F0 track, a minimum-phase response per pitch pulse, a
+ * shaped-noise response per pulse interval, overlap-add; it could not be checked against pyworld, which is not installed where this
+ * was written.  Unlike WORLD's newer versions the noise segment's mean is not removed.  All arithmetic is float64, contraction off.
+ * tests/synth_ref64.py restates the definition in NumPy.
+ *
+ * The caller (ops.world_synthesise) owns the plan and describes the batch by int64 device arrays it builds from host-known lengths:
+ *   frame_start [B]      first row of utterance b in f0 / sp / ap (packed rows: its offset; padded (B, T, .): b T)
+ *   n_frames [B]         n_b
+ *   sample_offsets [B+1] prefix sums of N_b = floor((n_b - 1) S) + 1 (n_b >= 1; 0 for n_b = 0), S = fs * frame_period / 1000
+ *   region_offsets [B+1] prefix sums of the pulse capacities N_b / 2 + 1: where utterance b's pulse records start
+ *   pulse_offsets [B+1]  prefix sums of the pulse counts the pulse kernel reported (read back once): the global pulse numbering g
+ *
+ * mg_synth_pulses, one workgroup per utterance (n_b < 2: nothing is written - the caller zero-fills counts).  For sample i:
+ *     u = i / S, j = min(floor(u), n - 1), j1 = min(j + 1, n - 1), w = u - j;   v_j = f0_j > 0, g_j = v_j ? f0_j : 500
+ *     v(i) = v_j (w < .5), v_j1 (w > .5), v_j && v_j1 (w == .5);   f(i) = v(i) ? min(max(g_j + (g_j1 - g_j) w, fs / F), fs / 2) : 500
+ *     inc(i) = llrint(f(i) * inc_scale), inc_scale = 2^32 / fs from the host;  Phi(i) = sum_{j <= i} inc(j) in int64
+ *   sample i carries a pulse iff (Phi(i) >> 32) > (Phi(i-1) >> 32); delta = (Phi(i) mod 2^32) / inc(i) in [0, 1) is how far before i
+ *   the crossing lies; T_m = i_{m+1} - i_m (N - i_m for the last pulse; <= F by the floor fs / F, and by fs <= 500 F, which is
+ *   required, where unvoiced); voiced_m = v(i_m).  Records
+ *   pulse_idx / pulse_delta / pulse_T / pulse_voiced [region_offsets[b] + m] in ascending m, counts[b] pulses (<= N_b / 2).
+ *   Integer scan: the same pulses on every call and in any chunking.
+ *
+ * mg_synth_responses, one workgroup per pulse g of [g_lo, g_hi), 32 F bytes of LDS (mg_synth_lds_bytes).  At pulse m of utterance b:
+ *     u = min(max((i_m - delta_m) / S, 0), n - 1) with j, j1, w as above;  s[k] = max(sp_j[k] + (sp_j1[k] - sp_j[k]) w, 0),
+ *     a[k] the same interpolation of ap, r[k] = min(max(a[k]^2, 0), 1)                      (a NaN stays a NaN in all of them)
+ *     minphase(P): L = .5 ln P, c = irfft(L, F), c^ = c folded (c[0], 2 c[q] for 0 < q < F/2, c[F/2], 0 above), exp(rfft(c^))
+ *     voiced:   h = irfft(minphase(s (1 - r) + 1e-12) e^{+2 pi i k delta / F});  x[p] = h[(p - F/2 + 1) mod F];
+ *               x -= d sum(x), d[p] = .5 - .5 cos(2 pi (p + 1) / (F + 1)) normalised to sum 1;  x *= sqrt(T_m)
+ *     always:   e[t] = z[sample_offsets[b] + i_m + t] for t < T_m, 0 up to F;  G = minphase(s r + 1e-12) where voiced,
+ *               minphase(s + 1e-12 + 0 r) where not (0 r: a NaN aperiodicity reaches the response);  irfft(rfft(e) G), placed as x
+ *   irfft as numpy.fft: 1 / F, the imaginary parts of bins 0 and F / 2 dropped.  workspace[(g - g_lo) F + p] = periodic + aperiodic
+ *   response at time p - F/2 + 1 relative to i_m.  sp, ap: float (x_f64 == 0) or double, read in place.  table f64 [2 F]: (cos, sin)
+ *   of 2 pi q / F for q < F / 2, then d[p] (ops.synth_table); z f64: the noise track of the packed samples (mg_synth_noise or the
+ *   caller's).  Each real transform is half of an in-place radix-2 complex transform of size F; per transform the l2 error is at most
+ *   8 log2(F) 2^-53 of the l2 norm of its input (tests/synth_ref64.py derives the bound of a sample from that).
+ *
+ * mg_synth_overlap_add, one thread per packed sample: y[i_m + t] += x_m[t + F/2 - 1], t in [-F/2 + 1, F/2], over the pulses of
+ *   [g_lo, g_hi) that cover the sample, one addition at a time in ascending m on the value y holds (the caller zero-fills y and walks
+ *   the ranges in ascending order: the bits do not depend on how the pulses are cut into ranges).  last != 0: out[s] = y[s] rounded
+ *   once to float (out_f64 == 0) or copied (out may be y itself).  An empty range with last is valid (no pulse at all).  No atomics.
+ *
+ * mg_synth_noise: z[i] = (double) of the float32 N(0, 1) value of flat element i, i < n (the packed sample index), of the noise mapping
+ *   of mg_vae_sample_f32 with counter used[0] (int64 on the device, one draw of the step counter per call).
+ * Refused (MG_EINVAL, nothing launched): F outside the range or no power of two, B outside [0, MG_SYNTH_MAX_ITEMS], S outside
+ *   [1, 2^20], fs outside (0, min(2^20, 500 F)], inc_scale not 2^32 / fs, a bad range, a NULL or misaligned pointer.  B == 0, an empty range (responses)
+ *   or no samples: MG_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define MG_SYNTH_MIN_FFT 32
+#define MG_SYNTH_MAX_FFT 4096
+#define MG_SYNTH_MAX_ITEMS 65535
+size_t mg_synth_lds_bytes(int F);
+int mg_synth_noise(double* z, int64_t n, uint64_t seed, uint32_t site, const int64_t* used, void* stream);
+int mg_synth_pulses(const double* f0, int B, const int64_t* frame_start, const int64_t* n_frames, const int64_t* sample_offsets,
+                    const int64_t* region_offsets, double S, double fs, double inc_scale, int F, int32_t* pulse_idx, double* pulse_delta,
+                    int32_t* pulse_T, int32_t* pulse_voiced, int64_t* counts, void* stream);
+int mg_synth_responses(const void* sp, int sp_f64, const void* ap, int ap_f64, int B, const int64_t* frame_start, const int64_t* n_frames,
+                       const int64_t* sample_offsets, const int64_t* region_offsets, const int64_t* pulse_offsets, const int32_t* pulse_idx,
+                       const double* pulse_delta, const int32_t* pulse_T, const int32_t* pulse_voiced, const double* z, const double* table,
+                       double S, int F, int64_t g_lo, int64_t g_hi, double* workspace, void* stream);
+int mg_synth_overlap_add(const double* workspace, int B, const int64_t* sample_offsets, const int64_t* region_offsets,
+                         const int64_t* pulse_offsets, const int32_t* pulse_idx, int F, int64_t g_lo, int64_t g_hi, int64_t total_samples,
+                         double* y, int last, int out_f64, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -633,7 +633,7 @@ class StreamModel(BaseSPSS):
         return total / float(len(self.streams)) if len(self.streams) > 1 else total
 
     def analysis_for_valid_batch(self, features, output_features, out_dir, sample_rate=16000, synthesiser=None, alpha=None, fft_size=None,
-                                 **kwargs):
+                                 frame_period=5., **kwargs):
         """Saves every stream's generated output per utterance under ``{out_dir}/feats/{stream}/{name}.npy``
         (``viz.io.save_batched_seqs``): the MLPG trajectory of a delta stream (present when the normalisers carry delta
         parameters, i.e. under ``ExperimentBuilder``), the probabilities of a 'sigmoid_bce' stream, the predicted classes of a 'ce'
@@ -645,7 +645,9 @@ class StreamModel(BaseSPSS):
         example ``pyworld.synthesize`` (``pyworld`` is not a dependency of this package).  With a synthesiser, and the streams ``lf0``,
         ``vuv``, ``mcep`` and ``bap`` among the outputs, each utterance is written to ``{out_dir}/synth/{name}.wav`` at
         ``sample_rate``; ``alpha`` and ``fft_size`` as ``world_features`` takes them.  ``synthesiser=None`` (the default) writes
-        exactly the feature files."""
+        exactly the feature files.  ``synthesiser='world'`` is the package's own synthesis (``viz.synthesis.synthesise_batch``,
+        ``csrc/synth.hip``) at ``frame_period`` ms per frame: the whole batch in one pass, the spectra never leave the device and only
+        the waveforms reach the host (``viz.synthesis.synthesise`` is the same synthesis as a callable, one utterance at a time)."""
         kwargs['sample_rate'] = sample_rate                     # models/RNN_SPSS.py:142: the base hooks see it
         super(StreamModel, self).analysis_for_valid_batch(features, output_features, out_dir, **kwargs)
         names = [st.name for st in self.streams if st.name in output_features]
@@ -662,6 +664,15 @@ class StreamModel(BaseSPSS):
                            'among the outputs' % (', '.join(missing), 'is' if len(missing) == 1 else 'are'))
         synth_dir = os.path.join(out_dir, 'synth')
         os.makedirs(synth_dir, exist_ok=True)
+        if isinstance(synthesiser, str):
+            if synthesiser != 'world':
+                raise ValueError("analysis_for_valid_batch: synthesiser=%r; the built-in synthesiser is 'world'" % (synthesiser,))
+            waves = viz.synthesis.synthesise_batch(output_features['lf0'], output_features['vuv'], output_features['mcep'],
+                                                   output_features['bap'], sample_rate, features['n_frames'], alpha=alpha,
+                                                   fft_size=fft_size, frame_period=frame_period)
+            for name, wav in zip(features['name'], waves):
+                viz.io.save_wav(os.path.join(synth_dir, name + '.wav'), wav, sample_rate)
+            return
         per_utterance = viz.synthesis.world_features(output_features['lf0'], output_features['vuv'], output_features['mcep'],
                                                      output_features['bap'], sample_rate, features['n_frames'], alpha=alpha,
                                                      fft_size=fft_size)

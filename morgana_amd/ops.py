@@ -3640,6 +3640,248 @@ def aperiodicity_bap(ap, sample_rate, n_bands=None, fft_size=None, *, offsets=No
     return out
 
 
+# ---------------------------------------------------------------------------------------------- waveform synthesis (csrc/synth.hip)
+SYNTH_NOISE_SITE = 0x53594E00     # the Philox site of the synthesiser's noise track: one more stream
+SYNTH_MIN_FFT, SYNTH_MAX_FFT, SYNTH_MAX_ITEMS = _lib.MG_SYNTH_MIN_FFT, _lib.MG_SYNTH_MAX_FFT, _lib.MG_SYNTH_MAX_ITEMS
+SYNTH_WORKSPACE_BYTES = 256 << 20
+_synth_tables = {}
+
+
+def synth_fft_size(fft_size):
+    """``fft_size`` as an int if it is a power of two in [SYNTH_MIN_FFT, SYNTH_MAX_FFT]; anything else is a ValueError."""
+    if (isinstance(fft_size, bool) or not isinstance(fft_size, numbers.Integral) or not SYNTH_MIN_FFT <= fft_size <= SYNTH_MAX_FFT
+            or fft_size & (fft_size - 1)):
+        raise ValueError('world_synthesise: fft_size=%r must be a power of two in [%d, %d]' % (fft_size, SYNTH_MIN_FFT, SYNTH_MAX_FFT))
+    return int(fft_size)
+
+
+def synth_table(fft_size):
+    """The (2 fft_size,) float64 table of mg_synth_responses as a host array: ``(cos, sin)(2 pi q / F)`` for q < F / 2, then the
+    DC-removal window ``d[p] = .5 - .5 cos(2 pi (p + 1) / (F + 1))`` normalised to sum 1."""
+    import numpy as np
+    f = synth_fft_size(fft_size)
+    angle = 2. * np.pi * np.arange(f // 2, dtype=np.float64) / float(f)
+    d = .5 - .5 * np.cos(2. * np.pi * (np.arange(f, dtype=np.float64) + 1.) / (f + 1.))
+    return np.concatenate([np.stack([np.cos(angle), np.sin(angle)], axis=1).reshape(-1), d / d.sum()])
+
+
+def synth_table_on(fft_size, device):
+    """``synth_table`` on ``device``, built once per (fft_size, device) and kept."""
+    device = torch.device(device)
+    key = (int(fft_size), device.type, device.index if device.index is not None else torch.cuda.current_device())
+    table = _synth_tables.get(key)
+    if table is None:
+        table = _synth_tables[key] = torch.from_numpy(synth_table(fft_size)).to(device)
+    return table
+
+
+def synth_samples_per_frame(sample_rate, frame_period):
+    """S = sample_rate * frame_period / 1000 samples per frame (frame_period in ms), at least 1; it need not be an integer."""
+    for name, value in (('sample_rate', sample_rate), ('frame_period', frame_period)):
+        if isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(value) or value <= 0:
+            raise ValueError('world_synthesise: %s=%r must be a positive finite number' % (name, value))
+    if sample_rate > 1 << 20:
+        raise ValueError('world_synthesise: sample_rate=%r Hz is above 2^20' % (sample_rate,))
+    s = float(sample_rate) * float(frame_period) / 1000.
+    if not 1. <= s <= float(1 << 20):
+        raise ValueError('world_synthesise: %g samples per frame (sample_rate * frame_period / 1000) outside [1, 2^20]' % s)
+    return s
+
+
+def synth_sample_counts(n_frames, samples_per_frame):
+    """Samples per utterance: ``floor((n - 1) S) + 1`` for n >= 1 frames, 0 for none - a list of Python integers."""
+    return [0 if n <= 0 else int(math.floor((int(n) - 1) * samples_per_frame)) + 1 for n in n_frames]
+
+
+def synth_pulse_ranges(n_pulses, fft_size, workspace_bytes=SYNTH_WORKSPACE_BYTES):
+    """The plan of ``world_synthesise``: ``n_pulses`` responses of ``fft_size`` float64 each cut into ascending ranges [lo, hi) that
+    fit ``workspace_bytes`` (one response at the least).  No pulse: one empty range - the overlap-add still casts the output."""
+    f = synth_fft_size(fft_size)
+    if isinstance(workspace_bytes, bool) or not isinstance(workspace_bytes, numbers.Integral) or workspace_bytes <= 0:
+        raise ValueError('world_synthesise: workspace_bytes=%r must be a positive integer' % (workspace_bytes,))
+    per = min(max(int(workspace_bytes) // (8 * f), 1), 0x7FFFFFFF)
+    n_pulses = int(n_pulses)
+    if n_pulses <= 0:
+        return [(0, 0)]
+    return [(lo, min(lo + per, n_pulses)) for lo in range(0, n_pulses, per)]
+
+
+def synth_noise(total_samples, seed, used, out=None):
+    """The synthesiser's N(0, 1) noise track (mg_synth_noise): float64 (total_samples,), element i from
+    (seed, SYNTH_NOISE_SITE, used[0], i) - the same numbers give the same bits.  ``used``: a 1-element int64 DEVICE tensor
+    (``dropout_draw``)."""
+    lib = _lib.load()
+    used = _require(used, torch.int64, 'used')
+    if used.numel() != 1:
+        raise ValueError('synth_noise: used must hold one element, got %s' % (tuple(used.shape),))
+    if isinstance(total_samples, bool) or not isinstance(total_samples, numbers.Integral) or total_samples < 0:
+        raise ValueError('synth_noise: total_samples=%r must be a non-negative integer' % (total_samples,))
+    z = torch.empty((int(total_samples),), dtype=torch.float64, device=used.device) if out is None else out
+    if total_samples:
+        _lib.check(lib.mg_synth_noise(_p(z), int(total_samples), int(seed) & 0xFFFFFFFFFFFFFFFF, SYNTH_NOISE_SITE, _p(used), _stream()),
+                   'mg_synth_noise')
+    return z
+
+
+def _synth_layout(f0, sp, ap, seq_len, offsets):
+    """The host side of the ragged input of ``world_synthesise`` -> (frame_start, n_frames) as lists of Python integers and the rows
+    of the feature tensors.  Needs no device: lengths given as device tensors are read once (they are host-known everywhere the
+    package calls this)."""
+    if (seq_len is None) == (offsets is None):
+        raise ValueError('world_synthesise: exactly one of seq_len (padded (B, T, K) input) and offsets (packed (rows, K) input) must be given')
+    for name, x in (('sp', sp), ('ap', ap)):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError('world_synthesise: %s must be a torch.Tensor, got %s' % (name, type(x)))
+        if x.dtype not in (torch.float32, torch.float64):
+            raise TypeError('world_synthesise: %s must be torch.float32 or torch.float64, got %s' % (name, x.dtype))
+    if not isinstance(f0, torch.Tensor):
+        raise TypeError('world_synthesise: f0 must be a torch.Tensor, got %s' % type(f0))
+    if sp.shape != ap.shape:
+        raise ValueError('world_synthesise: sp %s and ap %s differ in shape' % (tuple(sp.shape), tuple(ap.shape)))
+    lengths = (seq_len if seq_len is not None else offsets)
+    if isinstance(lengths, torch.Tensor):
+        lengths = lengths.detach().reshape(-1).cpu().tolist()
+    lengths = [int(v) for v in lengths]
+    if seq_len is not None:
+        if sp.dim() != 3:
+            raise ValueError('world_synthesise: with seq_len, sp must be padded (B, T, K), got %s' % (tuple(sp.shape),))
+        b, t = sp.shape[:2]
+        if len(lengths) != b:
+            raise ValueError('world_synthesise: seq_len holds %d lengths for %d items' % (len(lengths), b))
+        n_frames = [min(max(n, 0), t) for n in lengths]
+        frame_start = [i * t for i in range(b)]
+        rows = b * t
+    else:
+        if sp.dim() != 2:
+            raise ValueError('world_synthesise: with offsets, sp must be packed (rows, K), got %s' % (tuple(sp.shape),))
+        rows = sp.shape[0]
+        if not lengths or lengths[0] < 0 or any(hi < lo for lo, hi in zip(lengths, lengths[1:])) or lengths[-1] > rows:
+            raise ValueError('world_synthesise: offsets must be (B + 1,) ascending inside the %d packed rows' % rows)
+        n_frames = [hi - lo for lo, hi in zip(lengths, lengths[1:])]
+        frame_start = lengths[:-1]
+    if f0.numel() != rows:
+        raise ValueError('world_synthesise: f0 %s does not hold one value for each of the %d frames of sp' % (tuple(f0.shape), rows))
+    if len(n_frames) > SYNTH_MAX_ITEMS:
+        raise ValueError('world_synthesise: at most %d utterances, got %d' % (SYNTH_MAX_ITEMS, len(n_frames)))
+    return frame_start, n_frames, rows
+
+
+def world_synthesise(f0, sp, ap, sample_rate, frame_period=5., seq_len=None, *, offsets=None, noise=None, seed=None, used=None,
+                     out_dtype=torch.float32, workspace_bytes=SYNTH_WORKSPACE_BYTES, want_info=False, out=None, timings=None):
+    """WORLD-style waveform synthesis of a batch (csrc/synth.hip; the definition is include/morgana_hip.h K34): pulse positions from
+    the F0 track by an integer phase scan, per pulse a minimum-phase periodic response and a shaped-noise response from the
+    interpolated ``sp`` and ``ap`` (real FFTs of size ``2 (K - 1)`` in LDS, float64), and an overlap-add in ascending pulse order.
+
+    f0 : one value per frame, 0 where unvoiced (any float dtype; padded (B, T) / (B, T, 1) or packed (rows,) / (rows, 1));
+    sp, ap : power spectrum and aperiodicity in [0, 1], float32 or float64, read in place - padded (B, T, K) with ``seq_len`` (B,)
+    or packed (rows, K) with ``offsets`` (B + 1,).  The lengths must be known to the host (a device tensor is read once).
+    noise : the float64 N(0, 1) track of the packed samples (total_samples,); None draws it with ``synth_noise(total, seed, used)`` -
+    ``seed`` None is ``dropout_seed()``, ``used`` None reserves one draw of the device step counter (two calls then differ).
+    workspace_bytes : the budget of the responses of one pulse range; the output's bits do not depend on it.
+
+    Returns (wav (total_samples,) of ``out_dtype`` - float32 is the float64 waveform rounded once -, sample_offsets (B + 1,) int64 on
+    the device); utterance b is ``wav[sample_offsets[b]:sample_offsets[b + 1]]``, ``floor((n_b - 1) S) + 1`` samples.  ``out``: a
+    buffer of at least total_samples elements to write into.  ``want_info``: also a dict of the pulse arrays (``index``, ``delta``,
+    ``period``, ``voiced``: the padded-by-capacity records, ``region_offsets`` and ``counts`` to cut them with, and ``ranges``).
+    ``timings``: a dict that receives, per kernel name, the (start, end) device events of its launches (scripts/bench_synth.py).
+    The pulse counts are read back once, (B,) integers: this operator ends in host arrays and cannot be captured into a graph.
+    There is no host implementation: without the HIP library this raises."""
+    import numpy as np
+    frame_start, n_frames, rows = _synth_layout(f0, sp, ap, seq_len, offsets)
+    s_per = synth_samples_per_frame(sample_rate, frame_period)
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError('world_synthesise: out_dtype must be torch.float32 or torch.float64, got %s' % (out_dtype,))
+    fft_size = synth_fft_size(2 * (sp.shape[-1] - 1))
+    synth_pulse_ranges(0, fft_size, workspace_bytes)          # the budget's own checks, before anything is launched
+    if sample_rate > 500 * fft_size:
+        raise ValueError('world_synthesise: sample_rate=%r above 500 * fft_size = %d Hz: the 500 Hz unvoiced pulses would lie more than '
+                         'fft_size samples apart' % (sample_rate, 500 * fft_size))
+    counts_n = synth_sample_counts(n_frames, s_per)
+    b = len(n_frames)
+    sample_off = np.zeros(b + 1, np.int64)
+    np.cumsum(counts_n, out=sample_off[1:])
+    region_off = np.zeros(b + 1, np.int64)
+    np.cumsum([n // 2 + 1 for n in counts_n], out=region_off[1:])
+    total, capacity = int(sample_off[-1]), int(region_off[-1])
+    if any(n >= 1 << 31 for n in counts_n):
+        raise ValueError('world_synthesise: an utterance of 2^31 samples or more')
+
+    lib = _lib.load()
+    sp = _require(sp, sp.dtype, 'sp')
+    ap = _require(ap, ap.dtype, 'ap')
+    dev = sp.device
+    f0 = _require(f0, f0.dtype, 'f0').reshape(-1).to(torch.float64)
+    if ap.device != dev or f0.device != dev:
+        raise ValueError('world_synthesise: f0, sp and ap live on different devices')
+    if noise is not None:
+        noise = _require(noise, torch.float64, 'noise')
+        if noise.dim() != 1 or noise.shape[0] < total or noise.device != dev:
+            raise ValueError('world_synthesise: noise %s must be a float64 (at least %d,) tensor on the input\'s device' % (
+                tuple(noise.shape), total))
+    if out is None:
+        out = torch.empty((total,), dtype=out_dtype, device=dev)
+    else:
+        out = _require(out, out_dtype, 'out', contiguous=False)
+        if out.dim() != 1 or out.shape[0] < total or not out.is_contiguous() or out.device != dev:
+            raise ValueError('world_synthesise: out %s must be a contiguous (at least %d,) tensor on the input\'s device' % (
+                tuple(out.shape), total))
+    wav = out[:total]
+    layout = torch.from_numpy(np.concatenate([np.asarray(frame_start, np.int64).reshape(-1), np.asarray(n_frames, np.int64).reshape(-1),
+                                              sample_off, region_off])).to(dev)
+    frame_start_d, n_frames_d = layout[:b], layout[b:2 * b]
+    sample_off_d, region_off_d = layout[2 * b:3 * b + 1], layout[3 * b + 1:]
+    index = torch.zeros((capacity,), dtype=torch.int32, device=dev)
+    delta = torch.zeros((capacity,), dtype=torch.float64, device=dev)
+    period = torch.zeros((capacity,), dtype=torch.int32, device=dev)
+    voiced = torch.zeros((capacity,), dtype=torch.int32, device=dev)
+    counts = torch.zeros((b,), dtype=torch.int64, device=dev)
+    info = {'index': index, 'delta': delta, 'period': period, 'voiced': voiced, 'region_offsets': region_off, 'counts': np.zeros(b, np.int64),
+            'ranges': []}
+    if b == 0 or total == 0:              # an empty batch launches nothing
+        return (wav, sample_off_d, info) if want_info else (wav, sample_off_d)
+
+    def timed(name, rc):
+        _lib.check(rc, name)
+        if timings is not None:
+            end = torch.cuda.Event(enable_timing=True)
+            end.record()
+            timings.setdefault(name, []).append((mark[0], end))
+            mark[0] = torch.cuda.Event(enable_timing=True)
+            mark[0].record()
+
+    mark = [None]
+    if timings is not None:
+        mark[0] = torch.cuda.Event(enable_timing=True)
+        mark[0].record()
+    timed('mg_synth_pulses', lib.mg_synth_pulses(
+        _p(f0), b, _p(frame_start_d), _p(n_frames_d), _p(sample_off_d), _p(region_off_d), s_per, float(sample_rate),
+        4294967296. / float(sample_rate), fft_size, _p(index), _p(delta), _p(period), _p(voiced), _p(counts), _stream()))
+    if noise is None:
+        noise = synth_noise(total, dropout_seed() if seed is None else seed, dropout_draw(dev) if used is None else used)
+    counts_host = counts.cpu().numpy()                        # the one read: (B,) integers
+    pulse_off = np.zeros(b + 1, np.int64)
+    np.cumsum(counts_host, out=pulse_off[1:])
+    pulse_off_d = torch.from_numpy(pulse_off).to(dev)
+    ranges = synth_pulse_ranges(int(pulse_off[-1]), fft_size, workspace_bytes)
+    info['counts'], info['ranges'] = counts_host, ranges
+    y = wav if out_dtype == torch.float64 else torch.empty((total,), dtype=torch.float64, device=dev)
+    y.zero_()
+    table = synth_table_on(fft_size, dev)
+    space = workspace(max(hi - lo for lo, hi in ranges) * fft_size * 8, dev)
+    if timings is not None:
+        mark[0] = torch.cuda.Event(enable_timing=True)
+        mark[0].record()
+    for r, (lo, hi) in enumerate(ranges):
+        timed('mg_synth_responses', lib.mg_synth_responses(
+            _p(sp), int(sp.dtype == torch.float64), _p(ap), int(ap.dtype == torch.float64), b, _p(frame_start_d), _p(n_frames_d),
+            _p(sample_off_d), _p(region_off_d), _p(pulse_off_d), _p(index), _p(delta), _p(period), _p(voiced), _p(noise), _p(table), s_per,
+            fft_size, lo, hi, _p(space), _stream()))
+        timed('mg_synth_overlap_add', lib.mg_synth_overlap_add(
+            _p(space), b, _p(sample_off_d), _p(region_off_d), _p(pulse_off_d), _p(index), fft_size, lo, hi, total, _p(y),
+            int(r == len(ranges) - 1), int(out_dtype == torch.float64), _p(wav), _stream()))
+    return (wav, sample_off_d, info) if want_info else (wav, sample_off_d)
+
+
 # ---------------------------------------------------------------------------------------------- phone-rate first layer
 # MORGANA_PHONE_RATE=0: every product at frame rate (the reference's order of operations).  This is only the DEFAULT of a per-call
 # choice: utils.upsample_to_repetitions(..., phone_rate=) records the choice on the lazy sequence it returns, the layers that consume

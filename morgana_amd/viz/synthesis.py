@@ -7,6 +7,8 @@ LF0 / MCD metrics of ``loss``.  Here the delta streams never leave the device an
 
 ``mlpg_trajectory`` is the same solve as a differentiable layer (device tensors only), for losses taken on the trajectory itself.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -206,17 +208,8 @@ def smooth_f0(lf0, vuv, seq_len=None, window=7, threshold=0.5, dtype=torch.float
     return ops.smooth_f0(lf0, vuv, seq_len=lengths, packed_rows=rows, window=window, threshold=threshold, out_dtype=dtype), offsets
 
 
-def world_features(lf0, vuv, mcep, bap, sample_rate, seq_len, alpha=None, fft_size=None, f0_window=7, as_numpy=True):
-    r"""The three arrays a WORLD-style synthesiser takes for every utterance of a batch, from what an acoustic model generates.
-
-    lf0, vuv : (batch_size, seq_len, 1); mcep : (batch_size, seq_len, order); bap : (batch_size, seq_len, bands); seq_len : (batch_size,)
-    lengths; alpha : None looks the rate up in ``MERLIN_ALPHA`` (Merlin's WORLD values - what the corpus was analysed with is the
-    user's to know - and raises for any other rate); fft_size : None is WORLD's CheapTrick size (``default_fft_size``).
-
-    Returns a list of per-utterance ``(f0 (n,), sp (n, fft_size / 2 + 1), ap (n, fft_size / 2 + 1))``: float64, C-contiguous NumPy
-    arrays (``pyworld.synthesize`` takes exactly these), or with ``as_numpy=False`` views of the packed float64 device tensors.
-    ``seq_len`` is read once and each feature reaches the host in one copy.  The opposite direction - an analyser's ``f0``, ``sp``,
-    ``ap`` to ``lf0``, ``vuv``, ``mcep``, ``bap`` - is ``data.world_parameters``."""
+def _world_packed(lf0, vuv, mcep, bap, sample_rate, seq_len, alpha, fft_size, f0_window):
+    """``world_features`` up to its packed float64 device tensors -> (f0 (rows,), sp (rows, K), ap (rows, K), host lengths)."""
     alpha = default_alpha(sample_rate) if alpha is None else alpha
     fft_size = default_fft_size(sample_rate) if fft_size is None else fft_size
     if isinstance(seq_len, torch.Tensor):
@@ -230,12 +223,119 @@ def world_features(lf0, vuv, mcep, bap, sample_rate, seq_len, alpha=None, fft_si
     frames = f0.shape[0]
     if sp.shape[0] != frames or ap.shape[0] != frames:
         raise ValueError('world_features: the features disagree about the frames (%d, %d, %d)' % (frames, sp.shape[0], ap.shape[0]))
-    f0 = f0.reshape(-1)
+    return f0.reshape(-1), sp, ap, seq_len
+
+
+def world_features(lf0, vuv, mcep, bap, sample_rate, seq_len, alpha=None, fft_size=None, f0_window=7, as_numpy=True):
+    r"""The three arrays a WORLD-style synthesiser takes for every utterance of a batch, from what an acoustic model generates.
+
+    lf0, vuv : (batch_size, seq_len, 1); mcep : (batch_size, seq_len, order); bap : (batch_size, seq_len, bands); seq_len : (batch_size,)
+    lengths; alpha : None looks the rate up in ``MERLIN_ALPHA`` (Merlin's WORLD values - what the corpus was analysed with is the
+    user's to know - and raises for any other rate); fft_size : None is WORLD's CheapTrick size (``default_fft_size``).
+
+    Returns a list of per-utterance ``(f0 (n,), sp (n, fft_size / 2 + 1), ap (n, fft_size / 2 + 1))``: float64, C-contiguous NumPy
+    arrays (``pyworld.synthesize`` takes exactly these), or with ``as_numpy=False`` views of the packed float64 device tensors.
+    ``seq_len`` is read once and each feature reaches the host in one copy.  The opposite direction - an analyser's ``f0``, ``sp``,
+    ``ap`` to ``lf0``, ``vuv``, ``mcep``, ``bap`` - is ``data.world_parameters``."""
+    f0, sp, ap, seq_len = _world_packed(lf0, vuv, mcep, bap, sample_rate, seq_len, alpha, fft_size, f0_window)
     if as_numpy:
         f0, sp, ap = f0.cpu().numpy(), sp.cpu().numpy(), ap.cpu().numpy()
     # each item's length as its feature sees it (clamped to that feature's own T): the three agree where the shapes do
     ends = np.cumsum(np.clip(seq_len, 0, lf0.shape[-2]))
     return [(f0[e - n:e], sp[e - n:e], ap[e - n:e]) for e, n in zip(ends, np.clip(seq_len, 0, lf0.shape[-2]))]
+
+
+def synthesise(f0, sp, ap, sample_rate, frame_period=5.):
+    r"""One utterance's waveform from ``f0 (n,)``, ``sp (n, K)`` and ``ap (n, K)`` - ``pyworld.synthesize``'s signature, on the
+    device (``ops.world_synthesise``, ``csrc/synth.hip``): arrays are uploaded as float64, tensors are read as they are.  Returns the
+    float64 NumPy waveform of ``floor((n - 1) S) + 1`` samples, ``S = sample_rate * frame_period / 1000``.  The noise is drawn anew on
+    every call.  This follows WORLD's ``synthesis.cpp`` as remembered (without the mean removal of the noise segment that its newer
+    versions have); it could not be checked against ``pyworld``.  There is no host implementation: without the HIP library this raises."""
+    device = _device_of(f0, sp, ap)
+    f0, sp, ap = [_upload('synthesise', v, v.dtype if isinstance(v, torch.Tensor) else torch.float64, device) for v in (f0, sp, ap)]
+    if sp.dim() != 2:
+        raise ValueError('synthesise takes one utterance: sp must be (frames, bins), got %s' % (tuple(sp.shape),))
+    if sp.dtype not in (torch.float32, torch.float64):
+        sp = sp.to(torch.float64)
+    if ap.dtype not in (torch.float32, torch.float64):
+        ap = ap.to(torch.float64)
+    dev = sp.device
+    wav, _ = ops.world_synthesise(f0.to(dev), sp, ap.to(dev), sample_rate, frame_period, offsets=[0, sp.shape[0]], out_dtype=torch.float64)
+    return wav.cpu().numpy()
+
+
+def synthesise_batch(lf0, vuv, mcep, bap, sample_rate, seq_len, alpha=None, fft_size=None, f0_window=7, frame_period=5.):
+    r"""What an acoustic model generates, to waveforms: ``world_features(as_numpy=False)`` straight into ``ops.world_synthesise``.  The
+    float64 ``sp`` and ``ap`` never leave the device; only the waveforms cross to the host.  Arguments as ``world_features`` takes
+    them, ``frame_period`` in ms.  Returns the list of per-utterance float32 NumPy waveforms."""
+    if isinstance(seq_len, torch.Tensor):
+        seq_len = seq_len.detach().reshape(-1).cpu().numpy()           # the one read of the lengths
+    seq_len = np.clip(np.asarray(seq_len, dtype=np.int64).reshape(-1), 0, lf0.shape[-2])
+    f0, sp, ap, _ = _world_packed(lf0, vuv, mcep, bap, sample_rate, seq_len, alpha, fft_size, f0_window)
+    offsets = np.concatenate([[0], np.cumsum(seq_len)])
+    wav, _ = ops.world_synthesise(f0, sp, ap, sample_rate, frame_period, offsets=offsets.tolist())
+    wav = wav.cpu().numpy()                                          # the one copy out
+    ends = np.cumsum(ops.synth_sample_counts(seq_len, ops.synth_samples_per_frame(sample_rate, frame_period)))
+    return [wav[e - n:e] for e, n in zip(ends, np.diff(np.concatenate([[0], ends])))]
+
+
+def synthesise_files(ids, in_dir, out_dir, sample_rate, frame_period=5., alpha=None, fft_size=None, f0_window=7, device='cuda:0',
+                     max_batch_bytes=256 << 20, overwrite=False):
+    r"""Waveforms for a corpus of generated or analysed features (``scripts/synthesise.py``).  For every id of ``ids`` reads either
+    ``in_dir/{f0,sp,ap}/{id}.npy`` (an analyser's arrays, taken when ``in_dir/sp`` exists) or ``in_dir/{lf0,vuv,mcep,bap}/{id}.npy``
+    (what ``analysis_for_valid_batch`` writes) and writes ``out_dir/{id}.wav`` through ``viz.io.save_wav``.  Utterances are batched
+    up to ``max_batch_bytes`` of float64 spectra on the device.  An output that exists is a FileExistsError before anything is read,
+    unless ``overwrite``.  Returns the number of samples written."""
+    from . import io
+    ids = list(ids)
+    targets = [os.path.join(out_dir, name + '.wav') for name in ids]
+    existing = [t for t in targets if os.path.exists(t)]
+    if existing and not overwrite:
+        raise FileExistsError('%d of %d outputs exist (the first: %s): pass overwrite to replace them' % (len(existing), len(ids), existing[0]))
+    analysed = os.path.isdir(os.path.join(in_dir, 'sp'))
+    kinds = ('f0', 'sp', 'ap') if analysed else ('lf0', 'vuv', 'mcep', 'bap')
+    if fft_size is None and not analysed:
+        fft_size = default_fft_size(sample_rate)
+    os.makedirs(out_dir, exist_ok=True)
+    written, batch, batch_bytes = 0, [], 0
+
+    def flush():
+        nonlocal written, batch, batch_bytes
+        if not batch:
+            return
+        lengths = [len(item[1][0]) for item in batch]
+        if analysed:
+            f0 = torch.from_numpy(np.concatenate([np.asarray(item[1][0], np.float64).reshape(-1) for item in batch])).to(device)
+            sp, ap = [torch.from_numpy(np.concatenate([item[1][i] for item in batch], axis=0)).to(device) for i in (1, 2)]
+            wav, _ = ops.world_synthesise(f0, sp, ap, sample_rate, frame_period, offsets=np.concatenate([[0], np.cumsum(lengths)]).tolist())
+            wav = wav.cpu().numpy()
+            ends = np.cumsum(ops.synth_sample_counts(lengths, ops.synth_samples_per_frame(sample_rate, frame_period)))
+            waves = [wav[lo:hi] for lo, hi in zip(np.concatenate([[0], ends[:-1]]), ends)]
+        else:
+            padded = []
+            for i in range(4):
+                width = batch[0][1][i].reshape(lengths[0], -1).shape[1]
+                x = np.zeros((len(batch), max(lengths), width), np.float32)
+                for b, item in enumerate(batch):
+                    x[b, :lengths[b]] = item[1][i].reshape(lengths[b], -1)
+                padded.append(torch.from_numpy(x).to(device))
+            waves = synthesise_batch(*padded, sample_rate, lengths, alpha=alpha, fft_size=fft_size, f0_window=f0_window,
+                                     frame_period=frame_period)
+        for (target, _), wav in zip(batch, waves):
+            io.save_wav(target, wav, sample_rate)
+            written += len(wav)
+        batch, batch_bytes = [], 0
+
+    for name, target in zip(ids, targets):
+        arrays = [np.load(os.path.join(in_dir, kind, name + '.npy')) for kind in kinds]
+        bins = arrays[1].shape[-1] if analysed else fft_size // 2 + 1
+        cost = 2 * 8 * len(arrays[0]) * bins
+        if batch and (batch_bytes + cost > max_batch_bytes or (analysed and arrays[1].shape[-1] != batch[0][1][1].shape[-1])):
+            flush()
+        batch.append((target, arrays))
+        batch_bytes += cost
+    flush()
+    return written
 
 
 def mlpg_trajectory(means, variances, windows=None, padding_size=0, seq_len=None, variance_grad=False):
