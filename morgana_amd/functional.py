@@ -188,10 +188,10 @@ def _has_hooks(p):
 
 
 def _linear_grads_direct(w_param, b_param, g, a_in, rows, m, n, k):
-    """dW | db of one bf16 Linear into the optimiser (slabs deferred to its update kernel or reduced into .grad: _wgrad_into)."""
+    """dW | db of one bf16 Linear into the optimiser (slabs deferred to its update kernel or reduced into .grad: _GradSink.wgrad)."""
     opt = getattr(w_param, '_mg_optimizer', None)
-    mode = 'defer' if (opt is not None and opt.defers_slabs() and _grads_adjacent(w_param, b_param)) else 'direct'
-    _wgrad_into(mode, opt, w_param, b_param, g, a_in, rows, m, n, k)
+    sink = _DeferSink(opt) if (opt is not None and opt.defers_slabs() and _grads_adjacent(w_param, b_param)) else _DirectSink()
+    sink.wgrad(w_param, b_param, g, a_in, rows, m, n, k)
 
 
 class UpsampleFn(torch.autograd.Function):
@@ -824,7 +824,7 @@ class F0TailRowsF32Fn(torch.autograd.Function):
         dz2, flat = ctx.saved_tensors
         unit = _is_unit_grad(grad_loss)
         n_g = ops.F0_TAIL_F32_GRADS
-        grads = _deliver_param_grads(ctx.params, flat[:n_g], [0, 32 * 128, 32 * 128 + 32, 32 * 128 + 64], None if unit else grad_loss)
+        grads = _deliver_param_grads(ctx.params, flat[:n_g], _param_offsets(ctx.params)[0], None if unit else grad_loss)
         return (dz2 if unit else dz2 * grad_loss, None, None, None) + tuple(grads)
 
 
@@ -859,14 +859,7 @@ def _deliver_param_grads(params, flat, offsets, grad_loss=None):
     Otherwise ordinary per-parameter gradient tensors are returned.
     """
     live = [p for p in params if p is not None]
-    direct = all(getattr(p, '_mg_direct_grad', False) and p.grad is not None and p.grad.is_contiguous() for p in live)
-    if direct:
-        base = live[0].grad.data_ptr()
-        for p, off in zip(live, offsets):
-            if p.grad.data_ptr() != base + 4 * off or p.grad.dtype != torch.float32:
-                direct = False
-                break
-    if direct:
+    if _in_flat_grad(live):
         seg = live[0].grad.reshape(-1).as_strided((flat.numel(),), (1,))
         if grad_loss is None:
             seg.add_(flat)
@@ -884,44 +877,17 @@ def _deliver_param_grads(params, flat, offsets, grad_loss=None):
     return out
 
 
-def _deliver_early(params, flat, offsets, grad_loss):
-    """With an early-gradients hook installed and the optimiser's flat buffer as target: deliver everything but the first layer's
-    (weight, bias) now and fire the hook.  Returns True if it did (``_deliver_rest`` then hands over the first layer only)."""
-    if _EARLY_GRADS_HOOK is None or len(params) <= 2 or any(p is None for p in params):
-        return False
-    tail = _deliver_param_grads(params[2:], flat[offsets[2]:], [o - offsets[2] for o in offsets[2:]], grad_loss)
-    if any(t is not None for t in tail):
-        raise RuntimeError('early gradient exchange needs the parameters in morgana_amd.optim.Adam\'s flat buffer')
-    _EARLY_GRADS_HOOK(params)
-    return True
-
-
-def _deliver_rest(params, flat, offsets, grad_loss, early):
-    if not early:
-        return _deliver_param_grads(params, flat, offsets, grad_loss)
-    head = _deliver_param_grads(params[:2], flat[:offsets[2]], offsets[:2], grad_loss)
-    return list(head) + [None] * (len(params) - 2)
-
-
-def _grad_mode(params, grad_loss):
-    """How a backward pass hands over its parameter gradients: 'defer' (split-M slabs left for the optimiser's update kernel),
-    'direct' (accumulated straight into the optimiser's flat gradient) or 'temp' (ordinary tensors for autograd).  The first two need
-    the parameters' .grad to be consecutive views of morgana_amd.optim.Adam's flat buffer and the incoming loss gradient to be the
-    cached unit of ``backward`` (no scaling to apply).  Returns (mode, optimiser)."""
-    if any(p is None for p in params) or grad_loss is None or not any(grad_loss.data_ptr() == one.data_ptr() for one in _ONES.values()):
-        return 'temp', None
+def _in_flat_grad(params):
+    """Are the parameters' .grad consecutive fp32 views, in this order, of morgana_amd.optim.Adam's flat gradient (``_mg_direct_grad``)?"""
     if not all(getattr(p, '_mg_direct_grad', False) and p.grad is not None and p.grad.is_contiguous() and p.grad.dtype == torch.float32
                for p in params):
-        return 'temp', None
+        return False
     base, off = params[0].grad.data_ptr(), 0
     for p in params:
         if p.grad.data_ptr() != base + 4 * off:
-            return 'temp', None
+            return False
         off += p.numel()
-    opt = getattr(params[0], '_mg_optimizer', None)
-    if opt is not None and opt.defers_slabs():
-        return 'defer', opt
-    return 'direct', opt
+    return True
 
 
 def _grads_adjacent(w_param, b_param):
@@ -930,29 +896,194 @@ def _grads_adjacent(w_param, b_param):
             b_param.grad.data_ptr() == w_param.grad.data_ptr() + 4 * w_param.numel())
 
 
-def _slabs_into(mode, opt, w_param, b_param, slab, n_slabs, stride, n, k):
-    """Split-M slabs of one layer's dW | db to the optimiser: left for the update kernel to sum ('defer'), or summed now into .grad
-    (accumulating) by one reduce launch - a data-parallel rank needs the finished gradient for its all-reduce."""
-    w_param._mg_slab_buf = slab                          # one buffer per layer, reused every step (and by every graph replay)
-    if mode == 'defer':
-        opt.defer_slabs(w_param, n * k + n, slab, n_slabs, stride)
-    else:
-        ops.slab_reduce(slab, n_slabs, stride, n * k + n, w_param.grad.reshape(-1).as_strided((n * k + n,), (1,)), accumulate=True)
+def _slab_buf(param, keep=None, fused=False):
+    """The split-M slab buffer that a layer's weight-gradient launch writes, kept on a parameter of the layer: one buffer per layer,
+    reused every step (and by every graph replay).  ``keep``: the buffer the launch returned, stored for the next step; ``fused``: the
+    buffer of the fused first-layer backward (another size).  Returns the stored buffer, or None."""
+    key = '_mg_fused_slab_buf' if fused else '_mg_slab_buf'
+    if keep is not None:
+        setattr(param, key, keep)
+    return getattr(param, key, None)
 
 
-def _wgrad_into(mode, opt, w_param, b_param, g, a_in, rows, m, n, k):
-    """dW, db of one layer into the optimiser: as slabs where the shape has them (_slabs_into), else reduced into .grad (accumulating)
-    by the weight-gradient entry point's own two reduce launches."""
-    if ops.wgrad_slabs_ok(m, n, k, a_in.shape[1], g.shape[1]) and (mode == 'defer' or _grads_adjacent(w_param, b_param)):
-        slab, n_slabs, stride = ops.linear_wgrad_slabs_bf16(g, a_in, rows, m, n, k, slab=getattr(w_param, '_mg_slab_buf', None))
-        _slabs_into(mode, opt, w_param, b_param, slab, n_slabs, stride, n, k)
-    elif ops.wgrad_wide_ok(m, n, k, a_in.shape[1], g.shape[1]) and _grads_adjacent(w_param, b_param):
-        # frame-rate row counts: 192-256 slabs, which a reduce launch of its own sums as fast as the update kernel would - one launch
-        # for dW | db instead of the entry point's two
-        slab, n_slabs, stride = ops.linear_wgrad_slabs_bf16(g, a_in, rows, m, n, k, slab=getattr(w_param, '_mg_slab_buf', None))
-        _slabs_into('direct', opt, w_param, b_param, slab, n_slabs, stride, n, k)
-    else:
-        ops.linear_wgrad_bf16(g, a_in, rows, m, n, k, out_w=w_param.grad, out_b=b_param.grad, accumulate=True)
+def _grad_sink(params, grad_loss, scale, flat=None, offsets=None):
+    """How one backward pass of a fused stack node hands over its parameter gradients, chosen once: 'defer' (split-M slabs
+    left for the optimiser's update kernel), 'direct' (summed straight into the optimiser's flat gradient) or 'temp' (ordinary tensors
+    for autograd; ``scale`` - None = 1 - and the node's own ``flat`` buffer and ``offsets``, where its forward made one, serve it alone).
+    The first two need the parameters' .grad to be consecutive views of morgana_amd.optim.Adam's flat buffer and the incoming loss
+    gradient to be the cached unit of ``backward`` (no scaling to apply).  Neither ``requires_grad`` nor hooks are looked at here."""
+    if any(p is None for p in params) or not _is_unit_grad(grad_loss) or not _in_flat_grad(params):
+        return _TempSink(params, scale, flat, offsets)
+    opt = getattr(params[0], '_mg_optimizer', None)
+    return _DeferSink(opt) if opt is not None and opt.defers_slabs() else _DirectSink()
+
+
+class _DirectSink(object):
+    """Where a backward pass hands its parameter gradients over.  Parameters are named by their tensors; a run of
+    gradients by its first parameter and a count of floats.  This one is 'direct': every hand-over is summed into the optimiser's flat
+    ``.grad`` at once (a data-parallel rank needs the finished gradient for its all-reduce), and autograd gets None."""
+    final = True           # what has been handed over is already in .grad (F0StackX3Fn fires the early hook only then)
+    grid = True            # the phone-rate pair grid (weight gradient + dgrad in one launch) may be used
+    slab_buf = staticmethod(_slab_buf)
+    adjacent = staticmethod(_grads_adjacent)      # may dW | db leave as ONE run of slabs?  Where b.grad lies right behind W.grad
+
+    def into(self, w_param, b_param, n, k):
+        """Destinations of a launch that reduces dW, db itself (ops.linear_wgrad_bf16, ops.linear_bwd_fused_bf16)."""
+        return dict(out_w=w_param.grad, out_b=b_param.grad, accumulate=True)
+
+    def slabs(self, first, count, slab, n_slabs, stride):
+        """Elements [offset of ``first``, + count) of the flat gradient are the ordered sum of ``n_slabs`` slabs, ``stride`` floats apart."""
+        ops.slab_reduce(slab, n_slabs, stride, count, first.grad.reshape(-1).as_strided((count,), (1,)), accumulate=True)
+
+    def wgrad(self, w_param, b_param, g, a_in, rows, m, n, k):
+        """One layer's dW | db.  On the wide-tile kernel (any row count from 4096 up): its slabs, summed by ONE reduce launch for
+        dW | db; else the weight-gradient entry point's own two reduce launches."""
+        if ops.wgrad_wide_ok(m, n, k, a_in.shape[1], g.shape[1]) and _grads_adjacent(w_param, b_param):
+            slab, n_slabs, stride = ops.linear_wgrad_slabs_bf16(g, a_in, rows, m, n, k, slab=_slab_buf(w_param))
+            _DirectSink.slabs(self, w_param, n * k + n, _slab_buf(w_param, keep=slab), n_slabs, stride)
+        else:
+            ops.linear_wgrad_bf16(g, a_in, rows, m, n, k, **self.into(w_param, b_param, n, k))
+
+    def fused_first(self, w_param, b_param, g, wt1, h0, a0, rows, m, n0, k0):
+        """The first layer's dW | db straight from the second layer's dZ: dZ_0 = (dZ_1 W_1) * H_0 (1 - H_0) stays on chip."""
+        ops.linear_bwd_fused_bf16(g, wt1, h0, a0, rows, m, n0, k0, **self.into(w_param, b_param, n0, k0))
+
+    def fused2(self, params, g, wt1, h0, a0, rows, m, n0, k0):
+        """The first two layers' dW | db from one launch (ops.linear_bwd_fused2_slabs_bf16: the kernel stages dZ2 and H1 anyway, and the
+        stand-alone second-layer launch that re-read H1 from HBM goes), then the ordered sums: the same bits in every mode."""
+        slab, n_slabs, first, second = ops.linear_bwd_fused2_slabs_bf16(g, wt1, h0, a0, rows, m, n0, k0,
+                                                                        slab=self.slab_buf(params[0], fused=True))
+        self.slab_buf(params[0], keep=slab, fused=True)
+        floats = slab.view(torch.float32)
+        for p, (off, stride, count) in ((params[0], first), (params[2], second)):
+            self.slabs(p, count, floats[off:], n_slabs, stride)
+
+    def deferred_tail(self, tail, first, grid=False, alone=False):
+        """What the forward of a step captured whole left undone (DEFER_TAIL).  ``grid``: the caller's next launch is the pair grid,
+        which can carry it as riders; ``alone``: the update launch may take it although nothing else could (F0StackX3Fn).  Returns what
+        rides behind the pair grid.  Here: all of it where there is a grid, else it is finished now, as its own launch."""
+        if tail is None or grid:
+            return tail
+        ops.finish_deferred_tail(tail)
+        return None
+
+    def tail_grads(self, first, count, summed):
+        """The fused tail's gradients: ONE block, already summed (unless ``deferred_tail`` left its slabs to the update launch)."""
+        first.grad.reshape(-1).as_strided((count,), (1,)).add_(summed)
+
+    def early(self, params):
+        """Everything but the first layer's gradient is final."""
+        if _EARLY_GRADS_HOOK is not None:
+            _EARLY_GRADS_HOOK(params)
+
+    def grads(self, params):
+        """What ``backward`` returns for the parameters."""
+        return [None] * len(params)
+
+
+class _DeferSink(_DirectSink):
+    """'defer' (one rank, fused loop): split-M slabs stay where the launches wrote them and optim.Adam's update kernel sums them
+    (``defer_slabs``), so the backward pass has no reduce launch.  What has no slabs goes the 'direct' way."""
+    final = False
+
+    def __init__(self, opt):
+        self.opt, self._tail_slabs = opt, None
+
+    adjacent = staticmethod(lambda w_param, b_param: True)      # the update kernel's plan addresses the flat gradient by offset
+
+    def slabs(self, first, count, slab, n_slabs, stride):
+        self.opt.defer_slabs(first, count, slab, n_slabs, stride)
+
+    def wgrad(self, w_param, b_param, g, a_in, rows, m, n, k):
+        if ops.wgrad_slabs_ok(m, n, k, a_in.shape[1], g.shape[1]):
+            slab, n_slabs, stride = ops.linear_wgrad_slabs_bf16(g, a_in, rows, m, n, k, slab=_slab_buf(w_param))
+            self.slabs(w_param, n * k + n, _slab_buf(w_param, keep=slab), n_slabs, stride)
+        else:
+            # frame-rate row counts: 192-256 slabs, which a reduce launch of its own sums as fast as the update kernel would
+            _DirectSink.wgrad(self, w_param, b_param, g, a_in, rows, m, n, k)
+
+    def fused_first(self, w_param, b_param, g, wt1, h0, a0, rows, m, n0, k0):
+        slab, n_slabs, stride = ops.linear_bwd_fused_slabs_bf16(g, wt1, h0, a0, rows, m, n0, k0, slab=_slab_buf(w_param, fused=True))
+        self.slabs(w_param, n0 * k0 + n0, _slab_buf(w_param, keep=slab, fused=True), n_slabs, stride)
+
+    def deferred_tail(self, tail, first, grid=False, alone=False):
+        """The update kernel sums the tail's slabs itself (one more source of its plan) and its launch's first blocks repeat the
+        prediction and form the loss (optim.Adam.defer_tail: mg_adam_tail) - always for the frame-rate tail (only a reduce launch was
+        left out), else where MORGANA_TAIL_RIDERS says 'adam' (the default; measured against riders).  With any other value the two
+        jobs ride behind the pair grid as ``loss_only`` riders - the slabs still go to the update kernel - or are finished now."""
+        if tail is None:
+            return None
+        to_update = tail.get('rows') is None or ((grid or alone) and os.environ.get('MORGANA_TAIL_RIDERS', 'adam') == 'adam')
+        if not (to_update or grid):
+            ops.finish_deferred_tail(tail)
+            return None
+        self._tail_slabs = (tail['ws'].view(torch.float32), tail['n_slabs'], tail['stride'])
+        if to_update:
+            self.opt.defer_tail(first, tail)
+            return None
+        return dict(tail, loss_only=True)
+
+    def tail_grads(self, first, count, summed):
+        self.slabs(first, count, *(self._tail_slabs or (summed, 1, count)))
+
+
+class _TempSink(_DirectSink):
+    """'temp': ordinary tensors for autograd (``torch.autograd.grad``, a scaled loss, parameters that are not views of optim.Adam's flat
+    buffer).  The gradients are gathered in one flat buffer in parameter order - the node's own, where its forward made one - and
+    ``_deliver_param_grads`` turns it into what autograd gets: one fused add into the optimiser's buffer where the parameters do
+    live there, else a tensor each.  Slab sums wait until the node is done and run in parameter order.  The plain launches (weight
+    gradient, dgrad) are kept where the other two use the pair grid: merging them is a change of launches."""
+    final = grid = False
+
+    def __init__(self, params, scale, flat=None, offsets=None):
+        if flat is None:
+            offsets, total = _param_offsets(params)
+            flat = torch.empty((total,), dtype=torch.float32, device=params[0].device)
+        self.scale, self.flat, self.offsets = scale, flat, offsets
+        self._at = dict((id(p), off) for p, off in zip(params, offsets))
+        self._queue, self._early = [], False
+
+    slab_buf = staticmethod(lambda param, keep=None, fused=False: None)      # a buffer per call: nothing here outlives the pass
+    adjacent = staticmethod(lambda w_param, b_param: True)                  # by construction of the flat buffer
+
+    def _slot(self, param, count):
+        return self.flat[self._at[id(param)]:self._at[id(param)] + count]
+
+    def into(self, w_param, b_param, n, k):
+        return dict(out_w=self._slot(w_param, n * k).view(n, k), out_b=self._slot(b_param, n))
+
+    def slabs(self, first, count, slab, n_slabs, stride):
+        self._queue.append((self._at[id(first)], count, slab, n_slabs, stride))
+
+    def wgrad(self, w_param, b_param, g, a_in, rows, m, n, k):
+        ops.linear_wgrad_bf16(g, a_in, rows, m, n, k, **self.into(w_param, b_param, n, k))
+
+    def tail_grads(self, first, count, summed):
+        if summed.data_ptr() != self._slot(first, count).data_ptr():      # (LinearStackMSEFn's forward wrote them in place)
+            self._queue.append((self._at[id(first)], count, summed, 0, 0))
+
+    def early(self, params):
+        """With a hook installed: deliver everything but the first layer's (weight, bias) now - which needs the optimiser's flat
+        buffer as target - and fire it; ``grads`` then hands over the first layer only."""
+        offsets = self.offsets
+        if _EARLY_GRADS_HOOK is None or len(params) <= 2 or any(p is None for p in params):
+            return
+        rest = _deliver_param_grads(params[2:], self.flat[offsets[2]:], [o - offsets[2] for o in offsets[2:]], self.scale)
+        if any(t is not None for t in rest):
+            raise RuntimeError('early gradient exchange needs the parameters in morgana_amd.optim.Adam\'s flat buffer')
+        _EARLY_GRADS_HOOK(params)
+        self._early = True
+
+    def grads(self, params):
+        for off, count, src, n_slabs, stride in sorted(self._queue, key=lambda q: q[0]):
+            if n_slabs:
+                ops.slab_reduce(src, n_slabs, stride, count, self.flat[off:off + count])
+            else:
+                self.flat[off:off + count].copy_(src)
+        if not self._early:
+            return _deliver_param_grads(params, self.flat, self.offsets, self.scale)
+        head = _deliver_param_grads(params[:2], self.flat[:self.offsets[2]], self.offsets[:2], self.scale)
+        return list(head) + [None] * (len(params) - 2)
 
 
 class LinearStackMSESpec(typing.NamedTuple):
@@ -1096,173 +1227,70 @@ class LinearStackMSEFn(torch.autograd.Function):
         lead, m = ctx.lead, ctx.m
         hidden = list(saved[4:4 + lead - 1])                  # outputs of layers 0 .. lead-2
         w_t = [None] + list(saved[4 + lead - 1:])             # transposed bf16 weights of layers 1 .. lead-1
-        def grad_slots(i):
-            n_, k_ = ctx.dims[i]
-            return (flat[ctx.offsets[2 * i]:ctx.offsets[2 * i] + n_ * k_].view(n_, k_),
-                    flat[ctx.offsets[2 * i + 1]:ctx.offsets[2 * i + 1] + n_])
-
-        no_grads = (None,) * (5 + len(ctx.params))            # spec, x2d, rows, target, seq_len | the parameters (delivered directly)
-        mode, opt = _grad_mode(ctx.params, grad_loss)
+        params, acts, dims = ctx.params, ctx.acts, ctx.dims
+        # where the gradients go: the optimiser's flat buffer, its update kernel's plan, or this node's own flat buffer
+        sink = _grad_sink(params, grad_loss, grad_loss, flat[:flat.numel() - 1], ctx.offsets)
         tail = getattr(ctx, 'deferred_tail', None)            # forward left the repeated prediction and the tail's slab sum to us
         ctx.deferred_tail = None
-        if mode != 'temp':
-            # The gradients go where the optimiser reads them, without a temporary and an add in between: either straight into its flat
-            # buffer (the reduce launches accumulate there) or - one rank, fused loop - as split-M slabs the update kernel sums itself.
-            params = ctx.params
-            tail_off = ctx.offsets[2 * lead]
-            tail_count = flat.numel() - 1 - tail_off
-            m_rows = hidden[0].shape[0] if ctx.phone_rate else m
-            r0 = None if ctx.phone_rate else rows
-            top = lead - 1                                            # the 128-wide layer: its dZ came out of the fused tail
-            n, k = ctx.dims[top]
-            g_below = None
-            pair = (ctx.phone_rate and top > 0 and ctx.acts[top - 1] == ops.ACT_SIGMOID and
-                    ops.wgrad_slabs_ok(m_rows, n, k, hidden[top - 1].shape[1], g.shape[1]) and
-                    (mode == 'defer' or _grads_adjacent(params[2 * top], params[2 * top + 1])))
-            tail_slabs = None
-            if tail is not None and tail.get('rows') is None:         # frame-rate tail: only its reduce launch was left out
-                if mode == 'defer':
-                    tail_slabs = (tail['ws'].view(torch.float32), tail['n_slabs'], tail['stride'])
-                    opt.defer_tail(params[2 * lead], tail)            # the update launch forms the loss
-                else:
-                    ops.finish_deferred_tail(tail)
-                tail = None
-            if tail is not None and not pair:                         # no launch to ride in: the two jobs run now, as their own launch
-                ops.finish_deferred_tail(tail)
-                tail = None
-
-            def hand_over_tail_grads():
-                if tail_slabs is not None:                            # the update kernel sums the tail's slabs itself
-                    opt.defer_slabs(params[2 * lead], tail_count, tail_slabs[0], tail_slabs[1], tail_slabs[2])
-                elif mode == 'defer':
-                    opt.defer_slabs(params[2 * lead], tail_count, flat[tail_off:tail_off + tail_count], 1, tail_count)
-                else:
-                    params[2 * lead].grad.reshape(-1).as_strided((tail_count,), (1,)).add_(flat[tail_off:tail_off + tail_count])
-            # Frame rate, Linear + Sigmoid -> Linear(. -> 128) at the bottom of the stack: the second layer's weight gradient rides in
-            # the fused backward of the first (ops.linear_bwd_fused2_slabs_bf16: the kernel stages dZ2 and H1 anyway), and the
-            # stand-alone launch that re-read H1 from HBM goes.  Not beside an early gradient exchange: that one promises the second
-            # layer's gradient final BEFORE the fused kernel starts.
-            fuse2 = (not ctx.phone_rate and top == 1 and rows is not None and ctx.acts[0] == ops.ACT_SIGMOID and _EARLY_GRADS_HOOK is None and
-                     os.environ.get('MORGANA_FUSE_WGRAD2', '1') != '0' and ops.can_fuse_bwd(m, n, k, ctx.dims[0][1], a0.shape[1]) and
-                     (mode == 'defer' or (_grads_adjacent(params[0], params[1]) and _grads_adjacent(params[2], params[3]))))
-            if fuse2:
-                n0_, k0_ = ctx.dims[0]
-                slab, n_slabs, (off1, st1, cnt1), (off2, st2, cnt2) = ops.linear_bwd_fused2_slabs_bf16(
-                    g, w_t[1], hidden[0], a0, rows, m, n0_, k0_, slab=getattr(params[0], '_mg_fused_slab_buf', None))
-                params[0]._mg_fused_slab_buf = slab
-                floats = slab.view(torch.float32)
-                for first, off, st, cnt in ((params[0], off1, st1, cnt1), (params[2], off2, st2, cnt2)):
-                    if mode == 'defer':                               # the update kernel sums the slabs
-                        opt.defer_slabs(first, cnt, floats[off:], n_slabs, st)
-                    else:
-                        ops.slab_reduce(floats[off:], n_slabs, st, cnt, first.grad.reshape(-1).as_strided((cnt,), (1,)), accumulate=True)
-                hand_over_tail_grads()
-                return no_grads
-            if pair and tail is not None and mode == 'defer':
-                # the update kernel sums the tail's slabs itself (one more source of its plan), and its launch's first blocks repeat
-                # the prediction and form the loss (optim.Adam.defer_tail: mg_adam_tail) - measured against riders at the end of the
-                # pair grid below, which is where these two jobs go when the gradients must be complete before the update (a
-                # data-parallel rank: mode 'direct')
-                tail_slabs = (tail['ws'].view(torch.float32), tail['n_slabs'], tail['stride'])
-                if os.environ.get('MORGANA_TAIL_RIDERS', 'adam') == 'adam':
-                    opt.defer_tail(params[2 * lead], tail)
-                    tail = None
-                else:
-                    tail = dict(tail, loss_only=True)
-            if pair:
-                # this layer's weight gradient and the dgrad + sigmoid backward below it are independent and each fills part of the
-                # chip: one grid for both (mg_linear_wgrad_dgrad_bf16)
-                w_param = params[2 * top]
-                slab, n_slabs, stride, g_below = ops.linear_wgrad_dgrad_bf16(g, hidden[top - 1], m_rows, n, k, w_t[top],
-                                                                             slab=getattr(w_param, '_mg_slab_buf', None), tail=tail)
-                tail = None
-                _slabs_into(mode, opt, w_param, params[2 * top + 1], slab, n_slabs, stride, n, k)
-            else:
-                _wgrad_into(mode, opt, params[2 * top], params[2 * top + 1], g, hidden[top - 1] if top > 0 else a0,
-                            None if top > 0 else r0, m_rows, n, k)
-            hand_over_tail_grads()
-            for i in range(top, 0, -1):
-                n, k = ctx.dims[i]
-                if i == 1 and _EARLY_GRADS_HOOK is not None:
-                    _EARLY_GRADS_HOOK(params)                         # everything but the first layer's gradient is final
-                if (not ctx.phone_rate and i == 1 and ctx.acts[0] == ops.ACT_SIGMOID and
-                        ops.can_fuse_bwd(m, n, k, ctx.dims[0][1], a0.shape[1])):
-                    n0_, k0_ = ctx.dims[0]
-                    if mode == 'defer':                               # its split-M slabs stay for the update kernel to sum
-                        slab, n_slabs, stride = ops.linear_bwd_fused_slabs_bf16(g, w_t[1], hidden[0], a0, rows, m, n0_, k0_,
-                                                                                slab=getattr(params[0], '_mg_fused_slab_buf', None))
-                        params[0]._mg_fused_slab_buf = slab
-                        opt.defer_slabs(params[0], n0_ * k0_ + n0_, slab, n_slabs, stride)
-                    else:
-                        ops.linear_bwd_fused_bf16(g, w_t[1], hidden[0], a0, rows, m, n0_, k0_, out_w=params[0].grad, out_b=params[1].grad,
-                                                  accumulate=True)
-                    break
-                if i == top and g_below is not None:
-                    g = g_below
-                else:
-                    h = hidden[i - 1] if ctx.acts[i - 1] != ops.ACT_NONE else None
-                    g = ops.linear_dgrad_bf16(g, m_rows, n, w_t[i], k, h, act=ctx.acts[i - 1])
-                n_, k_ = ctx.dims[i - 1]
-                _wgrad_into(mode, opt, params[2 * (i - 1)], params[2 * (i - 1) + 1], g, hidden[i - 2] if i > 1 else a0,
-                            None if i > 1 else r0, m_rows, n_, k_)
-            return no_grads
-
-        if tail is not None:                                          # gradients as tensors for autograd: nothing to ride in
-            ops.finish_deferred_tail(tail)
-            tail = None
-        if ctx.phone_rate:
-            # g is dL/dZ_1 per TABLE row already (the tail ran on phone rows with the frames' summed loss weights), so the remaining
-            # backward is the ordinary chain on R + extra rows:  dW_1 = g^T H_table,  dZ_0 = (g W_1) * H (1 - H),  dW_0 = dZ_0^T X
-            (n1, k1), (n0, k0) = ctx.dims[1], ctx.dims[0]
-            table = hidden[0]
-            ow, ob = grad_slots(1)
-            ops.linear_wgrad_bf16(g, table, None, table.shape[0], n1, k1, out_w=ow, out_b=ob)
-            early = _deliver_early(ctx.params, flat[:flat.numel() - 1], ctx.offsets, grad_loss)
-            dz0 = ops.linear_dgrad_bf16(g, table.shape[0], n1, w_t[1], k1, table)
-            ow, ob = grad_slots(0)
-            ops.linear_wgrad_bf16(dz0, a0, None, table.shape[0], n0, k0, out_w=ow, out_b=ob)
-            grads = _deliver_rest(ctx.params, flat[:flat.numel() - 1], ctx.offsets, grad_loss, early)
-            return no_grads[:5] + tuple(grads)
-        early = False
-        if (lead == 2 and rows is not None and ctx.acts[0] == ops.ACT_SIGMOID and _EARLY_GRADS_HOOK is None and
-                os.environ.get('MORGANA_FUSE_WGRAD2', '1') != '0' and ops.can_fuse_bwd(m, ctx.dims[1][0], ctx.dims[1][1], ctx.dims[0][1], a0.shape[1])):
-            # the same one-launch backward as the optimiser-bound modes above (both layers' slabs, then the ordered reduces): whichever
-            # way the gradients are handed over, they are the same bits
-            n0_, k0_ = ctx.dims[0]
-            slab, n_slabs, (off1, st1, cnt1), (off2, st2, cnt2) = ops.linear_bwd_fused2_slabs_bf16(g, w_t[1], hidden[0], a0, rows, m, n0_, k0_)
-            floats = slab.view(torch.float32)
-            ops.slab_reduce(floats[off1:], n_slabs, st1, cnt1, flat[ctx.offsets[0]:ctx.offsets[0] + cnt1])
-            ops.slab_reduce(floats[off2:], n_slabs, st2, cnt2, flat[ctx.offsets[2]:ctx.offsets[2] + cnt2])
-            grads = _deliver_rest(ctx.params, flat[:flat.numel() - 1], ctx.offsets, grad_loss, False)
-            return no_grads[:5] + tuple(grads)
-        for i in range(lead - 1, -1, -1):
-            n, k = ctx.dims[i]
-            a_in, r = (a0, rows) if i == 0 else (hidden[i - 1], None)
-            ow, ob = grad_slots(i)
-            ops.linear_wgrad_bf16(g, a_in, r, m, n, k, out_w=ow, out_b=ob)
+        tail_first, tail_off = params[2 * lead], ctx.offsets[2 * lead]
+        tail_grads = flat[tail_off:flat.numel() - 1]          # what the fused tail summed for its own two layers
+        # At phone rate g is dL/dZ per TABLE row already (the tail ran on phone rows with the frames' summed loss weights), so the
+        # remaining backward is the ordinary chain on R + extra rows
+        m_rows, r0 = (hidden[0].shape[0], None) if ctx.phone_rate else (m, rows)
+        top = lead - 1                                        # the 128-wide layer: its dZ came out of the fused tail
+        n, k = dims[top]
+        w_top, b_top = params[2 * top], params[2 * top + 1]
+        # phone rate: this layer's weight gradient and the dgrad + sigmoid backward below it are independent and each fills part of
+        # the chip: one grid for both (mg_linear_wgrad_dgrad_bf16), which can also carry a deferred tail as riders
+        pair = (ctx.phone_rate and top > 0 and acts[top - 1] == ops.ACT_SIGMOID and sink.grid and
+                ops.wgrad_slabs_ok(m_rows, n, k, hidden[top - 1].shape[1], g.shape[1]) and sink.adjacent(w_top, b_top))
+        # frame rate, Linear + Sigmoid at the bottom of the stack: its dW | db come straight from the second layer's dZ ...
+        fused1 = (not ctx.phone_rate and top > 0 and acts[0] == ops.ACT_SIGMOID and
+                  ops.can_fuse_bwd(m, dims[1][0], dims[1][1], dims[0][1], a0.shape[1]))
+        # ... and where that second layer is the 128-wide one, its weight gradient rides in the same launch.  Not beside an early
+        # gradient exchange: that one promises the second layer's gradient final BEFORE the fused kernel starts.
+        fuse2 = (fused1 and top == 1 and rows is not None and _EARLY_GRADS_HOOK is None and
+                 os.environ.get('MORGANA_FUSE_WGRAD2', '1') != '0' and sink.adjacent(params[0], params[1]) and sink.adjacent(w_top, b_top))
+        tail = sink.deferred_tail(tail, tail_first, grid=pair)
+        g_below = None
+        if fuse2:
+            sink.fused2(params, g, w_t[1], hidden[0], a0, rows, m, *dims[0])
+        elif pair:
+            slab, n_slabs, stride, g_below = ops.linear_wgrad_dgrad_bf16(g, hidden[top - 1], m_rows, n, k, w_t[top],
+                                                                         slab=_slab_buf(w_top), tail=tail)
+            sink.slabs(w_top, n * k + n, _slab_buf(w_top, keep=slab), n_slabs, stride)
+        else:
+            sink.wgrad(w_top, b_top, g, hidden[top - 1] if top > 0 else a0, None if top > 0 else r0, m_rows, n, k)
+        sink.tail_grads(tail_first, tail_grads.numel(), tail_grads)
+        for i in range(0 if fuse2 else top, 0, -1):
+            n, k = dims[i]
             if i == 1:
-                early = _deliver_early(ctx.params, flat[:flat.numel() - 1], ctx.offsets, grad_loss)
-            if i == 1 and ctx.acts[0] == ops.ACT_SIGMOID and ops.can_fuse_bwd(m, n, k, ctx.dims[0][1], a0.shape[1]):
-                # layer 0's dW, db straight from this layer's dZ: dZ_0 = (dZ_1 W_1) * H_0 (1 - H_0) stays on chip
-                n0_, k0_ = ctx.dims[0]
-                ops.linear_bwd_fused_bf16(g, w_t[1], hidden[0], a0, rows, m, n0_, k0_,
-                                          out_w=flat[ctx.offsets[0]:ctx.offsets[0] + n0_ * k0_].view(n0_, k0_),
-                                          out_b=flat[ctx.offsets[1]:ctx.offsets[1] + n0_])
-                break
-            if i > 0:
-                h = hidden[i - 1] if ctx.acts[i - 1] != ops.ACT_NONE else None
-                g = ops.linear_dgrad_bf16(g, m, n, w_t[i], k, h, act=ctx.acts[i - 1])
-        grads = _deliver_rest(ctx.params, flat[:flat.numel() - 1], ctx.offsets, grad_loss, early)
-        return no_grads[:5] + tuple(grads)
+                sink.early(params)                            # everything but the first layer's gradient is final
+                if fused1:
+                    sink.fused_first(params[0], params[1], g, w_t[1], hidden[0], a0, rows, m, *dims[0])
+                    break
+            if i == top and g_below is not None:
+                g = g_below
+            else:
+                h = hidden[i - 1] if acts[i - 1] != ops.ACT_NONE else None
+                g = ops.linear_dgrad_bf16(g, m_rows, n, w_t[i], k, h, act=acts[i - 1])
+            sink.wgrad(params[2 * i - 2], params[2 * i - 1], g, hidden[i - 2] if i > 1 else a0, None if i > 1 else r0, m_rows, *dims[i - 1])
+        return (None,) * 5 + tuple(sink.grads(params))        # spec, x2d, rows, target, seq_len | the parameters
 
 
 def _flat_grads_and_loss(params, device):
-    """(offsets, flat): one fp32 buffer for every parameter's gradient in parameter order - ``offsets[j]`` = where parameter j's
-    starts - and one more float behind them: the loss (see ops.f0_tail)."""
+    """(offsets, flat): one fp32 buffer for every parameter's gradient in parameter order and one more float behind them: the loss
+    (see ops.f0_tail)."""
+    offsets, total = _param_offsets(params)
+    return offsets, torch.empty(total + 1, dtype=torch.float32, device=device)
+
+
+def _param_offsets(params):
+    """(offsets, total) of the parameters' gradients laid end to end in parameter order: ``offsets[j]`` = where parameter j's starts."""
     offsets = [0]
     for p in params[:-1]:
         offsets.append(offsets[-1] + p.numel())
-    return offsets, torch.empty(offsets[-1] + params[-1].numel() + 1, dtype=torch.float32, device=device)
+    return offsets, offsets[-1] + params[-1].numel()
 
 
 def _mse_node_done(ctx, offsets, a0, rows, dz2, flat, hidden, w_t, loss, pred):
@@ -1352,55 +1380,19 @@ class F0StackX3Fn(torch.autograd.Function):
         w1, b1, w2, b2, w3 = params[:5]
         (n1, k0), (n2, k1) = w1.shape, w2.shape
         m = ctx.n_rows
-        mode, opt = _grad_mode(params, grad_loss)
-        tail = getattr(ctx, 'deferred_tail', None)
-        ctx.deferred_tail = None
+        sink = _grad_sink(params, grad_loss, None if _is_unit_grad(grad_loss) else grad_loss)
+        tail, ctx.deferred_tail = getattr(ctx, 'deferred_tail', None), None
         n_tail = ops.F0_TAIL_X3_N - 1                             # db2 | dW3 | db3 | dW4 | db4 (the loss behind them)
-        tail_slabs = None
-        if tail is not None:
-            if mode == 'defer' and os.environ.get('MORGANA_TAIL_RIDERS', 'adam') == 'adam':
-                # the update kernel sums the tail's slabs (one more source of its plan), its first blocks repeat the prediction and
-                # form the loss (optim.Adam.defer_tail)
-                tail_slabs = (tail['ws'].view(torch.float32), tail['n_slabs'], tail['stride'])
-                opt.defer_tail(b2, tail)
-            else:
-                ops.finish_deferred_tail(tail)
-        slab2, s2, st2, dz1, colsum, n_cs = ops.linear_wgrad_dgrad_x3(dz2, h1, m, n2, k1, w2tp, slab=getattr(w2, '_mg_slab_buf', None),
-                                                                      colsum=getattr(b1, '_mg_slab_buf', None))
-        w2._mg_slab_buf, b1._mg_slab_buf = slab2, colsum
-        if mode == 'defer':
-            if tail_slabs is not None:
-                opt.defer_slabs(b2, n_tail, tail_slabs[0], tail_slabs[1], tail_slabs[2])
-            else:
-                opt.defer_slabs(b2, n_tail, flat_tail, 1, n_tail)
-            opt.defer_slabs(w2, n2 * k1, slab2, s2, st2)
-            opt.defer_slabs(b1, n1, colsum.view(torch.float32), n_cs, n1)
-        elif mode == 'direct':
-            b2.grad.reshape(-1).as_strided((n_tail,), (1,)).add_(flat_tail[:n_tail])
-            ops.slab_reduce(slab2, s2, st2, n2 * k1, w2.grad.reshape(-1), accumulate=True)
-            ops.slab_reduce(colsum, n_cs, n1, n1, b1.grad, accumulate=True)
-            if _EARLY_GRADS_HOOK is not None:
-                _EARLY_GRADS_HOOK(params)                         # everything but the first layer's weight gradient is final
-        slab1, s1, st1 = ops.linear_wgrad_slabs_x3(dz1, a0, m, n1, k0, slab=getattr(w1, '_mg_slab_buf', None))
-        w1._mg_slab_buf = slab1
-        if mode == 'defer':
-            opt.defer_slabs(w1, n1 * k0, slab1, s1, st1)
-            return (None, None, None, None) + (None,) * len(params)
-        if mode == 'direct':
-            ops.slab_reduce(slab1, s1, st1, n1 * k0, w1.grad.reshape(-1), accumulate=True)
-            return (None, None, None, None) + (None,) * len(params)
-        # gradients as tensors for autograd
-        sizes = [p.numel() for p in params]
-        offsets = [0]
-        for sz in sizes[:-1]:
-            offsets.append(offsets[-1] + sz)
-        flat = torch.empty((sum(sizes),), dtype=torch.float32, device=a0.device)
-        ops.slab_reduce(slab1, s1, st1, n1 * k0, flat[offsets[0]:offsets[0] + n1 * k0])
-        ops.slab_reduce(colsum, n_cs, n1, n1, flat[offsets[1]:offsets[1] + n1])
-        ops.slab_reduce(slab2, s2, st2, n2 * k1, flat[offsets[2]:offsets[2] + n2 * k1])
-        flat[offsets[3]:offsets[3] + n_tail].copy_(flat_tail[:n_tail])
-        grads = _deliver_param_grads(params, flat, offsets, None if _is_unit_grad(grad_loss) else grad_loss)
-        return (None, None, None, None) + tuple(grads)
+        sink.deferred_tail(tail, b2, alone=True)                  # no grid here carries riders: the update launch takes it, or it runs now
+        slab2, s2, st2, dz1, colsum, n_cs = ops.linear_wgrad_dgrad_x3(dz2, h1, m, n2, k1, w2tp, slab=_slab_buf(w2), colsum=_slab_buf(b1))
+        sink.tail_grads(b2, n_tail, flat_tail[:n_tail])
+        sink.slabs(w2, n2 * k1, _slab_buf(w2, keep=slab2), s2, st2)
+        sink.slabs(b1, n1, _slab_buf(b1, keep=colsum).view(torch.float32), n_cs, n1)
+        if sink.final:
+            sink.early(params)                                    # everything but the first layer's weight gradient is final
+        slab1, s1, st1 = ops.linear_wgrad_slabs_x3(dz1, a0, m, n1, k0, slab=_slab_buf(w1))
+        sink.slabs(w1, n1 * k0, _slab_buf(w1, keep=slab1), s1, st1)
+        return (None, None, None, None) + tuple(sink.grads(params))
 
 
 _STATE_ROWS = {}

@@ -71,7 +71,7 @@ class Adam(torch.optim.Optimizer):
                 flat_p[off:off + n].copy_(p.data.reshape(-1))
                 p.data = flat_p[off:off + n].view_as(p)
                 p.grad = flat_g[off:off + n].view_as(p)
-                p._mg_direct_grad = True          # functional._deliver_param_grads may add into flat_g directly
+                p._mg_direct_grad = True          # functional._DirectSink and _deliver_param_grads (both behind _in_flat_grad) may add into flat_g directly
                 p._mg_optimizer = self            # functional asks it whether slabs may be deferred (weak: the param outlives nothing here)
                 offsets[id(p)] = off
                 off += n
